@@ -8,10 +8,12 @@ step with auto-reset (cm_env_step), both writing straight into the HBM trajector
 Inputs are resident in HBM when the timed region starts; synthetic data = envs spawned by the
 reference's spawn rule on the Philox stream, random-init policy weights (reference init).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (contract fields + "roofline" + "cpu_baseline" + "train_loop").
+--dump-outputs DIR: rank 0 also writes what the last timed step handed its caller as DIR/<name>.npy (see last_step_outputs),
+so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -79,6 +81,31 @@ def make_policy(kind, spec, n_agents, device):
     if kind == "cent":
         return nets.CentralizedCategoricalMLPPolicy(spec, n_agents=n_agents, hidden_sizes=[128, 64, 32], device=device)
     return nets.CommCategoricalMLPPolicy(spec, n_agents=n_agents, device=device)
+
+
+DUMP_LIMIT = 64 << 20      # bytes --dump-outputs may write in all
+
+
+def last_step_outputs(eng, t):
+    """Slot t of the rollout as the sampler would receive it: the policy's actions, probs and attention and the env step's
+    next observation, rewards, dones and episode info, as host arrays (float32; the f64 reward stays float64).  Past
+    DUMP_LIMIT every array keeps the same fixed, seeded sample of envs (first axis), whose ids go to 'env_ids'."""
+    import numpy as np
+    dev = dict(actions=eng.actions[t], probs=None if eng.probs is None else eng.probs[t],
+               attn=None if eng.attn is None else eng.attn[t], **eng._out(t, 0, eng.env.B))
+    out = {}
+    for name, v in dev.items():
+        if v is not None:
+            a = v.cpu().numpy()
+            out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        B = eng.env.B
+        keep = max(1, B * DUMP_LIMIT // (total + 8 * B))            # 8 bytes per kept env: its id
+        ids = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        out = {name: a[ids] for name, a in out.items()}
+        out["env_ids"] = ids.astype(np.float64)
+    return out
 
 
 def host_cores():
@@ -152,10 +179,11 @@ def cpu_baseline(c, seed, budget_s=12.0, kind="commdp"):
                        f"OpenMP over envs), {dt:.1f} s")
 
 
-def measure_rollout(config, args, rank, world, dev, steps, warmup, envs=None, streams=None):
+def measure_rollout(config, args, rank, world, dev, steps, warmup, envs=None, streams=None, keep_outputs=False):
     """One config on this rank's GPU: K steps of the rollout under the timing contract (every graph captured, instantiated
     and replayed before t0; barrier + synchronize on both sides; max over ranks), then the per-kernel durations with HIP
-    events and the roofline rows.  Returns everything main() puts into the JSON line."""
+    events and the roofline rows.  Returns everything main() puts into the JSON line; with keep_outputs, also the last
+    timed step's outputs (copied before the kernel table reuses the buffers)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -236,6 +264,7 @@ def measure_rollout(config, args, rank, world, dev, steps, warmup, envs=None, st
         print(f"[bench] timed region {dt * 1e6:.1f} us, of which host-side issue {t_issue * 1e6:.1f} us", file=sys.stderr)
     assert len(eng._graphs) == n_captured, "a hipGraph was captured inside the timed region"
     eng.env.check_status()
+    outputs = last_step_outputs(eng, plan(steps)[-1] - 1) if keep_outputs else None
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -266,7 +295,8 @@ def measure_rollout(config, args, rank, world, dev, steps, warmup, envs=None, st
 
     if getattr(args, "no_kernel_table", False):
         return dict(c=c, B=B, env=env, policy=policy, spec=spec, eng=eng, ns=ns, G=G, value=value, dt=dt, n_captured=n_captured,
-                    timed_lengths=timed_lengths, extra_warm=extra_warm, use_graph=use_graph, roofline=None)
+                    timed_lengths=timed_lengths, extra_warm=extra_warm, use_graph=use_graph, roofline=None,
+                    outputs=outputs)
     env.reset_all()                                     # full-batch handle: per-launch kernel times at B envs
     adj0 = None if eng.dist_adj is None else eng.dist_adj[0]
     ch0 = None if eng.channels is None else eng.channels[0]
@@ -352,7 +382,8 @@ def measure_rollout(config, args, rank, world, dev, steps, warmup, envs=None, st
     if "frac_f16_pipe" in kernels[dom]:
         roofline["frac_f16_pipe"] = kernels[dom]["frac_f16_pipe"]
     return dict(c=c, B=B, env=env, policy=policy, spec=spec, eng=eng, ns=ns, G=G, value=value, dt=dt, n_captured=n_captured,
-                timed_lengths=timed_lengths, extra_warm=extra_warm, use_graph=use_graph, roofline=roofline)
+                timed_lengths=timed_lengths, extra_warm=extra_warm, use_graph=use_graph, roofline=roofline,
+                outputs=outputs)
 
 
 def main():
@@ -380,7 +411,12 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the config's env batch on EVERY GPU (default); strong: the batch split over the GPUs "
                          "(SURVEY.md §8e: 4096 -> 4096/2048/1024/512 envs per GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's envs) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_LIMIT >> 20} MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start N fresh ranks (one per GPU) and relay rank 0's line.
@@ -424,7 +460,12 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    m = measure_rollout(args.config, args, rank, world, dev, args.steps, args.warmup, envs=args.envs, streams=args.streams)
+    m = measure_rollout(args.config, args, rank, world, dev, args.steps, args.warmup, envs=args.envs, streams=args.streams,
+                        keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if m["outputs"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in m["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     c, B, env, policy, spec, eng, ns, G, value, dt = (m[k] for k in ("c", "B", "env", "policy", "spec", "eng", "ns", "G", "value", "dt"))
     n_captured, timed_lengths, extra_warm, use_graph, roofline = (m[k] for k in ("n_captured", "timed_lengths", "extra_warm", "use_graph", "roofline"))
 

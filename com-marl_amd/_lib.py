@@ -14,6 +14,7 @@ CM_PP, CM_CO = 0, 1
 PACK_F32, PACK_F16, PACK_WAVE, PACK_CHECK, PACK_ALL = 1, 2, 4, 8, 15      # cm_*_pack_sections (include/commarl.h)
 CHANNELS = {"FC": 0, "FL": 1, "IID": 2, "GE": 3}
 RNG_PHILOX, RNG_TAPE = 0, 1
+ENT_ADD, ENT_SOFTPLUS, ENT_STOP_GRAD = 1, 2, 4                              # cm_ppo_surrogate's add_entropy bits
 
 
 class EnvCfg(C.Structure):
@@ -163,6 +164,8 @@ _SIGNATURES = {
                                          C.c_void_p]),
     "cm_ppo_surrogate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_entropy_gae": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                 C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_discount_returns": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
                                       C.c_void_p]),
     "cm_gae": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,

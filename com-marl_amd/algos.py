@@ -21,6 +21,7 @@ import time
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch.distributions import Categorical
 
 from . import _lib as L
@@ -30,7 +31,8 @@ from .sampler import CentralizedMAOnPolicyVectorizedSampler, PathBatch, tabular
 class _SurrogateFn(torch.autograd.Function):
     """-(sum over valid steps of the clipped surrogate + entropy bonus) from the policy logits in one launch
     (cm_ppo_surrogate: the ~30 elementwise / reduction launches of :390-438 + :540-589 and as many again in their
-    autograd); the gradient wrt the logits is produced by the same launch.  Returns (total f32, count int64)."""
+    autograd); the gradient wrt the logits is produced by the same launch.  Returns (total f32, count int64).
+    add_entropy: the CM_ENT_* bits of include/commarl.h (0 / 1 = no term / the plain term)."""
 
     @staticmethod
     def forward(ctx, logits, actions, old_ll, adv, valids, clip, ent_coeff, add_entropy):
@@ -105,7 +107,8 @@ class _UpdateGraphs:
         # what a captured step has baked in besides its tensors: part of the cache key
         grp = lambda o: tuple((g["lr"], tuple(g["betas"]), g["eps"]) for g in o.param_groups)   # noqa: E731
         self.hyper = (T, grp(algo._optimizer), grp(algo._baseline_optimizer), algo._lr_clip_range, algo._policy_ent_coeff,
-                      algo._entropy_regularzied, algo._clip_grad_norm, os.environ.get("COMMARL_CRITIC_STREAM", "1"))
+                      algo._entropy_method, algo._use_softplus_entropy, algo._stop_entropy_gradient, algo._positive_adv,
+                      algo._clip_grad_norm, os.environ.get("COMMARL_CRITIC_STREAM", "1"))
         return self
 
     def __init__(self, algo, owner):
@@ -216,8 +219,6 @@ class CentralizedMAPPO:
         self._maximum_entropy = entropy_method == 'max'
         self._entropy_regularzied = entropy_method == 'regularized'
         self._check_entropy_configuration(entropy_method, center_adv, stop_entropy_gradient, policy_ent_coeff)
-        if use_softplus_entropy or self._maximum_entropy or stop_entropy_gradient:
-            raise NotImplementedError("only the runners' entropy settings ('regularized' / 'no_entropy') are built")
         # default: the multi-tensor Adam of optim.py (two launches per step, clip folded in); it and torch.optim.Adam are
         # the same update as the vendored torch-1.9 Adam (my_optimizer/_functional.py:72-98): pinned by tests against the
         # reference's optimiser.
@@ -341,6 +342,41 @@ class CentralizedMAPPO:
             adv = adv - adv.min()
         return adv
 
+    def _max_entropy_advantages(self, logits, rewards, baselines, in_place):
+        """entropy_method 'max' (:415-418): r' = r + c * H of the current policy, then compute_advantages, in one
+        cm_entropy_gae launch on the detached logits [P,T,N,A] (the entropy carries no gradient in this mode: the ctor
+        demands stop_entropy_gradient).  in_place writes r' back into `rewards`, as the reference's `rewards +=` does to the
+        epoch's full-batch tensor (the two quirks of the in-place add); a minibatch step leaves its rewards
+        buffer alone (the reference adds to a copy, and a replayed update graph would add c * H again every mini-epoch).
+        positive_adv subtracts the min of this call's advantages (:428-429)."""
+        P, T = rewards.shape
+        N, A = logits.shape[-2:]
+        lg = logits.detach().contiguous()
+        adv = torch.empty_like(rewards)
+        with torch.cuda.device(rewards.device):
+            L.check(L.lib().cm_entropy_gae(P, T, N, A, L.ptr(lg), L.ptr(rewards), L.ptr(baselines.contiguous()),
+                                           float(self.discount), float(self._gae_lambda), float(self._policy_ent_coeff),
+                                           int(self._use_softplus_entropy), L.ptr(rewards) if in_place else None, None,
+                                           L.ptr(adv), L.current_stream()), "cm_entropy_gae")
+        if self._positive_adv:
+            adv = adv - adv.min()
+        return adv
+
+    def _entropy_flags(self):
+        """cm_ppo_surrogate's add_entropy bits: the 'regularized' term and its two switches (:434-435, :509-536)."""
+        if not self._entropy_regularzied:
+            return 0
+        return (L.ENT_ADD | (L.ENT_SOFTPLUS if self._use_softplus_entropy else 0)
+                | (L.ENT_STOP_GRAD if self._stop_entropy_gradient else 0))
+
+    def _entropy_column(self, p):
+        """The logged Entropy (:366): mean over all padded steps of the per-step entropy (mean over agents), softplus per step
+        first when use_softplus_entropy is set (it goes through _compute_policy_entropy, :499-538)."""
+        h = -(p * torch.log(p)).sum(-1).mean(-1)
+        if self._use_softplus_entropy:
+            h = F.softplus(h)
+        return h.mean()
+
     @torch.no_grad()
     def _old_log_likelihood(self, obs, actions, dist_adjs, channels):
         """old_policy.log_likelihood (:561-566): one fused no-grad launch."""
@@ -360,31 +396,42 @@ class CentralizedMAPPO:
         """log-likelihood of the taken joint action from action probabilities [P,T,N,A] -> [P,T] (:561-566)."""
         return torch.log(probs.gather(-1, actions.long().unsqueeze(-1))).squeeze(-1).sum(-1)
 
-    @staticmethod
-    def _kl_entropy(p_old, p_new):
+    def _kl_entropy(self, p_old, p_new):
         """KL(old || new) mean and entropy mean of `p_new` over ALL padded steps (:440-538) from two probability tensors."""
         kl = (p_old * (torch.log(p_old) - torch.log(p_new))).sum(-1).mean()
-        ent = -(p_new * torch.log(p_new)).sum(-1).mean(-1).mean()
-        return float(kl), float(ent)
+        return float(kl), float(self._entropy_column(p_new))
 
     def _compute_loss(self, itr, obs, avail_actions, actions, rewards, valids, baselines, dist_adjs, channels,
-                      advantages=None, old_ll=None, reduce=True, logits=None):
+                      advantages=None, old_ll=None, reduce=True, logits=None, rewards_in_place=False):
         """:390-438.  Returns -(mean over valid steps of clipped surrogate + c * entropy); with
-        reduce=False returns (sum, count) for the count-weighted multi-GPU reduction."""
+        reduce=False returns (sum, count) for the count-weighted multi-GPU reduction.
+        entropy_method 'max' ignores `advantages`: they come from this call's entropy (_max_entropy_advantages), and
+        rewards_in_place says whether r + c * H is written back into `rewards` (the full-batch calls of train_once)."""
         T = obs.shape[1]
-        if advantages is None:
+        maxent = self._maximum_entropy
+        if advantages is None and not maxent:
             advantages = self._advantages(rewards, baselines, valids)
         if old_ll is None:
             old_ll = self._old_log_likelihood(obs, actions, dist_adjs, channels)
         if _fused_loss_ok(self.policy, obs, avail_actions, actions, valids):
             if logits is None:
                 logits = self.policy._logits(obs, dist_adjs, channels)               # [P,T,N,A]
+            if maxent:
+                advantages = self._max_entropy_advantages(logits, rewards, baselines, rewards_in_place)
             total, count = _SurrogateFn.apply(logits, actions, old_ll, advantages, valids, self._lr_clip_range,
-                                              self._policy_ent_coeff, self._entropy_regularzied)
+                                              self._policy_ent_coeff, self._entropy_flags())
             return (total, count) if not reduce else total / count
         probs, _ = self.policy._probs(obs, avail_actions, dist_adjs, channels)      # one trunk pass for both terms
         dist_n = Categorical(probs=probs)
         entropies = dist_n.entropy().mean(-1)                                        # policy.entropy (:121-126)
+        if self._stop_entropy_gradient:
+            entropies = entropies.detach()                                           # (:509-514: under no_grad)
+        if self._use_softplus_entropy:
+            entropies = F.softplus(entropies)                                        # (:535-536)
+        if maxent:                                                                   # :415-418
+            c = self._policy_ent_coeff
+            advantages = self._advantages(rewards.add_(c * entropies) if rewards_in_place else rewards + c * entropies,
+                                          baselines, valids)
         new_ll = dist_n.log_prob(actions).sum(-1)                                    # policy.log_likelihood (:128-137)
         ratio = (new_ll - old_ll).exp()
         surrogate = ratio * advantages
@@ -409,8 +456,7 @@ class CentralizedMAPPO:
         _, p_old, _ = self._old_policy.act_device(flat(obs), None, flat(dist_adjs), flat(channels),
                                                   want_actions=False, want_attn=False, policy_step=0)
         kl = (p_old * (torch.log(p_old) - torch.log(p_new))).sum(-1).mean()
-        ent = -(p_new * torch.log(p_new)).sum(-1).mean(-1).mean()
-        return float(kl), float(ent)
+        return float(kl), float(self._entropy_column(p_new))
 
     def _log_performance(self, itr, paths, returns, valids):
         """The progress.csv columns of centralized_ma_ppo.py:286-366 (per-path sums -> means over paths).
@@ -500,7 +546,11 @@ class CentralizedMAPPO:
         obs, avail, actions, rewards, valids, baselines, returns, dist_adjs, channels = self.process_samples(itr, paths)
         P, T = rewards.shape
         distributed = _dist_ready()
-        advantages = self._advantages(rewards, baselines, valids)
+        # entropy_method 'max': no epoch-wide advantages - every loss evaluation derives its own from the current policy's
+        # entropy (_max_entropy_advantages), and the full-batch evaluations before / after the update add c * H into `rewards`
+        # in place as the reference does (its minibatches are sliced from the tensor loss_before left behind)
+        maxent = self._maximum_entropy
+        advantages = None if maxent else self._advantages(rewards, baselines, valids)
         # The reference evaluates the two policies over the full batch eight times per epoch (old log-likelihood twice,
         # loss before / after, KL + entropy before / after with both nets each).  Only three distinct (weights, batch)
         # pairs are involved - last epoch's pre-update weights, this epoch's pre-update weights (which the old policy
@@ -512,7 +562,7 @@ class CentralizedMAPPO:
                 lg_new, p_new = self.policy.evaluate_nograd(obs, dist_adjs, channels)
                 old_ll0 = self._ll_from_probs(p_old0, actions)
                 loss_before = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                       channels, advantages, old_ll0, logits=lg_new))
+                                                       channels, advantages, old_ll0, logits=lg_new, rewards_in_place=maxent))
                 kl_before, _ = self._kl_entropy(p_old0, p_new)
                 del p_old0, lg_new
             self._old_policy.load_state_dict(self.policy.state_dict())              # :204
@@ -522,7 +572,7 @@ class CentralizedMAPPO:
             with torch.no_grad():
                 old_ll0 = self._old_log_likelihood(obs, actions, dist_adjs, channels)
                 loss_before = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                       channels, advantages, old_ll0))
+                                                       channels, advantages, old_ll0, rewards_in_place=maxent))
                 kl_before, _ = self._diagnostics(obs, actions, valids, dist_adjs, channels)
             self._old_policy.load_state_dict(self.policy.state_dict())              # :204
             with torch.no_grad():
@@ -541,7 +591,7 @@ class CentralizedMAPPO:
         for start in range(0, P, step_size):
             ids = torch.as_tensor(shuffled_ids[start:min(start + step_size, P)], device=obs.device)
             minibatches.append((obs[ids], actions[ids], rewards[ids], valids[ids], baselines[ids], sl(dist_adjs, ids),
-                                sl(channels, ids), advantages[ids], old_ll[ids], returns[ids]))
+                                sl(channels, ids), sl(advantages, ids), old_ll[ids], returns[ids]))
         # The critic has its own trunk (a-17): its forward / backward (/ optimiser step) share nothing with the policy's
         # but the minibatch, so they run on a second HIP stream and fill the gaps of the policy's launch chain.
         two_streams = obs.is_cuda and os.environ.get("COMMARL_CRITIC_STREAM", "1") != "0"
@@ -616,12 +666,12 @@ class CentralizedMAPPO:
             if shared:
                 lg_after, p_after = self.policy.evaluate_nograd(obs, dist_adjs, channels)
                 loss_after = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                      channels, advantages, old_ll, logits=lg_after))
+                                                      channels, advantages, old_ll, logits=lg_after, rewards_in_place=maxent))
                 kl, entropy = self._kl_entropy(p_new, p_after)
                 del lg_after, p_after, p_new
             else:
                 loss_after = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                      channels, advantages, old_ll))
+                                                      channels, advantages, old_ll, rewards_in_place=maxent))
                 kl, entropy = self._diagnostics(obs, actions, valids, dist_adjs, channels)
         perf = self._log_performance(itr, paths, returns, valids)
         avg_return = perf["AverageReturn"]

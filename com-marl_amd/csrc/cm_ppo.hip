@@ -5,6 +5,7 @@
 //   * cm_discount_returns             : garage/misc/tensor_utils.py:7-23 (f64 recurrence)
 //   * cm_gae                          : garage/torch/algos/_utils.py:56-113 + the per-path
 //                                       normalisation of centralized_ma_ppo.py:422-426
+//   * cm_entropy_gae                  : entropy_method "max" - entropy -> r + c H -> GAE (:415-418, :499-538)
 // Samples are [P*T] env states; a 256-thread workgroup owns EPB whole samples so that the
 // N x N mask tile and the N x 64 feature tile are read from HBM exactly once.
 #include <algorithm>
@@ -696,14 +697,19 @@ __global__ __launch_bounds__(256) void ppo_surrogate_kernel(int P, int T, int N,
         const float rc = fminf(fmaxf(r, 1.0f - clip), 1.0f + clip);
         const float sur = r * ad, clp = rc * ad;
         float obj = fminf(sur, clp);
-        if (add_entropy) obj += ent_coeff * ent;
+        // CM_ENT_* bits (include/commarl.h): softplus after the mean over agents (centralized_ma_ppo.py:535-536), torch's
+        // threshold 20; its derivative z / (z + 1) as torch's softplus_backward writes it
+        const bool ent_on = add_entropy & 1, ent_sp = add_entropy & 2, ent_grad = !(add_entropy & 4);
+        float ent_term = ent, ent_slope = 1.0f;
+        if (ent_sp && ent <= 20.0f) { const float z = expf(ent); ent_term = log1pf(z); ent_slope = z / (z + 1.0f); }
+        if (ent_on) obj += ent_coeff * ent_term;
         if (valid) part = -(double)obj;
         if (dlogits) {
             // d total / d new_ll: torch.min splits ties evenly; clamp passes the gradient inside [1 - c, 1 + c] (ends included)
             const float wa = sur < clp ? 1.0f : (sur == clp ? 0.5f : 0.0f), wb = sur > clp ? 1.0f : (sur == clp ? 0.5f : 0.0f);
             const float cg = (r >= 1.0f - clip && r <= 1.0f + clip) ? 1.0f : 0.0f;
             const float g_ll = valid ? -(ad * wa + ad * cg * wb) * r : 0.0f;
-            const float g_h = (valid && add_entropy) ? -ent_coeff / (float)N : 0.0f;     // d total / d H_i
+            const float g_h = (valid && ent_on && ent_grad) ? -ent_coeff * ent_slope / (float)N : 0.0f;     // d total / d H_i
             float *d0 = dlogits + s * N * A;
             for (int i = 0; i < N; ++i) {
                 float z[PPO_MAX_A], p[PPO_MAX_A], p1[PPO_MAX_A], p2[PPO_MAX_A], p3[PPO_MAX_A], d[PPO_MAX_A];
@@ -755,6 +761,68 @@ __global__ __launch_bounds__(256) void ppo_surrogate_kernel(int P, int T, int N,
     if (threadIdx.x == 0) {
         atomicAdd(total, sh_t[0] + sh_t[1] + sh_t[2] + sh_t[3]);
         atomicAdd((unsigned long long *)count, (unsigned long long)(sh_c[0] + sh_c[1] + sh_c[2] + sh_c[3]));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// entropy_method == "max" (centralized_ma_ppo.py:415-418, entropy :499-538): the advantages depend on the current policy's
+// entropy, so every loss evaluation runs  H -> r + c H -> GAE  on its own batch.  One 256-thread workgroup per path: the
+// threads over t compute the per-step entropy (N x A exp / log each - the parallel part) into LDS next to the path's
+// baselines, then one thread runs gae_kernel's recurrence over the padded length out of LDS (T f64 FMAs).
+// H[t] = mean_i H_i with ppo_surrogate_kernel's Categorical arithmetic (softmax normalised twice, log(clamp(p, eps, 1-eps))),
+// softplus after the mean when asked (:535-536).
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void entropy_gae_kernel(int T, int N, int A, const float *__restrict__ logits,
+                                                          const float *rewards, const float *__restrict__ baselines, float gamma,
+                                                          float lam, float ent_coeff, int softplus, float *rewards_out,
+                                                          float *__restrict__ entropy_out, float *__restrict__ adv) {
+    extern __shared__ float ent_lds[];                       // r' [T], V [T]
+    float *rs = ent_lds, *vs = ent_lds + T;
+    const int p = blockIdx.x;
+    const size_t row = (size_t)p * T;
+    const float EPS = 1.1920928955078125e-07f;
+    for (int t = threadIdx.x; t < T; t += blockDim.x) {
+        const float *z0 = logits + (row + t) * N * A;
+        float ent = 0.0f;
+        for (int i = 0; i < N; ++i) {
+            float z[PPO_MAX_A], q[PPO_MAX_A];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int b = 0; b < PPO_MAX_A; ++b) if (b < A) { z[b] = z0[i * A + b]; mx = fmaxf(mx, z[b]); }
+            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+            for (int b = 0; b < PPO_MAX_A; ++b) if (b < A) { q[b] = expf(z[b] - mx); s0 += q[b]; }
+#pragma unroll
+            for (int b = 0; b < PPO_MAX_A; ++b) if (b < A) { q[b] = q[b] / s0; s1 += q[b]; }
+#pragma unroll
+            for (int b = 0; b < PPO_MAX_A; ++b) if (b < A) { q[b] = q[b] / s1; s2 += q[b]; }
+            float h = 0.0f;
+#pragma unroll
+            for (int b = 0; b < PPO_MAX_A; ++b) if (b < A) {
+                const float p3 = q[b] / s2;
+                h -= logf(fminf(fmaxf(p3, EPS), 1.0f - EPS)) * p3;
+            }
+            ent += h;
+        }
+        ent /= (float)N;
+        if (softplus && ent <= 20.0f) ent = log1pf(expf(ent));          // F.softplus (threshold 20)
+        const float r = rewards[row + t] + ent_coeff * ent;              // rewards += c * H (f32, :415-416)
+        rs[t] = r;
+        vs[t] = baselines[row + t];
+        if (entropy_out) entropy_out[row + t] = ent;
+        if (rewards_out) rewards_out[row + t] = r;                       // (same thread read rewards[row + t]: aliasing is fine)
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float *a = adv + row;                                                // gae_kernel's recurrence, bit for bit
+    const double gl = (double)(gamma * lam);
+    double acc = 0.0, vnext = 0.0;
+#pragma unroll 8
+    for (int t = T - 1; t >= 0; --t) {
+        const float delta = (rs[t] + gamma * (float)vnext) - vs[t];
+        acc = (double)delta + gl * acc;
+        a[t] = (float)acc;
+        vnext = vs[t];
     }
 }
 
@@ -1080,6 +1148,19 @@ extern "C" int cm_ppo_surrogate(int32_t P, int32_t T, int32_t N, int32_t A, cons
     const long S = (long)P * T;
     hipLaunchKernelGGL(ppo_surrogate_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, T, N, A, logits, actions,
                        old_ll, adv, lens, clip, ent_coeff, add_entropy, total, (long long *)count, dlogits);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+extern "C" int cm_entropy_gae(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const float *rewards,
+                              const float *baselines, float gamma, float lam, float ent_coeff, int32_t softplus, float *rewards_out,
+                              float *entropy_out, float *adv, void *stream) {
+    if (A < 1 || A > PPO_MAX_A || N < 1) return set_error(CM_ERR_ARG, "cm_entropy_gae: 1 <= n_actions <= 8 and n_agents >= 1 required");
+    if (T > CM_ENT_GAE_MAX_T) return set_error(CM_ERR_ARG, "cm_entropy_gae: T above CM_ENT_GAE_MAX_T");
+    if (P <= 0 || T <= 0) return CM_OK;
+    if (!logits || !rewards || !baselines || !adv) return set_error(CM_ERR_ARG, "cm_entropy_gae: null argument");
+    hipLaunchKernelGGL(entropy_gae_kernel, dim3((unsigned)P), dim3(256), 2 * (size_t)T * sizeof(float), (hipStream_t)stream, T, N, A,
+                       logits, rewards, baselines, gamma, lam, ent_coeff, softplus, rewards_out, entropy_out, adv);
     CM_HIP(hipGetLastError());
     return CM_OK;
 }

@@ -6,7 +6,8 @@ import time
 import torch
 
 
-def train_loop_measurement(env, policy, cfg, spec, world, rank, dev, seed, epochs=2, kind="commdp", batch_size=None):
+def train_loop_measurement(env, policy, cfg, spec, world, rank, dev, seed, epochs=2, kind="commdp", batch_size=None,
+                           algo_kwargs=None):
     from . import nets
     from .algos import CentralizedMAPPO
     from .sampler import CentralizedMAOnPolicyVectorizedSampler
@@ -20,10 +21,10 @@ def train_loop_measurement(env, policy, cfg, spec, world, rank, dev, seed, epoch
         critic = nets.GaussianMLPBaseline(env_spec=spec, hidden_sizes=(64, 64, 64), device=dev)
     else:
         critic = nets.CommBaseCritic(spec, n_agents=env.N, device=dev)
-    algo = CentralizedMAPPO(env_spec=spec, policy=policy, baseline=critic, max_path_length=mpl, discount=0.99,
-                            center_adv=True, positive_adv=False, gae_lambda=0.97, policy_ent_coeff=0.1,
-                            entropy_method="regularized", clip_grad_norm=7, optimization_n_minibatches=3,
-                            optimization_mini_epochs=10, device=dev)
+    kw = dict(max_path_length=mpl, discount=0.99, center_adv=True, positive_adv=False, gae_lambda=0.97, policy_ent_coeff=0.1,
+              entropy_method="regularized", clip_grad_norm=7, optimization_n_minibatches=3, optimization_mini_epochs=10)
+    kw.update(algo_kwargs or {})                      # (e.g. entropy_method="max", center_adv=False, stop_entropy_gradient=True)
+    algo = CentralizedMAPPO(env_spec=spec, policy=policy, baseline=critic, device=dev, **kw)
     smp = CentralizedMAOnPolicyVectorizedSampler(algo, _Shell(env, spec), n_envs=env.B)
     smp.start_worker()
     bs = batch_size or env.B * env.N * mpl            # default: every env contributes at least one full path

@@ -447,10 +447,29 @@ int cm_gae(int32_t P, int32_t T, const float *rewards, const float *baselines, c
  * comm_categorical_mlp_policy.py:48-96, entropy / log_prob :121-137):
  *   *total = - sum over valid steps of [ min(r adv, clamp(r, 1 - clip, 1 + clip) adv) + ent_coeff * mean_i H_i ]   (f64)
  *   *count = number of valid steps (t < lens[p]);  dlogits (nullable) = d total / d logits, zero on padded steps.
- * add_entropy = 0 drops the entropy term (entropy_method != "regularized"). */
+ * add_entropy is a bit set (entropy_method == "regularized", centralized_ma_ppo.py:434-435 + :499-538):
+ *   CM_ENT_ADD       (1)  add the entropy term; 0 drops it (entropy_method != "regularized")
+ *   CM_ENT_SOFTPLUS  (2)  the term is ent_coeff * softplus(mean_i H_i) (use_softplus_entropy)
+ *   CM_ENT_STOP_GRAD (4)  the term stays in *total but contributes nothing to dlogits (stop_entropy_gradient)
+ * The values 0 and 1 are the kernel's original behaviour. */
+#define CM_ENT_ADD 1
+#define CM_ENT_SOFTPLUS 2
+#define CM_ENT_STOP_GRAD 4
 int cm_ppo_surrogate(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
                      const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff,
                      int32_t add_entropy, double *total, int64_t *count, float *dlogits, void *stream);
+
+/* entropy_method == "max" (centralized_ma_ppo.py:415-418 + :499-538): per step of a padded [P,T] batch
+ *   H[p,t] = mean_i H(Categorical_i(logits[p*T+t, i, :]))  (padded steps included; same Categorical arithmetic as
+ *            cm_ppo_surrogate), softplus(H) when softplus != 0,
+ *   r'     = rewards + ent_coeff * H,
+ *   adv    = compute_advantages(gamma, lam, r', baselines) over the padded length, no normalisation.
+ * logits [P*T,N,A] (1 <= A <= 8), rewards / baselines / adv [P,T].  rewards_out (nullable, may alias rewards) receives r';
+ * entropy_out (nullable) receives H [P,T] after the softplus.  T <= CM_ENT_GAE_MAX_T. */
+#define CM_ENT_GAE_MAX_T 8192
+int cm_entropy_gae(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const float *rewards,
+                   const float *baselines, float gamma, float lam, float ent_coeff, int32_t softplus, float *rewards_out,
+                   float *entropy_out, float *adv, void *stream);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,28 @@ _SIGNATURES = {
                                       C.c_void_p]),
     "cm_gae": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
                          C.c_float, C.c_void_p, C.c_void_p]),
+    # deterministic update mode: slab-workspace twins (include/commarl.h)
+    "cm_linear_act_backward_det_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "cm_linear_act_backward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
+    "cm_encoder_backward_det_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "cm_encoder_backward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cm_masked_agg_backward_det_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cm_masked_agg_backward_det": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cm_linear_wgrad_det_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "cm_linear_wgrad_det": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cm_ppo_surrogate_det_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cm_ppo_surrogate_det": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "cm_gauss_nll_forward_det_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "cm_gauss_nll_forward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 EXPORTED = tuple(_SIGNATURES)
 
@@ -196,6 +218,12 @@ def lib():
             raise CommarlError("libcommarl_hip.so ABI version mismatch")
         _lib = L
     return _lib
+
+
+def slab(nbytes, device):
+    """A slab workspace for a cm_*_det twin: torch memory (from the graph pool under capture), contents ignored."""
+    import torch
+    return torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=device)
 
 
 def check(rc, what=""):

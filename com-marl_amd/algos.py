@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from torch.distributions import Categorical
 
 from . import _lib as L
+from . import deterministic
 from .sampler import CentralizedMAOnPolicyVectorizedSampler, PathBatch, tabular
 
 
@@ -44,9 +45,16 @@ class _SurrogateFn(torch.autograd.Function):
         total = torch.empty((), dtype=torch.float64, device=dev)
         count = torch.empty((), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            L.check(L.lib().cm_ppo_surrogate(P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
-                                             L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
-                                             L.ptr(total), L.ptr(count), L.ptr(dl), L.current_stream()), "cm_ppo_surrogate")
+            if deterministic():                              # block sums summed in a fixed order (no f64 atomics)
+                nb = L.lib().cm_ppo_surrogate_det_ws_bytes(P, T)
+                L.check(L.lib().cm_ppo_surrogate_det(P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
+                                                     L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
+                                                     L.ptr(total), L.ptr(count), L.ptr(dl), L.ptr(L.slab(nb, dev)), nb, L.current_stream()),
+                        "cm_ppo_surrogate_det")
+            else:
+                L.check(L.lib().cm_ppo_surrogate(P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
+                                                 L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
+                                                 L.ptr(total), L.ptr(count), L.ptr(dl), L.current_stream()), "cm_ppo_surrogate")
         ctx.dl = dl
         ctx.mark_non_differentiable(count)
         return total.to(torch.float32), count
@@ -108,7 +116,7 @@ class _UpdateGraphs:
         grp = lambda o: tuple((g["lr"], tuple(g["betas"]), g["eps"]) for g in o.param_groups)   # noqa: E731
         self.hyper = (T, grp(algo._optimizer), grp(algo._baseline_optimizer), algo._lr_clip_range, algo._policy_ent_coeff,
                       algo._entropy_method, algo._use_softplus_entropy, algo._stop_entropy_gradient, algo._positive_adv,
-                      algo._clip_grad_norm, os.environ.get("COMMARL_CRITIC_STREAM", "1"))
+                      algo._clip_grad_norm, os.environ.get("COMMARL_CRITIC_STREAM", "1"), deterministic())
         return self
 
     def __init__(self, algo, owner):
@@ -540,6 +548,23 @@ class CentralizedMAPPO:
     # train_once (:175-388)
     # ------------------------------------------------------------------------------------------
     def train_once(self, runner=None, itr=None, paths=None):
+        if not deterministic():
+            return self._train_once(runner, itr, paths)
+        # deterministic mode: the framework / library operations of the update (the input-gradient GEMMs of nets._LinearFn and
+        # _MatmulWFn, the wide first layers, the layer-by-layer path) with torch's deterministic setting on - the library GEMMs
+        # then take no atomic split-K kernels; the caller's settings come back afterwards
+        import torch.utils.deterministic as tud
+        was_on, was_warn, was_fill = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(),
+                                      tud.fill_uninitialized_memory)
+        torch.use_deterministic_algorithms(True, warn_only=True)
+        tud.fill_uninitialized_memory = False                # (no NaN fill of every torch.empty: nothing here reads one unwritten)
+        try:
+            return self._train_once(runner, itr, paths)
+        finally:
+            torch.use_deterministic_algorithms(was_on, warn_only=was_warn)
+            tud.fill_uninitialized_memory = was_fill
+
+    def _train_once(self, runner=None, itr=None, paths=None):
         if runner is not None:
             itr, paths = runner.step_itr, runner.step_path
         t_start = time.time()

@@ -114,3 +114,22 @@ namespace mf {
 int pack_one(const float *Wt, int K, int OUT, int kpad, int out_pad, float *dst, void *stream);
 }
 }
+
+namespace cm {
+// ---- deterministic merges (include/commarl.h "Deterministic update mode") ----
+// In slab mode a workgroup plain-stores its partial sums into row blockIdx.x of a slab instead of adding them into the
+// output with float atomics; slab_reduce then sums the rows in index order.  The number of rows is the launch's grid
+// size, a function of the shape and the device's CU count only.
+template <bool DET>
+__device__ __forceinline__ void merge_add(float *p, float v) {
+    if constexpr (DET) *p = v;
+    else atomicAdd(p, v);
+}
+
+// out[i] += sum_{b < rows} slab[b * row_len + off + i], b ascending, for up to four segments of a slab row
+struct SlabSeg { float *out; int off, n; };
+struct SlabSegs { SlabSeg s[4]; int n_seg; };
+int slab_reduce(const float *slab, int rows, int row_len, const SlabSegs &segs, hipStream_t st);
+// a workspace of `need` bytes is present (else -1 with cm_last_error text naming `what`)
+int slab_check(const void *ws, size_t ws_bytes, size_t need, const char *what);
+}

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(TPB) void fwd_kernel(long R, int K, int O, const fl
 // ---------------------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------------------
-template <int MAXT, int ACT>
+template <int MAXT, int ACT, bool DET = false>
 __global__ __launch_bounds__(TPB, (MAXT == 8 ? 2 : 1)) void bwd_kernel(long R, int K, int O, const float *__restrict__ X, const float *__restrict__ W,
                                                  int layout, const float *__restrict__ DY, const float *__restrict__ DY2,
                                                  const float *__restrict__ Yv,
@@ -170,6 +170,12 @@ __global__ __launch_bounds__(TPB, (MAXT == 8 ? 2 : 1)) void bwd_kernel(long R, i
     const int P = layout == 0 ? O : K, Q = layout == 0 ? K : O;
     const int OT = (O + 15) >> 4, KT = (K + 15) >> 4;
     const int PT = layout == 0 ? OT : KT, QT = layout == 0 ? KT : OT, NT = PT * QT;
+    if constexpr (DET) {
+        // slab mode: DW / DB address row 0 of a slab of K O + O floats per workgroup
+        const size_t off = (size_t)blockIdx.x * ((size_t)K * O + O);
+        DW += off;
+        if (DB) DB += off;
+    }
     const int SZ = OT * 16 + 16, SXs = KT * 16 + 16;       // dz / x tile strides == 16 (mod 32): conflict-free column reads
     float *Zs = lds, *Xs = Zs + (size_t)ROWS * SZ;
     const float *As = layout == 0 ? Zs : Xs, *Bs = layout == 0 ? Xs : Zs;
@@ -269,11 +275,11 @@ __global__ __launch_bounds__(TPB, (MAXT == 8 ? 2 : 1)) void bwd_kernel(long R, i
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int pp = pt * 16 + 4 * g + r;
-                if (pp < P && q < Q) atomicAdd(DW + (size_t)pp * Q + q, acc[t][r]);
+                if (pp < P && q < Q) merge_add<DET>(DW + (size_t)pp * Q + q, acc[t][r]);
             }
         }
     }
-    if (DB && tid < O) atomicAdd(DB + tid, csum);
+    if (DB && tid < O) merge_add<DET>(DB + tid, csum);
 }
 
 }  // namespace lin
@@ -284,6 +290,11 @@ int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int 
                       const float *y, float *dx, float *dw, float *db, void *stream);   // cm_linear_bwd.hip: widths 32 / 64 / 128
 int encoder_bwd_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
                       float *dw2, float *db2, float *dw1, float *db1, void *stream);
+int linear_bwd_stream_det(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
+                          const float *y, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid);
+int encoder_bwd_chain_det(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
+                          float *slab, void *stream, int *grid);
+size_t lin2_slab_row(int d);                                                             // floats per workgroup of encoder_bwd_chain_det
 }
 using namespace cm;
 
@@ -303,31 +314,31 @@ extern "C" int cm_linear_act_forward(int64_t R, int32_t K, int32_t O, const floa
     return CM_OK;
 }
 
-extern "C" int cm_linear_act_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
-                                      const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
-                                      void *stream) {
-    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward: null argument");
-    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward: 1 <= in, out <= 128 required");
-    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward: w_layout must be 0 ([out,in]) or 1 ([in,out])");
-    if (R <= 0) return CM_OK;
-    if (const int rc = linear_bwd_stream(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream); rc != 1) return rc;
+// DET: dw / db address row 0 of a slab (K O + O floats per workgroup); *grid receives the number of rows written
+template <bool DET>
+static int linear_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout, const float *dy,
+                           const float *dy2, const float *y, float *dx, float *dw, float *db, void *stream, int *grid) {
+    if (const int rc = DET ? linear_bwd_stream_det(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream, grid)
+                           : linear_bwd_stream(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream); rc != 1) return rc;
     const int OT = (O + 15) / 16, KT = (K + 15) / 16, NT = OT * KT;
     const size_t lds = ((size_t)lin::ROWS * (OT * 16 + 16) + (size_t)lin::ROWS * (KT * 16 + 16)) * sizeof(float);
     const long chunks = (R + lin::ROWS - 1) / lin::ROWS;
     int blocks = (int)std::min<long>(chunks, 512);
     static const int force = [] { const char *e = getenv("COMMARL_LIN_BLOCKS"); return e ? atoi(e) : 0; }();
     if (force > 0) blocks = (int)std::min<long>(chunks, force);
+    if (DET) blocks = std::min(blocks, 512);               // the slab has min(chunks, 512) rows (cm_*_det_ws_bytes)
+    if (grid) *grid = blocks;
     const hipStream_t st = (hipStream_t)stream;
     const int per_wave = (NT + 3) / 4;
     static unsigned long long once = 0;
     if (cm::dev_first(once)) {
-#define CM_ATTR(M, A) CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&lin::bwd_kernel<M, A>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+#define CM_ATTR(M, A) CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&lin::bwd_kernel<M, A, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
         CM_ATTR(16, 0); CM_ATTR(8, 0); CM_ATTR(4, 0); CM_ATTR(2, 0); CM_ATTR(1, 0);
         CM_ATTR(16, 1); CM_ATTR(8, 1); CM_ATTR(4, 1); CM_ATTR(2, 1); CM_ATTR(1, 1);
 #undef CM_ATTR
     }
-#define CM_LB(M) do { if (y) hipLaunchKernelGGL((lin::bwd_kernel<M, 1>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); \
-                      else hipLaunchKernelGGL((lin::bwd_kernel<M, 0>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); } while (0)
+#define CM_LB(M) do { if (y) hipLaunchKernelGGL((lin::bwd_kernel<M, 1, DET>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); \
+                      else hipLaunchKernelGGL((lin::bwd_kernel<M, 0, DET>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); } while (0)
     if (per_wave <= 1) CM_LB(1); else if (per_wave <= 2) CM_LB(2); else if (per_wave <= 4) CM_LB(4);
     else if (per_wave <= 8) CM_LB(8); else CM_LB(16);
 #undef CM_LB
@@ -335,9 +346,69 @@ extern "C" int cm_linear_act_backward(int64_t R, int32_t K, int32_t O, const flo
     return CM_OK;
 }
 
+extern "C" int cm_linear_act_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                      const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
+                                      void *stream) {
+    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward: null argument");
+    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward: 1 <= in, out <= 128 required");
+    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward: w_layout must be 0 ([out,in]) or 1 ([in,out])");
+    if (R <= 0) return CM_OK;
+    return linear_backward<false>(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream, nullptr);
+}
+
+static size_t linear_slab_rows(int64_t R) { return (size_t)std::min<int64_t>((R + lin::ROWS - 1) / lin::ROWS, 512); }   // >= either kernel's grid
+
+extern "C" size_t cm_linear_act_backward_det_ws_bytes(int64_t R, int32_t K, int32_t O) {
+    if (R <= 0 || K < 1 || O < 1) return 0;
+    return linear_slab_rows(R) * ((size_t)K * O + O) * sizeof(float);
+}
+
+extern "C" int cm_linear_act_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                          const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
+                                          void *ws, size_t ws_bytes, void *stream) {
+    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: null argument");
+    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: 1 <= in, out <= 128 required");
+    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: w_layout must be 0 ([out,in]) or 1 ([in,out])");
+    if (const int rc = slab_check(ws, ws_bytes, cm_linear_act_backward_det_ws_bytes(R, K, O), "cm_linear_act_backward_det")) return rc;
+    if (R <= 0) return CM_OK;
+    float *slab = static_cast<float *>(ws);
+    const int row = K * O + O;
+    int grid = 0;
+    if (const int rc = linear_backward<true>(R, K, O, x, w, w_layout, dy, dy2, y, dx, slab, db ? slab + (size_t)K * O : nullptr, stream, &grid))
+        return rc;
+    SlabSegs segs{};
+    segs.s[0] = { dw, 0, K * O };
+    segs.s[1] = { db, K * O, O };
+    segs.n_seg = db ? 2 : 1;
+    return slab_reduce(slab, grid, row, segs, (hipStream_t)stream);
+}
+
 extern "C" int cm_encoder_backward(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
                                    const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *stream) {
     if (!obs || !a1 || !e || !w2 || !dy || !dw2 || !dw1) return set_error(CM_ERR_ARG, "cm_encoder_backward: null argument");
     if (R <= 0) return CM_OK;
     return encoder_bwd_chain(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream);
+}
+
+extern "C" size_t cm_encoder_backward_det_ws_bytes(int64_t R, int32_t d) {
+    if (R <= 0 || d < 1) return 0;
+    return linear_slab_rows(R) * lin2_slab_row(d) * sizeof(float);
+}
+
+extern "C" int cm_encoder_backward_det(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
+                                       const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *ws, size_t ws_bytes,
+                                       void *stream) {
+    if (!obs || !a1 || !e || !w2 || !dy || !dw2 || !dw1 || !db2 || !db1) return set_error(CM_ERR_ARG, "cm_encoder_backward_det: null argument");
+    if (const int rc = slab_check(ws, ws_bytes, cm_encoder_backward_det_ws_bytes(R, d), "cm_encoder_backward_det")) return rc;
+    if (R <= 0) return CM_OK;
+    float *slab = static_cast<float *>(ws);
+    int grid = 0;
+    if (const int rc = encoder_bwd_chain_det(R, d, obs, a1, e, w2, dy, dy2, slab, stream, &grid)) return rc;   // 1: shape not covered
+    SlabSegs segs{};
+    segs.s[0] = { dw2, 0, 128 * 64 };
+    segs.s[1] = { db2, 128 * 64, 64 };
+    segs.s[2] = { dw1, 128 * 64 + 64, 128 * d };
+    segs.s[3] = { db1, 128 * 64 + 64 + 128 * d, 128 };
+    segs.n_seg = 4;
+    return slab_reduce(slab, grid, (int)lin2_slab_row(d), segs, (hipStream_t)stream);
 }

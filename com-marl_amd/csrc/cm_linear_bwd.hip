@@ -61,6 +61,10 @@ __device__ __forceinline__ void issue_tile(unsigned lds_addr, const float *__res
     }
 }
 
+// floats per workgroup in slab mode: dW [O][K] (K = the ragged width KR for the first layer), db [O], and for the chained
+// encoder form dW1 [128][KO], db1 [128]
+__host__ __device__ constexpr size_t slab_row(int K, int O, int KO) { return (size_t)K * O + O + (KO > 0 ? (size_t)128 * KO + 128 : 0); }
+
 // First-layer form: the source rows are KR < W floats wide (the observation: 21 / 29 / 53 / 77) and only 4-byte aligned.
 // One dword per lane (256 bytes per wave-instruction); tile columns >= KR are fetched from a zero word.
 __device__ float zero_word[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
@@ -119,7 +123,7 @@ __device__ __forceinline__ void load_cols(const float *tile, int r, int c, int u
 // leaves the workgroup: multiplied by tanh'(x) it overwrites the x tile IN PLACE (every position is produced by exactly one
 // lane) and feeds the FIRST layer's weight / bias gradient against a WO-wide observation tile (rows KO <= WO floats wide):
 // DW1 [K][KO], DB1 [K]; DX is not written.
-template <int KT, int OT, int ACT, int LAYOUT, bool RAG = false, int WO = 0>
+template <int KT, int OT, int ACT, int LAYOUT, bool RAG = false, int WO = 0, bool DET = false>
 __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *__restrict__ X, const float *__restrict__ W,
                                                   const float *__restrict__ DY, const float *__restrict__ DY2,
                                                   const float *__restrict__ Yv,
@@ -132,6 +136,14 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
     constexpr int WA = LAYOUT == 0 ? O : K, WB = LAYOUT == 0 ? K : O;   // dW is [WA][WB]
     constexpr int NA = WA / 16, NBH = WB / 32;                          // A tiles; B tiles of this wave's half
     constexpr int NKT = KT / 2;                                         // dx column tiles per wave
+    if constexpr (DET) {
+        // slab mode: the gradient pointers address row 0 of the slab (lin2::slab_row floats per workgroup)
+        const size_t off = (size_t)blockIdx.x * slab_row(RAG ? KR : K, O, WO > 0 ? KO : 0);
+        DW += off;
+        if (DB) DB += off;
+        if (DW1) DW1 += off;
+        if (DB1) DB1 += off;
+    }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *Ys = lds + 2 * BUF;                            // y tile (ACT) and, behind it, the second gradient's tile (DY2)
     float *D2s = Ys + (ACT ? ZF : 0);
@@ -356,25 +368,25 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int q = 16 * j + c;
-                if (q < KO) atomicAdd(DW1 + (size_t)(16 * wave + 4 * g + r) * KO + q, acc2[j][r]);
+                if (q < KO) merge_add<DET>(DW1 + (size_t)(16 * wave + 4 * g + r) * KO + q, acc2[j][r]);
             }
         if (DB1) {
             float v = dbsum1;
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (g == 0) atomicAdd(DB1 + 16 * wave + c, v);
+            if (g == 0) merge_add<DET>(DB1 + 16 * wave + c, v);
         }
         // this layer: C[p = z column 4 (4 g + r) + ua][q = x column 64 ubh + 4 c + j]
         const int ua = wave >> 1, ubh = wave & 1;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(DW + (size_t)(4 * (4 * g + r) + ua) * K + 64 * ubh + 4 * c + j, acc1[j][r]);
+            for (int r = 0; r < 4; ++r) merge_add<DET>(DW + (size_t)(4 * (4 * g + r) + ua) * K + 64 * ubh + 4 * c + j, acc1[j][r]);
         if (DB && ubh == 0) {
             float v = zs1;
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (g == 0) atomicAdd(DB + 4 * c + ua, v);
+            if (g == 0) merge_add<DET>(DB + 4 * c + ua, v);
         }
         return;
     }
@@ -384,13 +396,13 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int q = col_of<K>(j, c);
-                if (q < KR) atomicAdd(DW + (size_t)col_of<O>(wave, 4 * g + r) * KR + q, accT[j][r]);
+                if (q < KR) merge_add<DET>(DW + (size_t)col_of<O>(wave, 4 * g + r) * KR + q, accT[j][r]);
             }
         if (DB) {
             float v = zs1;
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (g == 0) atomicAdd(DB + col_of<O>(wave, c), v);
+            if (g == 0) merge_add<DET>(DB + col_of<O>(wave, c), v);
         }
         return;
     }
@@ -423,7 +435,7 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
             const float sv[4] = { s.x, s.y, s.z, s.w };
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (!RAG || cbq < KR) atomicAdd(DW + (size_t)col_of<WA>(ua, 4 * lg + r) * (RAG ? KR : WB) + cbq, sv[r]);
+                if (!RAG || cbq < KR) merge_add<DET>(DW + (size_t)col_of<WA>(ua, 4 * lg + r) * (RAG ? KR : WB) + cbq, sv[r]);
         }
     }
     if (DB) {
@@ -453,20 +465,20 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
 #pragma unroll
                 for (int q = 0; q < 4; ++q) s += lds[(2 * q + h) * O + tid];
             }
-            atomicAdd(DB + tid, s);
+            merge_add<DET>(DB + tid, s);
         }
     }
 }
 
-template <int KT, int OT, int ACT, int LAYOUT, bool RAG = false, int WO = 0>
+template <int KT, int OT, int ACT, int LAYOUT, bool RAG = false, int WO = 0, bool DET = false>
 static int launch(long R, int KR, const float *x, const float *w, const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
-                  hipStream_t st, const float *obs = nullptr, int KO = 0, float *dw1 = nullptr, float *db1 = nullptr) {
+                  hipStream_t st, const float *obs = nullptr, int KO = 0, float *dw1 = nullptr, float *db1 = nullptr, int *grid = nullptr) {
     constexpr int K = 16 * KT, O = 16 * OT;
     const size_t lds = ((size_t)2 * ROWS * (K + O + WO) + (ACT ? (size_t)ROWS * O : 0) + (dy2 ? (size_t)ROWS * O : 0)) * sizeof(float);
     if (lds > 160 * 1024) return 1;
     static unsigned long long attr = 0;
     if (cm::dev_first(attr)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bwd_kernel<KT, OT, ACT, LAYOUT, RAG, WO>),
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&bwd_kernel<KT, OT, ACT, LAYOUT, RAG, WO, DET>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     const int n_cu = cm::cu_count();
@@ -478,7 +490,9 @@ static int launch(long R, int KR, const float *x, const float *w, const float *d
     int blocks = (int)std::min<long>(std::min<long>(chunks, n_cu), std::max<long>(1, std::lround(std::sqrt(29.0 * (double)chunks))));
     static const int force = [] { const char *e = getenv("COMMARL_LIN2_BLOCKS"); return e ? atoi(e) : 0; }();
     if (force > 0) blocks = (int)std::min<long>(chunks, force);
-    hipLaunchKernelGGL((bwd_kernel<KT, OT, ACT, LAYOUT, RAG, WO>), dim3(blocks), dim3(TPB), std::max<size_t>(lds, 33 * 1024), st, R, KR, x, w, dy, dy2, y, dx, dw,
+    if (DET) blocks = std::min(blocks, 512);               // the slab has min(chunks, 512) rows (cm_*_det_ws_bytes)
+    if (grid) *grid = blocks;
+    hipLaunchKernelGGL((bwd_kernel<KT, OT, ACT, LAYOUT, RAG, WO, DET>), dim3(blocks), dim3(TPB), std::max<size_t>(lds, 33 * 1024), st, R, KR, x, w, dy, dy2, y, dx, dw,
                        db, obs, KO, dw1, db1);
     CM_HIP(hipGetLastError());
     return CM_OK;
@@ -487,15 +501,18 @@ static int launch(long R, int KR, const float *x, const float *w, const float *d
 }  // namespace lin2
 
 // Returns 1 when this shape / alignment is not covered (the caller runs lin::bwd_kernel), else the launch status.
-int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                      const float *y, float *dx, float *dw, float *db, void *stream) {
+// DET: dw / db address row 0 of a slab (lin2::slab_row floats per workgroup), *grid receives the number of rows written.
+template <bool DET>
+static int bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
+                      const float *y, float *dx, float *dw, float *db, void *stream, int *grid) {
     static const bool off = [] { const char *e = getenv("COMMARL_LIN_BWD"); return e && e[0] == 'o'; }();   // "old"
     if (off) return 1;
     const auto ok_w = [](int v) { return v == 32 || v == 64 || v == 128; };
     const hipStream_t st = (hipStream_t)stream;
     if (!ok_w(K) && ok_w(O) && K <= 128 && !dx && layout == 0 && !(((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)y) & 15) && !((uintptr_t)x & 3)) {
         // first layer (observation -> hidden): ragged input rows, no input gradient
-#define CM_RG(KT_, OT_) (y ? lin2::launch<KT_, OT_, 1, 0, true>(R, K, x, w, dy, dy2, y, dx, dw, db, st) : lin2::launch<KT_, OT_, 0, 0, true>(R, K, x, w, dy, dy2, y, dx, dw, db, st))
+#define CM_RG(KT_, OT_) (y ? lin2::launch<KT_, OT_, 1, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
+                         : lin2::launch<KT_, OT_, 0, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid))
         const int kt = K <= 32 ? 2 : (K <= 64 ? 4 : 8);
         switch (kt * 1000 + O) {
         case 2032: return CM_RG(2, 2);
@@ -515,7 +532,8 @@ int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int 
     const uintptr_t al = (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)y | (uintptr_t)dx;
     if (al & 15) return 1;
     if (layout == 1 && !(K == 64 && O == 64)) return 1;   // the [in][out] weights are the 64 x 64 graph-convolution ones
-#define CM_B2(KT_, OT_, L_) (y ? lin2::launch<KT_, OT_, 1, L_>(R, K, x, w, dy, dy2, y, dx, dw, db, st) : lin2::launch<KT_, OT_, 0, L_>(R, K, x, w, dy, dy2, y, dx, dw, db, st))
+#define CM_B2(KT_, OT_, L_) (y ? lin2::launch<KT_, OT_, 1, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
+                             : lin2::launch<KT_, OT_, 0, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid))
     if (layout == 1) return CM_B2(4, 4, 1);
     switch (K * 1000 + O) {
     case 32032: return CM_B2(2, 2, 0);
@@ -531,18 +549,41 @@ int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int 
 #undef CM_B2
 }
 
+int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
+                      const float *y, float *dx, float *dw, float *db, void *stream) {
+    return bwd_stream<false>(R, K, O, x, w, layout, dy, dy2, y, dx, dw, db, stream, nullptr);
+}
+int linear_bwd_stream_det(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
+                          const float *y, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid) {
+    return bwd_stream<true>(R, K, O, x, w, layout, dy, dy2, y, dx, slab_dw, slab_db, stream, grid);
+}
+
 // Encoder backward in one pass (obs [R,d] -> a1 = tanh(.) [R,128] -> e = tanh(.) [R,64]): layer 2 as linear_bwd_stream
 // with dz = (dy + dy2) * (1 - e^2), its input gradient chained in LDS into layer 1's weight / bias gradient.
 // Returns 1 when the shape is not covered (d > 64, unaligned tensors): the caller runs the two layers one by one.
-int encoder_bwd_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
-                      float *dw2, float *db2, float *dw1, float *db1, void *stream) {
+template <bool DET>
+static int encoder_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
+                         float *dw2, float *db2, float *dw1, float *db1, void *stream, int *grid) {
     static const bool off = [] { const char *v = getenv("COMMARL_ENC_CHAIN"); return v && v[0] == '0'; }();
     if (off || d < 1 || d > 64) return 1;
     if (((uintptr_t)a1 | (uintptr_t)e | (uintptr_t)dy | (uintptr_t)dy2) & 15) return 1;
     if ((uintptr_t)obs & 3) return 1;
     const hipStream_t st = (hipStream_t)stream;
-    if (d <= 32) return lin2::launch<8, 4, 1, 0, false, 32>(R, 128, a1, w2, dy, dy2, e, nullptr, dw2, db2, st, obs, d, dw1, db1);
-    return lin2::launch<8, 4, 1, 0, false, 64>(R, 128, a1, w2, dy, dy2, e, nullptr, dw2, db2, st, obs, d, dw1, db1);
+    if (d <= 32) return lin2::launch<8, 4, 1, 0, false, 32, DET>(R, 128, a1, w2, dy, dy2, e, nullptr, dw2, db2, st, obs, d, dw1, db1, grid);
+    return lin2::launch<8, 4, 1, 0, false, 64, DET>(R, 128, a1, w2, dy, dy2, e, nullptr, dw2, db2, st, obs, d, dw1, db1, grid);
+}
+
+int encoder_bwd_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
+                      float *dw2, float *db2, float *dw1, float *db1, void *stream) {
+    return encoder_chain<false>(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream, nullptr);
+}
+size_t lin2_slab_row(int d) { return lin2::slab_row(128, 64, d); }
+
+// slab mode: one slab row (lin2::slab_row(128, 64, d) floats) per workgroup, laid out dW2 | db2 | dW1 | db1
+int encoder_bwd_chain_det(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
+                          float *slab, void *stream, int *grid) {
+    float *dw2 = slab, *db2 = dw2 + 128 * 64, *dw1 = db2 + 64, *db1 = dw1 + (size_t)128 * d;
+    return encoder_chain<true>(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream, grid);
 }
 
 }  // namespace cm

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(TPB) void agg_fwd_kernel(int S, int N, int EPB, con
     }
 }
 
-template <int E>
+template <int E, bool DET = false>
 __global__ __launch_bounds__(TPB) void agg_bwd_kernel(int S, int N, int EPB, const float *__restrict__ attn,
                                                      const float *__restrict__ adj, const float *__restrict__ chan,
                                                      long ch_stride, const float *__restrict__ hw,
@@ -170,7 +170,8 @@ __global__ __launch_bounds__(TPB) void agg_bwd_kernel(int S, int N, int EPB, con
         if (rg == 0) {
             float v = 0.0f;
             for (int q = 0; q < TPB / E; ++q) v += dbs[q * E + o];
-            atomicAdd(d_bias + o, v);
+            if constexpr (DET) d_bias[(size_t)blockIdx.x * E + o] = v;     // slab mode: row blockIdx.x
+            else atomicAdd(d_bias + o, v);
         }
     }
 }
@@ -345,6 +346,7 @@ __global__ __launch_bounds__(256) void attn_bwd4_kernel(int S, const float *__re
     }
 }
 
+template <bool DET = false>
 __global__ __launch_bounds__(256) void agg_bwd4_kernel(int S, const float *__restrict__ attn, const float *__restrict__ adj,
                                                        const float *__restrict__ chan, long ch_stride, const float *__restrict__ hw,
                                                        const float *__restrict__ outv, const float *__restrict__ out_minus,
@@ -441,14 +443,15 @@ __global__ __launch_bounds__(256) void agg_bwd4_kernel(int S, const float *__res
     if (d_bias) {
         // 64 atomics per workgroup on the same two cache lines: with 2048 workgroups they serialise in the L2 (0.8 ns each: 105 of the
         // kernel's 312 us at 275 k envs) - the caller may hand `bias_reps` copies of the row, workgroup b adds into copy b % reps
+        // (slab mode: bias_reps is the grid size, every workgroup stores into its own row)
         float *dbp = d_bias + (size_t)(blockIdx.x % (unsigned)bias_reps) * 64;
         dbs[tid] = db;
         __syncthreads();
         if (tid < 16) {
             float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
             for (int g2 = 0; g2 < 16; ++g2) { const float4 u = dbs[g2 * 16 + tid]; sum.x += u.x; sum.y += u.y; sum.z += u.z; sum.w += u.w; }
-            atomicAdd(dbp + 4 * tid + 0, sum.x); atomicAdd(dbp + 4 * tid + 1, sum.y);
-            atomicAdd(dbp + 4 * tid + 2, sum.z); atomicAdd(dbp + 4 * tid + 3, sum.w);
+            merge_add<DET>(dbp + 4 * tid + 0, sum.x); merge_add<DET>(dbp + 4 * tid + 1, sum.y);
+            merge_add<DET>(dbp + 4 * tid + 2, sum.z); merge_add<DET>(dbp + 4 * tid + 3, sum.w);
         }
     }
 }
@@ -478,13 +481,18 @@ __device__ __forceinline__ void stage_rows(float *dst, int stride, const float *
     }
 }
 
-template <int MAXT>   // accumulator tiles per wave
+template <int MAXT, bool DET = false>   // accumulator tiles per wave; DET: slab mode (C, colsum_a address row 0, P Q + P floats per workgroup)
 __global__ __launch_bounds__(TPB) void wgrad_kernel(long R, int P, int Q, const float *__restrict__ A, const float *__restrict__ B,
                                                    float *__restrict__ C, float *__restrict__ colsum_a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int PT = (P + 15) >> 4, QT = (Q + 15) >> 4, NT = PT * QT;
     const int SP = PT * 16 + 16, SQ = QT * 16 + 16;          // row strides == 16 (mod 32): conflict-free operand reads
+    if constexpr (DET) {
+        const size_t off = (size_t)blockIdx.x * ((size_t)P * Q + P);
+        C += off;
+        if (colsum_a) colsum_a += off;
+    }
     float *As = lds, *Bs = As + (size_t)WG_ROWS * SP;
     v4f acc[MAXT];
     int aoff[MAXT], boff[MAXT];       // per-tile operand offsets, hoisted out of the k loop (no division per MFMA)
@@ -529,11 +537,11 @@ __global__ __launch_bounds__(TPB) void wgrad_kernel(long R, int P, int Q, const 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int pp = pt * 16 + 4 * g + r;
-                if (pp < P && q < Q) atomicAdd(C + (size_t)pp * Q + q, acc[t][r]);
+                if (pp < P && q < Q) merge_add<DET>(C + (size_t)pp * Q + q, acc[t][r]);
             }
         }
     }
-    if (colsum_a && tid < P) atomicAdd(colsum_a + tid, csum);
+    if (colsum_a && tid < P) merge_add<DET>(colsum_a + tid, csum);
 }
 
 __global__ void returns_kernel(int P, int T, const double *__restrict__ rewards, const int32_t *__restrict__ lens,
@@ -648,6 +656,7 @@ __global__ __launch_bounds__(256) void multi_adam_kernel(TensorTable t, float *n
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int PPO_MAX_A = 8;
 
+template <bool DET = false>   // slab mode: `total` is a slab of one f64 per workgroup
 __global__ __launch_bounds__(256) void ppo_surrogate_kernel(int P, int T, int N, int A, const float *__restrict__ logits,
                                                             const int32_t *__restrict__ actions, const float *__restrict__ old_ll,
                                                             const float *__restrict__ adv, const int32_t *__restrict__ lens,
@@ -759,7 +768,8 @@ __global__ __launch_bounds__(256) void ppo_surrogate_kernel(int P, int T, int N,
     if ((threadIdx.x & 63) == 0) { sh_t[threadIdx.x >> 6] = part; sh_c[threadIdx.x >> 6] = valid_here; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(total, sh_t[0] + sh_t[1] + sh_t[2] + sh_t[3]);
+        if constexpr (DET) total[blockIdx.x] = sh_t[0] + sh_t[1] + sh_t[2] + sh_t[3];
+        else atomicAdd(total, sh_t[0] + sh_t[1] + sh_t[2] + sh_t[3]);
         atomicAdd((unsigned long long *)count, (unsigned long long)(sh_c[0] + sh_c[1] + sh_c[2] + sh_c[3]));
     }
 }
@@ -831,6 +841,8 @@ int agg_bwd_mfma(int S, int N, const float *attn, const float *adj, const float 
                  const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream);
 int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,
                   float *d_q, float *d_e, void *stream);
+int agg_bwd_mfma_det(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
+                     const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *slab_bias, void *stream, int *grid);
 
 // COMMARL_QUAD_BWD=0: teams of 4 take the generic aggregation / attention backward kernels (A/B and test hook)
 static bool quad_bwd_on() {
@@ -937,6 +949,7 @@ __device__ __forceinline__ float gauss_sigma(const float *log_std, float min_log
     return expf(ls);
 }
 
+template <bool DET = false>   // slab mode: `ws` is a slab of one f64 per workgroup, gauss_nll_finish_kernel ends the launch
 __global__ __launch_bounds__(256) void gauss_nll_fwd_kernel(long S, int N, const float *__restrict__ per_agent, const float *__restrict__ returns,
                                                             const float *__restrict__ log_std, float min_log_std, int has_min,
                                                             float *__restrict__ out, GaussWs *__restrict__ ws) {
@@ -952,6 +965,10 @@ __global__ __launch_bounds__(256) void gauss_nll_fwd_kernel(long S, int N, const
     red[threadIdx.x] = part;
     __syncthreads();
     for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
+    if constexpr (DET) {
+        if (threadIdx.x == 0) reinterpret_cast<double *>(ws)[blockIdx.x] = red[0];
+        return;
+    }
     if (threadIdx.x == 0) {
         atomicAdd(&ws->sum, red[0]);
         __threadfence();
@@ -968,6 +985,35 @@ __global__ __launch_bounds__(256) void gauss_nll_fwd_kernel(long S, int N, const
         out[1] = msq;
         ws->sum = 0.0;
         ws->done = 0u;
+    }
+}
+
+// sum of n f64 partials in a fixed order: thread t adds slab[t], slab[t + 256], ... in turn, then a fixed tree over the threads.
+// One 256-thread workgroup.
+__device__ double fixed_order_sum(const double *__restrict__ slab, int n) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < n; b += 256) s += slab[b];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
+    return red[0];
+}
+
+__global__ __launch_bounds__(256) void slab_total_kernel(const double *__restrict__ slab, int n, double *__restrict__ total) {
+    const double t = fixed_order_sum(slab, n);
+    if (threadIdx.x == 0) *total = t;
+}
+
+__global__ __launch_bounds__(256) void gauss_nll_finish_kernel(long S, const double *__restrict__ slab, int n, const float *__restrict__ log_std,
+                                                               float min_log_std, int has_min, float *__restrict__ out) {
+    const double total = fixed_order_sum(slab, n);
+    if (threadIdx.x == 0) {                                        // gauss_nll_fwd_kernel's last-block arithmetic
+        const float msq = (float)(total / (double)S);
+        const float sigma = gauss_sigma(log_std, min_log_std, has_min);
+        const float var = sigma * sigma, log_scale = logf(sigma);
+        out[0] = msq / (2.0f * var) + log_scale + 0.918938533204672742f;
+        out[1] = msq;
     }
 }
 
@@ -1031,7 +1077,7 @@ extern "C" int cm_masked_agg_backward_r(int32_t S, int32_t N, int32_t E, const f
         int blocks = (int)(chunks <= 512 ? std::min<long>(chunks, 64) : std::min<long>(chunks, 2048));
         static const int force = [] { const char *e = getenv("COMMARL_AGG4_BLOCKS"); return e ? atoi(e) : 0; }();
         if (force > 0) blocks = std::min(blocks, force);
-        hipLaunchKernelGGL(agg_bwd4_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
+        hipLaunchKernelGGL(agg_bwd4_kernel<>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
                            out_minus, d_out, d_attn, d_hw, d_bias, (int)bias_replicas);
         CM_HIP(hipGetLastError());
         return CM_OK;
@@ -1074,6 +1120,88 @@ extern "C" int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, 
 #undef CM_WG
     CM_HIP(hipGetLastError());
     return CM_OK;
+}
+
+// ---- deterministic twins (slab mode, include/commarl.h "Deterministic update mode") ----
+extern "C" size_t cm_masked_agg_backward_det_ws_bytes(int32_t S, int32_t N, int32_t E) {
+    if (S <= 0 || N < 1 || E < 1) return 0;
+    return (size_t)std::min<int32_t>(S, 2048) * E * sizeof(float);        // every backward kernel's grid is <= min(S, 2048)
+}
+
+extern "C" int cm_masked_agg_backward_det(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                                          const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
+                                          const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *ws, size_t ws_bytes,
+                                          void *stream) {
+    if (!attn || !hw || !out || !d_out || !d_attn || !d_hw) return set_error(CM_ERR_ARG, "cm_masked_agg_backward_det: null argument");
+    if (E != 64) return set_error(CM_ERR_ARG, "cm_masked_agg_backward_det: embedding dim 64 only");
+    if (const int rc = slab_check(ws, ws_bytes, cm_masked_agg_backward_det_ws_bytes(S, N, E), "cm_masked_agg_backward_det")) return rc;
+    if (S <= 0) return CM_OK;
+    if (!d_bias)   // no cross-workgroup sum left: the default kernels
+        return cm_masked_agg_backward_r(S, N, E, attn, dist_adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, nullptr, 1, stream);
+    const hipStream_t st = (hipStream_t)stream;
+    float *slab = static_cast<float *>(ws);
+    int grid = 0;
+    if (N == 4 && quad_bwd_on() && !(((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw) & 15)) {
+        const long chunks = ((long)S + 15) / 16;
+        grid = (int)(chunks <= 512 ? std::min<long>(chunks, 64) : std::min<long>(chunks, 2048));
+        hipLaunchKernelGGL(agg_bwd4_kernel<true>, dim3(grid), dim3(256), 0, st, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
+                           out_minus, d_out, d_attn, d_hw, slab, grid);
+        CM_HIP(hipGetLastError());
+    } else if (const int rc = agg_bwd_mfma_det(S, N, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, slab, stream, &grid);
+               rc != 1) {
+        if (rc) return rc;
+    } else {
+        const size_t lds = agg_lds_bwd(N, E);
+        if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "cm_masked_agg_backward_det: n_agents too large");
+        static unsigned long long once = 0;
+        if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
+        const int epb = agg_epb(N);
+        grid = (int)std::min<long>((S + epb - 1) / epb, 256 * 4);
+        hipLaunchKernelGGL((agg_bwd_kernel<64, true>), dim3(grid), dim3(TPB), lds, st, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus,
+                           d_out, d_attn, d_hw, slab);
+        CM_HIP(hipGetLastError());
+    }
+    SlabSegs segs{};
+    segs.s[0] = { d_bias, 0, 64 };
+    segs.n_seg = 1;
+    return slab_reduce(slab, grid, 64, segs, st);
+}
+
+extern "C" size_t cm_linear_wgrad_det_ws_bytes(int64_t R, int32_t P, int32_t Q) {
+    if (R <= 0 || P < 1 || Q < 1) return 0;
+    return (size_t)std::min<int64_t>((R + WG_ROWS - 1) / WG_ROWS, 512) * ((size_t)P * Q + P) * sizeof(float);
+}
+
+extern "C" int cm_linear_wgrad_det(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a, void *ws,
+                                   size_t ws_bytes, void *stream) {
+    if (!a || !b || !c) return set_error(CM_ERR_ARG, "cm_linear_wgrad_det: null argument");
+    if (P < 1 || Q < 1 || P > 128 || Q > 128) return set_error(CM_ERR_ARG, "cm_linear_wgrad_det: 1 <= P, Q <= 128 required");
+    if (const int rc = slab_check(ws, ws_bytes, cm_linear_wgrad_det_ws_bytes(R, P, Q), "cm_linear_wgrad_det")) return rc;
+    if (R <= 0) return CM_OK;
+    const int PT = (P + 15) / 16, QT = (Q + 15) / 16, NT = PT * QT;
+    const size_t lds = ((size_t)WG_ROWS * (PT * 16 + 16) + (size_t)WG_ROWS * (QT * 16 + 16)) * sizeof(float);
+    const int blocks = (int)std::min<long>((R + WG_ROWS - 1) / WG_ROWS, 512);
+    const hipStream_t st = (hipStream_t)stream;
+    const int per_wave = (NT + 3) / 4;
+    static unsigned long long once = 0;
+    if (cm::dev_first(once)) {
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
+    float *slab = static_cast<float *>(ws);
+#define CM_WG(M) hipLaunchKernelGGL((wgrad_kernel<M, true>), dim3(blocks), dim3(TPB), lds, st, (long)R, P, Q, a, b, slab, colsum_a ? slab + (size_t)P * Q : nullptr)
+    if (per_wave <= 1) CM_WG(1); else if (per_wave <= 2) CM_WG(2); else if (per_wave <= 4) CM_WG(4);
+    else if (per_wave <= 8) CM_WG(8); else CM_WG(16);
+#undef CM_WG
+    CM_HIP(hipGetLastError());
+    SlabSegs segs{};
+    segs.s[0] = { c, 0, P * Q };
+    segs.s[1] = { colsum_a, P * Q, P };
+    segs.n_seg = colsum_a ? 2 : 1;
+    return slab_reduce(slab, blocks, P * Q + P, segs, st);
 }
 
 static size_t attn_lds(int N, int E) { const int epb = agg_epb(N), rows = epb * N; return ((size_t)rows * (E + 4) * 2 + (size_t)rows * (N | 1)) * 4; }
@@ -1146,7 +1274,7 @@ extern "C" int cm_ppo_surrogate(int32_t P, int32_t T, int32_t N, int32_t A, cons
     if (P <= 0 || T <= 0) return CM_OK;
     if (!logits || !actions || !old_ll || !adv || !lens) return set_error(CM_ERR_ARG, "cm_ppo_surrogate: null argument");
     const long S = (long)P * T;
-    hipLaunchKernelGGL(ppo_surrogate_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, T, N, A, logits, actions,
+    hipLaunchKernelGGL(ppo_surrogate_kernel<>, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, T, N, A, logits, actions,
                        old_ll, adv, lens, clip, ent_coeff, add_entropy, total, (long long *)count, dlogits);
     CM_HIP(hipGetLastError());
     return CM_OK;
@@ -1170,7 +1298,7 @@ extern "C" int cm_gauss_nll_forward(int64_t S, int32_t N, const float *per_agent
     if (!per_agent || !returns || !log_std || !out || !ws) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward: null argument");
     if (S < 1 || N < 1) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward: S >= 1 and n_agents >= 1 required");
     const int blocks = (int)std::min<long>((S + 255) / 256, 256);
-    hipLaunchKernelGGL(gauss_nll_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
+    hipLaunchKernelGGL(gauss_nll_fwd_kernel<>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
                        has_min, out, reinterpret_cast<GaussWs *>(ws));
     CM_HIP(hipGetLastError());
     return CM_OK;
@@ -1183,6 +1311,53 @@ extern "C" int cm_gauss_nll_backward(int64_t S, int32_t N, const float *per_agen
     const int blocks = (int)std::min<long>((S + 255) / 256, 1024);
     hipLaunchKernelGGL(gauss_nll_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
                        has_min, out, g, d_per_agent, d_log_std);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+extern "C" size_t cm_ppo_surrogate_det_ws_bytes(int32_t P, int32_t T) {
+    if (P <= 0 || T <= 0) return 0;
+    return (size_t)(((long)P * T + 255) / 256) * sizeof(double);
+}
+
+extern "C" int cm_ppo_surrogate_det(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
+                                    const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff,
+                                    int32_t add_entropy, double *total, int64_t *count, float *dlogits, void *ws, size_t ws_bytes,
+                                    void *stream) {
+    if (!total || !count) return set_error(CM_ERR_ARG, "cm_ppo_surrogate_det: null argument");
+    if (A < 1 || A > PPO_MAX_A || N < 1) return set_error(CM_ERR_ARG, "cm_ppo_surrogate_det: 1 <= n_actions <= 8 and n_agents >= 1 required");
+    if (P > 0 && T > 0 && (!logits || !actions || !old_ll || !adv || !lens)) return set_error(CM_ERR_ARG, "cm_ppo_surrogate_det: null argument");
+    if (const int rc = slab_check(ws, ws_bytes, cm_ppo_surrogate_det_ws_bytes(P, T), "cm_ppo_surrogate_det")) return rc;
+    CM_HIP(hipMemsetAsync(total, 0, sizeof(double), (hipStream_t)stream));
+    CM_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), (hipStream_t)stream));    // (an integer sum: the default atomics are exact)
+    if (P <= 0 || T <= 0) return CM_OK;
+    const long S = (long)P * T;
+    const int blocks = (int)((S + 255) / 256);
+    double *slab = static_cast<double *>(ws);
+    hipLaunchKernelGGL(ppo_surrogate_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, T, N, A, logits, actions,
+                       old_ll, adv, lens, clip, ent_coeff, add_entropy, slab, (long long *)count, dlogits);
+    CM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(slab_total_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slab, blocks, total);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+extern "C" size_t cm_gauss_nll_forward_det_ws_bytes(int64_t S) {
+    if (S < 1) return 0;
+    return (size_t)std::min<long>((S + 255) / 256, 256) * sizeof(double);
+}
+
+extern "C" int cm_gauss_nll_forward_det(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std,
+                                        float min_log_std, int32_t has_min, float *out, void *ws, size_t ws_bytes, void *stream) {
+    if (!per_agent || !returns || !log_std || !out) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward_det: null argument");
+    if (S < 1 || N < 1) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward_det: S >= 1 and n_agents >= 1 required");
+    if (const int rc = slab_check(ws, ws_bytes, cm_gauss_nll_forward_det_ws_bytes(S), "cm_gauss_nll_forward_det")) return rc;
+    const int blocks = (int)std::min<long>((S + 255) / 256, 256);
+    hipLaunchKernelGGL(gauss_nll_fwd_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
+                       has_min, out, reinterpret_cast<GaussWs *>(ws));
+    CM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(gauss_nll_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long)S, static_cast<const double *>(ws), blocks, log_std,
+                       min_log_std, has_min, out);
     CM_HIP(hipGetLastError());
     return CM_OK;
 }

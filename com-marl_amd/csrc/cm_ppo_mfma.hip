@@ -37,7 +37,7 @@ __device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin
 // ---------------------------------------------------------------------------------------------------------------
 // masked aggregation backward.  MAXNT = row tiles the accumulator arrays are sized for (N <= 16 MAXNT).
 // ---------------------------------------------------------------------------------------------------------------
-template <int MAXNT>
+template <int MAXNT, bool DET = false>   // DET: slab mode, d_bias row blockIdx.x
 __global__ __launch_bounds__(TPB) void agg_bwd_kernel(int S, int N, const float *__restrict__ attn, const float *__restrict__ adj,
                                                      const float *__restrict__ chan, long ch_stride, const float *__restrict__ hw,
                                                      const float *__restrict__ outv, const float *__restrict__ out_minus,
@@ -217,7 +217,8 @@ __global__ __launch_bounds__(TPB) void agg_bwd_kernel(int S, int N, const float 
         if (rg == 0) {
             float v = 0.0f;
             for (int q = 0; q < TPB / 64; ++q) v += dbs[q * 64 + o];
-            atomicAdd(d_bias + o, v);
+            if constexpr (DET) d_bias[(size_t)blockIdx.x * 64 + o] = v;
+            else atomicAdd(d_bias + o, v);
         }
     }
 }
@@ -338,14 +339,15 @@ static int blocks_for(int S, size_t lds) {
     return (int)std::min<long>(S, 256L * per_cu);
 }
 
-template <int MAXNT>
+template <int MAXNT, bool DET>
 static int launch_agg(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
-                      const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, hipStream_t st) {
+                      const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, hipStream_t st, int *grid) {
     const size_t lds = agg_lds(N);
     static unsigned long long once = 0;
-    if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<MAXNT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
+    if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<MAXNT, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
     static const int stop = [] { const char *e = getenv("COMMARL_NXN_STOP"); return e ? atoi(e) : 0; }();
-    hipLaunchKernelGGL(agg_bwd_kernel<MAXNT>, dim3(blocks_for(S, lds)), dim3(TPB), lds, st, S, N, attn, adj, chan, ch_stride, hw, out, out_minus,
+    if (grid) *grid = blocks_for(S, lds);
+    hipLaunchKernelGGL((agg_bwd_kernel<MAXNT, DET>), dim3(blocks_for(S, lds)), dim3(TPB), lds, st, S, N, attn, adj, chan, ch_stride, hw, out, out_minus,
                        d_out, d_attn, d_hw, d_bias, stop);
     CM_HIP(hipGetLastError());
     return CM_OK;
@@ -370,16 +372,27 @@ static bool mfma_bwd_on() {
 }
 
 // Return 1 when the shape is not covered (N < 8, N > 128, unaligned rows): the caller runs the first-generation kernel.
-int agg_bwd_mfma(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
-                 const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream) {
+// DET: slab mode - d_bias is a slab of 64 floats per workgroup, *grid receives the number of rows written.
+template <bool DET>
+static int agg_bwd_m(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
+                     const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream, int *grid) {
     if (!mfma_bwd_on() || N < 8 || N > 128) return 1;
     if (((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw | (uintptr_t)adj | (uintptr_t)d_attn) & 15) return 1;
     if (pm::agg_lds(N) > 160 * 1024) return 1;
     const hipStream_t st = (hipStream_t)stream;
     const int NT = pm::np_of(N) / 16;
-    if (NT <= 2) return pm::launch_agg<2>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st);
-    if (NT <= 5) return pm::launch_agg<5>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st);
-    return pm::launch_agg<8>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st);
+    if (NT <= 2) return pm::launch_agg<2, DET>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st, grid);
+    if (NT <= 5) return pm::launch_agg<5, DET>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st, grid);
+    return pm::launch_agg<8, DET>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st, grid);
+}
+
+int agg_bwd_mfma(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
+                 const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream) {
+    return agg_bwd_m<false>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, stream, nullptr);
+}
+int agg_bwd_mfma_det(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
+                     const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *slab_bias, void *stream, int *grid) {
+    return agg_bwd_m<true>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, slab_bias, stream, grid);
 }
 
 int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,

@@ -23,6 +23,7 @@ from torch import nn
 from torch.distributions import Categorical, Normal
 
 from . import _lib as L
+from . import deterministic as _det
 
 
 MAX_KERNEL_AGENTS = 128      # team size up to which the N x N HIP kernels hold one env's matrix in LDS
@@ -136,9 +137,26 @@ def _wgrad(a2d, b2d, want_colsum):
     c = torch.zeros(P, Q, dtype=torch.float32, device=a2d.device)
     cs = torch.zeros(P, dtype=torch.float32, device=a2d.device) if want_colsum else None
     with torch.cuda.device(a2d.device):
-        L.check(L.lib().cm_linear_wgrad(R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs), L.current_stream()),
-                "cm_linear_wgrad")
+        if _det():
+            nb = L.lib().cm_linear_wgrad_det_ws_bytes(R, P, Q)
+            L.check(L.lib().cm_linear_wgrad_det(R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs), L.ptr(L.slab(nb, a2d.device)), nb,
+                                                L.current_stream()), "cm_linear_wgrad_det")
+        else:
+            L.check(L.lib().cm_linear_wgrad(R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs), L.current_stream()),
+                    "cm_linear_wgrad")
     return c, cs
+
+
+def _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y, dx, dw, db):
+    """cm_linear_act_backward, or its slab twin in deterministic mode."""
+    if _det():
+        nb = L.lib().cm_linear_act_backward_det_ws_bytes(R, K, O)
+        L.check(L.lib().cm_linear_act_backward_det(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y), L.ptr(dx),
+                                                   L.ptr(dw), L.ptr(db), L.ptr(L.slab(nb, w.device)), nb, L.current_stream()),
+                "cm_linear_act_backward_det")
+    else:
+        L.check(L.lib().cm_linear_act_backward(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y), L.ptr(dx),
+                                               L.ptr(dw), L.ptr(db), L.current_stream()), "cm_linear_act_backward")
 
 
 class _LinearFn(torch.autograd.Function):
@@ -207,9 +225,7 @@ class _LinearActFn(torch.autograd.Function):
         dw = torch.zeros_like(w)
         db = torch.zeros(O, dtype=torch.float32, device=w.device) if has_bias else None
         with torch.cuda.device(w.device):
-            L.check(L.lib().cm_linear_act_backward(x2.shape[0], K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), None, L.ptr(y),
-                                                   L.ptr(dx), L.ptr(dw), L.ptr(db), L.current_stream()),
-                    "cm_linear_act_backward")
+            _linear_act_backward(x2.shape[0], K, O, x2, w, layout, dy2, None, y, dx, dw, db)
         return (None if dx is None else dx.reshape(shape)), dw, db, None, None
 
 
@@ -267,9 +283,15 @@ class _MaskedAggregate(torch.autograd.Function):
         if chan_all is not None:
             chan_ptr, stride = chan_all.data_ptr() + 4 * ctx.hop * N * N, chan_all.shape[1] * N * N
         with torch.cuda.device(hw.device):
-            L.check(L.lib().cm_masked_agg_backward(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
-                                                   L.ptr(out), None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw),
-                                                   L.ptr(d_bias), L.current_stream()), "cm_masked_agg_backward")
+            if _det():
+                nb = L.lib().cm_masked_agg_backward_det_ws_bytes(S, N, E)
+                L.check(L.lib().cm_masked_agg_backward_det(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
+                                                           L.ptr(out), None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias),
+                                                           L.ptr(L.slab(nb, hw.device)), nb, L.current_stream()), "cm_masked_agg_backward_det")
+            else:
+                L.check(L.lib().cm_masked_agg_backward(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
+                                                       L.ptr(out), None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw),
+                                                       L.ptr(d_bias), L.current_stream()), "cm_masked_agg_backward")
         return d_attn, None, None, None, d_hw, d_bias
 
 
@@ -324,8 +346,7 @@ def _lin_bwd(x2, w, layout, dy2, y2, want_dx, has_bias, dy_add=None, pool=None):
     dw = pool.take(w.shape) if pool is not None else torch.zeros_like(w)
     db = (pool.take((O,)) if pool is not None else torch.zeros(O, dtype=torch.float32, device=w.device)) if has_bias else None
     with torch.cuda.device(w.device):
-        L.check(L.lib().cm_linear_act_backward(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y2), L.ptr(dx),
-                                               L.ptr(dw), L.ptr(db), L.current_stream()), "cm_linear_act_backward")
+        _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y2, dx, dw, db)
     return dx, dw, db
 
 
@@ -423,6 +444,7 @@ class _FusedNetFn(torch.autograd.Function):
         P = dict(net.named_parameters())
         g = {}
         pool = _ZeroPool(list(P.values()), obs2.device, extra=31 * 64 * len(net.gcn_layers))   # (+ the bias-gradient replicas below)
+        det = _det()
         if ctx.policy:
             hd = net.categorical_output_layer
             lins = [l.linear for l in hd._layers] + [hd._output_layers[0].linear]
@@ -449,14 +471,21 @@ class _FusedNetFn(torch.autograd.Function):
                 minus = e if (l == Lh - 1 and net.residual) else None       # saved x = E + H_L: the hop's tanh output is x - E
                 da, dhw = torch.empty_like(attn), torch.empty_like(e)
                 # large batches of teams of 4: the bias gradient over 32 rows summed afterwards (cm_masked_agg_backward_r)
-                reps = 32 if (N == 4 and S > 16 * 512) else 1
+                reps = 32 if (N == 4 and S > 16 * 512 and not det) else 1
                 dgb = pool.take((reps, 64)) if gl.bias is not None else None
                 chan_ptr, stride = None, 0
                 if ch is not None:
                     chan_ptr, stride = ch.data_ptr() + 4 * l * N * N, ch.shape[1] * N * N
-                L.check(L.lib().cm_masked_agg_backward_r(S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
-                                                         L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb),
-                                                         reps, L.current_stream()), "cm_masked_agg_backward_r")
+                if det:                                                  # one bias row, merged in a fixed order
+                    nb = L.lib().cm_masked_agg_backward_det_ws_bytes(S, N, 64)
+                    L.check(L.lib().cm_masked_agg_backward_det(S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
+                                                               L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb),
+                                                               L.ptr(L.slab(nb, obs2.device)), nb, L.current_stream()),
+                            "cm_masked_agg_backward_det")
+                else:
+                    L.check(L.lib().cm_masked_agg_backward_r(S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
+                                                             L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb),
+                                                             reps, L.current_stream()), "cm_masked_agg_backward_r")
                 if dgb is not None:
                     dgb = dgb.sum(0) if reps > 1 else dgb[0]
                 d_attn = da if d_attn is None else d_attn.add_(da)
@@ -485,8 +514,14 @@ class _FusedNetFn(torch.autograd.Function):
         dw2, db2 = pool.take(enc2.weight.shape), pool.take(enc2.bias.shape)
         dw1, db1 = pool.take(enc1.weight.shape), pool.take(enc1.bias.shape)
         with torch.cuda.device(obs2.device):
-            rc = L.lib().cm_encoder_backward(R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE), L.ptr(deq),
-                                             L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1), L.current_stream())
+            if det:
+                nb = L.lib().cm_encoder_backward_det_ws_bytes(R, obs2.shape[1])
+                rc = L.lib().cm_encoder_backward_det(R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE),
+                                                     L.ptr(deq), L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1), L.ptr(L.slab(nb, obs2.device)),
+                                                     nb, L.current_stream())
+            else:
+                rc = L.lib().cm_encoder_backward(R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE), L.ptr(deq),
+                                                 L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1), L.current_stream())
         if rc == 1:
             da1, dw2, db2 = _lin_bwd(t["a1"], enc2.weight, 0, dE, e, True, True, dy_add=deq)     # (dw2 .. db1 taken above stay zero, unused)
             _, dw1, db1 = _lin_bwd(obs2, enc1.weight, 0, da1, t["a1"], False, True)
@@ -1008,8 +1043,14 @@ class _GaussNLLFn(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=pa.device)
         has_min = 0 if min_log_std is None else 1
         with torch.cuda.device(pa.device):
-            L.check(L.lib().cm_gauss_nll_forward(S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min, L.ptr(out),
-                                                 L.ptr(ws), L.current_stream()), "cm_gauss_nll_forward")
+            if _det():                                       # block sums summed in a fixed order (no f64 atomics)
+                nb = L.lib().cm_gauss_nll_forward_det_ws_bytes(S)
+                L.check(L.lib().cm_gauss_nll_forward_det(S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
+                                                         L.ptr(out), L.ptr(L.slab(nb, pa.device)), nb, L.current_stream()),
+                        "cm_gauss_nll_forward_det")
+            else:
+                L.check(L.lib().cm_gauss_nll_forward(S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
+                                                     L.ptr(out), L.ptr(ws), L.current_stream()), "cm_gauss_nll_forward")
         ctx.save_for_backward(pa, r, log_std, out)
         ctx.min_log_std = min_log_std
         return out[0]

@@ -471,6 +471,39 @@ int cm_entropy_gae(int32_t P, int32_t T, int32_t N, int32_t A, const float *logi
                    const float *baselines, float gamma, float lam, float ent_coeff, int32_t softplus, float *rewards_out,
                    float *entropy_out, float *adv, void *stream);
 
+/* ---- Deterministic update mode (com_marl_amd.set_deterministic) ----
+ * Twins of the entry points above whose cross-workgroup float sums would otherwise be merged with atomics (an order that
+ * changes from run to run).  Each takes a slab workspace `ws` of DEVICE memory, at least cm_*_det_ws_bytes(shape) bytes,
+ * contents ignored: every workgroup plain-stores its partial sums into its own row, and a second launch sums the rows in
+ * index order.  The number of rows is fixed by the shape and the device's CU count, so two runs on the same GPU type
+ * give bit-identical results.  Outputs accumulate like the originals' (zero them on entry).  A NULL or too-small `ws`
+ * returns CM_ERR_ARG (text in cm_last_error) before anything is launched.  Concurrent launches need separate slabs. */
+size_t cm_linear_act_backward_det_ws_bytes(int64_t R, int32_t K, int32_t O);
+int cm_linear_act_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                               const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
+                               void *ws, size_t ws_bytes, void *stream);
+/* db2 and db1 are required here; returns 1 (nothing launched) where cm_encoder_backward does */
+size_t cm_encoder_backward_det_ws_bytes(int64_t R, int32_t d);
+int cm_encoder_backward_det(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
+                            const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *ws, size_t ws_bytes, void *stream);
+/* d_bias [E] (one row: no replicas) */
+size_t cm_masked_agg_backward_det_ws_bytes(int32_t S, int32_t N, int32_t E);
+int cm_masked_agg_backward_det(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                               const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
+                               const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *ws, size_t ws_bytes, void *stream);
+size_t cm_linear_wgrad_det_ws_bytes(int64_t R, int32_t P, int32_t Q);
+int cm_linear_wgrad_det(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a,
+                        void *ws, size_t ws_bytes, void *stream);
+/* *total: f64 block sums summed in a fixed order */
+size_t cm_ppo_surrogate_det_ws_bytes(int32_t P, int32_t T);
+int cm_ppo_surrogate_det(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
+                         const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff,
+                         int32_t add_entropy, double *total, int64_t *count, float *dlogits, void *ws, size_t ws_bytes, void *stream);
+/* the slab replaces cm_gauss_nll_forward's CM_GAUSS_WS_BYTES workspace (no zero state to keep) */
+size_t cm_gauss_nll_forward_det_ws_bytes(int64_t S);
+int cm_gauss_nll_forward_det(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std, float min_log_std,
+                             int32_t has_min, float *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,7 +63,7 @@ __device__ __forceinline__ void stage(float *dst, int stride, const float *__res
         for (int i = 0; i < 8; ++i) {
             if (i < ni) {
                 float4 v = q[i];
-                if (DZ) { v.x *= 1.0f - y[i].x * y[i].x; v.y *= 1.0f - y[i].y * y[i].y; v.z *= 1.0f - y[i].z * y[i].z; v.w *= 1.0f - y[i].w * y[i].w; }
+                if (DZ) { v.x *= fmaf(-y[i].x, y[i].x, 1.0f); v.y *= fmaf(-y[i].y, y[i].y, 1.0f); v.z *= fmaf(-y[i].z, y[i].z, 1.0f); v.w *= fmaf(-y[i].w, y[i].w, 1.0f); }
                 *reinterpret_cast<float4 *>(dst + (size_t)(rb + i * rstep) * stride + 4 * x) = v;
             }
         }
@@ -80,7 +80,7 @@ __device__ __forceinline__ void stage(float *dst, int stride, const float *__res
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (off[u] >= 0) dst[off[u]] = DZ ? v[u] * (1.0f - yy[u] * yy[u]) : v[u];
+                if (off[u] >= 0) dst[off[u]] = DZ ? v[u] * (fmaf(-yy[u], yy[u], 1.0f)) : v[u];
         }
     }
 }

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
                 }
                 if (ACT) {
                     const float4 y = *reinterpret_cast<const float4 *>(Ys + p);
-                    z.x *= 1.0f - y.x * y.x; z.y *= 1.0f - y.y * y.y; z.z *= 1.0f - y.z * y.z; z.w *= 1.0f - y.w * y.w;
+                    z.x *= fmaf(-y.x, y.x, 1.0f); z.y *= fmaf(-y.y, y.y, 1.0f); z.z *= fmaf(-y.z, y.z, 1.0f); z.w *= fmaf(-y.w, y.w, 1.0f);
                 }
                 if (p >= rows * O) z = make_float4(0.f, 0.f, 0.f, 0.f);
                 *reinterpret_cast<float4 *>(Zs + p) = z;
@@ -330,8 +330,8 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
                 for (int i = 0; i < NKT; ++i) {           // dz1 = dx * (1 - x^2), in place
                     float4 *px = reinterpret_cast<float4 *>(Xw + chunk_at<K>(r, 4 * (hb * NKT + i) + g));
                     const float4 x = *px;
-                    *px = make_float4(d[i][0] * (1.0f - x.x * x.x), d[i][1] * (1.0f - x.y * x.y), d[i][2] * (1.0f - x.z * x.z),
-                                      d[i][3] * (1.0f - x.w * x.w));
+                    *px = make_float4(d[i][0] * (fmaf(-x.x, x.x, 1.0f)), d[i][1] * (fmaf(-x.y, x.y, 1.0f)), d[i][2] * (fmaf(-x.z, x.z, 1.0f)),
+                                      d[i][3] * (fmaf(-x.w, x.w, 1.0f)));
                 }
                 __syncthreads();
                 // first layer's weight gradient, one x-column tile per wave over all 64 rows: C[p = x col][q = obs col]

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(TPB) void agg_bwd_kernel(int S, int N, int EPB, con
             const size_t g = (size_t)s0 * N * E + k;
             HW[(size_t)r * SE + c] = hw[g];
             const float y = out_minus ? outv[g] - out_minus[g] : outv[g];
-            const float dp = d_out[g] * (1.0f - y * y);          // tanh'
+            const float dp = d_out[g] * (fmaf(-y, y, 1.0f));          // tanh'
             DP[(size_t)r * SE + c] = dp;
         }
         __syncthreads();
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void agg_bwd4_kernel(int S, const float *__res
                     y.x -= u.x; y.y -= u.y; y.z -= u.z; y.w -= u.w;
                 }
                 const float4 d = *reinterpret_cast<const float4 *>(d_out + row0 + i * 64 + 4 * c);
-                dp[i] = make_float4(d.x * (1.0f - y.x * y.x), d.y * (1.0f - y.y * y.y), d.z * (1.0f - y.z * y.z), d.w * (1.0f - y.w * y.w));   // tanh'
+                dp[i] = make_float4(d.x * (fmaf(-y.x, y.x, 1.0f)), d.y * (fmaf(-y.y, y.y, 1.0f)), d.z * (fmaf(-y.z, y.z, 1.0f)), d.w * (fmaf(-y.w, y.w, 1.0f)));   // tanh'
             }
         }
         // normalised A, element (i = c / 4, j = c % 4)

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(TPB) void agg_bwd_kernel(int S, int N, const float 
                         const float4 d = dv[u];
                         *reinterpret_cast<float4 *>(HW + (size_t)r * SP + 4 * q) = hv[u];
                         *reinterpret_cast<float4 *>(DP + (size_t)r * SP + 4 * q) =
-                            make_float4(d.x * (1.0f - y.x * y.x), d.y * (1.0f - y.y * y.y), d.z * (1.0f - y.z * y.z), d.w * (1.0f - y.w * y.w));   // tanh'
+                            make_float4(d.x * (fmaf(-y.x, y.x, 1.0f)), d.y * (fmaf(-y.y, y.y, 1.0f)), d.z * (fmaf(-y.z, y.z, 1.0f)), d.w * (fmaf(-y.w, y.w, 1.0f)));   // tanh'
                     }
                 }
             }

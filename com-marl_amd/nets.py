@@ -28,6 +28,7 @@ from . import deterministic as _det
 
 MAX_KERNEL_AGENTS = 128      # team size up to which the N x N HIP kernels hold one env's matrix in LDS
 MAX_FUSED_AGENTS = 80        # ... and up to which the one-launch forward (rollout and training) does (cm_policy_h_dev.h LDS map)
+MAX_FUSED_OBS = 80           # per-agent observation size up to which the matrix-core pack, hence the training forward, exists
 
 # ---------------------------------------------------------------------------------------------
 # building blocks with the reference's state_dict names
@@ -353,9 +354,10 @@ def _lin_bwd(x2, w, layout, dy2, y2, want_dx, has_bias, dy_add=None, pool=None):
 def _fused_shape_ok(net, obs):
     """Shapes with a saved-forward instantiation (cm_*_forward_saved) and a backward chain."""
     # teams above 80 agents exceed the f16-split forward's LDS budget (its activation planes + the N x N score matrix):
-    # they keep the per-layer path
+    # they keep the per-layer path.  Observations above 80 features have no matrix-core operand pack (kpad_of,
+    # cm_policy_mfma_dev.h: cm_*_pack_bytes() == 0), without which the saved forward launches nothing
     return (obs.is_cuda and 1 <= net._n_agents <= MAX_FUSED_AGENTS and 1 <= len(net.gcn_layers) <= 4
-            and net._dec_obs_dim <= 96 and len(net.encoder._layers) == 1
+            and net._dec_obs_dim <= MAX_FUSED_OBS and len(net.encoder._layers) == 1
             and os.environ.get("COMMARL_FUSED_TRAIN", "1") != "0" and os.environ.get("COMMARL_POLICY_KERNEL", "")[:1] not in ("f", "v"))
 
 

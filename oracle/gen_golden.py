@@ -678,6 +678,58 @@ def record_net_options(env_fix, n_agents, seed=31, take=4):
     return out
 
 
+def record_net_grads(env_fix, n_agents, seed=51, take=2):
+    """The default net (attention_type='general', aggregator_type='sum') in the shape of record_net_options, with the
+    avail mask of record_policy (action 1 forbidden for ~30 % of the agents) and non-zero biases: forward outputs, the
+    PPO-shaped scalar / Gaussian NLL and the gradient of each with respect to every parameter.  For the large teams (N = 24 ..
+    128) whose training backward runs on the matrix-core kernels: only N = 4 had reference gradients of this net."""
+    ns = ref_loader.load_reference()
+    T1 = env_fix['obs'].shape[0]
+    d_total = env_fix['obs'].shape[2]
+    spec = ref_loader.make_env_spec(d_total)
+    idx = np.linspace(0, T1 - 1, take).astype(int)
+    obs = env_fix['obs'][idx].reshape(-1, d_total).astype(np.float32)
+    adj = env_fix['dist_adj'][idx].reshape(-1, n_agents, n_agents).astype(np.float32)
+    ch = env_fix['channels'][idx].reshape(-1, env_fix['channels'].shape[2], n_agents, n_agents).astype(np.float32)
+    S = obs.shape[0]
+    rng = np.random.RandomState(seed)
+    acts = rng.randint(0, 5, size=(S, n_agents))
+    wts = rng.randn(S).astype(np.float32)
+    returns = (rng.randn(S) * 3).astype(np.float32)
+    avail = np.ones((S, n_agents, 5), dtype=np.float32)
+    avail[rng.rand(S, n_agents) < 0.3, 1] = 0
+    avail = avail.reshape(S, -1)
+    torch.manual_seed(seed)
+    pol = ns.CommCategoricalMLPPolicy(spec, n_agents=n_agents)
+    crit = ns.CommBaseCritic(spec, n_agents=n_agents)
+    with torch.no_grad():
+        for net in (pol, crit):
+            for name, p in net.named_parameters():
+                if name.endswith('bias') and 'gcn' not in name:
+                    p.uniform_(-0.1, 0.1)
+    out = dict(obs=obs, adj=adj, channels=ch, avail=avail, actions=acts, weights=wts, returns=returns)
+    tobs, tav, tadj, tch = (torch.Tensor(obs), torch.Tensor(avail), torch.Tensor(adj.reshape(S, -1)),
+                            torch.Tensor(ch.reshape(S, -1, n_agents)))
+    with torch.no_grad():
+        dist, attn = pol.forward(obs, avail, adj, ch, get_actions=True)
+        out['probs'], out['attn'] = dist.probs.numpy(), attn.numpy()
+        out['values'] = crit.forward(tobs, tav, tadj, tch).numpy()
+    scalar = -(pol.log_likelihood(tobs, tav, tadj, tch, torch.Tensor(acts)) * torch.Tensor(wts)).mean() \
+        - 0.1 * pol.entropy(tobs, tav, tadj, tch).mean()
+    pol.zero_grad()
+    scalar.backward()
+    loss = crit.compute_loss(tobs, torch.Tensor(returns), tadj, tch)
+    crit.zero_grad()
+    loss.backward()
+    out['scalar'], out['critic_loss'] = scalar.detach().numpy(), loss.detach().numpy()
+    for pre, net in (('pol', pol), ('crit', crit)):
+        for name, p in net.state_dict().items():
+            out[f'{pre}.{name}'] = p.numpy()
+        for name, p in net.named_parameters():
+            out[f'g{pre}.{name}'] = (p.grad if p.grad is not None else torch.zeros_like(p)).clone().numpy()
+    return out
+
+
 def record_ppo_math(ns, seed=5):
     """GAE / returns / per-path normalisation on a ragged 3-path batch."""
     rng = np.random.RandomState(seed)
@@ -826,7 +878,7 @@ def main():
     ns = ref_loader.load_reference()
 
     def save(name, d):
-        if args.only and name != args.only:
+        if args.only and name != args.only and not (args.only.endswith('_') and name.startswith(args.only)):
             return
         if callable(d):
             d = d()
@@ -835,7 +887,8 @@ def main():
         print(f'{name:28s} {os.path.getsize(path) / 1024:8.1f} KiB')
 
     fx = {}
-    if args.only and args.only.startswith(('ppo_step', 'variants_', 'ppo_math', 'adam', 'adj_ties_grid32', 'faults_direct', 'env_pp_map10_cond', 'net_options_', 'env_pp_map40', 'env_co_map40')):
+    if args.only and args.only.startswith(('ppo_step', 'variants_', 'ppo_math', 'adam', 'adj_ties_grid32', 'faults_direct', 'env_pp_map10_cond', 'net_options_', 'env_pp_map40', 'env_co_map40',
+                                                       'net_grads_')):
         return late(save, args)
     # config 1/2: PP map10 sen1 den.04 cap2 (full 200-step horizon, chasing so captures happen)
     fx['pp_map10_cap2'] = record_env(ns, 'pp', pp_params(10, 1, 0.04, 2), B=3, T=230, seed=1, p_random=0.35)
@@ -917,6 +970,14 @@ def late(save, args, ns=None):
     save('variants_pp_map30', lambda: record_variants(np.load(os.path.join(args.out, 'env_pp_map30_cap4.npz')), 72, take=2))
     save('net_options_pp_map10', lambda: record_net_options(np.load(os.path.join(args.out, 'env_pp_map10_cap2.npz')), 4))
     save('net_options_co_map20', lambda: record_net_options(np.load(os.path.join(args.out, 'env_co_map20.npz')), 24, seed=33, take=2))
+    # the default net at every large team size (N = 24, 54, 72 on the fused training path, 96 and 128 on the per-layer one), on the
+    # committed env recordings (so that `--only net_grads_ --out DIR` reproduces them into any directory)
+    golden = os.path.join(HERE, '..', 'tests', 'golden')
+    for i, (fx_name, n) in enumerate((('co_map20', 24), ('co_map30_iid', 54), ('pp_map30_cap4', 72), ('co_map40', 96),
+                                      ('pp_map40_cap4', 128))):
+        tag = fx_name.replace('_cap4', '')
+        save('net_grads_' + tag, lambda fx_name=fx_name, n=n, i=i: record_net_grads(
+            np.load(os.path.join(golden, f'env_{fx_name}.npz')), n, seed=51 + i))
 
 
 if __name__ == '__main__':

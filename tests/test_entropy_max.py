@@ -295,7 +295,7 @@ def test_max_entropy_epoch_matches_reference(kind, torch_cuda, monkeypatch):
 
     def close(a, b, what):
         b = np.asarray(b, np.float64)
-        np.testing.assert_allclose(np.asarray(a, np.float64), b, rtol=0, atol=1e-5 * max(1.0, float(np.abs(b).max())),
+        np.testing.assert_allclose(np.asarray(a, np.float64), b, rtol=0, atol=1e-5 * max(float(np.abs(b).max()), 1e-6),
                                    err_msg=what)
     for i, (r_in, _, adv) in enumerate(rec):
         ref_adv = z[f"call{i}.adv"]

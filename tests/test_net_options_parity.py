@@ -81,7 +81,7 @@ def test_hip_net_options_forward_and_training_path(name):
             for pname, p in net.named_parameters():
                 want = z[f"{tag}.{pre}.{pname}"]
                 got = np.zeros_like(want) if p.grad is None else p.grad.cpu().numpy()
-                np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-5 * max(1.0, float(np.abs(want).max())), err_msg=f"{tag} {pre} {pname}")
+                np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-5 * max(float(np.abs(want).max()), 1e-6), err_msg=f"{tag} {pre} {pname}")
 
 
 def test_unbuilt_options_say_so():

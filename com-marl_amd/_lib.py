@@ -71,7 +71,7 @@ class FwdSaves(C.Structure):
 
 class MlpWeights(C.Structure):
     _fields_ = [("in_dim", C.c_int32), ("n_layers", C.c_int32), ("out_dim", C.c_int32 * MLP_MAX_LAYERS),
-                ("tanh_mask", C.c_int32), ("_pad", C.c_int32), ("wt", C.c_void_p * MLP_MAX_LAYERS),
+                ("tanh_mask", C.c_int32), ("relu_mask", C.c_int32), ("wt", C.c_void_p * MLP_MAX_LAYERS),
                 ("b", C.c_void_p * MLP_MAX_LAYERS), ("mfma_pack", C.c_void_p)]
 
 
@@ -149,6 +149,8 @@ _SIGNATURES = {
                                         C.c_int32, C.c_void_p, C.c_void_p]),
     "cm_linear_act_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_linear_act_backward_ex": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_encoder_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_multi_copy_t": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -175,6 +177,9 @@ _SIGNATURES = {
     "cm_linear_act_backward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.c_void_p]),
+    "cm_linear_act_backward_ex_det": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.c_void_p]),
     "cm_encoder_backward_det_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "cm_encoder_backward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -2,6 +2,7 @@
 //
 //   cm_linear_act_forward  : y = act(x.W^T + b)                               reads x, writes y
 //   cm_linear_act_backward : dz = dy * act'(y);  dx = dz.W;  dW += dz^T.x;  db += colsum(dz)
+//                            (act = tanh: dz = dy * (1 - y^2); act = ReLU: dz = y > 0 ? dy : 0, torch's threshold_backward)
 //                                                                              reads dy, y, x; writes dx
 // over R = P*T*N ~ 1e6 agent rows with in / out widths <= 128 (reference: nn.Linear + tanh of
 // garage/torch/modules/multi_headed_mlp_module.py:134-149, GraphConvolutionModule's H.W graph_conv_module.py:63,
@@ -36,17 +37,22 @@ __device__ __forceinline__ float w_at(const float *__restrict__ W, int layout, i
     return layout == 0 ? W[(size_t)o * K + k] : W[(size_t)k * O + o];
 }
 
-// A [ROWS x W] row tile from HBM to LDS, zero rows past `rows`; with `yv`: dz = dy * (1 - y^2) on the way in.
+// ReLU' as torch's threshold_backward on the saved output
+__device__ __forceinline__ float relu_bwd(float dy, float y) { return y > 0.0f ? dy : 0.0f; }
+
+// A [ROWS x W] row tile from HBM to LDS, zero rows past `rows`; ACT 1: dz = dy * (1 - y^2) on the way in, ACT 2:
+// dz = y > 0 ? dy : 0 (a select, not a multiply by a 0 / 1 mask: an inf / NaN gradient into a dead unit gives 0, as in torch).
 // Widths that are a power-of-two number of float4s (16 / 32 / 64 / 128: every hidden width of the nets) take the vector
 // path: ALL of a thread's loads (<= 8 float4 per operand) are issued before the first LDS write, so a chunk exposes ONE
 // HBM round trip (the row-loop staging of cm_linear_wgrad exposed one per 16-row slice: ~11 us per chunk).  Other widths
 // (the observation, the 5 logits, the critic's scalar) are small and go four loads at a time.
-template <bool DZ>
+template <int ACT>
 __device__ __forceinline__ void stage(float *dst, int stride, const float *__restrict__ src, const float *__restrict__ yv, int W,
                                       long r0, int rows, int tid, const float *__restrict__ src2 = nullptr) {
     const int w4 = W >> 2;
     if ((W & 3) == 0 && (w4 & (w4 - 1)) == 0 && w4 >= 4 && w4 <= 32) {
         const int x = tid & (w4 - 1), rstep = TPB / w4, rb = tid / w4, ni = ROWS / rstep;      // ni = w4 / 4 <= 8
+        constexpr bool DZ = ACT != 0;
         float4 q[8], y[DZ ? 8 : 1];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -63,7 +69,8 @@ __device__ __forceinline__ void stage(float *dst, int stride, const float *__res
         for (int i = 0; i < 8; ++i) {
             if (i < ni) {
                 float4 v = q[i];
-                if (DZ) { v.x *= fmaf(-y[i].x, y[i].x, 1.0f); v.y *= fmaf(-y[i].y, y[i].y, 1.0f); v.z *= fmaf(-y[i].z, y[i].z, 1.0f); v.w *= fmaf(-y[i].w, y[i].w, 1.0f); }
+                if (ACT == 1) { v.x *= fmaf(-y[i].x, y[i].x, 1.0f); v.y *= fmaf(-y[i].y, y[i].y, 1.0f); v.z *= fmaf(-y[i].z, y[i].z, 1.0f); v.w *= fmaf(-y[i].w, y[i].w, 1.0f); }
+                if (ACT == 2) { v.x = relu_bwd(v.x, y[i].x); v.y = relu_bwd(v.y, y[i].y); v.z = relu_bwd(v.z, y[i].z); v.w = relu_bwd(v.w, y[i].w); }
                 *reinterpret_cast<float4 *>(dst + (size_t)(rb + i * rstep) * stride + 4 * x) = v;
             }
         }
@@ -76,11 +83,11 @@ __device__ __forceinline__ void stage(float *dst, int stride, const float *__res
                 const int k = k0 + u * TPB, r = k / W, x = k - r * W;
                 off[u] = k < ROWS * W ? r * stride + x : -1;
                 v[u] = 0.0f; yy[u] = 0.0f;
-                if (k < ROWS * W && r < rows) { v[u] = src[(r0 + r) * W + x]; if (src2) v[u] += src2[(r0 + r) * W + x]; if (DZ) yy[u] = yv[(r0 + r) * W + x]; }
+                if (k < ROWS * W && r < rows) { v[u] = src[(r0 + r) * W + x]; if (src2) v[u] += src2[(r0 + r) * W + x]; if (ACT) yy[u] = yv[(r0 + r) * W + x]; }
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (off[u] >= 0) dst[off[u]] = DZ ? v[u] * (fmaf(-yy[u], yy[u], 1.0f)) : v[u];
+                if (off[u] >= 0) dst[off[u]] = ACT == 1 ? v[u] * (fmaf(-yy[u], yy[u], 1.0f)) : (ACT == 2 ? relu_bwd(v[u], yy[u]) : v[u]);
         }
     }
 }
@@ -118,7 +125,7 @@ __global__ __launch_bounds__(TPB) void fwd_kernel(long R, int K, int O, const fl
     for (long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
         const long r0 = ch * ROWS;
         const int rows = (int)min((long)ROWS, R - r0);
-        stage<false>(Xs, SX, X, nullptr, K, r0, rows, tid);
+        stage<0>(Xs, SX, X, nullptr, K, r0, rows, tid);
         __syncthreads();
         for (int rt = rt_start; rt < ROWS / 16; rt += rt_step) {
             const float4 *pa = reinterpret_cast<const float4 *>(Xs + (size_t)(rt * 16 + c) * SX + 4 * g);
@@ -147,7 +154,10 @@ __global__ __launch_bounds__(TPB) void fwd_kernel(long R, int K, int O, const fl
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = rt * 16 + 4 * g + r;
-                        if (row < rows) Y[(size_t)(r0 + row) * O + o] = ACT ? tanh_exact(acc[t][r]) : acc[t][r];
+                        if (row < rows) {
+                            const float z = acc[t][r];      // ACT 2: torch.relu (z < 0 ? 0 : z lets a NaN through; fmaxf would not)
+                            Y[(size_t)(r0 + row) * O + o] = ACT == 1 ? tanh_exact(z) : (ACT == 2 ? (z < 0.0f ? 0.0f : z) : z);
+                        }
                     }
                 }
             }
@@ -216,8 +226,8 @@ __global__ __launch_bounds__(TPB, (MAXT == 8 ? 2 : 1)) void bwd_kernel(long R, i
     for (long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
         const long r0 = ch * ROWS;
         const int rows = (int)min((long)ROWS, R - r0);
-        stage<ACT != 0>(Zs, SZ, DY, Yv, O, r0, rows, tid, DY2);
-        stage<false>(Xs, SXs, X, nullptr, K, r0, rows, tid);
+        stage<ACT>(Zs, SZ, DY, Yv, O, r0, rows, tid, DY2);
+        stage<0>(Xs, SXs, X, nullptr, K, r0, rows, tid);
         __syncthreads();
         if (DB && tid < O) { float s = 0.0f; for (int r = 0; r < ROWS; ++r) s += Zs[(size_t)r * SZ + tid]; csum += s; }
         // ---- weight gradient: C[p][q] += sum_r A[r][p] B[r][q] ----
@@ -287,11 +297,11 @@ __global__ __launch_bounds__(TPB, (MAXT == 8 ? 2 : 1)) void bwd_kernel(long R, i
 
 namespace cm {
 int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                      const float *y, float *dx, float *dw, float *db, void *stream);   // cm_linear_bwd.hip: widths 32 / 64 / 128
+                      const float *y, int act, float *dx, float *dw, float *db, void *stream);   // cm_linear_bwd.hip: widths 32 / 64 / 128
 int encoder_bwd_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
                       float *dw2, float *db2, float *dw1, float *db1, void *stream);
 int linear_bwd_stream_det(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                          const float *y, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid);
+                          const float *y, int act, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid);
 int encoder_bwd_chain_det(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
                           float *slab, void *stream, int *grid);
 size_t lin2_slab_row(int d);                                                             // floats per workgroup of encoder_bwd_chain_det
@@ -303,23 +313,26 @@ extern "C" int cm_linear_act_forward(int64_t R, int32_t K, int32_t O, const floa
     if (!x || !w || !y) return set_error(CM_ERR_ARG, "cm_linear_act_forward: null argument");
     if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_forward: 1 <= in, out <= 128 required");
     if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_forward: w_layout must be 0 ([out,in]) or 1 ([in,out])");
+    if (act < 0 || act > 2) return set_error(CM_ERR_ARG, "cm_linear_act_forward: act must be 0 (identity), 1 (tanh) or 2 (ReLU)");
     if (R <= 0) return CM_OK;
     const int KT = (K + 15) / 16;
     const size_t lds = (size_t)lin::ROWS * (KT * 16 + 4) * sizeof(float);
     const long chunks = (R + lin::ROWS - 1) / lin::ROWS;
     const int blocks = (int)std::min<long>(chunks, 512);
-    if (act) hipLaunchKernelGGL(lin::fwd_kernel<1>, dim3(blocks), dim3(lin::TPB), lds, (hipStream_t)stream, (long)R, K, O, x, w, w_layout, bias, y);
+    if (act == 1) hipLaunchKernelGGL(lin::fwd_kernel<1>, dim3(blocks), dim3(lin::TPB), lds, (hipStream_t)stream, (long)R, K, O, x, w, w_layout, bias, y);
+    else if (act == 2) hipLaunchKernelGGL(lin::fwd_kernel<2>, dim3(blocks), dim3(lin::TPB), lds, (hipStream_t)stream, (long)R, K, O, x, w, w_layout, bias, y);
     else hipLaunchKernelGGL(lin::fwd_kernel<0>, dim3(blocks), dim3(lin::TPB), lds, (hipStream_t)stream, (long)R, K, O, x, w, w_layout, bias, y);
     CM_HIP(hipGetLastError());
     return CM_OK;
 }
 
+// act: 0 identity, 1 tanh, 2 ReLU (y required when act != 0).
 // DET: dw / db address row 0 of a slab (K O + O floats per workgroup); *grid receives the number of rows written
 template <bool DET>
 static int linear_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout, const float *dy,
-                           const float *dy2, const float *y, float *dx, float *dw, float *db, void *stream, int *grid) {
-    if (const int rc = DET ? linear_bwd_stream_det(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream, grid)
-                           : linear_bwd_stream(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream); rc != 1) return rc;
+                           const float *dy2, const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid) {
+    if (const int rc = DET ? linear_bwd_stream_det(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, dw, db, stream, grid)
+                           : linear_bwd_stream(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, dw, db, stream); rc != 1) return rc;
     const int OT = (O + 15) / 16, KT = (K + 15) / 16, NT = OT * KT;
     const size_t lds = ((size_t)lin::ROWS * (OT * 16 + 16) + (size_t)lin::ROWS * (KT * 16 + 16)) * sizeof(float);
     const long chunks = (R + lin::ROWS - 1) / lin::ROWS;
@@ -335,9 +348,11 @@ static int linear_backward(int64_t R, int32_t K, int32_t O, const float *x, cons
 #define CM_ATTR(M, A) CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&lin::bwd_kernel<M, A, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
         CM_ATTR(16, 0); CM_ATTR(8, 0); CM_ATTR(4, 0); CM_ATTR(2, 0); CM_ATTR(1, 0);
         CM_ATTR(16, 1); CM_ATTR(8, 1); CM_ATTR(4, 1); CM_ATTR(2, 1); CM_ATTR(1, 1);
+        CM_ATTR(16, 2); CM_ATTR(8, 2); CM_ATTR(4, 2); CM_ATTR(2, 2); CM_ATTR(1, 2);
 #undef CM_ATTR
     }
-#define CM_LB(M) do { if (y) hipLaunchKernelGGL((lin::bwd_kernel<M, 1, DET>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); \
+#define CM_LB(M) do { if (act == 1) hipLaunchKernelGGL((lin::bwd_kernel<M, 1, DET>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); \
+                      else if (act == 2) hipLaunchKernelGGL((lin::bwd_kernel<M, 2, DET>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); \
                       else hipLaunchKernelGGL((lin::bwd_kernel<M, 0, DET>), dim3(blocks), dim3(lin::TPB), lds, st, (long)R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db); } while (0)
     if (per_wave <= 1) CM_LB(1); else if (per_wave <= 2) CM_LB(2); else if (per_wave <= 4) CM_LB(4);
     else if (per_wave <= 8) CM_LB(8); else CM_LB(16);
@@ -353,7 +368,25 @@ extern "C" int cm_linear_act_backward(int64_t R, int32_t K, int32_t O, const flo
     if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward: 1 <= in, out <= 128 required");
     if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward: w_layout must be 0 ([out,in]) or 1 ([in,out])");
     if (R <= 0) return CM_OK;
-    return linear_backward<false>(R, K, O, x, w, w_layout, dy, dy2, y, dx, dw, db, stream, nullptr);
+    return linear_backward<false>(R, K, O, x, w, w_layout, dy, dy2, y, y ? 1 : 0, dx, dw, db, stream, nullptr);
+}
+
+// act checks shared by the two _ex entry points
+static int act_check(int32_t act, const float *y, const char *what) {
+    if (act < 0 || act > 2) return set_error(CM_ERR_ARG, std::string(what) + ": act must be 0 (identity), 1 (tanh) or 2 (ReLU)");
+    if (act != 0 && !y) return set_error(CM_ERR_ARG, std::string(what) + ": y (the layer's output) is required when act != 0");
+    return CM_OK;
+}
+
+extern "C" int cm_linear_act_backward_ex(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                         const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
+                                         void *stream) {
+    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex: null argument");
+    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex: 1 <= in, out <= 128 required");
+    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex: w_layout must be 0 ([out,in]) or 1 ([in,out])");
+    if (const int rc = act_check(act, y, "cm_linear_act_backward_ex")) return rc;
+    if (R <= 0) return CM_OK;
+    return linear_backward<false>(R, K, O, x, w, w_layout, dy, dy2, act ? y : nullptr, act, dx, dw, db, stream, nullptr);
 }
 
 static size_t linear_slab_rows(int64_t R) { return (size_t)std::min<int64_t>((R + lin::ROWS - 1) / lin::ROWS, 512); }   // >= either kernel's grid
@@ -361,6 +394,21 @@ static size_t linear_slab_rows(int64_t R) { return (size_t)std::min<int64_t>((R 
 extern "C" size_t cm_linear_act_backward_det_ws_bytes(int64_t R, int32_t K, int32_t O) {
     if (R <= 0 || K < 1 || O < 1) return 0;
     return linear_slab_rows(R) * ((size_t)K * O + O) * sizeof(float);
+}
+
+// slab launch + ordered reduction of the two _det entry points (arguments checked by the caller)
+static int linear_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout, const float *dy,
+                               const float *dy2, const float *y, int act, float *dx, float *dw, float *db, void *ws, void *stream) {
+    float *slab = static_cast<float *>(ws);
+    const int row = K * O + O;
+    int grid = 0;
+    if (const int rc = linear_backward<true>(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, slab, db ? slab + (size_t)K * O : nullptr, stream, &grid))
+        return rc;
+    SlabSegs segs{};
+    segs.s[0] = { dw, 0, K * O };
+    segs.s[1] = { db, K * O, O };
+    segs.n_seg = db ? 2 : 1;
+    return slab_reduce(slab, grid, row, segs, (hipStream_t)stream);
 }
 
 extern "C" int cm_linear_act_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
@@ -371,16 +419,19 @@ extern "C" int cm_linear_act_backward_det(int64_t R, int32_t K, int32_t O, const
     if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: w_layout must be 0 ([out,in]) or 1 ([in,out])");
     if (const int rc = slab_check(ws, ws_bytes, cm_linear_act_backward_det_ws_bytes(R, K, O), "cm_linear_act_backward_det")) return rc;
     if (R <= 0) return CM_OK;
-    float *slab = static_cast<float *>(ws);
-    const int row = K * O + O;
-    int grid = 0;
-    if (const int rc = linear_backward<true>(R, K, O, x, w, w_layout, dy, dy2, y, dx, slab, db ? slab + (size_t)K * O : nullptr, stream, &grid))
-        return rc;
-    SlabSegs segs{};
-    segs.s[0] = { dw, 0, K * O };
-    segs.s[1] = { db, K * O, O };
-    segs.n_seg = db ? 2 : 1;
-    return slab_reduce(slab, grid, row, segs, (hipStream_t)stream);
+    return linear_backward_det(R, K, O, x, w, w_layout, dy, dy2, y, y ? 1 : 0, dx, dw, db, ws, stream);
+}
+
+extern "C" int cm_linear_act_backward_ex_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                             const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
+                                             void *ws, size_t ws_bytes, void *stream) {
+    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex_det: null argument");
+    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex_det: 1 <= in, out <= 128 required");
+    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex_det: w_layout must be 0 ([out,in]) or 1 ([in,out])");
+    if (const int rc = act_check(act, y, "cm_linear_act_backward_ex_det")) return rc;
+    if (const int rc = slab_check(ws, ws_bytes, cm_linear_act_backward_det_ws_bytes(R, K, O), "cm_linear_act_backward_ex_det")) return rc;
+    if (R <= 0) return CM_OK;
+    return linear_backward_det(R, K, O, x, w, w_layout, dy, dy2, act ? y : nullptr, act, dx, dw, db, ws, stream);
 }
 
 extern "C" int cm_encoder_backward(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,

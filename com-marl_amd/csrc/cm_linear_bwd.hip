@@ -1,6 +1,7 @@
 // cm_linear_bwd.hip - streaming backward of one dense layer for widths 32 / 64 / 128 (every hidden layer of the nets):
 //
 //   dz = (dy + dy2) * act'(y);  dx = dz.W;  dW += dz^T.x (or x^T.dz);  db += colsum(dz)      reads dy, y, x once; writes dx once
+//   (ACT 1 tanh: act'(y) = 1 - y^2; ACT 2 ReLU: dz = y > 0 ? dy + dy2 : 0, a select as torch's threshold_backward)
 //
 // (reference: the autograd of nn.Linear + tanh in garage/torch/modules/multi_headed_mlp_module.py:134-149,
 // GraphConvolutionModule's H.W graph_conv_module.py:63, AttentionModule.linear_in attention_module.py:36.)
@@ -190,7 +191,8 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
     const long n_chunks = (R + ROWS - 1) / ROWS;
     long ch = blockIdx.x;
     int cb = 0;
-    // dz = dy * (1 - y^2) in place, and zero rows past the end of the last chunk (the DMA re-read a valid row there)
+    // dz = dy * (1 - y^2) (ACT 1) or y > 0 ? dy : 0 (ACT 2) in place, and zero rows past the end of the last chunk (the DMA
+    // re-read a valid row there)
     auto finish_tile = [&](float *buf, int rows) {
         float *Zs = buf, *Xs = buf + ZF;
         if (ACT || DY2) {
@@ -202,9 +204,12 @@ __global__ __launch_bounds__(TPB) void bwd_kernel(long R, int KR, const float *_
                     const float4 u = *reinterpret_cast<const float4 *>(D2s + p);
                     z.x += u.x; z.y += u.y; z.z += u.z; z.w += u.w;
                 }
-                if (ACT) {
+                if (ACT == 1) {
                     const float4 y = *reinterpret_cast<const float4 *>(Ys + p);
                     z.x *= fmaf(-y.x, y.x, 1.0f); z.y *= fmaf(-y.y, y.y, 1.0f); z.z *= fmaf(-y.z, y.z, 1.0f); z.w *= fmaf(-y.w, y.w, 1.0f);
+                } else if (ACT == 2) {
+                    const float4 y = *reinterpret_cast<const float4 *>(Ys + p);
+                    z.x = y.x > 0.0f ? z.x : 0.0f; z.y = y.y > 0.0f ? z.y : 0.0f; z.z = y.z > 0.0f ? z.z : 0.0f; z.w = y.w > 0.0f ? z.w : 0.0f;
                 }
                 if (p >= rows * O) z = make_float4(0.f, 0.f, 0.f, 0.f);
                 *reinterpret_cast<float4 *>(Zs + p) = z;
@@ -501,61 +506,69 @@ static int launch(long R, int KR, const float *x, const float *w, const float *d
 }  // namespace lin2
 
 // Returns 1 when this shape / alignment is not covered (the caller runs lin::bwd_kernel), else the launch status.
+// act: 0 identity, 1 tanh, 2 ReLU (y is the saved output when act != 0).  ReLU is instantiated only where the ReLU nets
+// reach (Obs-DP head 64 -> 32; CENT 128 -> 64, 64 -> 32 and the ragged first layer into 128); other shapes return 1.
 // DET: dw / db address row 0 of a slab (lin2::slab_row floats per workgroup), *grid receives the number of rows written.
 template <bool DET>
 static int bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                      const float *y, float *dx, float *dw, float *db, void *stream, int *grid) {
+                      const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid) {
     static const bool off = [] { const char *e = getenv("COMMARL_LIN_BWD"); return e && e[0] == 'o'; }();   // "old"
     if (off) return 1;
     const auto ok_w = [](int v) { return v == 32 || v == 64 || v == 128; };
     const hipStream_t st = (hipStream_t)stream;
     if (!ok_w(K) && ok_w(O) && K <= 128 && !dx && layout == 0 && !(((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)y) & 15) && !((uintptr_t)x & 3)) {
         // first layer (observation -> hidden): ragged input rows, no input gradient
-#define CM_RG(KT_, OT_) (y ? lin2::launch<KT_, OT_, 1, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
-                         : lin2::launch<KT_, OT_, 0, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid))
+#define CM_RG(KT_, OT_) (act == 1 ? lin2::launch<KT_, OT_, 1, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
+                         : act == 0 ? lin2::launch<KT_, OT_, 0, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) : 1)
+#define CM_RG_RELU(KT_, OT_) (act == 2 ? lin2::launch<KT_, OT_, 2, 0, true, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
+                              : CM_RG(KT_, OT_))
         const int kt = K <= 32 ? 2 : (K <= 64 ? 4 : 8);
         switch (kt * 1000 + O) {
         case 2032: return CM_RG(2, 2);
         case 2064: return CM_RG(2, 4);
-        case 2128: return CM_RG(2, 8);
+        case 2128: return CM_RG_RELU(2, 8);
         case 4032: return CM_RG(4, 2);
         case 4064: return CM_RG(4, 4);
-        case 4128: return CM_RG(4, 8);
+        case 4128: return CM_RG_RELU(4, 8);
         case 8032: return CM_RG(8, 2);
         case 8064: return CM_RG(8, 4);
-        case 8128: return CM_RG(8, 8);
+        case 8128: return CM_RG_RELU(8, 8);
         default: return 1;
         }
+#undef CM_RG_RELU
 #undef CM_RG
     }
     if (!ok_w(K) || !ok_w(O) || (K == 128 && O == 128)) return 1;
     const uintptr_t al = (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)y | (uintptr_t)dx;
     if (al & 15) return 1;
     if (layout == 1 && !(K == 64 && O == 64)) return 1;   // the [in][out] weights are the 64 x 64 graph-convolution ones
-#define CM_B2(KT_, OT_, L_) (y ? lin2::launch<KT_, OT_, 1, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
-                             : lin2::launch<KT_, OT_, 0, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid))
+#define CM_B2(KT_, OT_, L_) (act == 1 ? lin2::launch<KT_, OT_, 1, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
+                             : act == 0 ? lin2::launch<KT_, OT_, 0, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) : 1)
+#define CM_B2_RELU(KT_, OT_, L_) (act == 2 ? lin2::launch<KT_, OT_, 2, L_, false, 0, DET>(R, K, x, w, dy, dy2, y, dx, dw, db, st, nullptr, 0, nullptr, nullptr, grid) \
+                                  : CM_B2(KT_, OT_, L_))
     if (layout == 1) return CM_B2(4, 4, 1);
     switch (K * 1000 + O) {
     case 32032: return CM_B2(2, 2, 0);
     case 32064: return CM_B2(2, 4, 0);
     case 32128: return CM_B2(2, 8, 0);
-    case 64032: return CM_B2(4, 2, 0);
+    case 64032: return CM_B2_RELU(4, 2, 0);
     case 64064: return CM_B2(4, 4, 0);
     case 64128: return CM_B2(4, 8, 0);
     case 128032: return CM_B2(8, 2, 0);
-    case 128064: return CM_B2(8, 4, 0);
+    case 128064: return CM_B2_RELU(8, 4, 0);
     default: return 1;
     }
+#undef CM_B2_RELU
 #undef CM_B2
 }
 
 int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                      const float *y, float *dx, float *dw, float *db, void *stream) {
-    return bwd_stream<false>(R, K, O, x, w, layout, dy, dy2, y, dx, dw, db, stream, nullptr);
+                      const float *y, int act, float *dx, float *dw, float *db, void *stream) {
+    return bwd_stream<false>(R, K, O, x, w, layout, dy, dy2, y, act, dx, dw, db, stream, nullptr);
 }
 int linear_bwd_stream_det(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                          const float *y, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid) {
-    return bwd_stream<true>(R, K, O, x, w, layout, dy, dy2, y, dx, slab_dw, slab_db, stream, grid);
+                          const float *y, int act, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid) {
+    return bwd_stream<true>(R, K, O, x, w, layout, dy, dy2, y, act, dx, slab_dw, slab_db, stream, grid);
 }
 
 // Encoder backward in one pass (obs [R,d] -> a1 = tanh(.) [R,128] -> e = tanh(.) [R,64]): layer 2 as linear_bwd_stream

@@ -6,6 +6,8 @@
 //       per env row  obs[N*d] -> 128 tanh -> 64 tanh -> 32 tanh -> N*5 logits -> per-agent softmax ..., sample
 //   * GaussianMLPBaseline.forward (com_marl/torch/baselines/gaussian_mlp_baseline.py:100-115):
 //       per env row  obs[N*d] -> 64 tanh -> 64 tanh -> 64 tanh -> 1
+// With hidden_nonlinearity=F.relu the policies' hidden layers (Obs-DP: the head's 32, CENT: all three) take ReLU instead
+// of tanh: per layer, bit l of relu_mask selects it.
 // Layer sizes are run-time values (cm_mlp_weights); every layer is  v_mfma_f32_16x16x4_f32  (f32 in, f32
 // accumulate - the 1e-5 parity bar), 32 rows (two 16-row tiles) per 256-thread workgroup, activations ping-pong
 // between two LDS tiles, the first layer streams its (possibly thousands of columns wide) input through LDS in
@@ -26,7 +28,7 @@ __device__ __forceinline__ float fast_tanh(float x) {      // same form as cm_po
 }
 
 struct Args {
-    int rows, in_dim, n_layers, tanh_mask, sw;
+    int rows, in_dim, n_layers, tanh_mask, relu_mask, sw;
     int out_dim[MAXL];
     const float *wt[MAXL], *b[MAXL];
     const float *pk[MAXL];          // per-layer B fragments (cm_mlp_pack) or NULL: [ct][kq][lane][4], kq over ceil(K/16)
@@ -40,15 +42,21 @@ struct Args {
 
 extern __shared__ float smem[];
 
+// activation after layer l: 1 = tanh (bit l of tanh_mask), 2 = ReLU (bit l of relu_mask), 0 = none
+__device__ __forceinline__ int layer_act(const Args &a, int l) {
+    return ((a.tanh_mask >> l) & 1) ? 1 : (((a.relu_mask >> l) & 1) ? 2 : 0);
+}
+
 // k-slot mapping shared by A and B: lane group g = lane>>4 supplies k = 16*kq + 4*g + j at MFMA (kq, j), so a
-// lane's four A words per kq are contiguous (one ds_read_b128).
+// lane's four A words per kq are contiguous (one ds_read_b128).  ReLU as torch.relu: v < 0 ? 0 : v lets a NaN through
+// (fmaxf would turn it into 0).
 __device__ __forceinline__ void store_tile(float *out, int sw, int rt, int ct, int lane, const v4f &acc, float bias,
-                                           bool th) {
+                                           int act) {
     const int c = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const float v = acc[r] + bias;
-        out[(size_t)(rt * 16 + 4 * g + r) * sw + ct * 16 + c] = th ? fast_tanh(v) : v;
+        out[(size_t)(rt * 16 + 4 * g + r) * sw + ct * 16 + c] = act == 1 ? fast_tanh(v) : (act == 2 ? (v < 0.0f ? 0.0f : v) : v);
     }
 }
 
@@ -107,15 +115,15 @@ __global__ __launch_bounds__(TPB) void mlp_kernel(Args a) {
                 }
             }
         }
-        const bool th = a.tanh_mask & 1;
+        const int act = layer_act(a, 0);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int ct = wave + 4 * t;
             if (ct >= nct) continue;
             const int col = ct * 16 + c;
             const float bias = (a.b[0] && col < OUT) ? a.b[0][col] : 0.0f;
-            store_tile(buf0, sw, 0, ct, lane, acc[t][0], bias, th);
-            store_tile(buf0, sw, 1, ct, lane, acc[t][1], bias, th);
+            store_tile(buf0, sw, 0, ct, lane, acc[t][0], bias, act);
+            store_tile(buf0, sw, 1, ct, lane, acc[t][1], bias, act);
         }
     }
     __syncthreads();
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(TPB) void mlp_kernel(Args a) {
         const int K = a.out_dim[l - 1], OUT = a.out_dim[l];
         const int nct = (OUT + 15) >> 4, k16 = (K + 15) >> 4;
         const float *__restrict__ Wt = a.wt[l];
-        const bool th = (a.tanh_mask >> l) & 1;
+        const int act = layer_act(a, l);
         for (int ct = wave; ct < nct; ct += 4) {
             const int col = ct * 16 + c;
             v4f acc0 = (v4f){ 0.f, 0.f, 0.f, 0.f }, acc1 = (v4f){ 0.f, 0.f, 0.f, 0.f };
@@ -152,8 +160,8 @@ __global__ __launch_bounds__(TPB) void mlp_kernel(Args a) {
                 }
             }
             const float bias = (a.b[l] && col < OUT) ? a.b[l][col] : 0.0f;
-            store_tile(out, sw, 0, ct, lane, acc0, bias, th);
-            store_tile(out, sw, 1, ct, lane, acc1, bias, th);
+            store_tile(out, sw, 0, ct, lane, acc0, bias, act);
+            store_tile(out, sw, 1, ct, lane, acc1, bias, act);
         }
         __syncthreads();
         float *t = in; in = out; out = t;
@@ -238,7 +246,8 @@ static int fill(Args &a, const cm_mlp_weights *w, int32_t rows, const float *x) 
     if (w->n_layers < 1 || w->n_layers > MAXL) return set_error(CM_ERR_ARG, "mlp forward: 1..6 linear layers supported");
     if (w->in_dim < 1) return set_error(CM_ERR_ARG, "mlp forward: in_dim < 1");
     if (w->out_dim[0] > 128) return set_error(CM_ERR_ARG, "mlp forward: first layer wider than 128 outputs");
-    a.rows = rows; a.in_dim = w->in_dim; a.n_layers = w->n_layers; a.tanh_mask = w->tanh_mask; a.x = x;
+    if (w->tanh_mask & w->relu_mask) return set_error(CM_ERR_ARG, "mlp forward: a layer has both its tanh_mask and relu_mask bit set");
+    a.rows = rows; a.in_dim = w->in_dim; a.n_layers = w->n_layers; a.tanh_mask = w->tanh_mask; a.relu_mask = w->relu_mask; a.x = x;
     for (int l = 0; l < w->n_layers; ++l) {
         if (w->out_dim[l] < 1 || w->out_dim[l] > 1024) return set_error(CM_ERR_ARG, "mlp forward: layer width outside 1..1024");
         if (!w->wt[l]) return set_error(CM_ERR_ARG, "mlp forward: null layer weight");

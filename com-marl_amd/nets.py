@@ -38,20 +38,44 @@ class _Tanh(nn.Module):
         return torch.tanh(x)
 
 
+class _ReLU(nn.Module):
+    def forward(self, x):
+        return torch.relu(x)
+
+
+ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2       # activation codes of cm_linear_act_* (include/commarl.h)
+
+
+def hidden_act_code(hidden_nonlinearity):
+    """The reference runners' ``hidden_nonlinearity`` (F.relu if --hidden_nonlinearity relu else torch.tanh,
+    exp_runners/*/runner_*_{obsDP,cent}.py) -> ACT_TANH / ACT_RELU.  Anything else raises: there is no silent fallback."""
+    f = hidden_nonlinearity
+    if f is torch.tanh or f is torch.nn.functional.tanh or isinstance(f, nn.Tanh):
+        return ACT_TANH
+    if f is torch.relu or f is torch.nn.functional.relu or isinstance(f, nn.ReLU):
+        return ACT_RELU
+    raise NotImplementedError(f"hidden_nonlinearity={f!r} is not supported: use torch.tanh, torch.relu, F.tanh, F.relu, "
+                              "nn.Tanh() or nn.ReLU()")
+
+
 class MLPModule(nn.Module):
     """garage MultiHeadedMLPModule with one head (multi_headed_mlp_module.py:54-149):
-    ``_layers.{i}.linear`` (+tanh) then ``_output_layers.0.linear`` (+ optional nonlinearity).
-    Init order mirrors the reference: nn.Linear default init, then xavier_uniform_ / zeros_."""
+    ``_layers.{i}.linear`` (+ hidden activation: ``hidden_act`` 1 = tanh, 2 = ReLU) then ``_output_layers.0.linear``
+    (+ optional tanh).  Init order mirrors the reference: nn.Linear default init, then xavier_uniform_ / zeros_."""
 
-    def __init__(self, input_dim, output_dim, hidden_sizes, output_tanh=False):
+    def __init__(self, input_dim, output_dim, hidden_sizes, output_tanh=False, hidden_act=ACT_TANH):
         super().__init__()
+        if hidden_act not in (ACT_TANH, ACT_RELU):
+            raise NotImplementedError(f"hidden_act must be {ACT_TANH} (tanh) or {ACT_RELU} (ReLU)")
+        self._hidden_act = hidden_act
         self._layers = nn.ModuleList()
         prev = input_dim
         for size in hidden_sizes:
             lin = HipLinear(prev, size)
             nn.init.xavier_uniform_(lin.weight)
             nn.init.zeros_(lin.bias)
-            self._layers.append(nn.Sequential(OrderedDict(linear=lin, non_linearity=_Tanh())))
+            act = _Tanh() if hidden_act == ACT_TANH else _ReLU()
+            self._layers.append(nn.Sequential(OrderedDict(linear=lin, non_linearity=act)))
             prev = size
         lin = HipLinear(prev, output_dim)
         nn.init.xavier_uniform_(lin.weight)
@@ -63,7 +87,7 @@ class MLPModule(nn.Module):
 
     def forward(self, x):
         for layer in self._layers:
-            x = hip_linear(x, layer.linear, act=1)                       # Sequential(linear, tanh) as one fused op
+            x = hip_linear(x, layer.linear, act=self._hidden_act)         # Sequential(linear, activation) as one fused op
         out = self._output_layers[0]
         return hip_linear(x, out.linear, act=1 if len(out) > 1 else 0)
 
@@ -148,9 +172,20 @@ def _wgrad(a2d, b2d, want_colsum):
     return c, cs
 
 
-def _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y, dx, dw, db):
-    """cm_linear_act_backward, or its slab twin in deterministic mode."""
-    if _det():
+def _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y, dx, dw, db, act=None):
+    """cm_linear_act_backward (y given = tanh layer), or with ``act`` (0 / 1 / 2) cm_linear_act_backward_ex; in
+    deterministic mode their slab twins."""
+    if act is not None:
+        if _det():
+            nb = L.lib().cm_linear_act_backward_det_ws_bytes(R, K, O)
+            L.check(L.lib().cm_linear_act_backward_ex_det(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y),
+                                                          int(act), L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(L.slab(nb, w.device)), nb,
+                                                          L.current_stream()), "cm_linear_act_backward_ex_det")
+        else:
+            L.check(L.lib().cm_linear_act_backward_ex(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y),
+                                                      int(act), L.ptr(dx), L.ptr(dw), L.ptr(db), L.current_stream()),
+                    "cm_linear_act_backward_ex")
+    elif _det():
         nb = L.lib().cm_linear_act_backward_det_ws_bytes(R, K, O)
         L.check(L.lib().cm_linear_act_backward_det(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y), L.ptr(dx),
                                                    L.ptr(dw), L.ptr(db), L.ptr(L.slab(nb, w.device)), nb, L.current_stream()),
@@ -226,7 +261,9 @@ class _LinearActFn(torch.autograd.Function):
         dw = torch.zeros_like(w)
         db = torch.zeros(O, dtype=torch.float32, device=w.device) if has_bias else None
         with torch.cuda.device(w.device):
-            _linear_act_backward(x2.shape[0], K, O, x2, w, layout, dy2, None, y, dx, dw, db)
+            # ReLU names its activation (cm_linear_act_backward_ex); tanh / identity keep the entry points they always used
+            _linear_act_backward(x2.shape[0], K, O, x2, w, layout, dy2, None, y, dx, dw, db,
+                                 act=act if act == ACT_RELU else None)
         return (None if dx is None else dx.reshape(shape)), dw, db, None, None
 
 
@@ -235,14 +272,16 @@ def _fused_ok(x, weight):
             and max(weight.shape) <= 128 and os.environ.get("COMMARL_FUSED_LINEAR", "1") != "0")
 
 
-def hip_linear(x, lin, act=0):
-    """nn.Linear (+ tanh when act) forward; on the GPU with autograd on it is the fused one-pass kernel pair."""
+def hip_linear(x, lin, act=ACT_NONE):
+    """nn.Linear followed by act (0 none, 1 tanh, 2 ReLU); on the GPU with autograd on it is the fused one-pass kernel pair."""
     if _fused_ok(x, lin.weight):
         return _LinearActFn.apply(x, lin.weight, lin.bias, act, 0)
     if x.is_cuda and torch.is_grad_enabled() and lin.weight.requires_grad and max(lin.weight.shape) <= 128:
         y = _LinearFn.apply(x, lin.weight, lin.bias)
     else:
         y = torch.nn.functional.linear(x, lin.weight, lin.bias)
+    if act == ACT_RELU:
+        return torch.relu(y)
     return torch.tanh(y) if act else y
 
 
@@ -1192,7 +1231,7 @@ class _RowMLPPolicy(_WeightPack):
     (cm_mlp_policy_forward, csrc/cm_mlp.hip) over the layer chain listed by ``_chain()``."""
 
     def _chain(self):
-        """-> list of (nn.Linear, tanh?) in forward order."""
+        """-> list of (nn.Linear, activation code) in forward order: 0 none, 1 (or True) tanh, 2 ReLU."""
         raise NotImplementedError
 
     def _pack_tensors(self):
@@ -1225,11 +1264,12 @@ class _RowMLPPolicy(_WeightPack):
         if len(chain) > L.MLP_MAX_LAYERS:
             raise L.CommarlError(f"fused MLP forward takes at most {L.MLP_MAX_LAYERS} linear layers")
         w = L.MlpWeights()
-        w.in_dim, w.n_layers, w.tanh_mask = chain[0][0].in_features, len(chain), 0
-        for i, (lin, th) in enumerate(chain):
+        w.in_dim, w.n_layers, w.tanh_mask, w.relu_mask = chain[0][0].in_features, len(chain), 0, 0
+        for i, (lin, act) in enumerate(chain):
             w.out_dim[i] = lin.out_features
             w.wt[i], w.b[i] = p[f"w{i}t"], p[f"b{i}"]
-            w.tanh_mask |= int(bool(th)) << i
+            w.tanh_mask |= int(int(act) == ACT_TANH) << i
+            w.relu_mask |= int(int(act) == ACT_RELU) << i
         return w
 
     def set_rng(self, seed, env_id_offset=0):
@@ -1331,13 +1371,17 @@ class DecCategoricalMLPPolicy(_RowMLPPolicy, MLPModule):
     first as in the reference) and ``encoder.*``."""
     _per_agent_rows = True
 
-    def __init__(self, env_spec, n_agents, hidden_sizes=(32, 32), name="DecCategoricalMLPPolicy", device="cpu",
-                 _embedding_dim=64, **unused):
+    def __init__(self, env_spec, n_agents, hidden_sizes=(32, 32), hidden_nonlinearity=torch.tanh,
+                 name="DecCategoricalMLPPolicy", device="cpu", _embedding_dim=64):
+        act = hidden_act_code(hidden_nonlinearity)
         self._n_agents = n_agents
         self._dec_obs_dim = self._obs_dim = int(env_spec.observation_space.flat_dim / n_agents)
         self._action_dim = env_spec.action_space.n
         self._embedding_dim = hidden_sizes[1]
-        MLPModule.__init__(self, self._embedding_dim, self._action_dim, (hidden_sizes[-1],))
+        # the head's hidden layers take hidden_nonlinearity (dec_categorical_mlp_policy.py:80-90); the encoder stays tanh
+        # (MLPEncoderModule's default, :92-95)
+        MLPModule.__init__(self, self._embedding_dim, self._action_dim, (hidden_sizes[-1],), hidden_act=act)
+        self.hidden_nonlinearity = "relu" if act == ACT_RELU else "tanh"      # a string: the net still pickles
         self.encoder = MLPModule(self._obs_dim, self._embedding_dim, (hidden_sizes[0],), output_tanh=True)
         self.device, self.name, self.step, self.centralized = device, name, 0, True
         self.seed, self.env_id_offset, self._policy_step = 1, 0, 0
@@ -1345,8 +1389,8 @@ class DecCategoricalMLPPolicy(_RowMLPPolicy, MLPModule):
 
     def _chain(self):
         e = self.encoder
-        return ([(l.linear, True) for l in e._layers] + [(e._output_layers[0].linear, True)]
-                + [(l.linear, True) for l in self._layers] + [(self._output_layers[0].linear, False)])
+        return ([(l.linear, ACT_TANH) for l in e._layers] + [(e._output_layers[0].linear, ACT_TANH)]
+                + [(l.linear, self._hidden_act) for l in self._layers] + [(self._output_layers[0].linear, ACT_NONE)])
 
     def _logits(self, obs_n, dist_adj=None, channels=None):
         """Raw per-agent logits [..., N, A] (what CentralizedMAPPO's one-launch surrogate loss consumes)."""
@@ -1363,19 +1407,21 @@ class CentralizedCategoricalMLPPolicy(_RowMLPPolicy, MLPModule):
     concatenated observation, N x 5 logits, agents' actions independent given the joint observation."""
     _per_agent_rows = False
 
-    def __init__(self, env_spec, n_agents, hidden_sizes=(32, 32), name="CentralizedCategoricalMLPPolicy", device="cpu",
-                 **unused):
+    def __init__(self, env_spec, n_agents, hidden_sizes=(32, 32), hidden_nonlinearity=torch.tanh,
+                 name="CentralizedCategoricalMLPPolicy", device="cpu"):
+        act = hidden_act_code(hidden_nonlinearity)                       # every hidden layer (centralized_...:40-50)
         self._n_agents = n_agents
         self._obs_dim = env_spec.observation_space.flat_dim
         self._dec_obs_dim = self._obs_dim // n_agents
         self._action_dim = env_spec.action_space.n
-        MLPModule.__init__(self, self._obs_dim, self._action_dim * n_agents, tuple(hidden_sizes))
+        MLPModule.__init__(self, self._obs_dim, self._action_dim * n_agents, tuple(hidden_sizes), hidden_act=act)
+        self.hidden_nonlinearity = "relu" if act == ACT_RELU else "tanh"
         self.device, self.name, self.step, self.centralized = device, name, 0, True
         self.seed, self.env_id_offset, self._policy_step = 1, 0, 0
         self.to(device)
 
     def _chain(self):
-        return [(l.linear, True) for l in self._layers] + [(self._output_layers[0].linear, False)]
+        return [(l.linear, self._hidden_act) for l in self._layers] + [(self._output_layers[0].linear, ACT_NONE)]
 
     def _logits(self, obs_n, dist_adj=None, channels=None):
         """Raw logits [..., N, A] (what CentralizedMAPPO's one-launch surrogate loss consumes)."""

@@ -305,12 +305,14 @@ int cm_chunk_tail(uint32_t *policy_step_base, uint32_t n_steps, const void *src0
 
 /* Plain row-wise MLPs: the non-communicating policies and the Gaussian baseline of the reference's Obs-DP / CENT
  * runners.  Layer l:  y = x . wt[l] + b[l]  (wt TRANSPOSED [in,out] as above), followed by tanh
- * when bit l of tanh_mask is set.  First layer at most 128 outputs; any layer at most 1024. */
+ * when bit l of tanh_mask is set, by ReLU (torch.relu: y < 0 ? 0 : y, NaN passes) when bit l of relu_mask is set
+ * (hidden_nonlinearity=F.relu); a layer with both bits set is refused (CM_ERR_ARG).  First layer at most 128 outputs;
+ * any layer at most 1024. */
 #define CM_MLP_MAX_LAYERS 6
 typedef struct cm_mlp_weights {
     int32_t in_dim, n_layers;
     int32_t out_dim[CM_MLP_MAX_LAYERS];
-    int32_t tanh_mask, _pad;
+    int32_t tanh_mask, relu_mask;
     const float *wt[CM_MLP_MAX_LAYERS];
     const float *b[CM_MLP_MAX_LAYERS];   /* NULL = no bias */
     const float *mfma_pack;              /* cm_mlp_pack() output (all layers, B fragments as in cm_policy_pack), or NULL:
@@ -374,7 +376,8 @@ int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, const float
 /* One dense per-agent layer of the PPO update, one HBM pass each way (csrc/cm_linear.hip).
  * w_layout 0: w is nn.Linear's [out,in] (multi_headed_mlp_module.py:134-149, attention_module.py:36);
  * w_layout 1: w is GraphConvolutionModule's [in,out] (graph_conv_module.py:63).  1 <= in, out <= 128.
- *   forward :  y[r][o] = act(bias[o] + sum_k x[r][k] w(k,o)),  act 0 = identity, 1 = tanh; bias may be NULL.
+ *   forward :  y[r][o] = act(bias[o] + sum_k x[r][k] w(k,o)),  act 0 = identity, 1 = tanh, 2 = ReLU (z < 0 ? 0 : z);
+ *              any other act is refused (CM_ERR_ARG); bias may be NULL.
  *   backward:  dz = (dy + dy2) * (1 - y^2) when y != NULL (tanh layer), dz = dy + dy2 when y == NULL; dy2 [R,out] or NULL
  *              is a second gradient flowing into the same output (saves the caller's accumulation pass);
  *              dx[r][k] = sum_o dz[r][o] w(k,o)   (dx may be NULL: first layer);
@@ -384,6 +387,12 @@ int cm_linear_act_forward(int64_t R, int32_t in_dim, int32_t out_dim, const floa
                           const float *bias, int32_t act, float *y, void *stream);
 int cm_linear_act_backward(int64_t R, int32_t in_dim, int32_t out_dim, const float *x, const float *w, int32_t w_layout,
                            const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db, void *stream);
+/* The same with the activation named: act 0 = identity (y unused, may be NULL), 1 = tanh (dz = (dy + dy2) * (1 - y^2)),
+ * 2 = ReLU (dz = y > 0 ? dy + dy2 : 0, a select as torch's threshold_backward: an inf / NaN gradient into a dead unit
+ * gives 0).  y is required when act != 0; any other act is refused (CM_ERR_ARG). */
+int cm_linear_act_backward_ex(int64_t R, int32_t in_dim, int32_t out_dim, const float *x, const float *w, int32_t w_layout,
+                              const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
+                              void *stream);
 
 /* Backward of the two-layer observation encoder (mlp_encoder_module: obs [R,d] -> a1 = tanh(W1 obs + b1) [R,128] ->
  * e = tanh(W2 a1 + b2) [R,64]; comm_base_net.py:80-84) in ONE pass over the saved activations: dz2 = (dy + dy2) * (1 - e^2),
@@ -482,6 +491,10 @@ size_t cm_linear_act_backward_det_ws_bytes(int64_t R, int32_t K, int32_t O);
 int cm_linear_act_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
                                const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
                                void *ws, size_t ws_bytes, void *stream);
+/* twin of cm_linear_act_backward_ex; the slab size is cm_linear_act_backward_det_ws_bytes(R, K, O) */
+int cm_linear_act_backward_ex_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                  const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
+                                  void *ws, size_t ws_bytes, void *stream);
 /* db2 and db1 are required here; returns 1 (nothing launched) where cm_encoder_backward does */
 size_t cm_encoder_backward_det_ws_bytes(int64_t R, int32_t d);
 int cm_encoder_backward_det(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,

@@ -231,6 +231,34 @@ def slab(nbytes, device):
     return torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=device)
 
 
+# deterministic update mode: default entry point -> (its slab twin, the twin's slab size).  A twin takes the default's
+# arguments up to its last output pointer (so bias_replicas of _r and the GaussWs of cm_gauss_nll_forward are dropped),
+# then (slab, slab bytes, stream).
+TWINS = {
+    "cm_linear_act_backward": ("cm_linear_act_backward_det", "cm_linear_act_backward_det_ws_bytes"),
+    "cm_linear_act_backward_ex": ("cm_linear_act_backward_ex_det", "cm_linear_act_backward_det_ws_bytes"),
+    "cm_encoder_backward": ("cm_encoder_backward_det", "cm_encoder_backward_det_ws_bytes"),
+    "cm_masked_agg_backward": ("cm_masked_agg_backward_det", "cm_masked_agg_backward_det_ws_bytes"),
+    "cm_masked_agg_backward_r": ("cm_masked_agg_backward_det", "cm_masked_agg_backward_det_ws_bytes"),
+    "cm_linear_wgrad": ("cm_linear_wgrad_det", "cm_linear_wgrad_det_ws_bytes"),
+    "cm_ppo_surrogate": ("cm_ppo_surrogate_det", "cm_ppo_surrogate_det_ws_bytes"),
+    "cm_gauss_nll_forward": ("cm_gauss_nll_forward_det", "cm_gauss_nll_forward_det_ws_bytes"),
+}
+
+
+def launch(name, args, ws_args):
+    """Entry point `name` with `args` (all but the stream) on the current stream -> its return code.  In deterministic mode
+    its twin instead (TWINS), with a slab of twin_ws_bytes(*ws_args) bytes on the current device."""
+    from . import deterministic
+    L = lib()
+    if not deterministic():
+        return getattr(L, name)(*args, current_stream())
+    twin, ws_bytes = TWINS[name]
+    nb = getattr(L, ws_bytes)(*ws_args)
+    n = len(_SIGNATURES[twin][1]) - 3
+    return getattr(L, twin)(*args[:n], ptr(slab(nb, "cuda")), nb, current_stream())
+
+
 def check(rc, what=""):
     if rc != 0:
         msg = lib().cm_last_error()

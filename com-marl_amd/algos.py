@@ -44,17 +44,10 @@ class _SurrogateFn(torch.autograd.Function):
         dl = torch.empty_like(lg) if need else None
         total = torch.empty((), dtype=torch.float64, device=dev)
         count = torch.empty((), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            if deterministic():                              # block sums summed in a fixed order (no f64 atomics)
-                nb = L.lib().cm_ppo_surrogate_det_ws_bytes(P, T)
-                L.check(L.lib().cm_ppo_surrogate_det(P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
-                                                     L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
-                                                     L.ptr(total), L.ptr(count), L.ptr(dl), L.ptr(L.slab(nb, dev)), nb, L.current_stream()),
-                        "cm_ppo_surrogate_det")
-            else:
-                L.check(L.lib().cm_ppo_surrogate(P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
-                                                 L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
-                                                 L.ptr(total), L.ptr(count), L.ptr(dl), L.current_stream()), "cm_ppo_surrogate")
+        with torch.cuda.device(dev):                         # (deterministic mode: block sums summed in a fixed order, no f64 atomics)
+            L.check(L.launch("cm_ppo_surrogate", (P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
+                                                  L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
+                                                  L.ptr(total), L.ptr(count), L.ptr(dl)), (P, T)), "cm_ppo_surrogate")
         ctx.dl = dl
         ctx.mark_non_differentiable(count)
         return total.to(torch.float32), count

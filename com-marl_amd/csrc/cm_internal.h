@@ -132,4 +132,21 @@ struct SlabSegs { SlabSeg s[4]; int n_seg; };
 int slab_reduce(const float *slab, int rows, int row_len, const SlabSegs &segs, hipStream_t st);
 // a workspace of `need` bytes is present (else -1 with cm_last_error text naming `what`)
 int slab_check(const void *ws, size_t ws_bytes, size_t need, const char *what);
+
+// ---- backward launchers called across translation units: return 1 when the shape / alignment is not covered (the caller
+// runs its generic kernel), else the launch status.  det: slab mode - the gradient outputs address their segments of slab
+// row 0 and *grid (when given) receives the number of rows written ----
+// cm_linear_bwd.hip: one dense layer, widths 32 / 64 / 128
+int linear_bwd_stream(bool det, long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
+                      const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid = nullptr);
+// cm_linear_bwd.hip: both encoder layers in one pass (slab row: dW2 | db2 | dW1 | db1, lin2_slab_row(d) floats)
+int encoder_bwd_chain(bool det, long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
+                      const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *stream, int *grid = nullptr);
+size_t lin2_slab_row(int d);
+// cm_ppo_mfma.hip: teams of 8 .. 128 on the matrix cores (slab row: d_bias, 64 floats)
+int agg_bwd_mfma(bool det, int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw,
+                 const float *out, const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream,
+                 int *grid = nullptr);
+int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,
+                  float *d_q, float *d_e, void *stream);
 }

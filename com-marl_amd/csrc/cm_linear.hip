@@ -295,17 +295,6 @@ __global__ __launch_bounds__(TPB, (MAXT == 8 ? 2 : 1)) void bwd_kernel(long R, i
 }  // namespace lin
 }  // namespace cm
 
-namespace cm {
-int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                      const float *y, int act, float *dx, float *dw, float *db, void *stream);   // cm_linear_bwd.hip: widths 32 / 64 / 128
-int encoder_bwd_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
-                      float *dw2, float *db2, float *dw1, float *db1, void *stream);
-int linear_bwd_stream_det(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                          const float *y, int act, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid);
-int encoder_bwd_chain_det(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
-                          float *slab, void *stream, int *grid);
-size_t lin2_slab_row(int d);                                                             // floats per workgroup of encoder_bwd_chain_det
-}
 using namespace cm;
 
 extern "C" int cm_linear_act_forward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
@@ -326,13 +315,11 @@ extern "C" int cm_linear_act_forward(int64_t R, int32_t K, int32_t O, const floa
     return CM_OK;
 }
 
-// act: 0 identity, 1 tanh, 2 ReLU (y required when act != 0).
+// The generic dense-layer backward (widths up to 128) for the shapes linear_bwd_stream does not cover.
 // DET: dw / db address row 0 of a slab (K O + O floats per workgroup); *grid receives the number of rows written
 template <bool DET>
-static int linear_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout, const float *dy,
-                           const float *dy2, const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid) {
-    if (const int rc = DET ? linear_bwd_stream_det(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, dw, db, stream, grid)
-                           : linear_bwd_stream(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, dw, db, stream); rc != 1) return rc;
+static int linear_bwd_generic(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout, const float *dy,
+                              const float *dy2, const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid) {
     const int OT = (O + 15) / 16, KT = (K + 15) / 16, NT = OT * KT;
     const size_t lds = ((size_t)lin::ROWS * (OT * 16 + 16) + (size_t)lin::ROWS * (KT * 16 + 16)) * sizeof(float);
     const long chunks = (R + lin::ROWS - 1) / lin::ROWS;
@@ -340,7 +327,7 @@ static int linear_backward(int64_t R, int32_t K, int32_t O, const float *x, cons
     static const int force = [] { const char *e = getenv("COMMARL_LIN_BLOCKS"); return e ? atoi(e) : 0; }();
     if (force > 0) blocks = (int)std::min<long>(chunks, force);
     if (DET) blocks = std::min(blocks, 512);               // the slab has min(chunks, 512) rows (cm_*_det_ws_bytes)
-    if (grid) *grid = blocks;
+    *grid = blocks;
     const hipStream_t st = (hipStream_t)stream;
     const int per_wave = (NT + 3) / 4;
     static unsigned long long once = 0;
@@ -361,34 +348,6 @@ static int linear_backward(int64_t R, int32_t K, int32_t O, const float *x, cons
     return CM_OK;
 }
 
-extern "C" int cm_linear_act_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
-                                      const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
-                                      void *stream) {
-    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward: null argument");
-    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward: 1 <= in, out <= 128 required");
-    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward: w_layout must be 0 ([out,in]) or 1 ([in,out])");
-    if (R <= 0) return CM_OK;
-    return linear_backward<false>(R, K, O, x, w, w_layout, dy, dy2, y, y ? 1 : 0, dx, dw, db, stream, nullptr);
-}
-
-// act checks shared by the two _ex entry points
-static int act_check(int32_t act, const float *y, const char *what) {
-    if (act < 0 || act > 2) return set_error(CM_ERR_ARG, std::string(what) + ": act must be 0 (identity), 1 (tanh) or 2 (ReLU)");
-    if (act != 0 && !y) return set_error(CM_ERR_ARG, std::string(what) + ": y (the layer's output) is required when act != 0");
-    return CM_OK;
-}
-
-extern "C" int cm_linear_act_backward_ex(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
-                                         const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
-                                         void *stream) {
-    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex: null argument");
-    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex: 1 <= in, out <= 128 required");
-    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex: w_layout must be 0 ([out,in]) or 1 ([in,out])");
-    if (const int rc = act_check(act, y, "cm_linear_act_backward_ex")) return rc;
-    if (R <= 0) return CM_OK;
-    return linear_backward<false>(R, K, O, x, w, w_layout, dy, dy2, act ? y : nullptr, act, dx, dw, db, stream, nullptr);
-}
-
 static size_t linear_slab_rows(int64_t R) { return (size_t)std::min<int64_t>((R + lin::ROWS - 1) / lin::ROWS, 512); }   // >= either kernel's grid
 
 extern "C" size_t cm_linear_act_backward_det_ws_bytes(int64_t R, int32_t K, int32_t O) {
@@ -396,49 +355,61 @@ extern "C" size_t cm_linear_act_backward_det_ws_bytes(int64_t R, int32_t K, int3
     return linear_slab_rows(R) * ((size_t)K * O + O) * sizeof(float);
 }
 
-// slab launch + ordered reduction of the two _det entry points (arguments checked by the caller)
-static int linear_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout, const float *dy,
-                               const float *dy2, const float *y, int act, float *dx, float *dw, float *db, void *ws, void *stream) {
+// The four cm_linear_act_backward* entry points.  ex: `act` is given (0 identity, 1 tanh, 2 ReLU; y required when act != 0);
+// otherwise the layer is tanh when y is given.  DET: the slab twin - ws is checked before anything runs and the per-workgroup
+// rows are summed into dw / db in index order afterwards.
+template <bool DET>
+static int linear_backward(const char *fn, bool ex, int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                           const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db, void *ws,
+                           size_t ws_bytes, void *stream) {
+    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, std::string(fn) + ": 1 <= in, out <= 128 required");
+    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, std::string(fn) + ": w_layout must be 0 ([out,in]) or 1 ([in,out])");
+    if (ex) {
+        if (act < 0 || act > 2) return set_error(CM_ERR_ARG, std::string(fn) + ": act must be 0 (identity), 1 (tanh) or 2 (ReLU)");
+        if (act != 0 && !y) return set_error(CM_ERR_ARG, std::string(fn) + ": y (the layer's output) is required when act != 0");
+        if (act == 0) y = nullptr;
+    } else {
+        act = y ? 1 : 0;
+    }
+    if (DET)
+        if (const int rc = slab_check(ws, ws_bytes, cm_linear_act_backward_det_ws_bytes(R, K, O), fn)) return rc;
+    if (R <= 0) return CM_OK;
     float *slab = static_cast<float *>(ws);
-    const int row = K * O + O;
+    float *gw = DET ? slab : dw, *gb = DET ? (db ? slab + (size_t)K * O : nullptr) : db;
     int grid = 0;
-    if (const int rc = linear_backward<true>(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, slab, db ? slab + (size_t)K * O : nullptr, stream, &grid))
-        return rc;
+    int rc = linear_bwd_stream(DET, R, K, O, x, w, w_layout, dy, dy2, y, act, dx, gw, gb, stream, &grid);
+    if (rc == 1) rc = linear_bwd_generic<DET>(R, K, O, x, w, w_layout, dy, dy2, y, act, dx, gw, gb, stream, &grid);
+    if (rc || !DET) return rc;
     SlabSegs segs{};
     segs.s[0] = { dw, 0, K * O };
     segs.s[1] = { db, K * O, O };
     segs.n_seg = db ? 2 : 1;
-    return slab_reduce(slab, grid, row, segs, (hipStream_t)stream);
+    return slab_reduce(slab, grid, K * O + O, segs, (hipStream_t)stream);
+}
+
+extern "C" int cm_linear_act_backward(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                      const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
+                                      void *stream) {
+    return linear_backward<false>(__func__, false, R, K, O, x, w, w_layout, dy, dy2, y, 0, dx, dw, db, nullptr, 0, stream);
+}
+
+extern "C" int cm_linear_act_backward_ex(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
+                                         const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
+                                         void *stream) {
+    return linear_backward<false>(__func__, true, R, K, O, x, w, w_layout, dy, dy2, y, act, dx, dw, db, nullptr, 0, stream);
 }
 
 extern "C" int cm_linear_act_backward_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
                                           const float *dy, const float *dy2, const float *y, float *dx, float *dw, float *db,
                                           void *ws, size_t ws_bytes, void *stream) {
-    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: null argument");
-    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: 1 <= in, out <= 128 required");
-    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_det: w_layout must be 0 ([out,in]) or 1 ([in,out])");
-    if (const int rc = slab_check(ws, ws_bytes, cm_linear_act_backward_det_ws_bytes(R, K, O), "cm_linear_act_backward_det")) return rc;
-    if (R <= 0) return CM_OK;
-    return linear_backward_det(R, K, O, x, w, w_layout, dy, dy2, y, y ? 1 : 0, dx, dw, db, ws, stream);
+    return linear_backward<true>(__func__, false, R, K, O, x, w, w_layout, dy, dy2, y, 0, dx, dw, db, ws, ws_bytes, stream);
 }
 
 extern "C" int cm_linear_act_backward_ex_det(int64_t R, int32_t K, int32_t O, const float *x, const float *w, int32_t w_layout,
                                              const float *dy, const float *dy2, const float *y, int32_t act, float *dx, float *dw, float *db,
                                              void *ws, size_t ws_bytes, void *stream) {
-    if (!x || !w || !dy || !dw) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex_det: null argument");
-    if (K < 1 || O < 1 || K > 128 || O > 128) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex_det: 1 <= in, out <= 128 required");
-    if (w_layout != 0 && w_layout != 1) return set_error(CM_ERR_ARG, "cm_linear_act_backward_ex_det: w_layout must be 0 ([out,in]) or 1 ([in,out])");
-    if (const int rc = act_check(act, y, "cm_linear_act_backward_ex_det")) return rc;
-    if (const int rc = slab_check(ws, ws_bytes, cm_linear_act_backward_det_ws_bytes(R, K, O), "cm_linear_act_backward_ex_det")) return rc;
-    if (R <= 0) return CM_OK;
-    return linear_backward_det(R, K, O, x, w, w_layout, dy, dy2, act ? y : nullptr, act, dx, dw, db, ws, stream);
-}
-
-extern "C" int cm_encoder_backward(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
-                                   const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *stream) {
-    if (!obs || !a1 || !e || !w2 || !dy || !dw2 || !dw1) return set_error(CM_ERR_ARG, "cm_encoder_backward: null argument");
-    if (R <= 0) return CM_OK;
-    return encoder_bwd_chain(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream);
+    return linear_backward<true>(__func__, true, R, K, O, x, w, w_layout, dy, dy2, y, act, dx, dw, db, ws, ws_bytes, stream);
 }
 
 extern "C" size_t cm_encoder_backward_det_ws_bytes(int64_t R, int32_t d) {
@@ -446,20 +417,36 @@ extern "C" size_t cm_encoder_backward_det_ws_bytes(int64_t R, int32_t d) {
     return linear_slab_rows(R) * lin2_slab_row(d) * sizeof(float);
 }
 
+// cm_encoder_backward and its slab twin (DET: one slab row of dW2 | db2 | dW1 | db1 per workgroup, summed in index order)
+template <bool DET>
+static int encoder_backward(const char *fn, int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2,
+                            const float *dy, const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *ws, size_t ws_bytes,
+                            void *stream) {
+    // the twin requires db2 and db1, the default does not
+    if (!obs || !a1 || !e || !w2 || !dy || !dw2 || !dw1 || (DET && (!db2 || !db1))) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    if (DET)
+        if (const int rc = slab_check(ws, ws_bytes, cm_encoder_backward_det_ws_bytes(R, d), fn)) return rc;
+    if (R <= 0) return CM_OK;
+    float *const out[4] = { dw2, db2, dw1, db1 };
+    const int off[4] = { 0, 128 * 64, 128 * 64 + 64, 128 * 64 + 64 + 128 * d }, len[4] = { 128 * 64, 64, 128 * d, 128 };
+    float *g[4];
+    for (int k = 0; k < 4; ++k) g[k] = DET ? static_cast<float *>(ws) + off[k] : out[k];
+    int grid = 0;
+    if (const int rc = encoder_bwd_chain(DET, R, d, obs, a1, e, w2, dy, dy2, g[0], g[1], g[2], g[3], stream, &grid); rc || !DET)
+        return rc;                                                          // 1: shape not covered
+    SlabSegs segs{};
+    for (int k = 0; k < 4; ++k) segs.s[k] = { out[k], off[k], len[k] };
+    segs.n_seg = 4;
+    return slab_reduce(static_cast<float *>(ws), grid, (int)lin2_slab_row(d), segs, (hipStream_t)stream);
+}
+
+extern "C" int cm_encoder_backward(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
+                                   const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *stream) {
+    return encoder_backward<false>(__func__, R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, nullptr, 0, stream);
+}
+
 extern "C" int cm_encoder_backward_det(int64_t R, int32_t d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
                                        const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *ws, size_t ws_bytes,
                                        void *stream) {
-    if (!obs || !a1 || !e || !w2 || !dy || !dw2 || !dw1 || !db2 || !db1) return set_error(CM_ERR_ARG, "cm_encoder_backward_det: null argument");
-    if (const int rc = slab_check(ws, ws_bytes, cm_encoder_backward_det_ws_bytes(R, d), "cm_encoder_backward_det")) return rc;
-    if (R <= 0) return CM_OK;
-    float *slab = static_cast<float *>(ws);
-    int grid = 0;
-    if (const int rc = encoder_bwd_chain_det(R, d, obs, a1, e, w2, dy, dy2, slab, stream, &grid)) return rc;   // 1: shape not covered
-    SlabSegs segs{};
-    segs.s[0] = { dw2, 0, 128 * 64 };
-    segs.s[1] = { db2, 128 * 64, 64 };
-    segs.s[2] = { dw1, 128 * 64 + 64, 128 * d };
-    segs.s[3] = { db1, 128 * 64 + 64 + 128 * d, 128 };
-    segs.n_seg = 4;
-    return slab_reduce(slab, grid, (int)lin2_slab_row(d), segs, (hipStream_t)stream);
+    return encoder_backward<true>(__func__, R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, ws, ws_bytes, stream);
 }

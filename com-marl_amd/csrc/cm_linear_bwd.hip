@@ -562,13 +562,10 @@ static int bwd_stream(long R, int K, int O, const float *x, const float *w, int 
 #undef CM_B2
 }
 
-int linear_bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                      const float *y, int act, float *dx, float *dw, float *db, void *stream) {
-    return bwd_stream<false>(R, K, O, x, w, layout, dy, dy2, y, act, dx, dw, db, stream, nullptr);
-}
-int linear_bwd_stream_det(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
-                          const float *y, int act, float *dx, float *slab_dw, float *slab_db, void *stream, int *grid) {
-    return bwd_stream<true>(R, K, O, x, w, layout, dy, dy2, y, act, dx, slab_dw, slab_db, stream, grid);
+int linear_bwd_stream(bool det, long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
+                      const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid) {
+    return det ? bwd_stream<true>(R, K, O, x, w, layout, dy, dy2, y, act, dx, dw, db, stream, grid)
+               : bwd_stream<false>(R, K, O, x, w, layout, dy, dy2, y, act, dx, dw, db, stream, grid);
 }
 
 // Encoder backward in one pass (obs [R,d] -> a1 = tanh(.) [R,128] -> e = tanh(.) [R,64]): layer 2 as linear_bwd_stream
@@ -586,17 +583,11 @@ static int encoder_chain(long R, int d, const float *obs, const float *a1, const
     return lin2::launch<8, 4, 1, 0, false, 64, DET>(R, 128, a1, w2, dy, dy2, e, nullptr, dw2, db2, st, obs, d, dw1, db1, grid);
 }
 
-int encoder_bwd_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
-                      float *dw2, float *db2, float *dw1, float *db1, void *stream) {
-    return encoder_chain<false>(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream, nullptr);
+int encoder_bwd_chain(bool det, long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
+                      const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *stream, int *grid) {
+    return det ? encoder_chain<true>(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream, grid)
+               : encoder_chain<false>(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream, grid);
 }
 size_t lin2_slab_row(int d) { return lin2::slab_row(128, 64, d); }
-
-// slab mode: one slab row (lin2::slab_row(128, 64, d) floats) per workgroup, laid out dW2 | db2 | dW1 | db1
-int encoder_bwd_chain_det(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
-                          float *slab, void *stream, int *grid) {
-    float *dw2 = slab, *db2 = dw2 + 128 * 64, *dw1 = db2 + 64, *db1 = dw1 + (size_t)128 * d;
-    return encoder_chain<true>(R, d, obs, a1, e, w2, dy, dy2, dw2, db2, dw1, db1, stream, grid);
-}
 
 }  // namespace cm

@@ -836,14 +836,6 @@ __global__ __launch_bounds__(256) void entropy_gae_kernel(int T, int N, int A, c
     }
 }
 
-// cm_ppo_mfma.hip: teams of 8 .. 128 on the matrix cores (return 1 = shape not covered)
-int agg_bwd_mfma(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
-                 const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream);
-int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,
-                  float *d_q, float *d_e, void *stream);
-int agg_bwd_mfma_det(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
-                     const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *slab_bias, void *stream, int *grid);
-
 // COMMARL_QUAD_BWD=0: teams of 4 take the generic aggregation / attention backward kernels (A/B and test hook)
 static bool quad_bwd_on() {
     static const bool v = [] { const char *e = getenv("COMMARL_QUAD_BWD"); return !(e && e[0] == '0'); }();
@@ -1058,47 +1050,94 @@ extern "C" int cm_masked_agg_forward(int32_t S, int32_t N, int32_t E, const floa
     return CM_OK;
 }
 
+extern "C" size_t cm_masked_agg_backward_det_ws_bytes(int32_t S, int32_t N, int32_t E) {
+    if (S <= 0 || N < 1 || E < 1) return 0;
+    return (size_t)std::min<int32_t>(S, 2048) * E * sizeof(float);        // every backward kernel's grid is <= min(S, 2048)
+}
+
+// cm_masked_agg_backward(_r) and the slab twin (DET: one 64-float row of d_bias per workgroup, summed in index order)
+template <bool DET>
+static int masked_agg_backward(const char *fn, int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                               const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
+                               const float *d_out, float *d_attn, float *d_hw, float *d_bias, int32_t bias_replicas, void *ws,
+                               size_t ws_bytes, void *stream) {
+    if (!attn || !hw || !out || !d_out || !d_attn || !d_hw) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    if (bias_replicas < 1) return set_error(CM_ERR_ARG, std::string(fn) + ": bias_replicas >= 1 required");
+    if (E != 64) return set_error(CM_ERR_ARG, std::string(fn) + ": embedding dim 64 only");
+    if (DET)
+        if (const int rc = slab_check(ws, ws_bytes, cm_masked_agg_backward_det_ws_bytes(S, N, E), fn)) return rc;
+    if (S <= 0) return CM_OK;
+    if (DET && !d_bias)   // the twin without a bias gradient has no cross-workgroup sum left: the default kernels
+        return cm_masked_agg_backward_r(S, N, E, attn, dist_adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, nullptr, 1, stream);
+    const hipStream_t st = (hipStream_t)stream;
+    float *const slab = static_cast<float *>(ws), *const gb = DET ? slab : d_bias;
+    int grid = 0;
+    if (N == 4 && quad_bwd_on() && !(((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw) & 15)) {
+        // small batches: fewer workgroups looping (the bias atomics again: 2 500 envs take 11.6 us on 64 workgroups, 19 on 157)
+        const long chunks = ((long)S + 15) / 16;
+        grid = (int)(chunks <= 512 ? std::min<long>(chunks, 64) : std::min<long>(chunks, 2048));
+        static const int force = [] { const char *e = getenv("COMMARL_AGG4_BLOCKS"); return e ? atoi(e) : 0; }();
+        if (!DET && force > 0) grid = std::min(grid, force);   // the COMMARL_AGG4_BLOCKS override applies in default mode only
+        // (slab mode: bias_reps = the grid size, every workgroup stores its own row)
+        hipLaunchKernelGGL(agg_bwd4_kernel<DET>, dim3(grid), dim3(256), 0, st, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
+                           out_minus, d_out, d_attn, d_hw, gb, DET ? grid : (int)bias_replicas);
+        CM_HIP(hipGetLastError());
+    } else if (const int rc = agg_bwd_mfma(DET, S, N, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, gb,
+                                           stream, &grid); rc != 1) {
+        if (rc) return rc;
+    } else {
+        const size_t lds = agg_lds_bwd(N, E);
+        if (lds > 160 * 1024) return set_error(CM_ERR_ARG, std::string(fn) + ": n_agents too large");
+        static unsigned long long once = 0;
+        if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<64, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
+        const int epb = agg_epb(N);
+        grid = (int)std::min<long>((S + epb - 1) / epb, 256 * 4);
+        hipLaunchKernelGGL((agg_bwd_kernel<64, DET>), dim3(grid), dim3(TPB), lds, st, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, out,
+                           out_minus, d_out, d_attn, d_hw, gb);
+        CM_HIP(hipGetLastError());
+    }
+    if (!DET) return CM_OK;
+    SlabSegs segs{};
+    segs.s[0] = { d_bias, 0, 64 };
+    segs.n_seg = 1;
+    return slab_reduce(slab, grid, 64, segs, st);
+}
+
 extern "C" int cm_masked_agg_backward(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
                                       const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
                                       const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream) {
     return cm_masked_agg_backward_r(S, N, E, attn, dist_adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, 1, stream);
 }
 
+// (both default entry points land here: their messages name the family)
 extern "C" int cm_masked_agg_backward_r(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
                                         const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
                                         const float *d_out, float *d_attn, float *d_hw, float *d_bias, int32_t bias_replicas, void *stream) {
-    if (!attn || !hw || !out || !d_out || !d_attn || !d_hw) return set_error(CM_ERR_ARG, "cm_masked_agg_backward: null argument");
-    if (bias_replicas < 1) return set_error(CM_ERR_ARG, "cm_masked_agg_backward: bias_replicas >= 1 required");
-    if (E != 64) return set_error(CM_ERR_ARG, "cm_masked_agg_backward: embedding dim 64 only");
-    if (S <= 0) return CM_OK;
-    if (N == 4 && quad_bwd_on() && !(((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw) & 15)) {
-        // small batches: fewer workgroups looping (the bias atomics again: 2 500 envs take 11.6 us on 64 workgroups, 19 on 157)
-        const long chunks = ((long)S + 15) / 16;
-        int blocks = (int)(chunks <= 512 ? std::min<long>(chunks, 64) : std::min<long>(chunks, 2048));
-        static const int force = [] { const char *e = getenv("COMMARL_AGG4_BLOCKS"); return e ? atoi(e) : 0; }();
-        if (force > 0) blocks = std::min(blocks, force);
-        hipLaunchKernelGGL(agg_bwd4_kernel<>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
-                           out_minus, d_out, d_attn, d_hw, d_bias, (int)bias_replicas);
-        CM_HIP(hipGetLastError());
-        return CM_OK;
-    }
-    if (const int rc = agg_bwd_mfma(S, N, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, stream); rc != 1)
-        return rc;
-    const size_t lds = agg_lds_bwd(N, E);
-    if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "cm_masked_agg_backward: n_agents too large");
-    static unsigned long long once = 0;
-    if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
-    const int epb = agg_epb(N);
-    const int blocks = (int)std::min<long>((S + epb - 1) / epb, 256 * 4);
-    hipLaunchKernelGGL(agg_bwd_kernel<64>, dim3(blocks), dim3(TPB), lds, (hipStream_t)stream, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return masked_agg_backward<false>("cm_masked_agg_backward", S, N, E, attn, dist_adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn,
+                                      d_hw, d_bias, bias_replicas, nullptr, 0, stream);
 }
 
-extern "C" int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a,
-                               void *stream) {
-    if (!a || !b || !c) return set_error(CM_ERR_ARG, "cm_linear_wgrad: null argument");
-    if (P < 1 || Q < 1 || P > 128 || Q > 128) return set_error(CM_ERR_ARG, "cm_linear_wgrad: 1 <= P, Q <= 128 required");
+extern "C" int cm_masked_agg_backward_det(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                                          const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
+                                          const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *ws, size_t ws_bytes,
+                                          void *stream) {
+    return masked_agg_backward<true>(__func__, S, N, E, attn, dist_adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, 1,
+                                     ws, ws_bytes, stream);
+}
+
+extern "C" size_t cm_linear_wgrad_det_ws_bytes(int64_t R, int32_t P, int32_t Q) {
+    if (R <= 0 || P < 1 || Q < 1) return 0;
+    return (size_t)std::min<int64_t>((R + WG_ROWS - 1) / WG_ROWS, 512) * ((size_t)P * Q + P) * sizeof(float);
+}
+
+// cm_linear_wgrad and its slab twin (DET: C and colsum_a from one P Q + P float row per workgroup, summed in index order)
+template <bool DET>
+static int linear_wgrad(const char *fn, int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a, void *ws,
+                        size_t ws_bytes, void *stream) {
+    if (!a || !b || !c) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    if (P < 1 || Q < 1 || P > 128 || Q > 128) return set_error(CM_ERR_ARG, std::string(fn) + ": 1 <= P, Q <= 128 required");
+    if (DET)
+        if (const int rc = slab_check(ws, ws_bytes, cm_linear_wgrad_det_ws_bytes(R, P, Q), fn)) return rc;
     if (R <= 0) return CM_OK;
     const int PT = (P + 15) / 16, QT = (Q + 15) / 16, NT = PT * QT;
     const size_t lds = ((size_t)WG_ROWS * (PT * 16 + 16) + (size_t)WG_ROWS * (QT * 16 + 16)) * sizeof(float);
@@ -1108,100 +1147,35 @@ extern "C" int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, 
     const int per_wave = (NT + 3) / 4;
     static unsigned long long once = 0;
     if (cm::dev_first(once)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<16, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<8, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<4, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<2, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<1, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
-#define CM_WG(M) hipLaunchKernelGGL(wgrad_kernel<M>, dim3(blocks), dim3(TPB), lds, st, (long)R, P, Q, a, b, c, colsum_a)
+    float *const slab = static_cast<float *>(ws);
+    float *const gc = DET ? slab : c, *const gs = DET ? (colsum_a ? slab + (size_t)P * Q : nullptr) : colsum_a;
+#define CM_WG(M) hipLaunchKernelGGL((wgrad_kernel<M, DET>), dim3(blocks), dim3(TPB), lds, st, (long)R, P, Q, a, b, gc, gs)
     if (per_wave <= 1) CM_WG(1); else if (per_wave <= 2) CM_WG(2); else if (per_wave <= 4) CM_WG(4);
     else if (per_wave <= 8) CM_WG(8); else CM_WG(16);
 #undef CM_WG
     CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-// ---- deterministic twins (slab mode, include/commarl.h "Deterministic update mode") ----
-extern "C" size_t cm_masked_agg_backward_det_ws_bytes(int32_t S, int32_t N, int32_t E) {
-    if (S <= 0 || N < 1 || E < 1) return 0;
-    return (size_t)std::min<int32_t>(S, 2048) * E * sizeof(float);        // every backward kernel's grid is <= min(S, 2048)
-}
-
-extern "C" int cm_masked_agg_backward_det(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
-                                          const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
-                                          const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *ws, size_t ws_bytes,
-                                          void *stream) {
-    if (!attn || !hw || !out || !d_out || !d_attn || !d_hw) return set_error(CM_ERR_ARG, "cm_masked_agg_backward_det: null argument");
-    if (E != 64) return set_error(CM_ERR_ARG, "cm_masked_agg_backward_det: embedding dim 64 only");
-    if (const int rc = slab_check(ws, ws_bytes, cm_masked_agg_backward_det_ws_bytes(S, N, E), "cm_masked_agg_backward_det")) return rc;
-    if (S <= 0) return CM_OK;
-    if (!d_bias)   // no cross-workgroup sum left: the default kernels
-        return cm_masked_agg_backward_r(S, N, E, attn, dist_adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, nullptr, 1, stream);
-    const hipStream_t st = (hipStream_t)stream;
-    float *slab = static_cast<float *>(ws);
-    int grid = 0;
-    if (N == 4 && quad_bwd_on() && !(((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw) & 15)) {
-        const long chunks = ((long)S + 15) / 16;
-        grid = (int)(chunks <= 512 ? std::min<long>(chunks, 64) : std::min<long>(chunks, 2048));
-        hipLaunchKernelGGL(agg_bwd4_kernel<true>, dim3(grid), dim3(256), 0, st, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
-                           out_minus, d_out, d_attn, d_hw, slab, grid);
-        CM_HIP(hipGetLastError());
-    } else if (const int rc = agg_bwd_mfma_det(S, N, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, slab, stream, &grid);
-               rc != 1) {
-        if (rc) return rc;
-    } else {
-        const size_t lds = agg_lds_bwd(N, E);
-        if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "cm_masked_agg_backward_det: n_agents too large");
-        static unsigned long long once = 0;
-        if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
-        const int epb = agg_epb(N);
-        grid = (int)std::min<long>((S + epb - 1) / epb, 256 * 4);
-        hipLaunchKernelGGL((agg_bwd_kernel<64, true>), dim3(grid), dim3(TPB), lds, st, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, out, out_minus,
-                           d_out, d_attn, d_hw, slab);
-        CM_HIP(hipGetLastError());
-    }
-    SlabSegs segs{};
-    segs.s[0] = { d_bias, 0, 64 };
-    segs.n_seg = 1;
-    return slab_reduce(slab, grid, 64, segs, st);
-}
-
-extern "C" size_t cm_linear_wgrad_det_ws_bytes(int64_t R, int32_t P, int32_t Q) {
-    if (R <= 0 || P < 1 || Q < 1) return 0;
-    return (size_t)std::min<int64_t>((R + WG_ROWS - 1) / WG_ROWS, 512) * ((size_t)P * Q + P) * sizeof(float);
-}
-
-extern "C" int cm_linear_wgrad_det(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a, void *ws,
-                                   size_t ws_bytes, void *stream) {
-    if (!a || !b || !c) return set_error(CM_ERR_ARG, "cm_linear_wgrad_det: null argument");
-    if (P < 1 || Q < 1 || P > 128 || Q > 128) return set_error(CM_ERR_ARG, "cm_linear_wgrad_det: 1 <= P, Q <= 128 required");
-    if (const int rc = slab_check(ws, ws_bytes, cm_linear_wgrad_det_ws_bytes(R, P, Q), "cm_linear_wgrad_det")) return rc;
-    if (R <= 0) return CM_OK;
-    const int PT = (P + 15) / 16, QT = (Q + 15) / 16, NT = PT * QT;
-    const size_t lds = ((size_t)WG_ROWS * (PT * 16 + 16) + (size_t)WG_ROWS * (QT * 16 + 16)) * sizeof(float);
-    const int blocks = (int)std::min<long>((R + WG_ROWS - 1) / WG_ROWS, 512);
-    const hipStream_t st = (hipStream_t)stream;
-    const int per_wave = (NT + 3) / 4;
-    static unsigned long long once = 0;
-    if (cm::dev_first(once)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    float *slab = static_cast<float *>(ws);
-#define CM_WG(M) hipLaunchKernelGGL((wgrad_kernel<M, true>), dim3(blocks), dim3(TPB), lds, st, (long)R, P, Q, a, b, slab, colsum_a ? slab + (size_t)P * Q : nullptr)
-    if (per_wave <= 1) CM_WG(1); else if (per_wave <= 2) CM_WG(2); else if (per_wave <= 4) CM_WG(4);
-    else if (per_wave <= 8) CM_WG(8); else CM_WG(16);
-#undef CM_WG
-    CM_HIP(hipGetLastError());
+    if (!DET) return CM_OK;
     SlabSegs segs{};
     segs.s[0] = { c, 0, P * Q };
     segs.s[1] = { colsum_a, P * Q, P };
     segs.n_seg = colsum_a ? 2 : 1;
     return slab_reduce(slab, blocks, P * Q + P, segs, st);
+}
+
+extern "C" int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a,
+                               void *stream) {
+    return linear_wgrad<false>(__func__, R, P, Q, a, b, c, colsum_a, nullptr, 0, stream);
+}
+
+extern "C" int cm_linear_wgrad_det(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a, void *ws,
+                                   size_t ws_bytes, void *stream) {
+    return linear_wgrad<true>(__func__, R, P, Q, a, b, c, colsum_a, ws, ws_bytes, stream);
 }
 
 static size_t attn_lds(int N, int E) { const int epb = agg_epb(N), rows = epb * N; return ((size_t)rows * (E + 4) * 2 + (size_t)rows * (N | 1)) * 4; }
@@ -1264,20 +1238,53 @@ extern "C" int cm_gae(int32_t P, int32_t T, const float *rewards, const float *b
     return CM_OK;
 }
 
+extern "C" size_t cm_ppo_surrogate_det_ws_bytes(int32_t P, int32_t T) {
+    if (P <= 0 || T <= 0) return 0;
+    return (size_t)(((long)P * T + 255) / 256) * sizeof(double);
+}
+
+// cm_ppo_surrogate and its slab twin (DET: one f64 block sum per workgroup, summed by slab_total_kernel in a fixed order)
+template <bool DET>
+static int ppo_surrogate(const char *fn, int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
+                         const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff, int32_t add_entropy,
+                         double *total, int64_t *count, float *dlogits, void *ws, size_t ws_bytes, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const bool empty = P <= 0 || T <= 0, no_input = !logits || !actions || !old_ll || !adv || !lens;
+    if (!total || !count) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    if (A < 1 || A > PPO_MAX_A || N < 1) return set_error(CM_ERR_ARG, std::string(fn) + ": 1 <= n_actions <= 8 and n_agents >= 1 required");
+    if (DET) {   // the twin checks its pointers and the slab before clearing total / count, the default clears them first
+        if (!empty && no_input) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+        if (const int rc = slab_check(ws, ws_bytes, cm_ppo_surrogate_det_ws_bytes(P, T), fn)) return rc;
+    }
+    CM_HIP(hipMemsetAsync(total, 0, sizeof(double), st));      // an empty minibatch still reports (0, 0)
+    CM_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), st));     // (an integer sum: the default atomics are exact)
+    if (empty) return CM_OK;
+    if (no_input) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    const long S = (long)P * T;
+    const int blocks = (int)((S + 255) / 256);
+    double *const slab = static_cast<double *>(ws);
+    hipLaunchKernelGGL(ppo_surrogate_kernel<DET>, dim3((unsigned)blocks), dim3(256), 0, st, P, T, N, A, logits, actions, old_ll, adv, lens,
+                       clip, ent_coeff, add_entropy, DET ? slab : total, (long long *)count, dlogits);
+    CM_HIP(hipGetLastError());
+    if (!DET) return CM_OK;
+    hipLaunchKernelGGL(slab_total_kernel, dim3(1), dim3(256), 0, st, slab, blocks, total);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
 extern "C" int cm_ppo_surrogate(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
                                 const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff,
                                 int32_t add_entropy, double *total, int64_t *count, float *dlogits, void *stream) {
-    if (!total || !count) return set_error(CM_ERR_ARG, "cm_ppo_surrogate: null argument");
-    if (A < 1 || A > PPO_MAX_A || N < 1) return set_error(CM_ERR_ARG, "cm_ppo_surrogate: 1 <= n_actions <= 8 and n_agents >= 1 required");
-    CM_HIP(hipMemsetAsync(total, 0, sizeof(double), (hipStream_t)stream));      // an empty minibatch still reports (0, 0)
-    CM_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), (hipStream_t)stream));
-    if (P <= 0 || T <= 0) return CM_OK;
-    if (!logits || !actions || !old_ll || !adv || !lens) return set_error(CM_ERR_ARG, "cm_ppo_surrogate: null argument");
-    const long S = (long)P * T;
-    hipLaunchKernelGGL(ppo_surrogate_kernel<>, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, T, N, A, logits, actions,
-                       old_ll, adv, lens, clip, ent_coeff, add_entropy, total, (long long *)count, dlogits);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return ppo_surrogate<false>(__func__, P, T, N, A, logits, actions, old_ll, adv, lens, clip, ent_coeff, add_entropy, total, count, dlogits,
+                                nullptr, 0, stream);
+}
+
+extern "C" int cm_ppo_surrogate_det(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
+                                    const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff,
+                                    int32_t add_entropy, double *total, int64_t *count, float *dlogits, void *ws, size_t ws_bytes,
+                                    void *stream) {
+    return ppo_surrogate<true>(__func__, P, T, N, A, logits, actions, old_ll, adv, lens, clip, ent_coeff, add_entropy, total, count, dlogits,
+                               ws, ws_bytes, stream);
 }
 
 extern "C" int cm_entropy_gae(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const float *rewards,
@@ -1293,15 +1300,40 @@ extern "C" int cm_entropy_gae(int32_t P, int32_t T, int32_t N, int32_t A, const 
     return CM_OK;
 }
 
-extern "C" int cm_gauss_nll_forward(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std, float min_log_std,
-                                    int32_t has_min, float *out, void *ws, void *stream) {
-    if (!per_agent || !returns || !log_std || !out || !ws) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward: null argument");
-    if (S < 1 || N < 1) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward: S >= 1 and n_agents >= 1 required");
+extern "C" size_t cm_gauss_nll_forward_det_ws_bytes(int64_t S) {
+    if (S < 1) return 0;
+    return (size_t)std::min<long>((S + 255) / 256, 256) * sizeof(double);
+}
+
+// cm_gauss_nll_forward and its slab twin (DET: one f64 block sum per workgroup, gauss_nll_finish_kernel ends the launch)
+template <bool DET>
+static int gauss_nll_forward(const char *fn, int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std,
+                             float min_log_std, int32_t has_min, float *out, void *ws, size_t ws_bytes, void *stream) {
+    // the default requires its GaussWs; the twin's ws is the slab, checked by slab_check
+    if (!per_agent || !returns || !log_std || !out || (!DET && !ws)) return set_error(CM_ERR_ARG, std::string(fn) + ": null argument");
+    if (S < 1 || N < 1) return set_error(CM_ERR_ARG, std::string(fn) + ": S >= 1 and n_agents >= 1 required");
+    if (DET)
+        if (const int rc = slab_check(ws, ws_bytes, cm_gauss_nll_forward_det_ws_bytes(S), fn)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
     const int blocks = (int)std::min<long>((S + 255) / 256, 256);
-    hipLaunchKernelGGL(gauss_nll_fwd_kernel<>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
+    hipLaunchKernelGGL(gauss_nll_fwd_kernel<DET>, dim3(blocks), dim3(256), 0, st, (long)S, N, per_agent, returns, log_std, min_log_std,
                        has_min, out, reinterpret_cast<GaussWs *>(ws));
     CM_HIP(hipGetLastError());
+    if (!DET) return CM_OK;
+    hipLaunchKernelGGL(gauss_nll_finish_kernel, dim3(1), dim3(256), 0, st, (long)S, static_cast<const double *>(ws), blocks, log_std,
+                       min_log_std, has_min, out);
+    CM_HIP(hipGetLastError());
     return CM_OK;
+}
+
+extern "C" int cm_gauss_nll_forward(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std, float min_log_std,
+                                    int32_t has_min, float *out, void *ws, void *stream) {
+    return gauss_nll_forward<false>(__func__, S, N, per_agent, returns, log_std, min_log_std, has_min, out, ws, 0, stream);
+}
+
+extern "C" int cm_gauss_nll_forward_det(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std,
+                                        float min_log_std, int32_t has_min, float *out, void *ws, size_t ws_bytes, void *stream) {
+    return gauss_nll_forward<true>(__func__, S, N, per_agent, returns, log_std, min_log_std, has_min, out, ws, ws_bytes, stream);
 }
 
 extern "C" int cm_gauss_nll_backward(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std, float min_log_std,
@@ -1311,53 +1343,6 @@ extern "C" int cm_gauss_nll_backward(int64_t S, int32_t N, const float *per_agen
     const int blocks = (int)std::min<long>((S + 255) / 256, 1024);
     hipLaunchKernelGGL(gauss_nll_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
                        has_min, out, g, d_per_agent, d_log_std);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-extern "C" size_t cm_ppo_surrogate_det_ws_bytes(int32_t P, int32_t T) {
-    if (P <= 0 || T <= 0) return 0;
-    return (size_t)(((long)P * T + 255) / 256) * sizeof(double);
-}
-
-extern "C" int cm_ppo_surrogate_det(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
-                                    const float *old_ll, const float *adv, const int32_t *lens, float clip, float ent_coeff,
-                                    int32_t add_entropy, double *total, int64_t *count, float *dlogits, void *ws, size_t ws_bytes,
-                                    void *stream) {
-    if (!total || !count) return set_error(CM_ERR_ARG, "cm_ppo_surrogate_det: null argument");
-    if (A < 1 || A > PPO_MAX_A || N < 1) return set_error(CM_ERR_ARG, "cm_ppo_surrogate_det: 1 <= n_actions <= 8 and n_agents >= 1 required");
-    if (P > 0 && T > 0 && (!logits || !actions || !old_ll || !adv || !lens)) return set_error(CM_ERR_ARG, "cm_ppo_surrogate_det: null argument");
-    if (const int rc = slab_check(ws, ws_bytes, cm_ppo_surrogate_det_ws_bytes(P, T), "cm_ppo_surrogate_det")) return rc;
-    CM_HIP(hipMemsetAsync(total, 0, sizeof(double), (hipStream_t)stream));
-    CM_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), (hipStream_t)stream));    // (an integer sum: the default atomics are exact)
-    if (P <= 0 || T <= 0) return CM_OK;
-    const long S = (long)P * T;
-    const int blocks = (int)((S + 255) / 256);
-    double *slab = static_cast<double *>(ws);
-    hipLaunchKernelGGL(ppo_surrogate_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, T, N, A, logits, actions,
-                       old_ll, adv, lens, clip, ent_coeff, add_entropy, slab, (long long *)count, dlogits);
-    CM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(slab_total_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slab, blocks, total);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-extern "C" size_t cm_gauss_nll_forward_det_ws_bytes(int64_t S) {
-    if (S < 1) return 0;
-    return (size_t)std::min<long>((S + 255) / 256, 256) * sizeof(double);
-}
-
-extern "C" int cm_gauss_nll_forward_det(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std,
-                                        float min_log_std, int32_t has_min, float *out, void *ws, size_t ws_bytes, void *stream) {
-    if (!per_agent || !returns || !log_std || !out) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward_det: null argument");
-    if (S < 1 || N < 1) return set_error(CM_ERR_ARG, "cm_gauss_nll_forward_det: S >= 1 and n_agents >= 1 required");
-    if (const int rc = slab_check(ws, ws_bytes, cm_gauss_nll_forward_det_ws_bytes(S), "cm_gauss_nll_forward_det")) return rc;
-    const int blocks = (int)std::min<long>((S + 255) / 256, 256);
-    hipLaunchKernelGGL(gauss_nll_fwd_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (long)S, N, per_agent, returns, log_std, min_log_std,
-                       has_min, out, reinterpret_cast<GaussWs *>(ws));
-    CM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(gauss_nll_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long)S, static_cast<const double *>(ws), blocks, log_std,
-                       min_log_std, has_min, out);
     CM_HIP(hipGetLastError());
     return CM_OK;
 }

@@ -386,13 +386,11 @@ static int agg_bwd_m(int S, int N, const float *attn, const float *adj, const fl
     return pm::launch_agg<8, DET>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, st, grid);
 }
 
-int agg_bwd_mfma(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
-                 const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream) {
-    return agg_bwd_m<false>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, stream, nullptr);
-}
-int agg_bwd_mfma_det(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
-                     const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *slab_bias, void *stream, int *grid) {
-    return agg_bwd_m<true>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, slab_bias, stream, grid);
+int agg_bwd_mfma(bool det, int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw,
+                 const float *out, const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream,
+                 int *grid) {
+    return det ? agg_bwd_m<true>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, stream, grid)
+               : agg_bwd_m<false>(S, N, attn, adj, chan, ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, d_bias, stream, grid);
 }
 
 int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,

@@ -162,37 +162,16 @@ def _wgrad(a2d, b2d, want_colsum):
     c = torch.zeros(P, Q, dtype=torch.float32, device=a2d.device)
     cs = torch.zeros(P, dtype=torch.float32, device=a2d.device) if want_colsum else None
     with torch.cuda.device(a2d.device):
-        if _det():
-            nb = L.lib().cm_linear_wgrad_det_ws_bytes(R, P, Q)
-            L.check(L.lib().cm_linear_wgrad_det(R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs), L.ptr(L.slab(nb, a2d.device)), nb,
-                                                L.current_stream()), "cm_linear_wgrad_det")
-        else:
-            L.check(L.lib().cm_linear_wgrad(R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs), L.current_stream()),
-                    "cm_linear_wgrad")
+        L.check(L.launch("cm_linear_wgrad", (R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs)), (R, P, Q)), "cm_linear_wgrad")
     return c, cs
 
 
 def _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y, dx, dw, db, act=None):
-    """cm_linear_act_backward (y given = tanh layer), or with ``act`` (0 / 1 / 2) cm_linear_act_backward_ex; in
-    deterministic mode their slab twins."""
-    if act is not None:
-        if _det():
-            nb = L.lib().cm_linear_act_backward_det_ws_bytes(R, K, O)
-            L.check(L.lib().cm_linear_act_backward_ex_det(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y),
-                                                          int(act), L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(L.slab(nb, w.device)), nb,
-                                                          L.current_stream()), "cm_linear_act_backward_ex_det")
-        else:
-            L.check(L.lib().cm_linear_act_backward_ex(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y),
-                                                      int(act), L.ptr(dx), L.ptr(dw), L.ptr(db), L.current_stream()),
-                    "cm_linear_act_backward_ex")
-    elif _det():
-        nb = L.lib().cm_linear_act_backward_det_ws_bytes(R, K, O)
-        L.check(L.lib().cm_linear_act_backward_det(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y), L.ptr(dx),
-                                                   L.ptr(dw), L.ptr(db), L.ptr(L.slab(nb, w.device)), nb, L.current_stream()),
-                "cm_linear_act_backward_det")
-    else:
-        L.check(L.lib().cm_linear_act_backward(R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y), L.ptr(dx),
-                                               L.ptr(dw), L.ptr(db), L.current_stream()), "cm_linear_act_backward")
+    """cm_linear_act_backward (y given = tanh layer), or with ``act`` (0 / 1 / 2) cm_linear_act_backward_ex (their slab twins
+    in deterministic mode)."""
+    name = "cm_linear_act_backward" if act is None else "cm_linear_act_backward_ex"
+    args = (R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y)) + (() if act is None else (int(act),))
+    L.check(L.launch(name, args + (L.ptr(dx), L.ptr(dw), L.ptr(db)), (R, K, O)), name)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -323,15 +302,9 @@ class _MaskedAggregate(torch.autograd.Function):
         if chan_all is not None:
             chan_ptr, stride = chan_all.data_ptr() + 4 * ctx.hop * N * N, chan_all.shape[1] * N * N
         with torch.cuda.device(hw.device):
-            if _det():
-                nb = L.lib().cm_masked_agg_backward_det_ws_bytes(S, N, E)
-                L.check(L.lib().cm_masked_agg_backward_det(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
-                                                           L.ptr(out), None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias),
-                                                           L.ptr(L.slab(nb, hw.device)), nb, L.current_stream()), "cm_masked_agg_backward_det")
-            else:
-                L.check(L.lib().cm_masked_agg_backward(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
-                                                       L.ptr(out), None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw),
-                                                       L.ptr(d_bias), L.current_stream()), "cm_masked_agg_backward")
+            L.check(L.launch("cm_masked_agg_backward", (S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw), L.ptr(out), None,
+                                                        L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias)), (S, N, E)),
+                    "cm_masked_agg_backward")
         return d_attn, None, None, None, d_hw, d_bias
 
 
@@ -404,6 +377,23 @@ def _fused_train_ok(net, obs):
     return torch.is_grad_enabled() and _fused_shape_ok(net, obs)
 
 
+def _fwd_wave_ok(N, S):
+    """Teams of 4, large batches: the wave-owned kernel of the rollout as training forward (cm_*_forward_saved_wave: a
+    persistent workgroup per CU, activations in registers: 0.97 -> 0.5 ms at 1.1 M agent rows).  Small (launch-bound)
+    batches keep the f16-split kernel.  Decided on every call."""
+    return (N == 4 and S >= int(os.environ.get("COMMARL_TRAIN_FWD_WAVE_MIN", "16384"))
+            and (os.environ.get("COMMARL_POLICY_KERNEL") or "w")[0] not in "hfv")
+
+
+def _forward_saved(name, wave, *args):
+    """`name` (cm_policy_forward_saved / cm_critic_forward_saved) on the current stream, preceded by its _wave form when
+    `wave`: the wave kernel's return of 1 (shape not covered) falls back to `name` -> the return code."""
+    rc = getattr(L.lib(), name + "_wave")(*args, L.current_stream()) if wave else 1
+    if rc == 1:
+        rc = getattr(L.lib(), name)(*args, L.current_stream())
+    return rc
+
+
 class _FusedNetFn(torch.autograd.Function):
     """CommBaseNet trunk + head as ONE forward launch (cm_policy_forward_saved / cm_critic_forward_saved: the rollout
     kernel with stores of every activation the backward needs) and a hand-written backward chain:
@@ -437,34 +427,20 @@ class _FusedNetFn(torch.autograd.Function):
         adj_c = None if adj is None else adj.contiguous()
         ch_c = None if ch is None else ch.contiguous()
         net._train_fwd = True                          # the weight pack refreshes the f16-split section only (_WeightPack._packed)
-        # teams of 4, large batches: the wave-owned kernel of the rollout as training forward (cm_policy_forward_saved_wave: a
-        # persistent workgroup per CU, activations in registers: 0.97 -> 0.5 ms at 1.1 M agent rows); its fragments are the
-        # CM_PACK_WAVE section, refreshed together with the f16-split one then.  Small (launch-bound) batches keep the one section.
-        wave = (N == 4 and S >= int(os.environ.get("COMMARL_TRAIN_FWD_WAVE_MIN", "16384"))
-                and (os.environ.get("COMMARL_POLICY_KERNEL") or "w")[0] not in "hfv")
-        net._train_fwd_wave = wave
+        # ... and the CM_PACK_WAVE section with it when the wave-owned kernel runs (its fragments)
+        wave = net._train_fwd_wave = _fwd_wave_ok(N, S)
         try:
             with torch.cuda.device(dev):
                 if policy:
                     w = net._weights_struct()
-                    rc = 1
-                    if wave:
-                        rc = L.lib().cm_policy_forward_saved_wave(C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
-                                                                  C.byref(sv), L.current_stream())
-                    if rc == 1:
-                        rc = L.lib().cm_policy_forward_saved(C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
-                                                             C.byref(sv), L.current_stream())
+                    rc = _forward_saved("cm_policy_forward_saved", wave, C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
+                                        C.byref(sv))
                 else:
                     w = net._struct_from(net._packed())
                     w.mfma_pack = None if net._mfma is None else net._mfma.data_ptr()
                     vals = z(S)
-                    rc = 1
-                    if wave:
-                        rc = L.lib().cm_critic_forward_saved_wave(C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
-                                                                  L.ptr(vals), C.byref(sv), L.current_stream())
-                    if rc == 1:
-                        rc = L.lib().cm_critic_forward_saved(C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
-                                                             L.ptr(vals), C.byref(sv), L.current_stream())
+                    rc = _forward_saved("cm_critic_forward_saved", wave, C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
+                                        L.ptr(vals), C.byref(sv))
         finally:
             net._train_fwd = net._train_fwd_wave = False
         if rc == 1:
@@ -517,16 +493,10 @@ class _FusedNetFn(torch.autograd.Function):
                 chan_ptr, stride = None, 0
                 if ch is not None:
                     chan_ptr, stride = ch.data_ptr() + 4 * l * N * N, ch.shape[1] * N * N
-                if det:                                                  # one bias row, merged in a fixed order
-                    nb = L.lib().cm_masked_agg_backward_det_ws_bytes(S, N, 64)
-                    L.check(L.lib().cm_masked_agg_backward_det(S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
-                                                               L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb),
-                                                               L.ptr(L.slab(nb, obs2.device)), nb, L.current_stream()),
-                            "cm_masked_agg_backward_det")
-                else:
-                    L.check(L.lib().cm_masked_agg_backward_r(S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
-                                                             L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb),
-                                                             reps, L.current_stream()), "cm_masked_agg_backward_r")
+                # (deterministic mode: one bias row, merged in a fixed order)
+                L.check(L.launch("cm_masked_agg_backward_r", (S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
+                                                              L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb), reps),
+                                 (S, N, 64)), "cm_masked_agg_backward_r")
                 if dgb is not None:
                     dgb = dgb.sum(0) if reps > 1 else dgb[0]
                 d_attn = da if d_attn is None else d_attn.add_(da)
@@ -555,14 +525,8 @@ class _FusedNetFn(torch.autograd.Function):
         dw2, db2 = pool.take(enc2.weight.shape), pool.take(enc2.bias.shape)
         dw1, db1 = pool.take(enc1.weight.shape), pool.take(enc1.bias.shape)
         with torch.cuda.device(obs2.device):
-            if det:
-                nb = L.lib().cm_encoder_backward_det_ws_bytes(R, obs2.shape[1])
-                rc = L.lib().cm_encoder_backward_det(R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE),
-                                                     L.ptr(deq), L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1), L.ptr(L.slab(nb, obs2.device)),
-                                                     nb, L.current_stream())
-            else:
-                rc = L.lib().cm_encoder_backward(R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE), L.ptr(deq),
-                                                 L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1), L.current_stream())
+            rc = L.launch("cm_encoder_backward", (R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE),
+                                                  L.ptr(deq), L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1)), (R, obs2.shape[1]))
         if rc == 1:
             da1, dw2, db2 = _lin_bwd(t["a1"], enc2.weight, 0, dE, e, True, True, dy_add=deq)     # (dw2 .. db1 taken above stay zero, unused)
             _, dw1, db1 = _lin_bwd(obs2, enc1.weight, 0, da1, t["a1"], False, True)
@@ -591,18 +555,11 @@ def _fused_logits_nograd(net, obs, adj, ch, want_probs=False):
         sv.probs = probs.data_ptr()
     adj_c = None if adj is None else adj.contiguous()
     ch_c = None if ch is None else ch.contiguous()
-    # large batches of teams of 4: the same kernel the training forward takes (both sides of the PPO ratio from one arithmetic)
-    wave = (N == 4 and S >= int(os.environ.get("COMMARL_TRAIN_FWD_WAVE_MIN", "16384"))
-            and (os.environ.get("COMMARL_POLICY_KERNEL") or "w")[0] not in "hfv")
     with torch.cuda.device(obs.device):
         w = net._weights_struct()                            # (no-grad user: every section of the pack is current)
-        rc = 1
-        if wave:
-            rc = L.lib().cm_policy_forward_saved_wave(C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn), C.byref(sv),
-                                                      L.current_stream())
-        if rc == 1:
-            rc = L.lib().cm_policy_forward_saved(C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn), C.byref(sv),
-                                                 L.current_stream())
+        # large batches of teams of 4: the same kernel the training forward takes (both sides of the PPO ratio from one arithmetic)
+        rc = _forward_saved("cm_policy_forward_saved", _fwd_wave_ok(N, S), C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c),
+                            L.ptr(attn), C.byref(sv))
     if rc == 1:
         raise L.CommarlError("no saved-forward instantiation for this shape")
     L.check(rc, "cm_policy_forward_saved")
@@ -1083,15 +1040,9 @@ class _GaussNLLFn(torch.autograd.Function):
         pa, r = per_agent.contiguous(), returns.contiguous()
         out = torch.empty(2, dtype=torch.float32, device=pa.device)
         has_min = 0 if min_log_std is None else 1
-        with torch.cuda.device(pa.device):
-            if _det():                                       # block sums summed in a fixed order (no f64 atomics)
-                nb = L.lib().cm_gauss_nll_forward_det_ws_bytes(S)
-                L.check(L.lib().cm_gauss_nll_forward_det(S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
-                                                         L.ptr(out), L.ptr(L.slab(nb, pa.device)), nb, L.current_stream()),
-                        "cm_gauss_nll_forward_det")
-            else:
-                L.check(L.lib().cm_gauss_nll_forward(S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
-                                                     L.ptr(out), L.ptr(ws), L.current_stream()), "cm_gauss_nll_forward")
+        with torch.cuda.device(pa.device):                   # (deterministic mode: block sums summed in a fixed order, no f64 atomics)
+            L.check(L.launch("cm_gauss_nll_forward", (S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
+                                                      L.ptr(out), L.ptr(ws)), (S,)), "cm_gauss_nll_forward")
         ctx.save_for_backward(pa, r, log_std, out)
         ctx.min_log_std = min_log_std
         return out[0]

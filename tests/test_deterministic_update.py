@@ -57,6 +57,13 @@ def test_twins_are_exported():
         assert n in _lib.EXPORTED and n + "_ws_bytes" in _lib.EXPORTED
         assert hasattr(lib, n) and hasattr(lib, n + "_ws_bytes")
     assert lib.cm_abi_version() == 3
+    # _lib.launch's table: every twin reached, each with the default's leading arguments, then (slab, slab bytes, stream)
+    assert {twin for twin, _ in _lib.TWINS.values()} == {n for n in _lib.EXPORTED if n.endswith("_det")} >= set(_TWINS)
+    for name, (twin, ws_bytes) in _lib.TWINS.items():
+        assert {name, twin, ws_bytes} <= set(_lib.EXPORTED), name
+        args, twin_args = _lib._SIGNATURES[name][1], _lib._SIGNATURES[twin][1]
+        n = len(twin_args) - 3
+        assert twin_args[:n] == args[:n] and twin_args[n:] == [C.c_void_p, C.c_size_t, C.c_void_p], name
 
 
 def _calls(ws, nb):

@@ -141,7 +141,7 @@ class _UpdateGraphs:
         if self.cur[i] is None:
             key = self._key(i, inputs)
             ent = self.cache.get(key)
-            if ent is not None and os.environ.get("COMMARL_UPDATE_GRAPH_REUSE", "1") != "0":
+            if ent is not None:
                 with torch.no_grad():
                     for dst, src in zip(ent[2], inputs):
                         if dst is not None and dst.data_ptr() != src.data_ptr():
@@ -183,7 +183,7 @@ class _UpdateGraphs:
                 net._pack_sig = None
         with L.capture_guard(), torch.cuda.stream(self.stream):
             kw = {} if self.pool is None else dict(pool=self.pool)
-            g.capture_begin(capture_error_mode=os.environ.get("COMMARL_CAPTURE_MODE", "thread_local"), **kw)
+            g.capture_begin(capture_error_mode="thread_local", **kw)
             try:
                 out = fn()
             finally:

@@ -9,8 +9,6 @@
 // overlaps the matrix phases of its CU neighbour, the actions go from the sampler to the env step through LDS, and a
 // step costs one launch / one grid drain instead of two.  Results are bit-identical to cm_policy_forward followed by
 // cm_env_step (same device bodies, same Philox counters); tests/test_hip_fused_parity.py checks exactly that.
-#include <stdlib.h>
-
 #include "cm_env_dev.h"
 #include "cm_policy_mfma_dev.h"
 #include "cm_policy_h_dev.h"
@@ -82,10 +80,6 @@ __global__ __launch_bounds__(mf::TPB, 2) void rollout_chunk_kernel(mf::FwdArgs a
     int32_t *act = reinterpret_cast<int32_t *>(lds + act_off);
     const int envs = min(a.EPB, a.S - (int)blockIdx.x * a.EPB);
     const cm_rng_tape no_tape{};
-    // De-phase the workgroups that share a CU: the grid is dispatched round-robin, so workgroup b and b + gridDim / 2 are
-    // neighbours; the late one's matrix phases then meet the early one's env phases for the whole chunk.
-    if (c.stagger > 0 && blockIdx.x >= gridDim.x / 2)
-        for (int i = 0; i < c.stagger; ++i) __builtin_amdgcn_s_sleep(32);
     for (int t = 0; t < c.n_steps; ++t) {
         asm volatile("" ::: "memory");                                   // keep each step's loads inside the step
         const int grp = thread_x() / LPE;
@@ -155,7 +149,6 @@ static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     const int blocks = (a.S + a.EPB - 1) / a.EPB;
-    static const int pre_flag = [] { const char *e = getenv("COMMARL_ENV_PREFETCH"); return (e && e[0] == '0') ? 0 : 1; }();
     if (chunk) {
         static unsigned long long attr_set_c = 0;
         if (cm::dev_first(attr_set_c)) {
@@ -168,8 +161,7 @@ static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &
         return CM_OK;
     }
     if constexpr (MAXMK < 0 && POL == 1) {
-        static const bool full_on = [] { const char *e = getenv("COMMARL_FWD_FULL"); return !(e && e[0] == '0'); }();
-        if (full_on && a.EPB == 8 && a.S % 8 == 0) {
+        if (a.EPB == 8 && a.S % 8 == 0) {
 #define CM_FULL_LAUNCH(PRE)                                                                                                       \
     do {                                                                                                                          \
         static unsigned long long attr_set_f = 0;                                                                                           \
@@ -183,7 +175,7 @@ static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &
         probe_dump(d, stream);                                                                                                    \
         return CM_OK;                                                                                                             \
     } while (0)
-            if (pre_flag && env_prefetch_ok<SCEN, LPE>(d)) CM_FULL_LAUNCH(true);
+            if (env_prefetch_ok<SCEN, LPE>(d)) CM_FULL_LAUNCH(true);
             CM_FULL_LAUNCH(false);
 #undef CM_FULL_LAUNCH
         }
@@ -198,12 +190,6 @@ static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &
 
 using namespace cm;
 
-// COMMARL_FUSED=0 disables the fused step (A/B timing): the entry point then reports "not available"
-static bool fused_enabled() {
-    static const bool v = [] { const char *e = getenv("COMMARL_FUSED"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs, const float *avail,
                         const float *dist_adj, const float *channels, uint64_t seed, int32_t env_id_offset,
                         uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy, int32_t *actions,
@@ -213,7 +199,7 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
     const EnvDev &d = h->dev;
     if (w->n_agents != d.N || w->d != d.d || w->n_hops != d.L)
         return set_error(CM_ERR_ARG, "cm_rollout_step: policy shape (n_agents, d, n_hops) does not match the env handle");
-    if (!fused_enabled() || !w->mfma_pack || !policy_shape_ok(w)) return 1;
+    if (!w->mfma_pack || !policy_shape_ok(w)) return 1;
     if (int rc = check_tape(h, tape, false)) return rc;
     cm_rng_tape t{};
     if (tape) t = *tape;
@@ -228,8 +214,7 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
     const float *P = w->mfma_pack;
     const mf::TrunkW tw{ P + lo.enc1, w->enc_b1, P + lo.enc2, w->enc_b2, P + lo.attn, P + lo.gcn, w->gcn_b };
     const mf::PolHead ph{ P + lo.x1, w->hd_b1, P + lo.h2, w->hd_b2, P + lo.h3, w->hd_b3, P + lo.h4, w->hd_b4, w->n_act };
-    static const int mk_min = [] { const char *e = getenv("COMMARL_MK_MIN"); return e ? atoi(e) : 16; }();   // N x N products on MFMA tiles from 16 agents up
-    const int mk = d.N < mk_min ? 0 : (d.N <= 80 ? 25 : 64);                 // as mf::dispatch
+    const int mk = d.N < 16 ? 0 : (d.N <= 80 ? 25 : 64);                    // as mf::dispatch
     // instantiations: the four BASELINE shapes (PP sen1 small teams; CO sen2 mid teams; PP / CO sen2 large teams)
     const bool quad = d.N == 4 && mf::pick_epb(4) * 4 <= 32;
     const int kh = mh::kh_of(d.d);
@@ -245,9 +230,8 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
         // teams of 4: 8 envs per workgroup.  With 32 lanes per env the env phase occupies all four waves (16 lanes leave two of
         // them idle): its lane-parallel loops (observation emission, tile rebuild) halve - 28.5 -> 27.4 us per step at the
         // headline config.  The stand-alone env kernel keeps the handle's own choice (16: more envs per wave); the env body
-        // is bit-identical at every width (tests/test_hip_scale_parity.py).  COMMARL_FUSED_LPE=16 for the A/B.
-        static const int fused_lpe = [] { const char *e = getenv("COMMARL_FUSED_LPE"); return e ? atoi(e) : 32; }();
-        if (d.scen == CM_PP && d.lpe <= 32 && kh == 32 && quad && fused_lpe == 32 && !chunk)
+        // is bit-identical at every width (tests/test_hip_scale_parity.py).
+        if (d.scen == CM_PP && d.lpe <= 32 && kh == 32 && quad && !chunk)
             return launch_fused<CM_PP, 32, 32, -1, 1>(a, tw, ph, twh, phh, h, t, *out, stream, chunk);
         if (d.scen == CM_PP && d.lpe == 16 && kh == 32 && quad) return launch_fused<CM_PP, 16, 32, -1, 1>(a, tw, ph, twh, phh, h, t, *out, stream, chunk);
         if (d.scen == CM_PP && d.lpe == 16 && kh == 32 && mk == 0) return launch_fused<CM_PP, 16, 32, 0, 1>(a, tw, ph, twh, phh, h, t, *out, stream, chunk);
@@ -282,8 +266,7 @@ extern "C" int cm_rollout_chunk(cm_env_t h, const cm_policy_weights *w, int32_t 
     if (n_steps < 0) return set_error(CM_ERR_ARG, "cm_rollout_chunk: negative step count");
     if (h && h->cfg.rng_mode == CM_RNG_TAPE) return set_error(CM_ERR_ARG, "cm_rollout_chunk: tape mode steps one launch at a time");
     if (n_steps == 0) return CM_OK;
-    static const int stagger = [] { const char *e = getenv("COMMARL_CHUNK_STAGGER"); return e ? atoi(e) : 0; }();
-    ChunkArgs c{ n_steps, stagger, st->obs, st->actions, st->probs, st->attn, st->reward, st->reward_f64, st->done, st->details,
+    ChunkArgs c{ n_steps, st->obs, st->actions, st->probs, st->attn, st->reward, st->reward_f64, st->done, st->details,
                  st->dist_adj, st->channels, st->prey_alive, st->success, st->path_len };
     return rollout_impl(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy, actions,
                         probs, attn, nullptr, out, stream, &c);
@@ -298,12 +281,9 @@ extern "C" int cm_rollout_chunk_tail(cm_env_t h, const cm_policy_weights *w, int
     if (n_steps < 1) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: at least one step");
     if (!h || !out || !out->obs || !obs_next || !policy_step_base) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: null argument");
     if (h->cfg.rng_mode == CM_RNG_TAPE) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: tape mode steps one launch at a time");
-    static const int stagger = [] { const char *e = getenv("COMMARL_CHUNK_STAGGER"); return e ? atoi(e) : 0; }();
-    static const bool fold = [] { const char *e = getenv("COMMARL_FOLD_TAIL"); return !(e && e[0] == '0'); }();
     int folded = 0;
-    ChunkArgs c{ n_steps, stagger, st->obs, st->actions, st->probs, st->attn, st->reward, st->reward_f64, st->done, st->details,
-                 st->dist_adj, st->channels, st->prey_alive, st->success, st->path_len };
-    if (fold) { c.tail_obs = obs_next; c.tail_base = policy_step_base; c.tail_folded = &folded; }
+    ChunkArgs c{ n_steps, st->obs, st->actions, st->probs, st->attn, st->reward, st->reward_f64, st->done, st->details,
+                 st->dist_adj, st->channels, st->prey_alive, st->success, st->path_len, obs_next, policy_step_base, &folded };
     const int rc = rollout_impl(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy, actions,
                                 probs, attn, nullptr, out, stream, &c);
     if (rc != CM_OK || folded) return rc;

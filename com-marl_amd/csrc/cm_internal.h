@@ -99,7 +99,6 @@ namespace cm {
 // (cm_rollout_chunk): step t reads / writes base + t * stride.
 struct ChunkArgs {
     int n_steps;
-    int stagger;              // late start of the second half of the grid, in units of s_sleep 32 (~2048 clocks)
     long long obs, actions, probs, attn, reward, reward_f64, done, details, dist_adj, channels, prey_alive, success, path_len;
     // cm_rollout_chunk_tail: the tail the caller wants behind the chunk - the last step's observation into `tail_obs` (slot 0) and
     // *tail_base += n_steps.  A kernel that does it itself sets *tail_folded (host) to 1; otherwise the entry point launches cm_chunk_tail.

@@ -323,10 +323,7 @@ static int linear_bwd_generic(int64_t R, int32_t K, int32_t O, const float *x, c
     const int OT = (O + 15) / 16, KT = (K + 15) / 16, NT = OT * KT;
     const size_t lds = ((size_t)lin::ROWS * (OT * 16 + 16) + (size_t)lin::ROWS * (KT * 16 + 16)) * sizeof(float);
     const long chunks = (R + lin::ROWS - 1) / lin::ROWS;
-    int blocks = (int)std::min<long>(chunks, 512);
-    static const int force = [] { const char *e = getenv("COMMARL_LIN_BLOCKS"); return e ? atoi(e) : 0; }();
-    if (force > 0) blocks = (int)std::min<long>(chunks, force);
-    if (DET) blocks = std::min(blocks, 512);               // the slab has min(chunks, 512) rows (cm_*_det_ws_bytes)
+    const int blocks = (int)std::min<long>(chunks, 512);   // the slab twin's min(chunks, 512) rows (cm_*_det_ws_bytes)
     *grid = blocks;
     const hipStream_t st = (hipStream_t)stream;
     const int per_wave = (NT + 3) / 4;

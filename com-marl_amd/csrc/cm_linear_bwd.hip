@@ -20,7 +20,6 @@
 //     through LDS, then one float atomic per element per workgroup;
 //   * dx is computed transposed (weights as the A operand) so that a lane ends with four consecutive input features:
 //     one 16-byte store per tile.
-#include <stdlib.h>
 
 #include <algorithm>
 #include <cmath>
@@ -490,11 +489,9 @@ static int launch(long R, int KR, const float *x, const float *w, const float *d
     const long chunks = (R + ROWS - 1) / ROWS;
     // One workgroup per CU for the large batches.  A small batch is spread over FEWER workgroups: every workgroup ends with one
     // float atomic per weight-gradient element (4 - 8 k of them on the same addresses), ~0.1 us of serialised L2 atomics per
-    // workgroup against ~3 us per 64-row chunk streamed - the sum is least at ~sqrt(29 chunks) workgroups (measured on MI355X,
-    // tools/lin_bwd_sweep.py: 10 000 rows of 64 -> 64: 17 us with 64 workgroups, 32 us with one per chunk)
+    // workgroup against ~3 us per 64-row chunk streamed - the sum is least at ~sqrt(29 chunks) workgroups (measured on MI355X:
+    // 10 000 rows of 64 -> 64: 17 us with 64 workgroups, 32 us with one per chunk)
     int blocks = (int)std::min<long>(std::min<long>(chunks, n_cu), std::max<long>(1, std::lround(std::sqrt(29.0 * (double)chunks))));
-    static const int force = [] { const char *e = getenv("COMMARL_LIN2_BLOCKS"); return e ? atoi(e) : 0; }();
-    if (force > 0) blocks = (int)std::min<long>(chunks, force);
     if (DET) blocks = std::min(blocks, 512);               // the slab has min(chunks, 512) rows (cm_*_det_ws_bytes)
     if (grid) *grid = blocks;
     hipLaunchKernelGGL((bwd_kernel<KT, OT, ACT, LAYOUT, RAG, WO, DET>), dim3(blocks), dim3(TPB), std::max<size_t>(lds, 33 * 1024), st, R, KR, x, w, dy, dy2, y, dx, dw,
@@ -512,8 +509,6 @@ static int launch(long R, int KR, const float *x, const float *w, const float *d
 template <bool DET>
 static int bwd_stream(long R, int K, int O, const float *x, const float *w, int layout, const float *dy, const float *dy2,
                       const float *y, int act, float *dx, float *dw, float *db, void *stream, int *grid) {
-    static const bool off = [] { const char *e = getenv("COMMARL_LIN_BWD"); return e && e[0] == 'o'; }();   // "old"
-    if (off) return 1;
     const auto ok_w = [](int v) { return v == 32 || v == 64 || v == 128; };
     const hipStream_t st = (hipStream_t)stream;
     if (!ok_w(K) && ok_w(O) && K <= 128 && !dx && layout == 0 && !(((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)y) & 15) && !((uintptr_t)x & 3)) {
@@ -574,8 +569,7 @@ int linear_bwd_stream(bool det, long R, int K, int O, const float *x, const floa
 template <bool DET>
 static int encoder_chain(long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy, const float *dy2,
                          float *dw2, float *db2, float *dw1, float *db1, void *stream, int *grid) {
-    static const bool off = [] { const char *v = getenv("COMMARL_ENC_CHAIN"); return v && v[0] == '0'; }();
-    if (off || d < 1 || d > 64) return 1;
+    if (d < 1 || d > 64) return 1;
     if (((uintptr_t)a1 | (uintptr_t)e | (uintptr_t)dy | (uintptr_t)dy2) & 15) return 1;
     if ((uintptr_t)obs & 3) return 1;
     const hipStream_t st = (hipStream_t)stream;

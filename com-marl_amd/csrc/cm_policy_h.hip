@@ -49,8 +49,7 @@ static int launch_h(FwdArgs a, const TrunkH &tw, const PolHeadH &ph, const CritH
     }
     const int blocks = (a.S + a.EPB - 1) / a.EPB;
     if constexpr (MAXMK < 0 && NW == 4) {
-        static const int occ_min = [] { const char *e = getenv("COMMARL_FWD_OCC3_MIN"); return e ? atoi(e) : 4096; }();   // workgroups; 0 = never
-        if (occ_min > 0 && blocks >= occ_min) {
+        if (blocks >= 4096) {
             static unsigned long long attr3 = 0;
             if (cm::dev_first(attr3)) {
                 CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_h_occ3_kernel<HEAD, KH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -59,8 +58,7 @@ static int launch_h(FwdArgs a, const TrunkH &tw, const PolHeadH &ph, const CritH
             CM_HIP(hipGetLastError());
             return CM_OK;
         }
-        static const bool full_on = [] { const char *e = getenv("COMMARL_FWD_FULL"); return !(e && e[0] == '0'); }();
-        if (full_on && a.EPB == 8 && a.S % 8 == 0) {
+        if (a.EPB == 8 && a.S % 8 == 0) {
             static unsigned long long attrf = 0;
             if (cm::dev_first(attrf)) {
                 CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_h_full_kernel<HEAD, KH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -79,15 +77,12 @@ template <int HEAD>
 static int dispatch_h(const FwdArgs &a, const TrunkH &tw, const PolHeadH &ph, const CritHeadH &chd, void *stream) {
     const int kh = kh_of(a.d);
     if (!kh || a.N > 128) return 1;
-    static const int mk_min = [] { const char *e = getenv("COMMARL_MK_MIN"); return e ? atoi(e) : 16; }();
-    const int mk = a.N < mk_min ? 0 : (a.N <= 80 ? 25 : 64);
+    const int mk = a.N < 16 ? 0 : (a.N <= 80 ? 25 : 64);   // as mf::dispatch
     const bool quad = a.N == 4 && mf::pick_epb(4) * 4 <= 32;
-    static const bool w8_on = [] { const char *e = getenv("COMMARL_FWD_WAVES"); return !(e && e[0] == '4'); }();
-    static const int w8_min = [] { const char *e = getenv("COMMARL_FWD_W8MIN"); return e ? atoi(e) : 32; }();
-    const bool w8 = w8_on && a.N >= w8_min;
+    const bool w8 = a.N >= 32;                               // 8-wave workgroups (every team with mk == 64)
 #define CM_FWH(K) (quad ? launch_h<HEAD, K, -1>(a, tw, ph, chd, stream) : mk == 0 ? launch_h<HEAD, K, 0>(a, tw, ph, chd, stream) \
                    : mk == 25 ? (w8 ? launch_h<HEAD, K, 15, 8>(a, tw, ph, chd, stream) : launch_h<HEAD, K, 25>(a, tw, ph, chd, stream)) \
-                              : (w8 ? launch_h<HEAD, K, 32, 8>(a, tw, ph, chd, stream) : launch_h<HEAD, K, 64>(a, tw, ph, chd, stream)))
+                              : launch_h<HEAD, K, 32, 8>(a, tw, ph, chd, stream))
     switch (kh) {
     case 32: return CM_FWH(32);
     case 64: return CM_FWH(64);

@@ -89,20 +89,13 @@ static int dispatch(const FwdArgs &a, const TrunkW &tw, const PolHead &ph, const
     if (kpad == 16) kpad = 32;            // smallest instantiation (obs dims 1..32)
     if (kpad == 48) kpad = 64;
     if (a.N > 128) return 1;             // N x N MFMA tiles are built for teams of up to 128 agents
-    const int nn = a.N * a.N;
-    // N x N products on MFMA from N = 32 up (measured: at N = 24 the padded 32 x 32 tiles lose to the VALU form)
-    static const int mk_min = [] { const char *e = getenv("COMMARL_MK_MIN"); return e ? atoi(e) : 16; }();   // N x N products on MFMA tiles from 16 agents up
-    const int mk = a.N < mk_min ? 0 : (a.N <= 80 ? 25 : 64);    // (row blocks) x (column blocks) of 16
-    (void)nn;
+    const int mk = a.N < 16 ? 0 : (a.N <= 80 ? 25 : 64);    // N x N products on MFMA tiles from 16 agents up: (row blocks) x (column blocks) of 16
     const bool quad = a.N == 4 && pick_epb(4) * 4 <= 32;    // teams of 4: the register-resident attention / aggregation kernel
-    // large teams run 8-wave workgroups (one workgroup per CU fits in LDS: two waves per SIMD hide each other's
-    // latencies); COMMARL_FWD_WAVES=4 selects the 4-wave build of the same code for A/B timing
-    static const bool w8_on = [] { const char *e = getenv("COMMARL_FWD_WAVES"); return !(e && e[0] == '4'); }();
-    static const int w8_min = [] { const char *e = getenv("COMMARL_FWD_W8MIN"); return e ? atoi(e) : 32; }();
-    const bool w8 = w8_on && a.N >= w8_min;   // measured: N = 54 245 -> 178 us, N = 72 280 -> 213 us; N = 24 (48 rows) is faster on 4 waves
+    // large teams run 8-wave workgroups (one workgroup per CU fits in LDS: two waves per SIMD hide each other's latencies)
+    const bool w8 = a.N >= 32;   // measured: N = 54 245 -> 178 us, N = 72 280 -> 213 us; N = 24 (48 rows) is faster on 4 waves
 #define CM_FWD(K) (quad ? launch<HEAD, K, -1>(a, tw, ph, chd, stream) : mk == 0 ? launch<HEAD, K, 0>(a, tw, ph, chd, stream) \
                    : mk == 25 ? (w8 ? launch<HEAD, K, 15, 8>(a, tw, ph, chd, stream) : launch<HEAD, K, 25>(a, tw, ph, chd, stream)) \
-                              : (w8 ? launch<HEAD, K, 32, 8>(a, tw, ph, chd, stream) : launch<HEAD, K, 64>(a, tw, ph, chd, stream)))
+                              : launch<HEAD, K, 32, 8>(a, tw, ph, chd, stream))
     switch (kpad) {      // obs dims of the reference scenarios: PP sen1 21, CO sen1 29, PP sen2 53, CO sen2 77 (+clock 78)
     case 32: return CM_FWD(32);
     case 64: return CM_FWD(64);

@@ -4,7 +4,6 @@
 #pragma once
 #include "cm_internal.h"
 #include "cm_rng.h"
-#include <stdlib.h>
 
 namespace cm {
 namespace mf {
@@ -786,11 +785,10 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &a, const TrunkW &tw, con
 // ---- host-side helpers shared by the stand-alone and the fused launchers ----
 inline int pick_epb(int N) {
     if (N % 4 != 0) return 1;                 // aggregation tiles must not straddle envs
-    static const int forced = [] { const char *e = getenv("COMMARL_FWD_ROWS"); return e ? atoi(e) : 0; }();
     // ~32 rows per workgroup (2 row tiles, >= 2 workgroups per CU); mid-size teams take two envs so that the 16-row
     // tiles are full and every weight fragment serves three of them (N = 24: 48 rows, measured 145 -> 117 us;
     // three envs = 72 rows drop to one workgroup per CU and lose: 184 us)
-    const int target = forced ? forced : ((N > 16 && N < 32) ? 2 * N : 32);
+    const int target = (N > 16 && N < 32) ? 2 * N : 32;
     const int e = target / N;
     return e > 0 ? e : 1;
 }

@@ -10,8 +10,6 @@
 // N x N mask tile and the N x 64 feature tile are read from HBM exactly once.
 #include <algorithm>
 
-#include <stdlib.h>
-
 #include "cm_internal.h"
 
 namespace cm {
@@ -836,12 +834,6 @@ __global__ __launch_bounds__(256) void entropy_gae_kernel(int T, int N, int A, c
     }
 }
 
-// COMMARL_QUAD_BWD=0: teams of 4 take the generic aggregation / attention backward kernels (A/B and test hook)
-static bool quad_bwd_on() {
-    static const bool v = [] { const char *e = getenv("COMMARL_QUAD_BWD"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 }  // namespace cm
 
 using namespace cm;
@@ -1072,12 +1064,10 @@ static int masked_agg_backward(const char *fn, int32_t S, int32_t N, int32_t E, 
     const hipStream_t st = (hipStream_t)stream;
     float *const slab = static_cast<float *>(ws), *const gb = DET ? slab : d_bias;
     int grid = 0;
-    if (N == 4 && quad_bwd_on() && !(((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw) & 15)) {
+    if (N == 4 && !(((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw) & 15)) {
         // small batches: fewer workgroups looping (the bias atomics again: 2 500 envs take 11.6 us on 64 workgroups, 19 on 157)
         const long chunks = ((long)S + 15) / 16;
         grid = (int)(chunks <= 512 ? std::min<long>(chunks, 64) : std::min<long>(chunks, 2048));
-        static const int force = [] { const char *e = getenv("COMMARL_AGG4_BLOCKS"); return e ? atoi(e) : 0; }();
-        if (!DET && force > 0) grid = std::min(grid, force);   // the COMMARL_AGG4_BLOCKS override applies in default mode only
         // (slab mode: bias_reps = the grid size, every workgroup stores its own row)
         hipLaunchKernelGGL(agg_bwd4_kernel<DET>, dim3(grid), dim3(256), 0, st, S, attn, dist_adj, chan, (long)ch_stride, hw, out,
                            out_minus, d_out, d_attn, d_hw, gb, DET ? grid : (int)bias_replicas);
@@ -1202,7 +1192,7 @@ extern "C" int cm_attention_backward(int32_t S, int32_t N, int32_t E, const floa
     if (d_e == d_e_add0 || d_e == d_e_add1) return set_error(CM_ERR_ARG, "cm_attention_backward: d_e must not alias its addends");
     if (E != 64) return set_error(CM_ERR_ARG, "cm_attention_backward: embedding dim 64 only");
     if (S <= 0) return CM_OK;
-    if (N == 4 && quad_bwd_on() && !(((uintptr_t)q | (uintptr_t)e | (uintptr_t)d_e_add0 | (uintptr_t)d_e_add1 | (uintptr_t)d_q | (uintptr_t)d_e) & 15)) {
+    if (N == 4 && !(((uintptr_t)q | (uintptr_t)e | (uintptr_t)d_e_add0 | (uintptr_t)d_e_add1 | (uintptr_t)d_q | (uintptr_t)d_e) & 15)) {
         const int blocks = (int)std::min<long>((S + 15) / 16, 4096);
         hipLaunchKernelGGL(attn_bwd4_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, q, e, m, d_m, d_e_add0, d_e_add1, d_q, d_e);
         CM_HIP(hipGetLastError());

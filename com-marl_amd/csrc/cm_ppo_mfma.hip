@@ -366,17 +366,12 @@ static int launch_attn(int S, int N, const float *q, const float *e, const float
 
 }  // namespace pm
 
-static bool mfma_bwd_on() {
-    static const bool v = [] { const char *e = getenv("COMMARL_NXN_BWD"); return !(e && e[0] == 'o'); }();   // "old": first-generation kernels
-    return v;
-}
-
 // Return 1 when the shape is not covered (N < 8, N > 128, unaligned rows): the caller runs the first-generation kernel.
 // DET: slab mode - d_bias is a slab of 64 floats per workgroup, *grid receives the number of rows written.
 template <bool DET>
 static int agg_bwd_m(int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw, const float *out,
                      const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream, int *grid) {
-    if (!mfma_bwd_on() || N < 8 || N > 128) return 1;
+    if (N < 8 || N > 128) return 1;
     if (((uintptr_t)hw | (uintptr_t)out | (uintptr_t)out_minus | (uintptr_t)d_out | (uintptr_t)d_hw | (uintptr_t)adj | (uintptr_t)d_attn) & 15) return 1;
     if (pm::agg_lds(N) > 160 * 1024) return 1;
     const hipStream_t st = (hipStream_t)stream;
@@ -395,7 +390,7 @@ int agg_bwd_mfma(bool det, int S, int N, const float *attn, const float *adj, co
 
 int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,
                   float *d_q, float *d_e, void *stream) {
-    if (!mfma_bwd_on() || N < 8 || N > 128) return 1;
+    if (N < 8 || N > 128) return 1;
     if (((uintptr_t)q | (uintptr_t)e | (uintptr_t)add0 | (uintptr_t)add1 | (uintptr_t)d_q | (uintptr_t)d_e) & 15) return 1;
     if (pm::attn_lds(N) > 160 * 1024) return 1;
     const hipStream_t st = (hipStream_t)stream;

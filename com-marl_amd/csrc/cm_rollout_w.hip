@@ -3,7 +3,6 @@
 // (reference: centralized_ma_on_policy_vectorized_sampler.py:119-232 - get_actions, vec_env.step, obses = next_obses).
 // Its own translation unit: built with -fno-slp-vectorize (Makefile), which the older kernels of cm_fused.hip are not.
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "cm_env_dev.h"
 #include "cm_policy_w_dev.h"
@@ -173,20 +172,17 @@ int launch_rollout_w(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pa
     }
     const bool use_tape = t.prey || t.spawn || t.iid_u || t.ge_u || t.ge_init_u;
     const int blocks = (a.S + mw::WG_ENVS - 1) / mw::WG_ENVS;
-    static const int pre_flag = [] { const char *e = getenv("COMMARL_ENV_PREFETCH"); return (e && e[0] == '0') ? 0 : 1; }();
-    const bool pre = pre_flag && env_prefetch_ok<CM_PP, 16>(d), full = a.S % mw::WG_ENVS == 0;
+    const bool pre = env_prefetch_ok<CM_PP, 16>(d), full = a.S % mw::WG_ENVS == 0;
     // carried form (state and observation from step to step inside the wave, no fence between steps): multi-step launches on
     // a constant adjacency without a channel model; the observation copy needs 4 rows x 24 floats in the env area's claim table
-    static const int carry_flag = [] { const char *e = getenv("COMMARL_ROLLOUT_CARRY"); return (e && e[0] == '0') ? 0 : 1; }();
-    const bool carry = carry_flag && pre && !use_tape && c.n_steps > 1 && d.adj_const && d.ch_const && !a.adj && !a.chan &&
+    const bool carry = pre && !use_tape && c.n_steps > 1 && d.adj_const && d.ch_const && !a.adj && !a.chan &&
                        a.d <= OBS_COPY_STRIDE && 4 * d.S * d.S >= 4 * OBS_COPY_STRIDE * 4;
     TailW tl{};
     if (carry && chunk && chunk->tail_obs && chunk->tail_base && chunk->tail_folded) {
         tl = TailW{ chunk->tail_obs, chunk->tail_base, d.tail_ticket, 1 };
         *chunk->tail_folded = 1;
     }
-    static const int shape_flag = [] { const char *e = getenv("COMMARL_ROLLOUT_SHAPE"); return (e && e[0] == '0') ? 0 : 1; }();
-    const bool map10 = shape_flag && carry && d.S == 10 && d.M == 4 && d.R == 1 && d.W == 3 && d.d == 21 && d.lds_env == lds_env_bytes(10, 4, 4);
+    const bool map10 = carry && d.S == 10 && d.M == 4 && d.R == 1 && d.W == 3 && d.d == 21 && d.lds_env == lds_env_bytes(10, 4, 4);
 #define CM_RW_(LH, PR, FU, TP, CA, SH)                                                                                          \
     do {                                                                                                                        \
         static unsigned long long done = 0;                                                                                     \

@@ -248,7 +248,7 @@ class _LinearActFn(torch.autograd.Function):
 
 def _fused_ok(x, weight):
     return (x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled() and weight.requires_grad
-            and max(weight.shape) <= 128 and os.environ.get("COMMARL_FUSED_LINEAR", "1") != "0")
+            and max(weight.shape) <= 128)
 
 
 def hip_linear(x, lin, act=ACT_NONE):
@@ -600,8 +600,7 @@ class _WeightPack:
         # a training forward (_FusedNetFn sets _train_fwd around its launch) reads the f16-split fragments only: between two optimiser steps just that section is
         # refreshed (cm_*_pack_sections); the rest goes stale and is packed - with the range check - by the next no-grad user
         # (sync_weights() before a rollout, evaluate_nograd, act_device)
-        partial = self._train_fwd and os.environ.get("COMMARL_PACK_PARTIAL", "1") != "0"
-        need = (L.PACK_F16 | (L.PACK_WAVE if self._train_fwd_wave else 0)) if partial else L.PACK_ALL
+        need = (L.PACK_F16 | (L.PACK_WAVE if self._train_fwd_wave else 0)) if self._train_fwd else L.PACK_ALL
         if sig == self._pack_sig and not (need & 7 & ~self._pack_fresh):     # every section this user reads is current
             return self._pack[1]
         with torch.no_grad():
@@ -1162,7 +1161,7 @@ class CommBaseCritic(CommBaseNet):
         lead, S, obs, adj, ch = self._flatten(obs_n, dist_adj, channels)
         ag = self.baseline_aggregator
         if (self._fused_head_ok(obs) and torch.is_tensor(returns) and returns.is_cuda and returns.dtype == torch.float32
-                and ag._init_std.numel() == 1 and os.environ.get("COMMARL_FUSED_NLL", "1") != "0"):
+                and ag._init_std.numel() == 1):
             per_agent, _ = _FusedNetFn.apply(self, obs, adj, ch, *self.parameters())  # [S,N] per-agent means
             ws = getattr(self, "_nll_ws", None)
             if ws is None or ws.device != per_agent.device:

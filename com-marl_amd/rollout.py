@@ -103,9 +103,8 @@ class RolloutEngine:
         self._persistent = bool(persistent and fused)
         self._capturing = False
         # captured chunks: one fused launch per step (cm_rollout_step) or the two-kernel form - measured per config in
-        # bench.py; COMMARL_GRAPH_FUSED=0/1 forces either for A/B runs
-        gf_env = os.environ.get("COMMARL_GRAPH_FUSED")
-        self._fused_in_graph = bool(fused) and (gf_env == "1" if gf_env is not None else bool(graph_fused))
+        # bench.py
+        self._fused_in_graph = bool(fused) and bool(graph_fused)
         self.t = 0
         self.generation = 0                      # bumped by reset(): a PathBatch of an earlier rollout refuses to read the buffers
 
@@ -257,21 +256,6 @@ class RolloutEngine:
         capture order, so issuing one shard's whole chain first would start the other shard's chain only after it
         (measured: ~100 us stagger per replay, profiles/r02_trace_short.txt).  tail=False (the sampler's spans): no carry
         of slot t0+n into slot 0 and no bump of the sampler's Philox base - the caller bumps once per rollout."""
-        spl = int(os.environ.get("COMMARL_STEPS_PER_LAUNCH", "1"))
-        if spl > 1 and self._fused is not False and self._fused_in_graph:
-            # experiment: several steps per launch (cm_rollout_chunk with a short trip count) - one grid drain per spl steps
-            t = 0
-            while t < n:
-                m = min(spl, n - t)
-                if not self.steps_fused(t0 + t, m):
-                    raise L.CommarlError("COMMARL_STEPS_PER_LAUNCH needs the fused chunk kernel")
-                t += m
-            if tail:
-                for k, st in enumerate(self.streams):
-                    with torch.cuda.stream(st) if st is not None else _null():
-                        self._chunk_tail(k, t0 + n)
-                self.join()
-            return
         if self._persistent and self.steps_fused(t0, n, tail=tail):    # one launch per shard for the whole span, its tail included
             return
         self.fork()
@@ -332,7 +316,7 @@ class RolloutEngine:
             # garbage-collected env handle, the cause of round 2's invalidated captures - is kept out by L.capture_guard():
             # garbage is collected before the capture opens and handle destruction is deferred until it has closed.
             with L.capture_guard():
-                with torch.cuda.graph(g, capture_error_mode=os.environ.get("COMMARL_CAPTURE_MODE", "thread_local")):
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._chunk(n, t0, tail)
         finally:
             self._capturing = False

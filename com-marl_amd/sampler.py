@@ -7,7 +7,6 @@ the whole loop stays on the GPU (rollout.RolloutEngine).
 (materialised to numpy only when indexed) that also exposes the device-resident trajectory and
 the (env, start, length) index, which CentralizedMAPPO consumes directly without a host trip.
 """
-import os
 import time
 from collections.abc import Sequence
 
@@ -302,19 +301,17 @@ class CentralizedMAOnPolicyVectorizedSampler:
         eng._pol_share = t_pol / max(t_pol + t_env, 1e-9)
         return eng._pol_share
 
-    def obtain_samples(self, itr, batch_size=None, whole_paths=True, chunk=16, use_graph=None):
+    def obtain_samples(self, itr, batch_size=None, whole_paths=True, chunk=16, use_graph=True):
         """Roll until the completed paths hold >= batch_size agent-steps (:119), checking the stop rule once per `chunk`
         steps on the device; returns the completed paths up to the exact step at which the reference loop would have
         stopped.  The stepping loop replays one captured hipGraph per `chunk`-step span of trajectory slots
         (RolloutEngine.run_span; captured on the first rollout of an engine, reused by every later one) - eager
-        stepping (``use_graph=False`` / COMMARL_SAMPLER_GRAPH=0) gives the same PathBatch, 2.3x slower at the headline
+        stepping (``use_graph=False``) gives the same PathBatch, 2.3x slower at the headline
         config.  No check happens before step batch_size / (B N): the completed paths cannot hold the batch earlier."""
         mpl = self.algo.max_path_length
         B, N = self._n_envs, self._n_agents
         if not batch_size:
             batch_size = mpl * B
-        if use_graph is None:
-            use_graph = os.environ.get("COMMARL_SAMPLER_GRAPH", "1") != "0"
         chunk = max(1, int(chunk))
         # after t steps the completed paths hold >= B*N*(t - mpl) samples  =>  t <= batch/(B*N) + mpl
         t_min = int(np.ceil(batch_size / (B * N)))

@@ -262,7 +262,7 @@ int cm_critic_forward_saved_wave(const cm_critic_weights *w, int32_t n_samples, 
  * of the two calls (n_samples is the handle's B; obs / dist_adj / channels are the CURRENT step's inputs, `out` receives
  * the next step's), bit-identical to calling them back to back.
  * Returns 0 on success, < 0 on error, and 1 - having done nothing - when this (scenario, team size, obs dim) has no
- * fused instantiation, no operand pack was supplied, or COMMARL_FUSED=0: call the two entry points instead. */
+ * fused instantiation or no operand pack was supplied: call the two entry points instead. */
 int cm_rollout_step(cm_env_t h, const cm_policy_weights *w, const float *obs, const float *avail,
                     const float *dist_adj, const float *channels, uint64_t seed, int32_t env_id_offset,
                     uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy, int32_t *actions,

@@ -1,5 +1,4 @@
-"""Training-size forward of the teams-of-4 nets (cm_policy_forward_saved / cm_critic_forward_saved, 274 k envs): time per call;
-COMMARL_FWD_OCC3_MIN=0 selects the two-workgroups-per-CU build for comparison."""
+"""Training-size forward of the teams-of-4 nets (cm_policy_forward_saved / cm_critic_forward_saved, 274 k envs): time per call."""
 import os, sys
 sys.path.insert(0, '.')
 import numpy as np, torch
@@ -23,4 +22,4 @@ tp = t(lambda: pol._probs(obs, None, None, None))
 tc = t(lambda: crit._values_grad(obs, None, None))
 with torch.no_grad():
     tn = t(lambda: pol.evaluate_nograd(obs, None, None))
-print(f"occ3_min={os.environ.get('COMMARL_FWD_OCC3_MIN', 'default')}: policy training forward {tp:.3f} ms, critic {tc:.3f} ms, policy no-save forward {tn:.3f} ms")
+print(f"policy training forward {tp:.3f} ms, critic {tc:.3f} ms, policy no-save forward {tn:.3f} ms")

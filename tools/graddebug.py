@@ -1,4 +1,4 @@
-import os, sys; sys.path.insert(0, '.')
+import sys; sys.path.insert(0, '.')
 import numpy as np, torch
 from tests import dist_train_child as D
 from com_marl_amd import envs as E, nets
@@ -25,14 +25,8 @@ def grads(idx, reduce):
     if reduce: out.backward(); return {n: p.grad.clone() for n, p in pol.named_parameters()}, None
     tot, cnt = out; tot.backward(); return {n: p.grad.clone() for n, p in pol.named_parameters()}, float(cnt)
 P = obs.shape[0]; allidx = torch.arange(P, device="cuda"); sel = paths.env_idx < D.SPLIT
-for fused in ("1", "0"):
-    os.environ["COMMARL_FUSED_LINEAR"] = fused
-    gu, _ = grads(allidx, True)
-    ga, ca = grads(allidx[sel], False); gb, cb = grads(allidx[~sel], False)
-    print("fused =", fused)
-    for n in gu:
-        s = (ga[n] + gb[n]) / (ca + cb)
-        print(f"  {n:60s} |g|max {float(gu[n].abs().max()):.3e}  shards-vs-union {float((s - gu[n]).abs().max() / gu[n].abs().max()):.2e}")
-    if fused == "1": g1 = gu
-    else:
-        for n in gu: print(f"  fused-vs-unfused {n:50s} {float((g1[n]-gu[n]).abs().max()/gu[n].abs().max()):.2e}")
+gu, _ = grads(allidx, True)
+ga, ca = grads(allidx[sel], False); gb, cb = grads(allidx[~sel], False)
+for n in gu:
+    s = (ga[n] + gb[n]) / (ca + cb)
+    print(f"  {n:60s} |g|max {float(gu[n].abs().max()):.3e}  shards-vs-union {float((s - gu[n]).abs().max() / gu[n].abs().max()):.2e}")

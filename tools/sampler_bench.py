@@ -1,5 +1,5 @@
 """Time CentralizedMAOnPolicyVectorizedSampler.obtain_samples at the headline config (4096 envs, one full horizon per env):
-    python tools/sampler_bench.py [epochs]      (COMMARL_SAMPLER_GRAPH=0 / COMMARL_PERSISTENT=0 for the A/B forms)"""
+    python tools/sampler_bench.py [epochs]      (COMMARL_PERSISTENT=0 for the A/B form)"""
 import os, sys, time
 sys.path.insert(0, '.')
 import numpy as np, torch

@@ -2,7 +2,7 @@
 # HIP API calls issued between hipStreamBeginCapture and hipStreamEndCapture (anything but launches / event / wait calls is suspect)
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-export COMMARL_SKIP_CHILD_CASES=1 COMMARL_CAPTURE_MODE=relaxed
+export COMMARL_SKIP_CHILD_CASES=1
 rocprofv3 --hip-runtime-trace --output-format csv -d /tmp/hiptrace -o t -- python3 -m pytest $ROOT/tests/test_hip_ppo_parity.py -m gpu -q -x -k "test_two_ppo or test_multi_tensor or test_sampler or sharded_multistream" > $ROOT/gpurun_out/trace_capture.log 2>&1
 python3 - <<'PY' > $ROOT/gpurun_out/trace_capture_calls.txt
 import csv, glob, collections

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "cm_env_dev.h"
+#include "cm_env_pp10_dev.h"
 #include "cm_policy_w_dev.h"
 
 namespace cm {
@@ -61,6 +62,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (probe) { g_w_probe[3] = __builtin_amdgcn_s_memtime() - t_in; g_w_probe[0] = g_w_probe[1] = g_w_probe[2] = g_w_probe[4] = 0; }
     const int envs = FULLWG ? mw::WG_ENVS : min(mw::WG_ENVS, a.S - (int)blockIdx.x * mw::WG_ENVS);
     EnvPre pre{};
+    pp10::State st{};                                                    // SHAPE 1: the env in registers (cm_env_pp10_dev.h)
+    pp10::Pre pp{};
+    pp10::Emit em{};
     int obs_row = 0, obs_env = -1;                                       // LDS copy: this lane's row (policy) / this group's env (emission)
     if constexpr (CARRY) {
         const int tx = thread_x(), grp = tx / LPE, lane = tx & 63, cc = lane & 15;
@@ -78,7 +82,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int i = k / OBS_COPY_STRIDE, f = k - i * OBS_COPY_STRIDE;
             oc[k] = (ok && f < a.d) ? a.obs[((size_t)b0 * 4 + i) * a.d + f] : 0.0f;
         }
-        pre = env_prefetch<CM_PP, LPE>(p, b0, live);
+        if constexpr (SHAPE == 1) {                                      // the state as three words per lane from here on
+            const int b = (live && b0 < p.B) ? b0 : p.B - 1;             // as env_prefetch
+            st = pp10::load_state(p, b);
+            pp = pp10::load_pre(p, b, tx % LPE, tx);
+            em = pp10::emit_codes(tx % LPE);
+        } else pre = env_prefetch<CM_PP, LPE>(p, b0, live);
     }
     for (int t = 0; t < c.n_steps; ++t) {
         asm volatile("" ::: "memory");                                   // keep each step's loads inside the step
@@ -112,7 +121,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (ot.path_len) ot.path_len += (size_t)t * c.path_len;
         if (env_wave) {
             const int32_t *my_act = act + (live ? grp : 0) * 4;
-            if constexpr (CARRY) {
+            if constexpr (CARRY && SHAPE == 1) {
+                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, grp, b_raw, live, ENV_BASE, FULLWG, obs_env);
+            } else if constexpr (CARRY) {
                 const bool bad = env_stage<CM_PP, LPE>(p, pre, my_act, grp, ENV_BASE);
                 EnvCarry carry{ pre.step_count_in, pre.succ, 0 };
                 env_body<CM_PP, LPE>(p, nullptr, my_act, tape, ot, 0, grp, b_raw, live, ENV_BASE, nullptr, true, pre.rng_step, pre.step_count_in,

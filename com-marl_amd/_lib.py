@@ -60,6 +60,11 @@ class ChunkStrides(C.Structure):
                                          "dist_adj", "channels", "prey_alive", "success", "path_len")]
 
 
+class PolicySetT(C.Structure):
+    """cm_policy_set: device tables of a multi-policy chunk (cm_rollout_chunk_multi)."""
+    _fields_ = [("n_policies", C.c_int32), ("n_wg", C.c_int32), ("packs", C.c_void_p), ("wg_policy", C.c_void_p)]
+
+
 MLP_MAX_LAYERS = 6
 
 
@@ -102,6 +107,10 @@ _SIGNATURES = {
     "cm_rollout_chunk": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.c_int32, C.POINTER(ChunkStrides), C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StepOut), C.c_void_p]),
+    "cm_rollout_chunk_multi": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.POINTER(PolicySetT), C.c_int32,
+                                         C.POINTER(ChunkStrides), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32,
+                                         C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(StepOut), C.c_void_p]),
     "cm_rollout_chunk_tail": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.c_int32, C.POINTER(ChunkStrides), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StepOut), C.c_void_p, C.c_void_p, C.c_void_p,

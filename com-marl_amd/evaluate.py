@@ -21,6 +21,7 @@ Differences a maintainer should know (documented, not silent):
 import numpy as np
 import torch
 
+from .nets import PolicySet
 from .rollout import RolloutEngine
 
 VECTORS = ['reward', 'capture_cnt', 'step_cnt', 'move_cnt', 'penalty_cnt', 'nodeDeg', 'variable', 'vars2']   # testing.py:209
@@ -95,6 +96,98 @@ def eval_model(env, policy, itr, n_eval_episodes=100, max_env_steps=200, eval_gr
     env.eval_n_epi = len(episode_data)
     env.last_eval_average_reward = (sum(eval_rewards) / len(eval_rewards)) / base.bound_return    # eval_pp.py:95
     return episode_data, epi_success, epi_rewards, base.bound_return
+
+
+def _episode(h, b, N, pp):
+    """Env b's first episode of a round (host arrays of _first_episodes / _rounds) -> what eval_model appends for it."""
+    n = int(h["first"][b]) + 1
+    det = h["details"][:n, b].astype(np.float64)
+    rew = h["reward"][:n, b]
+    deg = np.concatenate([h["deg"][1:n, b], h["deg"][n - 1:n, b]]) if "deg" in h else np.full(n, N)
+    nA = float(N)
+    if pp:                                                                  # predator_prey.py:440-448
+        cols = dict(capture_cnt=det[:, 0], move_cnt=det[:, 1] / nA, penalty_cnt=det[:, 2],
+                    variable=det[:, 4] / nA, vars2=np.zeros(n))
+    else:                                                                   # coverage.py:308-315
+        cols = dict(capture_cnt=det[:, 0] / nA, move_cnt=det[:, 1] / nA, penalty_cnt=det[:, 2] / nA,
+                    variable=det[:, 4] / nA, vars2=det[:, 3] / nA)
+    cols.update(reward=rew, step_cnt=np.ones(n), nodeDeg=deg)
+    return n, cols, rew
+
+
+def _rounds(eng, base, T, greedy):
+    """_first_episodes with the T steps as chunk launches where the engine has them (one launch for every member of a
+    PolicySet on the wave-owned kernel); bit-identical to stepping them one by one."""
+    eng.reset()
+    if not eng.steps_fused(0, T, greedy=greedy):
+        eng.fork()
+        for t in range(T):
+            eng.step(t, greedy=greedy)
+        eng.join()
+    eng.bump(T)
+    base.batch.check_status()
+    pl = eng.path_len[:T]
+    ended = pl > 0
+    first = torch.where(ended.any(0), ended.to(torch.int32).argmax(0), torch.full_like(pl[0], T - 1)).long()
+    h = dict(first=first.cpu().numpy(), reward=eng.reward64[:T].cpu().numpy(), details=eng.details[:T].cpu().numpy(),
+             success=eng.success[:T].cpu().numpy(), done=eng.done[:T].cpu().numpy())
+    if eng.dist_adj is not None:
+        h["deg"] = eng.dist_adj[:T + 1].sum(-1).mean(-1).cpu().numpy()
+    return h
+
+
+def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, render=False,
+                inspect_steps=False, seed=1, flag=None):
+    """eval_model for K policies of one architecture at once (e.g. the checkpoints of a run): the B envs of `env` are split
+    into K contiguous groups of B / K, policy k playing on group k, all K in the same rollout (one launch per round's chunk
+    on the wave-owned kernel of teams of 4, nets.PolicySet).  -> list of K tuples (episode_data, epi_success, epi_rewards,
+    bound_return); tuple k is exactly eval_model(W_k, policies[k], ...) for W_k a fresh wrapper of env's class, params and seed
+    with n_envs = B / K and env_id_offset = env's + k B / K.  Afterwards env.eval_n_epi is the episode count of one policy and
+    env.last_eval_average_reward the list of the K policies' averages."""
+    if render or inspect_steps:
+        raise NotImplementedError("rendering is outside the MI355X path")
+    if flag is not None and flag[0]:
+        return [(None, None, None, None) for _ in policies]
+    ps = policies if isinstance(policies, PolicySet) else PolicySet(policies)
+    base = getattr(env, "env", env)
+    batch = base.batch
+    B, N, K = batch.B, batch.N, len(ps)
+    if B % K:
+        raise ValueError(f"eval_models: the {B} envs of the wrapper do not split evenly between {K} policies")
+    Bk = B // K
+    pp = batch.scenario == "pp"
+    T = int(max_env_steps)
+    if T > batch.cfg.max_path_length:
+        raise ValueError(f"max_env_steps={T} exceeds the env's max_path_length={batch.cfg.max_path_length}")
+    env.eval_n_epi = 0
+    ps.sync_weights()
+    ps.reset([True] * Bk)
+    eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, groups=[Bk] * K)
+    data = [[] for _ in range(K)]
+    success = [[] for _ in range(K)]
+    epi_rewards = [{vec: [] for vec in VECTORS} for _ in range(K)]
+    eval_rewards = [[] for _ in range(K)]
+    while len(data[0]) < n_eval_episodes:                 # every group has Bk envs: the same number of rounds for each
+        h = _rounds(eng, base, T, bool(eval_greedy))
+        take = min(Bk, n_eval_episodes - len(data[0]))
+        for k, (lo, _) in enumerate(eng.groups):
+            for b in range(lo, lo + take):
+                n, cols, rew = _episode(h, b, N, pp)
+                data[k].append((h["success"][:n, b].tolist(), {vec: cols[vec].tolist() for vec in VECTORS}))
+                success[k].append(int(h["success"][n - 1, b]))
+                for vec in VECTORS:
+                    epi_rewards[k][vec].append(float(np.mean(cols[vec]) if vec == 'nodeDeg' else np.sum(cols[vec])))
+                eval_rewards[k].append(float(rew.sum()))
+    env.eval_n_epi = len(data[0])
+    env.last_eval_average_reward = [(sum(r) / len(r)) / base.bound_return for r in eval_rewards]
+    return [(data[k], success[k], epi_rewards[k], base.bound_return) for k in range(K)]
+
+
+def eval_models_co(env, policies, itr=None, **kwargs):
+    """eval_models with eval_model_co's contract: the fourth value of each tuple is the per-episode list of
+    ``env.bound_return``."""
+    return [out if out[0] is None else (out[0], out[1], out[2], [out[3]] * len(out[0]))
+            for out in eval_models(env, policies, itr, **kwargs)]
 
 
 def eval_model_co(env, policy, itr, **kwargs):

@@ -1435,3 +1435,81 @@ class GaussianMLPBaseline(_WeightPack, nn.Module):
         _RowMLPPolicy._need_gpu(obs)
         mean, std = self.module(obs.reshape(-1, self.input_dim))                  # :93-96
         return -Normal(mean, std, validate_args=False).log_prob(returns.reshape(-1, 1)).mean()      # (no host sync, as above)
+
+
+# ---------------------------------------------------------------------------------------------
+# policy sets (several policies of one architecture in one rollout)
+# ---------------------------------------------------------------------------------------------
+def _architecture(p):
+    """(name, value) pairs that must agree between the members of a PolicySet, in the order they are checked."""
+    comm = isinstance(p, CommBaseNet)
+    act = p.categorical_output_layer._hidden_act if comm else getattr(p, "_hidden_act", ACT_TANH)
+    return [("class", type(p).__name__), ("team size", p._n_agents), ("observation dim", p._dec_obs_dim),
+            ("action dim", p._action_dim),
+            ("hops", len(p.gcn_layers) if comm else None),
+            ("attention type", p.attention_layer.attention_type if comm else None),
+            ("residual", bool(p.residual) if comm else None),
+            ("hidden sizes", tuple((n, tuple(t.shape)) for n, t in p.named_parameters())),
+            ("hidden nonlinearity", int(act)),
+            ("device", next(p.parameters()).device)]
+
+
+class PolicySet:
+    """K policies of ONE architecture (class, team size, observation dim, hops, attention type, residual, hidden sizes, hidden
+    nonlinearity, device) that one RolloutEngine runs side by side, each on its own contiguous range of the envs - e.g. the
+    checkpoints of one run evaluated at once (evaluate.eval_models).  What the engine reads from a policy (``_n_agents``,
+    ``_action_dim``, ``comm``, ...) comes from member 0; ``sync_weights()`` refreshes every member's pack and
+    ``pack_table()`` keeps the device table of the members' pack addresses that cm_rollout_chunk_multi reads."""
+    _SHARED = ("_n_agents", "_action_dim", "_dec_obs_dim", "_obs_dim", "_embedding_dim", "comm", "centralized", "device",
+               "n_gcn_layers", "residual")
+
+    def __init__(self, policies):
+        policies = list(policies)
+        if not policies:
+            raise ValueError("PolicySet needs at least one policy")
+        ref = _architecture(policies[0])
+        for i, p in enumerate(policies[1:], 1):
+            for (name, v0), (_, v) in zip(ref, _architecture(p)):
+                if v != v0:
+                    raise ValueError(f"PolicySet: policies[{i}] differs from policies[0] in {name}: {v!r} != {v0!r}")
+        self.policies = policies
+        self._table = None                      # (pack addresses, int64 device tensor of them)
+
+    def __getattr__(self, name):
+        if name in PolicySet._SHARED:
+            return getattr(self.policies[0], name)
+        raise AttributeError(name)
+
+    def __len__(self):
+        return len(self.policies)
+
+    def __getitem__(self, k):
+        return self.policies[k]
+
+    def __iter__(self):
+        return iter(self.policies)
+
+    @property
+    def seed(self):
+        """The sampler seed the members share, or None when they differ (one launch keys one Philox stream)."""
+        seeds = {p.seed for p in self.policies}
+        return seeds.pop() if len(seeds) == 1 else None
+
+    def sync_weights(self):
+        for p in self.policies:
+            p.sync_weights()
+
+    def reset(self, dones=None):
+        for p in self.policies:
+            p.reset(dones)
+
+    def pack_table(self):
+        """int64 device tensor [K] of the members' operand-pack addresses (cm_policy_pack outputs); rebuilt when a member's pack
+        buffer was (re)allocated, packing the members that have none yet."""
+        if any(getattr(p, "_mfma", None) is None for p in self.policies):
+            self.sync_weights()
+        ptrs = tuple(p._mfma.data_ptr() for p in self.policies)
+        if self._table is None or self._table[0] != ptrs:
+            dev = self.policies[0]._mfma.device
+            self._table = (ptrs, torch.tensor(ptrs, dtype=torch.int64).to(dev))
+        return self._table[1]

@@ -13,11 +13,15 @@ contiguous [B, ...] slabs and the kernels write straight into them (zero-copy). 
 steps can be captured into a hipGraph and replayed (the launch-bound regime at 4096 x N=4).
 """
 import contextlib
+import ctypes as C
 import os
 
 import torch
 
 from . import _lib as L
+from .nets import PolicySet
+
+WG_ENVS = 16                 # envs per workgroup of the wave-owned kernels: a multi-policy launch gives each workgroup one policy
 
 _null = contextlib.nullcontext
 
@@ -47,11 +51,16 @@ class _Parts:
 
 class RolloutEngine:
     def __init__(self, env, policy, horizon, store_attn=True, store_probs=True, fused="auto", persistent="auto",
-                 graph_fused=True):
+                 graph_fused=True, groups=None):
         """env: envs.GridEnvBatch, or a list of shards of one batch (then every shard runs its own
         policy -> env chain on its own HIP stream: the chains are independent, so kernels of different
         shards overlap and their phases drift apart instead of contending in lockstep).
-        policy: nets.CommCategoricalMLPPolicy (or the Obs-DP / CENT policy) on the same device."""
+        policy: nets.CommCategoricalMLPPolicy (or the Obs-DP / CENT policy) on the same device, or a nets.PolicySet of K
+        policies on one GridEnvBatch: `groups` lists the env count of each member (default: B / K each), member k owning the
+        contiguous envs [lo_k, hi_k).  Each env plays exactly what it would play in a single-policy engine whose env batch
+        starts at the same global env id.  Teams of 4 whose groups start on multiples of 16 envs run a chunk as ONE
+        cm_rollout_chunk_multi launch (multi_form "wave"); every other set steps member by member on its envs, then one env
+        step over the batch (multi_form "loop")."""
         if isinstance(env, (list, tuple)):
             env = _Parts(list(env)) if len(env) > 1 else env[0]
         self.env, self.policy, self.H = env, policy, int(horizon)
@@ -107,6 +116,80 @@ class RolloutEngine:
         self._fused_in_graph = bool(fused) and bool(graph_fused)
         self.t = 0
         self.generation = 0                      # bumped by reset(): a PathBatch of an earlier rollout refuses to read the buffers
+        self.multi_form = None                   # PolicySet: "wave" (one launch per chunk for all members) or "loop"
+        if isinstance(policy, PolicySet):
+            self._init_multi(groups)
+        elif groups is not None:
+            raise ValueError("groups= splits the envs between the members of a nets.PolicySet")
+
+    def _init_multi(self, groups):
+        ps, B = self.policy, self.env.B
+        if len(self.parts) != 1:
+            raise ValueError("a PolicySet runs on one GridEnvBatch, not on shards")
+        K = len(ps)
+        if groups is None:
+            if B % K:
+                raise ValueError(f"{B} envs do not split evenly between {K} policies: pass groups=")
+            groups = [B // K] * K
+        groups = [int(g) for g in groups]
+        if len(groups) != K or min(groups) < 1 or sum(groups) != B:
+            raise ValueError(f"groups must give each of the {K} policies at least one env and sum to B={B}: {groups}")
+        self.groups, lo = [], 0
+        for g in groups:
+            self.groups.append((lo, lo + g))
+            lo += g
+        # one launch for the whole set: teams of 4 on the default (wave-owned) kernel, every member's envs in whole workgroups of
+        # 16, one sampler seed; the library may still answer "not for this shape" (1), and the engine then loops from there on
+        pk = os.environ.get("COMMARL_POLICY_KERNEL", "w")[:1]
+        wave = (hasattr(ps[0], "chunk_fused") and ps._n_agents == 4 and pk not in ("h", "f", "v") and ps.seed is not None
+                and all(lo % WG_ENVS == 0 for lo, _ in self.groups) and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
+        self.multi_form = "wave" if wave else "loop"
+        self._persistent, self._fused = wave, None
+        if wave:
+            n_wg = (B + WG_ENVS - 1) // WG_ENVS
+            wg = [k for k, (lo, hi) in enumerate(self.groups) for _ in range(lo // WG_ENVS, (hi + WG_ENVS - 1) // WG_ENVS)]
+            assert len(wg) == n_wg and all(0 <= k < K for k in wg)       # checked here: the kernel trusts the table
+            self._wg_policy = torch.tensor(wg, dtype=torch.int32).to(self.env.device)
+
+    def _multi_chunk(self, t0, n, greedy):
+        """Slots t0 .. t0+n-1 of every member in ONE cm_rollout_chunk_multi launch.  False - nothing launched - when the
+        library has no multi-policy kernel for this shape (the engine loops member by member from then on).  The members'
+        packs are used as they are: sync_weights() (run_chunk, prepare_graph, eval_models) refreshes them."""
+        if self.multi_form != "wave":
+            return False
+        ps, env, B = self.policy, self.env, self.env.B
+        w = ps[0]._weights_struct()                                         # the shape every member shares
+        st = L.PolicySetT(len(ps), self._wg_policy.numel(), L.ptr(ps.pack_table()), L.ptr(self._wg_policy))
+        with torch.cuda.device(env.device):
+            rc = L.lib().cm_rollout_chunk_multi(
+                env._h, C.byref(w), C.byref(st), int(n), C.byref(self._strides()), L.ptr(self.obs[t0]),
+                L.ptr(None if self.dist_adj is None else self.dist_adj[t0]),
+                L.ptr(None if self.channels is None else self.channels[t0]), ps.seed, self.id0, t0 & 0xFFFFFFFF,
+                L.ptr(self.step_bases[0]), int(greedy), L.ptr(self.actions[t0]),
+                L.ptr(None if self.probs is None else self.probs[t0]), L.ptr(None if self.attn is None else self.attn[t0]),
+                C.byref(env._out(self._out(t0, 0, B))), L.current_stream())
+        if rc == 1:
+            self.multi_form, self._persistent = "loop", False
+            return False
+        L.check(rc, "cm_rollout_chunk_multi")
+        return True
+
+    def _multi_step(self, t, greedy):
+        """Slot t -> t+1 for every member: one launch (a chunk of one step) where the set has the multi-policy kernel, else each
+        member's forward + sample on its envs (env ids id0 + lo_k, the shared Philox base) and one env step over the batch."""
+        if self._multi_chunk(t, 1, greedy):
+            return
+        for pol, (lo, hi) in zip(self.policy, self.groups):
+            pol.act_device(
+                self.obs[t][lo:hi].view(hi - lo, -1), None,
+                None if self.dist_adj is None else self.dist_adj[t][lo:hi],
+                None if self.channels is None else self.channels[t][lo:hi],
+                greedy=greedy, out_actions=self.actions[t][lo:hi],
+                out_probs=None if self.probs is None else self.probs[t][lo:hi],
+                out_attn=None if self.attn is None else self.attn[t][lo:hi],
+                want_probs=self.probs is not None, want_attn=self.attn is not None,
+                policy_step=t, step_base=self.step_bases[0], env_id_offset=self.id0 + lo)
+        self.env.step_device(self.actions[t], out=self._out(t, 0, self.env.B))
 
     @property
     def step_base(self):
@@ -144,6 +227,9 @@ class RolloutEngine:
         self.generation += 1
 
     def _step_part(self, k, t, greedy):
+        if self.multi_form is not None:
+            self._multi_step(t, greedy)
+            return
         part, (lo, hi) = self.parts[k], self.bounds[k]
         nb = hi - lo
         if self._fused is not False and (not self._capturing or self._fused_in_graph) and hasattr(self.policy, "step_fused"):
@@ -223,6 +309,12 @@ class RolloutEngine:
         """Slots t0 .. t0+n-1 in one persistent launch per shard (cm_rollout_chunk); tail: followed by the chunk's tail - slot
         t0+n into slot 0, Philox base += n (cm_rollout_chunk_tail: the same launch where the library can).  False when the
         library has no fused kernel for this shape (nothing was launched)."""
+        if self.multi_form is not None:                     # PolicySet: every member in one launch, or False (loop form)
+            if not self._multi_chunk(t0, n, greedy):
+                return False
+            if tail:
+                self._chunk_tail(0, t0 + n)
+            return True
         if self._fused is False or not hasattr(self.policy, "chunk_fused") or getattr(self.parts[0].cfg, "rng_mode", 0) != L.RNG_PHILOX:
             return False
         st = self._strides()

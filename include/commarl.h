@@ -282,6 +282,27 @@ int cm_rollout_chunk(cm_env_t h, const cm_policy_weights *w, int32_t n_steps, co
                      int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy,
                      int32_t *actions, float *probs, float *attn, const cm_step_out *out, void *stream);
 
+/* cm_rollout_chunk with SEVERAL policies of one architecture in the same launch (evaluating many checkpoints at once): the B envs
+ * of `h` are split into workgroups of 16 consecutive envs, and workgroup g runs the policy whose pack is packs[wg_policy[g]].
+ * `w` gives the shape every member shares (its weight pointers are not read).  Every other argument is that of cm_rollout_chunk, and
+ * env b draws what it would draw in a single-policy launch at the same global env id (env_id_offset + b): a workgroup's results
+ * are bit-identical to cm_rollout_chunk with its policy.  Preconditions, NOT checked on the device:
+ *   - each workgroup's 16 envs belong to one policy, i.e. every policy's env range except the last one's ends on a multiple of 16;
+ *   - every wg_policy value lies in [0, n_policies) (build and check the table on the host, then upload it);
+ *   - the CM_PACK_WAVE section of every pack is current.
+ * Returns 0 when the multi-policy kernel was launched, < 0 on error, and 1 - having done nothing - when the shape is not teams of 4
+ * on the wave-owned kernel (or the sizes do not fit it): the caller then runs each policy on its envs (cm_policy_forward on the
+ * group's rows) and one cm_env_step per step. */
+typedef struct cm_policy_set {
+    int32_t n_policies, n_wg;        /* n_wg = ceil(B / 16) */
+    const float *const *packs;       /* DEVICE array [n_policies] of cm_policy_pack() outputs */
+    const int32_t *wg_policy;        /* DEVICE array [n_wg], values in [0, n_policies) */
+} cm_policy_set;
+int cm_rollout_chunk_multi(cm_env_t h, const cm_policy_weights *w, const cm_policy_set *set, int32_t n_steps,
+                           const cm_chunk_strides *strides, const float *obs, const float *dist_adj, const float *channels,
+                           uint64_t seed, int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base,
+                           int32_t greedy, int32_t *actions, float *probs, float *attn, const cm_step_out *out, void *stream);
+
 /* cm_rollout_chunk followed by cm_chunk_tail (below) for the same chunk: the observation (and masks, where the env produces
  * them) the last step wrote - out->obs + (n_steps - 1) * strides->obs, ... - carried into obs_next / dist_adj_next /
  * channels_next (slot 0 of the caller's ring; the mask pointers may be NULL) and *policy_step_base += n_steps.  Where the wave-owned

@@ -132,14 +132,38 @@ __device__ __forceinline__ void tanh_stage(float (&v)[N]) {
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 __host__ __device__ inline void split_u(float x, h16 &h, h16 &l) { h = (h16)x; l = (h16)(x - (float)h); }
-template <int N>
+// The residual y - hi, three forms (tools/micro/wave_chain.hip times them; all three give the same bits: hi * -1 is
+// exact, so the fused form rounds y - hi once, as the subtraction does, and y - hi is itself exact in f32 short of overflow):
+//   SPLIT_SUB    v_cvt_f32_f16 + v_sub_f32 per value, v_cvt_pk_f16_f32 per pair
+//   SPLIT_MIX    v_fma_mix_f32 per value (reads the f16 half of the hi pair as a source), v_cvt_pk_f16_f32 per pair
+//   SPLIT_MIXLO  v_fma_mixlo_f16 / v_fma_mixhi_f16 per value, writing the lo pair directly
+// hipcc folds fma(x, -1, y) to y - x and then converts x on its own again, so the -1 comes out of a register it cannot see through;
+// from there on the compiler selects, schedules and pads the mix instructions like any other.
+// SPLIT_MIXLO is what the kernels run: 430 vector instructions fewer per step of the headline rollout than SPLIT_SUB, and the
+// fastest of the three in that kernel (DESIGN.md §5 has the figures, and those of the layer-pair benchmark, which prefers SPLIT_MIX).
+enum { SPLIT_SUB = 0, SPLIT_MIX = 1, SPLIT_MIXLO = 2 };
+constexpr int SPLIT_DEFAULT = SPLIT_MIXLO;
+__device__ __forceinline__ float opaque_minus_one() { float m; asm("s_mov_b32 %0, -1.0" : "=s"(m)); return m; }
+template <int N, int MODE = SPLIT_DEFAULT>
 __device__ __forceinline__ void split_stage(const float (&y)[N], h16 (&h)[N], h16 (&l)[N]) {
     static_assert(N % 2 == 0, "pairs");
     float d[N];
 #pragma unroll
     for (int i = 0; i < N; i += 2) { const v2h p = __builtin_convertvector((v2f){ y[i], y[i + 1] }, v2h); h[i] = p[0]; h[i + 1] = p[1]; }
+    if constexpr (MODE == SPLIT_MIXLO) {
+        const float m1 = opaque_minus_one();
 #pragma unroll
-    for (int i = 0; i < N; ++i) d[i] = y[i] - (float)h[i];
+        for (int i = 0; i < N; ++i) l[i] = (h16)__builtin_fmaf((float)h[i], m1, y[i]);
+        return;
+    }
+    if constexpr (MODE == SPLIT_MIX) {
+        const float m1 = opaque_minus_one();
+#pragma unroll
+        for (int i = 0; i < N; ++i) d[i] = __builtin_fmaf((float)h[i], m1, y[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) d[i] = y[i] - (float)h[i];
+    }
 #pragma unroll
     for (int i = 0; i < N; i += 2) { const v2h p = __builtin_convertvector((v2f){ d[i], d[i + 1] }, v2h); l[i] = p[0]; l[i + 1] = p[1]; }
 }
@@ -150,7 +174,7 @@ __device__ __forceinline__ void split_stage(const float (&y)[N], h16 (&h)[N], h1
 // [CT] (the embedding E, which the residual needs again).
 // sv (may be null): this lane's row of a [rows][16 CT] f32 matrix that receives the layer's output (training forward: what the
 // backward pass reads back) - features 16 ct + 4 g .. + 3 of row c are one 16-byte store.
-template <int KB, int CT, bool TANH, bool BIAS>
+template <int KB, int CT, bool TANH, bool BIAS, int SPLIT = SPLIT_DEFAULT>
 __device__ __forceinline__ void dense_act(const Frags<KB, CT> &f, const float *bias, const Act<KB> &x, Act<CT / 2> &y, v4f *keep, int lane,
                                           float *sv = nullptr) {
     const int g = lane >> 4;
@@ -186,7 +210,7 @@ __device__ __forceinline__ void dense_act(const Frags<KB, CT> &f, const float *b
                 *reinterpret_cast<float4 *>(sv + 16 * (2 * (p - 1) + 1) + 4 * g) = make_float4(v[4], v[5], v[6], v[7]);
             }
             h16 h[8], l[8];
-            split_stage<8>(v, h, l);
+            split_stage<8, SPLIT>(v, h, l);
 #pragma unroll
             for (int e = 0; e < 8; ++e) { y.hi[p - 1][e] = h[e]; y.lo[p - 1][e] = l[e]; }
         }
@@ -247,7 +271,16 @@ __device__ __forceinline__ void stage_w(const WeightsW &w, unsigned char *lds, i
 struct ResidentW {
     Frags<4, 4> h2;
     template <int LHOPS>
-    __device__ __forceinline__ void fetch(const WeightsW &w, int lane) { h2.fetch(w.pack + pack_w(LHOPS).h2, lane); }
+    __device__ __forceinline__ void fetch(const WeightsW &w, int lane) {
+        h2.fetch(w.pack + pack_w(LHOPS).h2, lane);
+        // 128 registers that live for the whole launch: the allocator parks them in AGPRs either way, and left to itself copies
+        // each one back (v_accvgpr_read_b32) in front of the MFMA that takes it, every step.  Defined in AGPRs they stay there
+        // and the MFMA names them directly (a gfx950 MFMA reads its A / B operands from either file).
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { asm volatile("" : "+a"(h2.h[ct][q])); asm volatile("" : "+a"(h2.l[ct][q])); }
+    }
 };
 
 // ---- one wave's tile: rows [16 * wave, 16 * wave + 16) of workgroup blk.  No workgroup barrier: everything is the wave's own. ----

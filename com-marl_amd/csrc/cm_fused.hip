@@ -12,16 +12,10 @@
 #include "cm_env_dev.h"
 #include "cm_policy_mfma_dev.h"
 #include "cm_policy_h_dev.h"
+#include "cm_rollout_w_dev.h"   // host side only: the wave-owned launch and what the rollout entry points share
 
 namespace cm {
 
-// cm_rollout_w.hip: teams of 4 on wave-owned rows (single step, or a persistent chunk); 1 = not available for this handle
-int launch_rollout_w(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pack, const cm_env *h, const cm_rng_tape &t, const cm_step_out &out,
-                     void *stream, const ChunkArgs *chunk);
-bool shape_ok_rollout_w(int N, int d, int L, int n_act);
-
-bool policy_w_enabled();                                 // cm_policy_w.hip: wave-owned teams-of-4 kernel (default where the shape allows)
-size_t policy_pack_h_bytes(int d, int L, bool policy);   // cm_policy_h.hip: size of the f16 pack the wave-owned fragments sit behind
 bool policy_h_enabled();                                 // cm_policy_h.hip: f16-split dense layers (default) or the all-f32 body
 
 // POL selects the policy body: 0 = cm_policy_mfma_dev.h (all f32), 1 = cm_policy_h_dev.h (f16-split dense layers).  Both
@@ -117,17 +111,6 @@ __global__ __launch_bounds__(mf::TPB, 2) void rollout_chunk_kernel(mf::FwdArgs a
     }
 }
 
-// diagnostic (COMMARL_ENV_STOP=-1): phase clocks of workgroup 0's env phase inside the fused step (ENV_PROBE, cm_env_dev.h)
-static void probe_dump(const EnvDev &d, void *stream) {
-    if (d.stop >= 0) return;
-    unsigned long long h_probe[16];
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return;
-    if (hipMemcpyFromSymbol(h_probe, HIP_SYMBOL(g_env_probe), sizeof(h_probe)) != hipSuccess) return;
-    fprintf(stderr, "[fused env probe] clk since env entry:");
-    for (int i = 1; i < 10; ++i) fprintf(stderr, " p%d=%lld", i, (long long)(h_probe[i] - h_probe[0]));
-    fprintf(stderr, "\n");
-}
-
 template <int SCEN, int LPE, int KPAD, int MAXMK, int POL>
 static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &ph, const mh::TrunkH &twh, const mh::PolHeadH &phh,
                         const cm_env *h, const cm_rng_tape &t, const cm_step_out &out, void *stream, const ChunkArgs *chunk = nullptr) {
@@ -172,7 +155,7 @@ static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &
         hipLaunchKernelGGL((rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL, true, PRE>), dim3(blocks), dim3(mf::TPB), lds,       \
                            (hipStream_t)stream, a, tw, ph, twh, phh, d, t, out, (int)pol_floats);                                 \
         CM_HIP(hipGetLastError());                                                                                                \
-        probe_dump(d, stream);                                                                                                    \
+        if (d.stop < 0) env_probe_dump("fused", HIP_SYMBOL(g_env_probe), stream);                                                 \
         return CM_OK;                                                                                                             \
     } while (0)
             if (env_prefetch_ok<SCEN, LPE>(d)) CM_FULL_LAUNCH(true);
@@ -195,20 +178,14 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
                         uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy, int32_t *actions,
                         float *probs, float *attn, const cm_rng_tape *tape, const cm_step_out *out, void *stream,
                         const ChunkArgs *chunk) {
-    if (!h || !w || !obs || !out) return set_error(CM_ERR_ARG, "cm_rollout_step: null argument");
+    if (int rc = check_rollout_args("cm_rollout_step", h, w, obs, out)) return rc;
     const EnvDev &d = h->dev;
-    if (w->n_agents != d.N || w->d != d.d || w->n_hops != d.L)
-        return set_error(CM_ERR_ARG, "cm_rollout_step: policy shape (n_agents, d, n_hops) does not match the env handle");
     if (!w->mfma_pack || !policy_shape_ok(w)) return 1;
     if (int rc = check_tape(h, tape, false)) return rc;
     cm_rng_tape t{};
     if (tape) t = *tape;
-    mf::FwdArgs a{};
-    a.S = d.B; a.N = d.N; a.d = d.d; a.L = d.L;
-    a.obs = obs; a.avail = avail; a.adj = dist_adj; a.chan = channels;
-    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;
-    a.env_id_offset = env_id_offset; a.greedy = greedy; a.no_residual = w->no_residual;
-    a.actions = actions; a.probs = probs; a.attn = attn;
+    const mf::FwdArgs a = rollout_fwd_args(h, w, obs, avail, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy,
+                                           actions, probs, attn);
     const int kpad = mf::kpad_of(d.d);
     const mf::PackLayout lo = mf::pack_layout(kpad, d.L, true);
     const float *P = w->mfma_pack;
@@ -219,7 +196,7 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
     const bool quad = d.N == 4 && mf::pick_epb(4) * 4 <= 32;
     const int kh = mh::kh_of(d.d);
     if (policy_w_enabled() && shape_ok_rollout_w(d.N, d.d, d.L, w->n_act)) {    // teams of 4: wave-owned rows, single step or persistent chunk
-        const int rc = launch_rollout_w(a, w, reinterpret_cast<const char *>(P + lo.total) + policy_pack_h_bytes(d.d, d.L, true), h, t, *out, stream, chunk);
+        const int rc = launch_rollout_w(a, w, reinterpret_cast<const char *>(P) + wave_pack(d), h, t, *out, stream, chunk);
         if (rc != 1) return rc;
     }
     if (policy_h_enabled() && kh) {                  // f16-split dense layers: the operand pack behind the f32 one
@@ -262,12 +239,9 @@ extern "C" int cm_rollout_chunk(cm_env_t h, const cm_policy_weights *w, int32_t 
                                 const float *obs, const float *dist_adj, const float *channels, uint64_t seed,
                                 int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy,
                                 int32_t *actions, float *probs, float *attn, const cm_step_out *out, void *stream) {
-    if (!st) return set_error(CM_ERR_ARG, "cm_rollout_chunk: null strides");
-    if (n_steps < 0) return set_error(CM_ERR_ARG, "cm_rollout_chunk: negative step count");
-    if (h && h->cfg.rng_mode == CM_RNG_TAPE) return set_error(CM_ERR_ARG, "cm_rollout_chunk: tape mode steps one launch at a time");
+    if (int rc = check_chunk_args("cm_rollout_chunk", h, st, n_steps, 0)) return rc;
     if (n_steps == 0) return CM_OK;
-    ChunkArgs c{ n_steps, st->obs, st->actions, st->probs, st->attn, st->reward, st->reward_f64, st->done, st->details,
-                 st->dist_adj, st->channels, st->prey_alive, st->success, st->path_len };
+    const ChunkArgs c = chunk_args(n_steps, *st);
     return rollout_impl(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy, actions,
                         probs, attn, nullptr, out, stream, &c);
 }
@@ -277,13 +251,11 @@ extern "C" int cm_rollout_chunk_tail(cm_env_t h, const cm_policy_weights *w, int
                                      int32_t env_id_offset, uint32_t policy_step, uint32_t *policy_step_base, int32_t greedy,
                                      int32_t *actions, float *probs, float *attn, const cm_step_out *out, float *obs_next,
                                      float *dist_adj_next, float *channels_next, void *stream) {
-    if (!st) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: null strides");
-    if (n_steps < 1) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: at least one step");
+    if (int rc = check_chunk_args("cm_rollout_chunk_tail", h, st, n_steps, 1)) return rc;
     if (!h || !out || !out->obs || !obs_next || !policy_step_base) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: null argument");
-    if (h->cfg.rng_mode == CM_RNG_TAPE) return set_error(CM_ERR_ARG, "cm_rollout_chunk_tail: tape mode steps one launch at a time");
     int folded = 0;
-    ChunkArgs c{ n_steps, st->obs, st->actions, st->probs, st->attn, st->reward, st->reward_f64, st->done, st->details,
-                 st->dist_adj, st->channels, st->prey_alive, st->success, st->path_len, obs_next, policy_step_base, &folded };
+    ChunkArgs c = chunk_args(n_steps, *st);
+    c.tail_obs = obs_next; c.tail_base = policy_step_base; c.tail_folded = &folded;
     const int rc = rollout_impl(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy, actions,
                                 probs, attn, nullptr, out, stream, &c);
     if (rc != CM_OK || folded) return rc;

@@ -106,6 +106,10 @@ struct ChunkArgs {
     uint32_t *tail_base = nullptr;
     int *tail_folded = nullptr;
 };
+static inline ChunkArgs chunk_args(int n_steps, const cm_chunk_strides &st) {
+    return ChunkArgs{ n_steps, st.obs, st.actions, st.probs, st.attn, st.reward, st.reward_f64, st.done, st.details,
+                      st.dist_adj, st.channels, st.prey_alive, st.success, st.path_len };
+}
 
 int check_tape(const cm_env *h, const cm_rng_tape *tape, bool is_reset);   // cm_env.hip: tape pointers the config needs
 namespace mf {

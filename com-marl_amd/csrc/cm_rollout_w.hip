@@ -2,13 +2,9 @@
 // the env step (cm_env_dev.h) of a wave's four envs, by that wave alone, for one step or a whole chunk of steps per launch
 // (reference: centralized_ma_on_policy_vectorized_sampler.py:119-232 - get_actions, vec_env.step, obses = next_obses).
 // Its own translation unit: built with -fno-slp-vectorize (Makefile), which the older kernels of cm_fused.hip are not.
-#include <stdio.h>
-
 #include "cm_rollout_w_dev.h"
 
 namespace cm {
-
-bool policy_w_enabled();                                 // cm_policy_w.hip
 
 template <int LHOPS, bool PRE, bool FULLWG, bool TAPE, bool CARRY = false, int SHAPE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_w_kernel(mf::FwdArgs a, mw::WeightsW w, EnvDev p, cm_rng_tape tape_arg, cm_step_out out, StridesW c, TailW tl) {
@@ -58,37 +54,11 @@ int launch_rollout_w(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pa
     RolloutWPlan pl;
     if (plan_rollout_w(a, h, use_tape, chunk, pl)) return 1;
     const mw::WeightsW ww{ reinterpret_cast<const uint4 *>(w_pack), w->n_act };
-    const int blocks = pl.blocks;
-    const size_t lds = pl.lds;
-    const StridesW &c = pl.c;
-    const TailW &tl = pl.tl;
-    const bool pre = pl.pre, full = pl.full, carry = pl.carry, map10 = pl.map10;
-#define CM_RW_(LH, PR, FU, TP, CA, SH)                                                                                          \
-    do {                                                                                                                        \
-        static unsigned long long done = 0;                                                                                     \
-        if (cm::dev_first(done))                                                                                                \
-            CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_w_kernel<LH, PR, FU, TP, CA, SH>),               \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                \
-        hipLaunchKernelGGL((rollout_w_kernel<LH, PR, FU, TP, CA, SH>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, a, ww, d, t, out, c, tl); \
-    } while (0)
-#define CM_RW(LH, PR, FU, TP, CA) do { if (CA && map10) CM_RW_(LH, PR, FU, TP, CA, (CA ? 1 : 0)); else CM_RW_(LH, PR, FU, TP, CA, 0); } while (0)
-#define CM_RW2(LH) do { if (use_tape) CM_RW(LH, false, false, true, false);                                                     \
-                        else if (carry) { if (full) CM_RW(LH, true, true, false, true); else CM_RW(LH, true, false, false, true); } \
-                        else if (pre) { if (full) CM_RW(LH, true, true, false, false); else CM_RW(LH, true, false, false, false); } \
-                        else { if (full) CM_RW(LH, false, true, false, false); else CM_RW(LH, false, false, false, false); } } while (0)
-    if (d.L == 1) CM_RW2(1); else CM_RW2(2);
-#undef CM_RW2
-#undef CM_RW
-#undef CM_RW_
-    CM_HIP(hipGetLastError());
-    if (d.stop == -1) {                                                  // env phase clocks of workgroup 0 (ENV_PROBE, cm_env_dev.h)
-        unsigned long long hp[16];
-        if (hipStreamSynchronize((hipStream_t)stream) == hipSuccess && hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_env_probe), sizeof(hp)) == hipSuccess) {
-            fprintf(stderr, "[rollout_w env probe] clk since env entry:");
-            for (int i = 1; i < 10; ++i) fprintf(stderr, " p%d=%lld", i, (long long)(hp[i] - hp[0]));
-            fprintf(stderr, "\n");
-        }
-    }
+    const int rc = for_rollout_w_variant(d.L, use_tape, pl, [&](auto LH, auto PR, auto FU, auto TP, auto CA, auto SH) {
+        return launch_rollout_w_variant<&rollout_w_kernel<LH.value, PR.value, FU.value, TP.value, CA.value, SH.value>>(pl, stream, a, ww, d, t, out, pl.c, pl.tl);
+    });
+    if (rc != CM_OK) return rc;
+    if (d.stop == -1) env_probe_dump("rollout_w", HIP_SYMBOL(g_env_probe), stream);
     if (d.stop == -2) {
         unsigned long long hp[5];
         if (hipStreamSynchronize((hipStream_t)stream) == hipSuccess && hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_w_probe), sizeof(hp)) == hipSuccess && hp[0])

@@ -2,6 +2,10 @@
 // rollout_w_kernel (cm_rollout_w.hip, one weight image per launch) and rollout_wm_kernel (cm_rollout_wm.hip, a workgroup picks its
 // policy's image at entry).  Both translation units are built with -fno-slp-vectorize (Makefile).
 #pragma once
+#include <stdio.h>
+
+#include <type_traits>
+
 #include "cm_env_dev.h"
 #include "cm_env_pp10_dev.h"
 #include "cm_policy_w_dev.h"
@@ -25,7 +29,59 @@ static __device__ unsigned long long g_w_probe[5];
 struct TailW { float *obs_dst; uint32_t *base; unsigned int *ticket; int on; };
 struct StridesW { int n_steps, obs, actions, probs, attn, reward, reward_f64, done, details, dist_adj, channels, prey_alive, success, path_len; };
 
-// host: how a launch of the wave-owned rollout runs (cm_rollout_w.hip: plan_rollout_w)
+// ---- host: what the rollout entry points share (cm_fused.hip: cm_rollout_step / _chunk / _chunk_tail; cm_rollout_wm.hip:
+// cm_rollout_chunk_multi).  The helpers defined here are static: the library exports every external symbol, and these are not ABI ----
+bool policy_w_enabled();                                 // cm_policy_w.hip: wave-owned teams-of-4 kernel (default where the shape allows)
+size_t policy_pack_h_bytes(int d, int L, bool policy);   // cm_policy_h.hip: size of the f16 pack the wave-owned fragments sit behind
+bool shape_ok_rollout_w(int N, int d, int L, int n_act);   // cm_rollout_w.hip: teams of 4 on the wave-owned kernel, where enabled
+
+// handle, weights and buffers are there and of one shape; `who` (the entry point) opens the error text
+static inline int check_rollout_args(const char *who, const cm_env *h, const cm_policy_weights *w, const void *obs, const cm_step_out *out) {
+    if (!h || !w || !obs || !out) return set_error(CM_ERR_ARG, std::string(who) + ": null argument");
+    if (w->n_agents != h->dev.N || w->d != h->dev.d || w->n_hops != h->dev.L)
+        return set_error(CM_ERR_ARG, std::string(who) + ": policy shape (n_agents, d, n_hops) does not match the env handle");
+    return CM_OK;
+}
+// the multi-step forms: strides, at least min_steps (0 or 1) steps, and no RNG tape
+static inline int check_chunk_args(const char *who, const cm_env *h, const cm_chunk_strides *st, int n_steps, int min_steps) {
+    if (!st) return set_error(CM_ERR_ARG, std::string(who) + ": null strides");
+    if (n_steps < min_steps) return set_error(CM_ERR_ARG, std::string(who) + (min_steps ? ": at least one step" : ": negative step count"));
+    if (h && h->cfg.rng_mode == CM_RNG_TAPE) return set_error(CM_ERR_ARG, std::string(who) + ": tape mode steps one launch at a time");
+    return CM_OK;
+}
+
+// the policy forward's arguments of a rollout launch: shape from the env handle, the rest as the entry point received it
+static inline mf::FwdArgs rollout_fwd_args(const cm_env *h, const cm_policy_weights *w, const float *obs, const float *avail, const float *dist_adj,
+                                           const float *channels, uint64_t seed, int32_t env_id_offset, uint32_t policy_step,
+                                           const uint32_t *policy_step_base, int32_t greedy, int32_t *actions, float *probs, float *attn) {
+    const EnvDev &d = h->dev;
+    mf::FwdArgs a{};
+    a.S = d.B; a.N = d.N; a.d = d.d; a.L = d.L;
+    a.obs = obs; a.avail = avail; a.adj = dist_adj; a.chan = channels;
+    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;
+    a.env_id_offset = env_id_offset; a.greedy = greedy; a.no_residual = w->no_residual;
+    a.actions = actions; a.probs = probs; a.attn = attn;
+    return a;
+}
+
+// bytes from the start of a cm_policy_pack() output to its wave-owned section: behind the all-f32 fragments and the f16-split pack
+static inline size_t wave_pack(const EnvDev &d) {
+    return mf::pack_layout(mf::kpad_of(d.d), d.L, true).total * sizeof(float) + policy_pack_h_bytes(d.d, d.L, true);
+}
+
+// diagnostic (COMMARL_ENV_STOP < 0): phase clocks of workgroup 0's env phase (ENV_PROBE, cm_env_dev.h).  The caller passes
+// HIP_SYMBOL(g_env_probe): the array is each translation unit's own, and a unit that never names it on the host side keeps no
+// stores to it in its kernels
+static void env_probe_dump(const char *tag, const void *probe, void *stream) {
+    unsigned long long hp[16];
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return;
+    if (hipMemcpyFromSymbol(hp, probe, sizeof(hp), 0, hipMemcpyDeviceToHost) != hipSuccess) return;
+    fprintf(stderr, "[%s env probe] clk since env entry:", tag);
+    for (int i = 1; i < 10; ++i) fprintf(stderr, " p%d=%lld", i, (long long)(hp[i] - hp[0]));
+    fprintf(stderr, "\n");
+}
+
+// ---- host: how a launch of the wave-owned rollout runs (cm_rollout_w.hip: plan_rollout_w) ----
 struct RolloutWPlan {
     size_t lds;                                          // dynamic LDS bytes: policy image | actions | 16 env areas
     int blocks;                                          // workgroups of 16 envs
@@ -34,6 +90,33 @@ struct RolloutWPlan {
     bool pre, full, carry, map10;                        // env prefetch / every workgroup full / carried form / its map-10 shape build
 };
 int plan_rollout_w(const mf::FwdArgs &a, const cm_env *h, bool use_tape, const ChunkArgs *chunk, RolloutWPlan &pl);
-bool shape_ok_rollout_w(int N, int d, int L, int n_act);   // cm_rollout_w.hip: teams of 4 on the wave-owned kernel, where enabled
+// cm_rollout_w.hip: single step, or a persistent chunk; 1 = not available for this handle
+int launch_rollout_w(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pack, const cm_env *h, const cm_rng_tape &t, const cm_step_out &out,
+                     void *stream, const ChunkArgs *chunk);
+
+// The one ladder from a plan to a build of a wave-owned kernel: f(LHOPS, PRE, FULLWG, TAPE, CARRY, SHAPE), each a
+// std::integral_constant.  Per hop count: the tape variant, and {plain, env prefetch, carried, carried map10} x {ragged, full}.
+template <class F>
+static int for_rollout_w_variant(int L, bool use_tape, const RolloutWPlan &pl, F &&f) {
+    using T = std::true_type;
+    using N = std::false_type;
+    using S0 = std::integral_constant<int, 0>;
+    auto hops = [&](auto LH) {
+        auto fill = [&](auto PR, auto CA, auto SH) { return pl.full ? f(LH, PR, T{}, N{}, CA, SH) : f(LH, PR, N{}, N{}, CA, SH); };
+        if (use_tape) return f(LH, N{}, N{}, T{}, N{}, S0{});
+        if (pl.carry) return pl.map10 ? fill(T{}, T{}, std::integral_constant<int, 1>{}) : fill(T{}, T{}, S0{});
+        return pl.pre ? fill(T{}, N{}, S0{}) : fill(N{}, N{}, S0{});
+    };
+    return L == 1 ? hops(std::integral_constant<int, 1>{}) : hops(std::integral_constant<int, 2>{});
+}
+// what f does with its kernel: the 160 KB dynamic-LDS attribute once per device, then the launch
+template <auto KERN, class... A>
+static int launch_rollout_w_variant(const RolloutWPlan &pl, void *stream, const A &...args) {
+    static unsigned long long done = 0;
+    if (dev_first(done)) CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(KERN, dim3(pl.blocks), dim3(256), pl.lds, (hipStream_t)stream, args...);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
 
 }  // namespace cm

@@ -953,23 +953,32 @@ class CommCategoricalMLPPolicy(CommBaseNet):
             attn.copy_(M.reshape(attn.shape))
         return a_out, p_out, attn
 
+    def _rollout_call(self, name, env_batch, head, obs, after_obs, dist_adj, channels, step_out, before_out, after_out, greedy,
+                      out_actions, out_probs, out_attn, policy_step, step_base, env_id_offset):
+        """One call of the cm_rollout_* family: what they share (handle, weights, slot pointers, sampler counters, outputs),
+        with the entry point's own arguments spliced in where its signature has them.  False when the library answers
+        "not for this shape" (1), having done nothing."""
+        w = self._weights_struct()
+        with torch.cuda.device(obs.device):
+            rc = getattr(L.lib(), name)(
+                env_batch._h, C.byref(w), *head, L.ptr(obs), *after_obs, L.ptr(dist_adj), L.ptr(channels), self.seed,
+                self.env_id_offset if env_id_offset is None else int(env_id_offset), policy_step & 0xFFFFFFFF,
+                L.ptr(step_base), int(greedy), L.ptr(out_actions), L.ptr(out_probs), L.ptr(out_attn), *before_out,
+                C.byref(step_out), *after_out, L.current_stream())
+        if rc == 1:
+            return False
+        L.check(rc, name)
+        return True
+
     @torch.no_grad()
     def step_fused(self, env_batch, obs, dist_adj, channels, step_out, greedy=False, out_actions=None, out_probs=None,
                    out_attn=None, policy_step=0, step_base=None, env_id_offset=None, tape=None):
         """One sampler iteration in ONE launch (cm_rollout_step): this policy's forward + sample on `obs`, then the env
         step of `env_batch` on the sampled actions, results into `step_out` (an _lib.StepOut of device pointers).
         Returns False - having done nothing - when the library has no fused kernel for this shape."""
-        w = self._weights_struct()
-        with torch.cuda.device(obs.device):
-            rc = L.lib().cm_rollout_step(
-                env_batch._h, C.byref(w), L.ptr(obs), None, L.ptr(dist_adj), L.ptr(channels), self.seed,
-                self.env_id_offset if env_id_offset is None else int(env_id_offset), policy_step & 0xFFFFFFFF,
-                L.ptr(step_base), int(greedy), L.ptr(out_actions), L.ptr(out_probs), L.ptr(out_attn),
-                C.byref(tape) if tape is not None else None, C.byref(step_out), L.current_stream())
-        if rc == 1:
-            return False
-        L.check(rc, "cm_rollout_step")
-        return True
+        return self._rollout_call("cm_rollout_step", env_batch, (), obs, (None,), dist_adj, channels, step_out,
+                                  (C.byref(tape) if tape is not None else None,), (), greedy, out_actions, out_probs, out_attn,
+                                  policy_step, step_base, env_id_offset)
 
     @torch.no_grad()
     def chunk_fused(self, env_batch, n_steps, strides, obs, dist_adj, channels, step_out, greedy=False, out_actions=None,
@@ -979,24 +988,10 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         dist_adj | None, channels | None) of the slot that receives the last step's outputs, with the advance of `step_base`
         by n_steps (cm_rollout_chunk_tail: part of the same launch where the library can).  Returns False - having done
         nothing - when the library has no fused kernel for this shape."""
-        w = self._weights_struct()
-        eid = self.env_id_offset if env_id_offset is None else int(env_id_offset)
-        with torch.cuda.device(obs.device):
-            if tail_next is not None:
-                rc = L.lib().cm_rollout_chunk_tail(
-                    env_batch._h, C.byref(w), int(n_steps), C.byref(strides), L.ptr(obs), L.ptr(dist_adj), L.ptr(channels),
-                    self.seed, eid, policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(out_actions), L.ptr(out_probs),
-                    L.ptr(out_attn), C.byref(step_out), L.ptr(tail_next[0]), L.ptr(tail_next[1]), L.ptr(tail_next[2]),
-                    L.current_stream())
-            else:
-                rc = L.lib().cm_rollout_chunk(
-                    env_batch._h, C.byref(w), int(n_steps), C.byref(strides), L.ptr(obs), L.ptr(dist_adj), L.ptr(channels),
-                    self.seed, eid, policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(out_actions), L.ptr(out_probs),
-                    L.ptr(out_attn), C.byref(step_out), L.current_stream())
-        if rc == 1:
-            return False
-        L.check(rc, "cm_rollout_chunk_tail" if tail_next is not None else "cm_rollout_chunk")
-        return True
+        tail = () if tail_next is None else tuple(L.ptr(x) for x in tail_next)
+        return self._rollout_call("cm_rollout_chunk_tail" if tail else "cm_rollout_chunk", env_batch, (int(n_steps), C.byref(strides)),
+                                  obs, (), dist_adj, channels, step_out, (), tail, greedy, out_actions, out_probs, out_attn,
+                                  policy_step, step_base, env_id_offset)
 
     def get_actions(self, obs_n, avail_actions_n, dist_adj, channels, greedy=False):
         """numpy in / numpy out, as the reference sampler calls it (:98-119)."""

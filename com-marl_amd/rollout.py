@@ -160,13 +160,11 @@ class RolloutEngine:
         ps, env, B = self.policy, self.env, self.env.B
         w = ps[0]._weights_struct()                                         # the shape every member shares
         st = L.PolicySetT(len(ps), self._wg_policy.numel(), L.ptr(ps.pack_table()), L.ptr(self._wg_policy))
+        obs, adj, ch, actions, probs, attn = self._slot(t0, 0, B)
         with torch.cuda.device(env.device):
             rc = L.lib().cm_rollout_chunk_multi(
-                env._h, C.byref(w), C.byref(st), int(n), C.byref(self._strides()), L.ptr(self.obs[t0]),
-                L.ptr(None if self.dist_adj is None else self.dist_adj[t0]),
-                L.ptr(None if self.channels is None else self.channels[t0]), ps.seed, self.id0, t0 & 0xFFFFFFFF,
-                L.ptr(self.step_bases[0]), int(greedy), L.ptr(self.actions[t0]),
-                L.ptr(None if self.probs is None else self.probs[t0]), L.ptr(None if self.attn is None else self.attn[t0]),
+                env._h, C.byref(w), C.byref(st), int(n), C.byref(self._strides()), L.ptr(obs), L.ptr(adj), L.ptr(ch), ps.seed,
+                self.id0, t0 & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
                 C.byref(env._out(self._out(t0, 0, B))), L.current_stream())
         if rc == 1:
             self.multi_form, self._persistent = "loop", False
@@ -180,13 +178,9 @@ class RolloutEngine:
         if self._multi_chunk(t, 1, greedy):
             return
         for pol, (lo, hi) in zip(self.policy, self.groups):
+            obs, adj, ch, actions, probs, attn = self._slot(t, lo, hi)
             pol.act_device(
-                self.obs[t][lo:hi].view(hi - lo, -1), None,
-                None if self.dist_adj is None else self.dist_adj[t][lo:hi],
-                None if self.channels is None else self.channels[t][lo:hi],
-                greedy=greedy, out_actions=self.actions[t][lo:hi],
-                out_probs=None if self.probs is None else self.probs[t][lo:hi],
-                out_attn=None if self.attn is None else self.attn[t][lo:hi],
+                obs, None, adj, ch, greedy=greedy, out_actions=actions, out_probs=probs, out_attn=attn,
                 want_probs=self.probs is not None, want_attn=self.attn is not None,
                 policy_step=t, step_base=self.step_bases[0], env_id_offset=self.id0 + lo)
         self.env.step_device(self.actions[t], out=self._out(t, 0, self.env.B))
@@ -202,6 +196,13 @@ class RolloutEngine:
                 self.step_bases[k].add_(n)
 
     # ------------------------------------------------------------------------------------------
+    def _slot(self, t, lo, hi):
+        """The policy-side views of slot t for envs lo .. hi-1: obs as [nb, N*d], dist_adj, channels, actions, probs, attn
+        (None where the engine keeps no such buffer)."""
+        cut = lambda b: None if b is None else b[t][lo:hi]                           # noqa: E731
+        return self.obs[t][lo:hi].view(hi - lo, -1), cut(self.dist_adj), cut(self.channels), self.actions[t][lo:hi], \
+            cut(self.probs), cut(self.attn)
+
     def _out(self, t, lo, hi):
         o = dict(obs=self.obs[t + 1][lo:hi], reward=self.reward[t][lo:hi], reward_f64=self.reward64[t][lo:hi],
                  done=self.done[t][lo:hi], details=self.details[t][lo:hi], success=self.success[t][lo:hi],
@@ -231,31 +232,21 @@ class RolloutEngine:
             self._multi_step(t, greedy)
             return
         part, (lo, hi) = self.parts[k], self.bounds[k]
-        nb = hi - lo
+        obs, adj, ch, actions, probs, attn = self._slot(t, lo, hi)
         if self._fused is not False and (not self._capturing or self._fused_in_graph) and hasattr(self.policy, "step_fused"):
             # policy forward + sample + env step of this shard in one launch (cm_rollout_step); shapes without a fused
             # kernel report "not available" once and the two-launch path below is used from then on
             ok = self.policy.step_fused(
-                part, self.obs[t][lo:hi].view(nb, -1),
-                None if self.dist_adj is None else self.dist_adj[t][lo:hi],
-                None if self.channels is None else self.channels[t][lo:hi],
-                part._out(self._out(t, lo, hi)), greedy=greedy, out_actions=self.actions[t][lo:hi],
-                out_probs=None if self.probs is None else self.probs[t][lo:hi],
-                out_attn=None if self.attn is None else self.attn[t][lo:hi],
+                part, obs, adj, ch, part._out(self._out(t, lo, hi)), greedy=greedy, out_actions=actions, out_probs=probs, out_attn=attn,
                 policy_step=t, step_base=self.step_bases[k], env_id_offset=self.id0 + lo)
             self._fused = ok
             if ok:
                 return
         self.policy.act_device(
-            self.obs[t][lo:hi].view(nb, -1), None,
-            None if self.dist_adj is None else self.dist_adj[t][lo:hi],
-            None if self.channels is None else self.channels[t][lo:hi],
-            greedy=greedy, out_actions=self.actions[t][lo:hi],
-            out_probs=None if self.probs is None else self.probs[t][lo:hi],
-            out_attn=None if self.attn is None else self.attn[t][lo:hi],
+            obs, None, adj, ch, greedy=greedy, out_actions=actions, out_probs=probs, out_attn=attn,
             want_probs=self.probs is not None, want_attn=self.attn is not None,
             policy_step=t, step_base=self.step_bases[k], env_id_offset=self.id0 + lo)
-        part.step_device(self.actions[t][lo:hi], out=self._out(t, lo, hi))
+        part.step_device(actions, out=self._out(t, lo, hi))
 
     def step(self, t, greedy=False):
         """Slot t -> t+1 (asynchronous).  With several shards each chain goes to its own stream; call
@@ -321,18 +312,12 @@ class RolloutEngine:
         self.fork()
         for k, stream in enumerate(self.streams):
             part, (lo, hi) = self.parts[k], self.bounds[k]
-            nb = hi - lo
+            obs, adj, ch, actions, probs, attn = self._slot(t0, lo, hi)
             with torch.cuda.stream(stream) if stream is not None else _null():
                 ok = self.policy.chunk_fused(
-                    part, n, st, self.obs[t0][lo:hi].view(nb, -1),
-                    None if self.dist_adj is None else self.dist_adj[t0][lo:hi],
-                    None if self.channels is None else self.channels[t0][lo:hi],
-                    part._out(self._out(t0, lo, hi)), greedy=greedy, out_actions=self.actions[t0][lo:hi],
-                    out_probs=None if self.probs is None else self.probs[t0][lo:hi],
-                    out_attn=None if self.attn is None else self.attn[t0][lo:hi],
-                    policy_step=t0, step_base=self.step_bases[k], env_id_offset=self.id0 + lo,
-                    tail_next=None if not tail else (self.obs[0][lo:hi], None if self.dist_adj is None else self.dist_adj[0][lo:hi],
-                                                     None if self.channels is None else self.channels[0][lo:hi]))
+                    part, n, st, obs, adj, ch, part._out(self._out(t0, lo, hi)), greedy=greedy, out_actions=actions,
+                    out_probs=probs, out_attn=attn, policy_step=t0, step_base=self.step_bases[k], env_id_offset=self.id0 + lo,
+                    tail_next=self._slot(0, lo, hi)[:3] if tail else None)
             if not ok:
                 assert k == 0, "fused chunk availability must not differ between shards"
                 self._fused = False

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from tests import isa
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -98,90 +100,46 @@ def test_bench_contract_helpers():
     assert bench.host_cores() >= 1
 
 
-def test_env_kernels_use_no_flat_or_scratch_addressing(tmp_path):
+def test_env_kernels_use_no_flat_or_scratch_addressing():
     """Static guard against the one GPU abort on record (round 1, gpurun_out/smoke.log: HSA_STATUS_ERROR_MEMORY_
     APERTURE_VIOLATION in env_kernel<0>, private_seg_size=88, group_seg_size=288): that fault class
     can only be raised by FLAT / SCRATCH instructions whose address lands in the LDS or scratch aperture beyond the
     wave's allocation - `ds_*` accesses out of range are dropped silently.  The env step therefore addresses LDS
     through integer offsets only (ds ops) and keeps no dynamically indexed local arrays (no scratch): pinned here on
     the gfx950 ISA of every env kernel instantiation."""
-    import re
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "com-marl_amd", "csrc", "cm_env.hip")
-    out = tmp_path / "cm_env.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm",
-                           "-amdgpu-mfma-vgpr-form", "-S", "--cuda-device-only", "-w", "-o", str(out), src])
-    asm = out.read_text()
-    kernels = re.findall(r"\.name:\s+(\S*env_kernel\S*)", asm)
-    assert len(kernels) >= 8, kernels                         # PP / CO x 16 / 32 / 64 lanes + the two wide forms
-    assert not re.search(r"^\s+(flat_(load|store|atomic)|scratch_)", asm, re.M)
-    assert len(re.findall(r"^\s+ds_", asm, re.M)) > 1000
-    for m in re.finditer(r"\.private_segment_fixed_size:\s+(\d+)", asm):
-        assert m.group(1) == "0"
+    asm = isa.listing("cm_env")
+    assert len(isa.kernels(asm, "env_kernel")) >= 8                        # PP / CO x 16 / 32 / 64 lanes + the two wide forms
+    every = isa.kernels(asm)                                              # the whole unit: every kernel it holds
+    assert asm.count("\n.Lfunc_end") == len(every)                        # ... and no function outside them
+    for k in every:
+        assert not k.has_flat_or_scratch, k.name
+        assert k.private_segment_fixed_size == 0, k.name
+    assert sum(k.count("ds_") for k in every) > 1000
 
 
-def test_fused_step_kernels_use_no_flat_or_scratch_addressing(tmp_path):
+def test_fused_step_kernels_use_no_flat_or_scratch_addressing():
     """The same guard for the fused rollout step (cm_fused.hip: the env body runs inside the policy's workgroup): every
     rollout_step_kernel instantiation - the kernels of the default rollout path - must request no private segment and
     contain no flat / scratch instruction.  (The opt-in persistent chunk kernels are not covered: the all-f32 large-team
     form spills two registers.)"""
-    import re
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "com-marl_amd", "csrc", "cm_fused.hip")
-    out = tmp_path / "cm_fused.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm",
-                           "-amdgpu-mfma-vgpr-form", "-S", "--cuda-device-only", "-w", "-o", str(out), src])
-    asm = out.read_text()
-    seen = 0
-    for blk in re.split(r"\n\s+- \.agpr_count:", asm)[1:]:                 # one metadata block per kernel
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        if "rollout_step_kernel" not in name:
-            continue
-        seen += 1
-        assert re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1) == "0", name
-        assert re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1) == "0", name
-    assert seen >= 10, seen                                               # five shapes x two policy bodies (+ the full-workgroup builds)
-    bodies = list(re.finditer(r"^(_ZN2cm19rollout_step_kernel\S+):[^\n]*\n(.*?)\n\.Lfunc_end", asm, re.M | re.S))
-    assert len(bodies) == seen                                            # (the label line carries a trailing "; @name" comment)
-    for m in bodies:
-        assert not re.search(r"^\s+(flat_(load|store|atomic)|scratch_)", m.group(2), re.M), m.group(1)
+    ks = isa.kernels(isa.listing("cm_fused"), "rollout_step_kernel")
+    assert len(ks) >= 10, len(ks)                                         # five shapes x two policy bodies (+ the full-workgroup builds)
+    for k in ks:
+        assert k.private_segment_fixed_size == 0, k.name
+        assert k.vgpr_spill_count == 0, k.name
+        assert not k.has_flat_or_scratch, k.name
 
 
-def test_wave_owned_rollout_kernels_use_no_flat_or_scratch_addressing(tmp_path):
+def test_wave_owned_rollout_kernels_use_no_flat_or_scratch_addressing():
     """The same guard for the default rollout path of teams of 4 (cm_rollout_w.hip: policy forward + sample + env step of a
     wave's four envs, for a whole chunk of steps per launch): every rollout_w_kernel instantiation must request no private
     segment, spill nothing and contain no flat / scratch instruction - with 256 VGPRs + ~120 AGPRs in use (one wave per SIMD,
     the 128 -> 64 head layer resident in registers) this is the kernel closest to the register limit."""
-    import re
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "com-marl_amd", "csrc", "cm_rollout_w.hip")
-    out = tmp_path / "cm_rollout_w.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm",
-                           "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-w", "-o", str(out), src])
-    asm = out.read_text()
-    seen = 0
-    for blk in re.split(r"\n\s+- \.agpr_count:", asm)[1:]:                 # one metadata block per kernel
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        if "rollout_w_kernel" not in name:
-            continue
-        seen += 1
-        assert re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1) == "0", name
-        assert re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1) == "0", name
-    assert seen == 18, seen     # 1 / 2 hops x (env prefetch on / off x full / ragged workgroups + the tape variant + carried full / ragged, generic and map10 shape)
-    bodies = list(re.finditer(r"^(_ZN2cm16rollout_w_kernel\S+):[^\n]*\n(.*?)\n\.Lfunc_end", asm, re.M | re.S))
-    assert len(bodies) == seen                                            # (the label line carries a trailing "; @name" comment)
-    for m in bodies:
-        assert not re.search(r"^\s+(flat_(load|store|atomic)|scratch_)", m.group(2), re.M), m.group(1)
-        assert len(re.findall(r"^\s+s_barrier", m.group(2), re.M)) == 1, "one workgroup barrier per launch (behind the weight staging)"
+    ks = isa.kernels(isa.listing("cm_rollout_w"), "rollout_w_kernel")
+    # 1 / 2 hops x (env prefetch on / off x full / ragged workgroups + the tape variant + carried full / ragged, generic and map10 shape)
+    assert len(ks) == 18, len(ks)
+    for k in ks:
+        assert k.private_segment_fixed_size == 0, k.name
+        assert k.vgpr_spill_count == 0, k.name
+        assert not k.has_flat_or_scratch, k.name
+        assert k.barriers == 1, "one workgroup barrier per launch (behind the weight staging)"

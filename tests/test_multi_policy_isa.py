@@ -2,39 +2,24 @@
 spills or flat / scratch addressing, and the entry point is part of the C ABI without a version bump."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
+
+from tests import isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_multi_policy_rollout_kernels_use_no_flat_or_scratch_addressing(tmp_path):
+def test_multi_policy_rollout_kernels_use_no_flat_or_scratch_addressing():
     """Every rollout_wm_kernel instantiation (cm_rollout_wm.hip) is held to what test_cabi holds rollout_w_kernel to: no
     private segment, no VGPR spill, no flat / scratch instruction, one workgroup barrier (behind the weight staging)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "com-marl_amd", "csrc", "cm_rollout_wm.hip")
-    out = tmp_path / "cm_rollout_wm.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm",
-                           "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-w", "-o", str(out), src])
-    asm = out.read_text()
-    seen = 0
-    for blk in re.split(r"\n\s+- \.agpr_count:", asm)[1:]:                 # one metadata block per kernel
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        if "rollout_wm_kernel" not in name:
-            continue
-        seen += 1
-        assert re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1) == "0", name
-        assert re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1) == "0", name
-    assert seen == 16, seen     # 1 / 2 hops x (plain, env prefetch, carried, carried map10) x (full / ragged workgroups)
-    bodies = list(re.finditer(r"^(_ZN2cm17rollout_wm_kernel\S+):[^\n]*\n(.*?)\n\.Lfunc_end", asm, re.M | re.S))
-    assert len(bodies) == seen
-    for m in bodies:
-        assert not re.search(r"^\s+(flat_(load|store|atomic)|scratch_)", m.group(2), re.M), m.group(1)
-        assert len(re.findall(r"^\s+s_barrier", m.group(2), re.M)) == 1, m.group(1)
+    ks = isa.kernels(isa.listing("cm_rollout_wm"), "rollout_wm_kernel")
+    assert len(ks) == 16, len(ks)   # 1 / 2 hops x (plain, env prefetch, carried, carried map10) x (full / ragged workgroups)
+    for k in ks:
+        assert k.private_segment_fixed_size == 0, k.name
+        assert k.vgpr_spill_count == 0, k.name
+        assert not k.has_flat_or_scratch, k.name
+        assert k.barriers == 1, k.name
 
 
 def test_chunk_multi_is_declared_and_exported_at_abi_3():

@@ -1,15 +1,11 @@
 """The headline rollout kernel's env step on registers (rollout_w_kernel SHAPE 1, cm_env_pp10_dev.h): the carried persistent
 launch at the benchmark's shape against stepwise two-launch stepping, long enough that every env auto-resets at least twice,
 and the register budget of that instantiation on the gfx950 ISA."""
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import isa
+
 HEADLINE = "_ZN2cm16rollout_w_kernelILi2ELb1ELb1ELb0ELb1ELi1E"   # <2 hops, PRE, full workgroups, no tape, CARRY, SHAPE 1>
 
 
@@ -62,18 +58,7 @@ def test_headline_persistent_rollout_matches_stepwise_launches_across_resets(B):
             np.testing.assert_array_equal(a[k], b[k], err_msg=k)
 
 
-def test_headline_rollout_kernel_has_no_scratch_and_no_vgpr_spill(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "com-marl_amd", "csrc", "cm_rollout_w.hip")
-    out = tmp_path / "cm_rollout_w.s"
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm",
-                           "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-w", "-o", str(out), src])
-    asm = out.read_text()
-    blocks = [blk for blk in re.split(r"\n\s+- \.agpr_count:", asm)[1:]
-              if re.search(r"\.name:\s+(\S+)", blk).group(1).startswith(HEADLINE)]
-    assert len(blocks) == 1
-    blk = blocks[0]
-    assert re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1) == "0"
-    assert re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1) == "0"
+def test_headline_rollout_kernel_has_no_scratch_and_no_vgpr_spill():
+    k = isa.kernel(isa.listing("cm_rollout_w"), HEADLINE)
+    assert k.private_segment_fixed_size == 0
+    assert k.vgpr_spill_count == 0

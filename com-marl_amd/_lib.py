@@ -65,6 +65,17 @@ class PolicySetT(C.Structure):
     _fields_ = [("n_policies", C.c_int32), ("n_wg", C.c_int32), ("packs", C.c_void_p), ("wg_policy", C.c_void_p)]
 
 
+class ForwardSetWg(C.Structure):
+    """cm_forward_set_wg: one workgroup of a cm_policy_forward_multi launch."""
+    _fields_ = [("member", C.c_int32), ("block", C.c_int32)]
+
+
+class ForwardSetMember(C.Structure):
+    """cm_forward_set_member: one member's group and weight pointers in the table cm_policy_forward_multi reads."""
+    _fields_ = [("first_env", C.c_int32), ("n_envs", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("pack", "enc_b1", "enc_b2", "gcn_b", "hd_b1", "hd_b2", "hd_b3", "hd_b4")]
+
+
 MLP_MAX_LAYERS = 6
 
 
@@ -111,6 +122,11 @@ _SIGNATURES = {
                                          C.POINTER(ChunkStrides), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32,
                                          C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(StepOut), C.c_void_p]),
+    "cm_policy_forward_multi_plan": (C.c_int64, [C.POINTER(PolicyWeights), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.c_size_t, C.POINTER(C.c_int32)]),
+    "cm_policy_forward_multi": (C.c_int, [C.POINTER(PolicyWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_rollout_chunk_tail": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.c_int32, C.POINTER(ChunkStrides), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StepOut), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1469,6 +1469,7 @@ class PolicySet:
                     raise ValueError(f"PolicySet: policies[{i}] differs from policies[0] in {name}: {v!r} != {v0!r}")
         self.policies = policies
         self._table = None                      # (pack addresses, int64 device tensor of them)
+        self._fwd_table = None                  # (key, device image | None, workgroup count): forward_table()
 
     def __getattr__(self, name):
         if name in PolicySet._SHARED:
@@ -1508,3 +1509,35 @@ class PolicySet:
             dev = self.policies[0]._mfma.device
             self._table = (ptrs, torch.tensor(ptrs, dtype=torch.int64).to(dev))
         return self._table[1]
+
+    def forward_table(self, groups):
+        """(device table, workgroup count) of the set forward - cm_policy_forward_multi, every member's acting forward in one
+        launch - with member k on the next groups[k] envs; (None, 0) when the library has no set kernel for the shape or the
+        members have no operand pack.  Kept until a member's operand pack or flat weight copy was reallocated or the groups
+        change, packing the members that have no pack yet; the weights themselves are read as they are (sync_weights()
+        refreshes them in place).  A set the planner refuses (a group without envs, ...) raises."""
+        if not all(hasattr(p, "_weights_struct") for p in self.policies):
+            return None, 0
+        if any(p._mfma is None or p._pack is None for p in self.policies):
+            self.sync_weights()
+            if any(p._mfma is None for p in self.policies):
+                return None, 0
+        groups = tuple(int(g) for g in groups)
+        if len(groups) != len(self.policies):
+            raise ValueError(f"forward_table: {len(groups)} groups for {len(self.policies)} policies")
+        key = (groups, tuple((p._mfma.data_ptr(), p._pack[0].data_ptr()) for p in self.policies))
+        if self._fwd_table is None or self._fwd_table[0] != key:
+            K = len(self.policies)
+            ws = (L.PolicyWeights * K)(*[p._weights_struct() for p in self.policies])
+            sizes, n_wg = (C.c_int32 * len(groups))(*groups), C.c_int32(0)
+            plan = L.lib().cm_policy_forward_multi_plan
+            need = plan(ws, sizes, K, sum(groups), None, 0, C.byref(n_wg))
+            table = None
+            if need > 0:
+                image = bytearray(need)
+                need = plan(ws, sizes, K, sum(groups), (C.c_char * need).from_buffer(image), need, C.byref(n_wg))
+                table = torch.frombuffer(image, dtype=torch.uint8).to(self.policies[0]._mfma.device)
+            if need < 0:
+                L.check(int(need), "cm_policy_forward_multi_plan")
+            self._fwd_table = (key, table, n_wg.value)
+        return self._fwd_table[1], self._fwd_table[2]

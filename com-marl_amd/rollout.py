@@ -59,8 +59,10 @@ class RolloutEngine:
         policies on one GridEnvBatch: `groups` lists the env count of each member (default: B / K each), member k owning the
         contiguous envs [lo_k, hi_k).  Each env plays exactly what it would play in a single-policy engine whose env batch
         starts at the same global env id.  Teams of 4 whose groups start on multiples of 16 envs run a chunk as ONE
-        cm_rollout_chunk_multi launch (multi_form "wave"); every other set steps member by member on its envs, then one env
-        step over the batch (multi_form "loop")."""
+        cm_rollout_chunk_multi launch (multi_form "wave"); every other set takes one forward + one env step over the batch per
+        step (multi_form "loop"), the forward being ONE cm_policy_forward_multi launch for all members where the library has
+        a set kernel for the shape (multi_forward "set": Comm-DP teams other than 4, up to 80 agents, one sampler seed) and one
+        cm_policy_forward per member on its envs otherwise (multi_forward "member")."""
         if isinstance(env, (list, tuple)):
             env = _Parts(list(env)) if len(env) > 1 else env[0]
         self.env, self.policy, self.H = env, policy, int(horizon)
@@ -117,6 +119,7 @@ class RolloutEngine:
         self.t = 0
         self.generation = 0                      # bumped by reset(): a PathBatch of an earlier rollout refuses to read the buffers
         self.multi_form = None                   # PolicySet: "wave" (one launch per chunk for all members) or "loop"
+        self.multi_forward = None                # loop form: "set" (one forward launch for all members) or "member"
         if isinstance(policy, PolicySet):
             self._init_multi(groups)
         elif groups is not None:
@@ -145,6 +148,10 @@ class RolloutEngine:
                 and all(lo % WG_ENVS == 0 for lo, _ in self.groups) and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_form = "wave" if wave else "loop"
         self._persistent, self._fused = wave, None
+        # loop form: one forward launch for the whole set (cm_policy_forward_multi) - Comm-DP members, one sampler seed, production
+        # RNG; the library answers "not for this shape" (1) for the teams it has no set kernel for, and the engine remembers it
+        set_fwd = hasattr(ps[0], "chunk_fused") and ps.seed is not None and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX
+        self.multi_forward = None if wave else ("set" if set_fwd else "member")
         if wave:
             n_wg = (B + WG_ENVS - 1) // WG_ENVS
             wg = [k for k, (lo, hi) in enumerate(self.groups) for _ in range(lo // WG_ENVS, (hi + WG_ENVS - 1) // WG_ENVS)]
@@ -167,22 +174,45 @@ class RolloutEngine:
                 self.id0, t0 & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
                 C.byref(env._out(self._out(t0, 0, B))), L.current_stream())
         if rc == 1:
-            self.multi_form, self._persistent = "loop", False
+            self.multi_form, self._persistent, self.multi_forward = "loop", False, "member"     # (teams of 4: no set forward)
             return False
         L.check(rc, "cm_rollout_chunk_multi")
         return True
 
+    def _set_forward(self, t, greedy):
+        """Slot t's forward + sample of every member in ONE cm_policy_forward_multi launch over the batch.  False - nothing
+        launched - when the library has no set kernel for this shape (the engine launches member by member from then on).
+        The members' packs are used as they are, as in _multi_chunk."""
+        ps, B = self.policy, self.env.B
+        table, n_wg = ps.forward_table([hi - lo for lo, hi in self.groups])
+        rc = 1
+        if table is not None:
+            w = ps[0]._weights_struct()                                     # the shape every member shares
+            obs, adj, ch, actions, probs, attn = self._slot(t, 0, B)
+            with torch.cuda.device(self.env.device):
+                rc = L.lib().cm_policy_forward_multi(
+                    C.byref(w), L.ptr(table), n_wg, B, L.ptr(obs), None, L.ptr(adj), L.ptr(ch), ps.seed, self.id0,
+                    t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
+                    L.current_stream())
+        if rc == 1:
+            self.multi_forward = "member"
+            return False
+        L.check(rc, "cm_policy_forward_multi")
+        return True
+
     def _multi_step(self, t, greedy):
-        """Slot t -> t+1 for every member: one launch (a chunk of one step) where the set has the multi-policy kernel, else each
-        member's forward + sample on its envs (env ids id0 + lo_k, the shared Philox base) and one env step over the batch."""
+        """Slot t -> t+1 for every member: one launch (a chunk of one step) where the set has the multi-policy kernel, else the
+        members' forward + sample - one launch for the set, or each member on its envs (env ids id0 + lo_k, the shared Philox
+        base) - and one env step over the batch."""
         if self._multi_chunk(t, 1, greedy):
             return
-        for pol, (lo, hi) in zip(self.policy, self.groups):
-            obs, adj, ch, actions, probs, attn = self._slot(t, lo, hi)
-            pol.act_device(
-                obs, None, adj, ch, greedy=greedy, out_actions=actions, out_probs=probs, out_attn=attn,
-                want_probs=self.probs is not None, want_attn=self.attn is not None,
-                policy_step=t, step_base=self.step_bases[0], env_id_offset=self.id0 + lo)
+        if self.multi_forward != "set" or not self._set_forward(t, greedy):
+            for pol, (lo, hi) in zip(self.policy, self.groups):
+                obs, adj, ch, actions, probs, attn = self._slot(t, lo, hi)
+                pol.act_device(
+                    obs, None, adj, ch, greedy=greedy, out_actions=actions, out_probs=probs, out_attn=attn,
+                    want_probs=self.probs is not None, want_attn=self.attn is not None,
+                    policy_step=t, step_base=self.step_bases[0], env_id_offset=self.id0 + lo)
         self.env.step_device(self.actions[t], out=self._out(t, 0, self.env.B))
 
     @property

@@ -303,6 +303,40 @@ int cm_rollout_chunk_multi(cm_env_t h, const cm_policy_weights *w, const cm_poli
                            uint64_t seed, int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base,
                            int32_t greedy, int32_t *actions, float *probs, float *attn, const cm_step_out *out, void *stream);
 
+/* cm_policy_forward for SEVERAL policies of one architecture in ONE launch, each on its own contiguous range of the envs: member k
+ * acts on the group_sizes[k] envs behind those of members 0 .. k-1.  Every output is bit-identical to cm_policy_forward with member
+ * k's weights on its group's rows and env_id_offset + the group's first env (one seed for the set).  For the teams the f16-split
+ * workgroup-tiled kernel serves; teams of 4 have cm_rollout_chunk_multi.
+ *
+ * cm_policy_forward_multi_plan (host only, no device work): checks the set - n_policies >= 1, every group size >= 1, the sizes sum
+ * to n_envs, every member has the shape of members[0], an operand pack (mfma_pack, with a current CM_PACK_F16 section) and its bias
+ * pointers - and returns the size in bytes of the table the launch reads, *n_wg = the launch's workgroup count (a group ends in a
+ * ragged workgroup of its own, never shared with the next member); with `image` non-NULL (image_bytes >= that size) the table's
+ * host image is written there: n_wg cm_forward_set_wg descriptors, then n_policies cm_forward_set_member records.  The caller
+ * uploads the image to device memory it owns and rebuilds it when a member's pack or weight buffers move or the groups change.
+ * Returns 0 (*n_wg = 0, nothing written) when the shape has no set kernel - teams of 4, more than 80 agents, an observation
+ * dim without an f16 instantiation, COMMARL_POLICY_KERNEL=f32 / valu, an LDS need above 160 KB - and < 0 on a refused set.
+ *
+ * cm_policy_forward_multi: the launch.  `shape` = any member's weights (dims, n_act, no_residual; its weight pointers are not
+ * read), table_dev = the uploaded image, n_wg / n_envs = the planner's; every other argument is cm_policy_forward's over the
+ * whole batch.  No allocation, copy or synchronisation: it can be captured in a hipGraph.  The kernel trusts the table.  Returns
+ * 0 when launched, < 0 on error, and 1 - nothing launched - where the planner returns 0 or `shape` has no operand pack: the
+ * caller then runs cm_policy_forward per member. */
+typedef struct cm_forward_set_wg {
+    int32_t member, block;           /* workgroup -> member, and its block index inside the member's group */
+} cm_forward_set_wg;
+typedef struct cm_forward_set_member {
+    int32_t first_env, n_envs;       /* the member's group */
+    const void *pack;                /* the f16-split section of the member's operand pack */
+    const float *enc_b1, *enc_b2, *gcn_b, *hd_b1, *hd_b2, *hd_b3, *hd_b4;   /* biases: plain f32, outside the pack */
+} cm_forward_set_member;
+int64_t cm_policy_forward_multi_plan(const cm_policy_weights *members, const int32_t *group_sizes, int32_t n_policies,
+                                     int32_t n_envs, void *image, size_t image_bytes, int32_t *n_wg);
+int cm_policy_forward_multi(const cm_policy_weights *shape, const void *table_dev, int32_t n_wg, int32_t n_envs,
+                            const float *obs, const float *avail, const float *dist_adj, const float *channels, uint64_t seed,
+                            int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy,
+                            int32_t *actions, float *probs, float *attn, void *stream);
+
 /* cm_rollout_chunk followed by cm_chunk_tail (below) for the same chunk: the observation (and masks, where the env produces
  * them) the last step wrote - out->obs + (n_steps - 1) * strides->obs, ... - carried into obs_next / dist_adj_next /
  * channels_next (slot 0 of the caller's ring; the mask pointers may be NULL) and *policy_step_base += n_steps.  Where the wave-owned

@@ -15,7 +15,8 @@
 // the tile of the env's LDS area is only used by an auto-reset (do_reset, rare), whose result the group reads back.
 //
 // Diagnostics: this body does not honour the early-return switch COMMARL_ENV_STOP > 0 (p.stop = 1..7) nor COMMARL_ENV_SMALL=0
-// (p.no_small) of env_body - the carried map10 build always runs the whole step.  Its ENV_PROBE stamps (COMMARL_ENV_STOP=-1) mark
+// (p.no_small) of env_body - the carried map10 build always runs the whole step.  Its ENV_PROBE stamps (COMMARL_ENV_STOP=-1; they
+// exist in rollout_w_probe_kernel only, every other build of this step sets p.stop = 0 at entry and they fold away) mark
 // its own phases: p1 = p2 actions read, p3 agents, p8 prey trials, p4 (count, move) exchange and watch count, p5 prey moves,
 // p6 reward and per-env stores, p7 reset, p9 emission and state write-back.
 #pragma once
@@ -122,11 +123,39 @@ __device__ __forceinline__ Pre load_pre(const EnvDev &p, int b, int sl, int tx) 
     return e;
 }
 
+// What the launcher (plan_rollout_w) has established for this build: every cm_step_out member stored below is non-null, and every
+// trajectory buffer and state array stays below 2^31 bytes over the launch.  So the stores take the LAUNCH's base pointer as a
+// scalar operand plus one 32-bit byte offset per lane (global saddr + voffset), and a step's slot is an element offset
+// t * stride (StepOff, one scalar multiply per buffer) instead of a rebuilt 64-bit pointer.
+struct StepOff { uint32_t obs, reward, reward_f64, done, details, prey_alive, success, path_len; };
+template <class T>
+__device__ __forceinline__ T *at32(T *base, uint32_t elem) { return reinterpret_cast<T *>(reinterpret_cast<char *>(base) + (uint32_t)(elem * (uint32_t)sizeof(T))); }
+
+// the env's record in the global state arrays (lane j < 4: agent j, prey j; lane 0: the per-env scalars)
+__device__ __forceinline__ void write_back(const EnvDev &p, uint32_t b, int sl, uint32_t apos, uint32_t ppos, uint32_t flags, int step_count,
+                                           int succ, uint32_t rng_step) {
+    if (sl == 0) {
+        *at32(p.rng_step, b) = rng_step;
+        *at32(p.step_count, b) = step_count;
+        *at32(p.success, b) = succ;
+    }
+    if (sl < M) {
+        const uint32_t ca = byte_at(apos, sl), cp = byte_at(ppos, sl);
+        *at32(p.agent_pos, b * N + sl) = make_int2(row_of(ca), col_of(ca));
+        *at32(p.prey_pos, b * M + sl) = make_int2(row_of(cp), col_of(cp));
+        *at32(p.alive, b * M + sl) = (uint8_t)((flags >> sl) & 1u);
+    }
+}
+
 // One env step of a 16-lane group: env_stage + env_body + env_pre_carry of the generic carried form.  `act_off`: byte offset of
 // the group's four action words in LDS; `obs_copy`: byte offset of the env's LDS observation copy.  Updates `st` and `pre`.
+// `out`: the launch's bases, `off`: this step's element offsets into them.  `last`: the launch's last step - the only one whose
+// state write-back anything reads (no load of the launch reads the state arrays: the next launch and the host see what the last
+// step left), so the others keep the state in registers only.
 // Reference lines as in env_body / pp_small_step.
-__device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const Emit em, int act_off, const cm_step_out &out, int grp,
-                                     int b_raw, bool grp_live, int lds_base, bool all_valid, int obs_copy) {
+__device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const Emit em, int act_off, const cm_step_out &out,
+                                     const StepOff &off, bool last, int grp, int b_raw, bool grp_live, int lds_base, bool all_valid,
+                                     int obs_copy) {
     Grp<16> g;
     const int tx = thread_x();
     g.sub = (tx & (WAVE - 1)) / 16; g.sl = tx % 16;
@@ -150,7 +179,13 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
         const int faulty = ((st.flags >> (4 + i)) & 1u) == 0u;          // pseudo-action 5, as env_stage encodes it
         act[i] = bi ? 4 : ((faulty & (a != 4)) ? 5 : a);
     }
-    if (bad && sl == 0 && valid) raise(p, CM_ERR_ACTION);               // the reference raises (predator_prey.py:255)
+    if (bad && valid) {
+        if (sl == 0) raise(p, CM_ERR_ACTION);                           // the reference raises (predator_prey.py:255)
+        // a step that does not commit stores no state, so memory keeps the record of the step before it.  With the write-back
+        // deferred to the launch's last step that record may never have been stored: stored here, from the registers the step
+        // came in with.  (Not reached in this kernel: the action words were written 0..4 by the sampler of the same step.)
+        write_back(p, (uint32_t)b, sl, st.apos, st.ppos, st.flags, pre.step_count_in, pre.succ, pre.rng_step);
+    }
     const bool commit = valid && !bad;
     ENV_PROBE(1);
     ENV_PROBE(2);                                      // no tile to build: p2 = p1
@@ -228,21 +263,19 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
     double reward = __shfl(pre.t_rew, capture, 16) + __shfl(pre.t_rew, (M + 1) + moving, 16);
     if (p.load == 2) reward = reward + p.penalty * (double)penalty;
     const cm_step_out &o = out;
-    if (o.prey_alive && commit && mine) o.prey_alive[(size_t)b * M + sl] = (uint8_t)((flags >> sl) & 1u);
+    const uint32_t ub = (uint32_t)b;
+    if (commit && mine) *at32(o.prey_alive, off.prey_alive + ub * M + sl) = (uint8_t)((flags >> sl) & 1u);
     int step_count = pre.step_count_in + 1, succ = pre.succ;
     int done = (step_count >= p.max_steps) || !alive_any;                       // :511-517
     if (done) succ = alive_any ? 0 : 1;
     if (step_count >= p.mpl) done = 1;                                           // vec_env_executor.py:33-34
     if (sl == 0 && commit) {
-        if (o.reward) o.reward[b] = (float)reward;
-        if (o.reward_f64) o.reward_f64[b] = reward;
-        if (o.done) o.done[b] = (uint8_t)done;
-        if (o.path_len) o.path_len[b] = done ? step_count : 0;
-        if (o.details) {
-            int2 *dd = reinterpret_cast<int2 *>(o.details + (size_t)b * 6);      // 24-byte rows: three 8-byte stores
-            dd[0] = make_int2(capture, moving); dd[1] = make_int2(penalty, 0); dd[2] = make_int2(wsum, 0);
-        }
-        p.rng_step[b] = rng.step + 1;
+        *at32(o.reward, off.reward + ub) = (float)reward;
+        *at32(o.reward_f64, off.reward_f64 + ub) = reward;
+        *at32(o.done, off.done + ub) = (uint8_t)done;
+        *at32(o.path_len, off.path_len + ub) = done ? step_count : 0;
+        int2 *dd = reinterpret_cast<int2 *>(at32(o.details, off.details + ub * 6));   // 24-byte rows: three 8-byte stores
+        dd[0] = make_int2(capture, moving); dd[1] = make_int2(penalty, 0); dd[2] = make_int2(wsum, 0);
     }
     ENV_PROBE(6);
     // auto-reset (:36-43): rare, so it keeps the tile-based spawn of the generic body.  A resetting group's do_reset clears its
@@ -291,28 +324,19 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
         pre.t_step = p.lut_step[sc <= p.max_steps ? sc : p.max_steps];
     }
     if (!commit) return;
-    if (sl == 0) {
-        p.step_count[b] = step_count;
-        p.success[b] = succ;
-        if (o.success) o.success[b] = succ;
-    }
-    float *ob = o.obs ? o.obs + (size_t)b * N * D : nullptr;
+    if (sl == 0) *at32(o.success, off.success + ub) = succ;
+    const uint32_t ob = off.obs + ub * (N * D) + (uint32_t)sl;
     float *oc = reinterpret_cast<float *>(smem + obs_copy);
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
         if (16 * u + sl < N * D) {
-            if (ob) ob[16 * u + sl] = vv[u];
+            *at32(o.obs, ob + 16u * u) = vv[u];
             oc[ci_copy[u]] = vv[u];
         }
     }
     static_assert(OBS_COPY_STRIDE == D + 3, "the copy index k + 3i assumes rows of 24 floats");
-    // ---- state write-back (lane j: agent j, prey j) ----
-    if (mine) {
-        const uint32_t ca = byte_at(apos, sl), cp = byte_at(ppos, sl);
-        p.agent_pos[(size_t)b * N + sl] = make_int2(row_of(ca), col_of(ca));
-        p.prey_pos[(size_t)b * M + sl] = make_int2(row_of(cp), col_of(cp));
-        p.alive[(size_t)b * M + sl] = (uint8_t)((flags >> sl) & 1u);
-    }
+    // ---- state write-back: the launch's last step only ----
+    if (last) write_back(p, ub, sl, apos, ppos, flags, step_count, succ, rng.step + 1);
     ENV_PROBE(9);
 }
 

@@ -293,9 +293,16 @@ struct ResidentW {
 // HEADK 1: the critic's head behind the same trunk (training forward only; cm_critic_forward_saved_wave) - decoder layer 64 -> 64
 // (fragments in the policy's x1 slot of the image), value layer 64 -> 1 as a 16-wide tile (h3 slot), per-agent values to a.sv_out,
 // their sum over the team to a.values.  `res` is not touched then.
-template <int LHOPS, bool OBS_LDS = false, bool TRAIN = false, int HEADK = 0>
+// STEP32 (the carried map-10 rollout, whose launcher has checked that every trajectory buffer stays below 2^31 bytes): a.actions /
+// a.probs / a.attn are the LAUNCH's bases and `so` the step's element offsets into them - the stores take the base as a scalar
+// operand and one 32-bit byte offset per lane, instead of a 64-bit address per lane from a base rebuilt every step.
+struct StepOff { uint32_t actions, probs, attn; };
+template <class T>
+__device__ __forceinline__ T *at32(T *base, uint32_t elem) { return reinterpret_cast<T *>(reinterpret_cast<char *>(base) + (uint32_t)(elem * (uint32_t)sizeof(T))); }
+template <int LHOPS, bool OBS_LDS = false, bool TRAIN = false, int HEADK = 0, bool STEP32 = false>
 __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const ResidentW &res, const unsigned char *lds, int blk,
-                                              int32_t *act_lds, int obs_row = 0) {
+                                              int32_t *act_lds, int obs_row = 0, const StepOff so = StepOff{}) {
+    static_assert(!STEP32 || (!TRAIN && HEADK == 0), "step offsets: the acting forward of the rollout");
     static_assert(HEADK == 0 || TRAIN, "the critic head exists as training forward only");
     static_assert(LHOPS >= 1 && LHOPS <= 2, "wave-owned forward: one or two hops");
     const int tid = thread_x(), wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
@@ -365,7 +372,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     }
     const size_t env_g = (size_t)s0 + env_l;
     if (a.attn && diag && rv) {                                 // row `agent` of the env's 4 x 4 matrix: one 16-byte store
-        float *dst = a.attn + env_g * 16 + 4 * agent;
+        float *dst = STEP32 ? at32(a.attn, so.attn + (uint32_t)env_g * 16u + 4u * (uint32_t)agent) : a.attn + env_g * 16 + 4 * agent;
         __builtin_nontemporal_store(m[0], dst); __builtin_nontemporal_store(m[1], dst + 1);
         __builtin_nontemporal_store(m[2], dst + 2); __builtin_nontemporal_store(m[3], dst + 3);
     }
@@ -516,7 +523,8 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     if (g == 0 && rv) {
         if (a.probs) {
 #pragma unroll
-            for (int cc = 0; cc < 5; ++cc) if (cc < A) __builtin_nontemporal_store(p[cc], a.probs + grow * A + cc);
+            for (int cc = 0; cc < 5; ++cc) if (cc < A)
+                __builtin_nontemporal_store(p[cc], STEP32 ? at32(a.probs, so.probs + (uint32_t)grow * (uint32_t)A + cc) : a.probs + grow * A + cc);
         }
         if (a.actions || act_lds) {
             int act = 0;
@@ -531,7 +539,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
                 for (int cc = 0; cc < 5; ++cc) if (cc < A) { if (p[cc] > 0.0f) lastc = cc; acc += p[cc]; if (sel < 0 && u < acc) sel = cc; }
                 act = sel < 0 ? lastc : sel;
             }
-            if (a.actions) a.actions[grow] = act;
+            if (a.actions) *(STEP32 ? at32(a.actions, so.actions + (uint32_t)grow) : a.actions + grow) = act;
             if (act_lds) act_lds[row] = act;
         }
     }

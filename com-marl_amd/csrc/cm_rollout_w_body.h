@@ -1,20 +1,29 @@
 // cm_rollout_w_body.h - the BODY of the wave-owned rollout kernels (no include guard: it is included inside a kernel's braces).
 // The including kernel provides the template parameters <int LHOPS, bool PRE, bool FULLWG, bool TAPE, bool CARRY, int SHAPE> and
 // the locals  mf::FwdArgs a, mw::WeightsW w, EnvDev p, cm_rng_tape tape_arg, cm_step_out out, StridesW c, TailW tl  (a and p are
-// modified).  A textual include rather than an inlined device function: it leaves rollout_w_kernel's code exactly what it was
+// modified) and  constexpr bool PROBES  (whether the diagnostic clocks of COMMARL_ENV_STOP < 0 exist in this build: always in the
+// generic builds, where they are gated at run time; in the SHAPE 1 builds only in the probe entry).  A textual include rather than an inlined device function: it leaves rollout_w_kernel's code exactly what it was
 // when the loop was written in place (an inlined call reorders the IR enough to move the register allocation).
 // CARRY (PRE builds, constant adjacency, no channel model, no tape): a wave's envs hand observation and state from step to step
 // through LDS and registers (EnvCarry, env_pre_carry, the observation copy in the env area's unused claim table); no load of a
 // step depends on a store of the launch, so the fence between two steps goes and the trajectory stores of step t drain under
 // the policy forward of step t + 1.
 // SHAPE 1 (carried builds): the grid of BASELINE config 2 - 10 x 10 cells, 4 preys, sensing range 1 (3 x 3 window, 21 observation
-// entries) - as compile-time constants: index divisions by constants, constant LDS offsets, unrolled element loops.
+// entries) - as compile-time constants: index divisions by constants, constant LDS offsets, unrolled element loops; and what else
+// plan_rollout_w has established for it: five actions, no avail mask, sampling (not greedy), every output the engine passes by
+// default present, every trajectory buffer below 2^31 bytes.  The sampling tail is straight-line code, a step's slot in a
+// buffer is a 32-bit element offset from the launch's base (no per-step pointer rebuild, no null test at a store), and the
+// state arrays are written by the launch's last step only.
     static_assert(SHAPE == 0 || CARRY, "shape constants are built into the carried form only");
     if constexpr (SHAPE == 1) {
         p.S = 10; p.M = 4; p.R = 1; p.W = 3; p.d = 21; p.rcp_d = 1.0f / 21.0f; p.rcp_W = 1.0f / 3.0f; p.rcp_WW = 1.0f / 9.0f;
         p.lds_env = lds_env_bytes(10, 4, 4);
         a.N = 4; a.d = 21; a.L = LHOPS;
+        a.avail = nullptr; a.greedy = 0; a.adj = nullptr; a.chan = nullptr; a.probe = nullptr;
+        __builtin_assume(a.actions != nullptr); __builtin_assume(a.probs != nullptr); __builtin_assume(a.attn != nullptr);
+        if constexpr (!PROBES) p.stop = 0;                               // ENV_PROBE folds away
     }
+    const int n_act = SHAPE == 1 ? 5 : w.n_act;
     static_assert(!CARRY || (PRE && !TAPE), "the carried form is the prefetching, tape-less build");
     const cm_rng_tape tape = TAPE ? tape_arg : cm_rng_tape{};
     // what the launcher has already established, as compile-time constants of the by-value config: the branches on them fold away
@@ -25,7 +34,7 @@
     constexpr int LPE = 16;
     constexpr int ACT_OFF = mw::pack_w(LHOPS).lds_u4 * 16, ENV_BASE = ACT_OFF + mw::WG_ROWS * 4;
     int32_t *act = reinterpret_cast<int32_t *>(lds_w + ACT_OFF);
-    const bool probe = p.stop == -2 && blockIdx.x == 0 && thread_x() == 0;
+    const bool probe = PROBES && p.stop == -2 && blockIdx.x == 0 && thread_x() == 0;
     const unsigned long long t_in = probe ? __builtin_amdgcn_s_memtime() : 0ull;
     mw::stage_w<LHOPS>(w, lds_w, thread_x());
     mw::ResidentW res;
@@ -68,19 +77,26 @@
         const bool env_wave = FULLWG || (tx & ~63) / LPE < envs;        // a wave with an env of its own
         const int b_raw = blockIdx.x * mw::WG_ENVS + (live ? grp : 0);
         mf::FwdArgs at = a;
+        at.policy_step = a.policy_step + (uint32_t)t;
+        const uint32_t ut = (uint32_t)t;
+        if constexpr (SHAPE != 1) {
         at.obs = a.obs + (size_t)t * c.obs;
         at.adj = a.adj ? a.adj + (size_t)t * c.dist_adj : nullptr;
         at.chan = a.chan ? a.chan + (size_t)t * c.channels : nullptr;
-        at.policy_step = a.policy_step + (uint32_t)t;
         at.actions = a.actions ? a.actions + (size_t)t * c.actions : nullptr;
         at.probs = a.probs ? a.probs + (size_t)t * c.probs : nullptr;
         at.attn = a.attn ? a.attn + (size_t)t * c.attn : nullptr;
+        }
         const unsigned long long t0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
         if constexpr (PRE && !CARRY) pre = env_prefetch<CM_PP, LPE>(p, b_raw, live);   // env state requested in front of the policy forward
-        mw::policy_tile_w<LHOPS, CARRY>(at, w.n_act, res, lds_w, blockIdx.x, act, obs_row);
+        if constexpr (SHAPE == 1)
+            mw::policy_tile_w<LHOPS, true, false, 0, true>(at, n_act, res, lds_w, blockIdx.x, act, obs_row,
+                                                           mw::StepOff{ ut * (uint32_t)c.actions, ut * (uint32_t)c.probs, ut * (uint32_t)c.attn });
+        else mw::policy_tile_w<LHOPS, CARRY>(at, n_act, res, lds_w, blockIdx.x, act, obs_row);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's action words are in LDS
         const unsigned long long t1 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
         cm_step_out ot = out;
+        if constexpr (SHAPE != 1) {
         if (ot.obs) ot.obs += (size_t)t * c.obs;
         if (ot.reward) ot.reward += (size_t)t * c.reward;
         if (ot.reward_f64) ot.reward_f64 += (size_t)t * c.reward_f64;
@@ -91,10 +107,13 @@
         if (ot.prey_alive) ot.prey_alive += (size_t)t * c.prey_alive;
         if (ot.success) ot.success += (size_t)t * c.success;
         if (ot.path_len) ot.path_len += (size_t)t * c.path_len;
+        }
         if (env_wave) {
             const int32_t *my_act = act + (live ? grp : 0) * 4;
             if constexpr (CARRY && SHAPE == 1) {
-                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, grp, b_raw, live, ENV_BASE, FULLWG, obs_env);
+                const pp10::StepOff so{ ut * (uint32_t)c.obs, ut * (uint32_t)c.reward, ut * (uint32_t)c.reward_f64, ut * (uint32_t)c.done,
+                                        ut * (uint32_t)c.details, ut * (uint32_t)c.prey_alive, ut * (uint32_t)c.success, ut * (uint32_t)c.path_len };
+                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, so, t == c.n_steps - 1, grp, b_raw, live, ENV_BASE, FULLWG, obs_env);
             } else if constexpr (CARRY) {
                 const bool bad = env_stage<CM_PP, LPE>(p, pre, my_act, grp, ENV_BASE);
                 EnvCarry carry{ pre.step_count_in, pre.succ, 0 };

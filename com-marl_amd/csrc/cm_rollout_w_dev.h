@@ -83,11 +83,14 @@ static void env_probe_dump(const char *tag, const void *probe, void *stream) {
 
 // ---- host: how a launch of the wave-owned rollout runs (cm_rollout_w.hip: plan_rollout_w) ----
 struct RolloutWPlan {
+    int n_act;                                           // in: the policy's action count and the launch's outputs (what map10 folds)
+    const cm_step_out *out;
     size_t lds;                                          // dynamic LDS bytes: policy image | actions | 16 env areas
     int blocks;                                          // workgroups of 16 envs
     StridesW c;
     TailW tl;
     bool pre, full, carry, map10;                        // env prefetch / every workgroup full / carried form / its map-10 shape build
+    bool probes;                                         // map10 under COMMARL_ENV_STOP < 0: the build that has the diagnostic clocks
 };
 int plan_rollout_w(const mf::FwdArgs &a, const cm_env *h, bool use_tape, const ChunkArgs *chunk, RolloutWPlan &pl);
 // cm_rollout_w.hip: single step, or a persistent chunk; 1 = not available for this handle

@@ -22,6 +22,7 @@ struct PolicySetW {
 template <int LHOPS, bool PRE, bool FULLWG, bool CARRY = false, int SHAPE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_wm_kernel(mf::FwdArgs a, mw::PolicySetW ps, EnvDev p, cm_step_out out, StridesW c) {
     constexpr bool TAPE = false;
+    constexpr bool PROBES = SHAPE != 1;                  // the host of this entry never reads the clocks: no probe twin of its SHAPE 1 builds
     // uniform per workgroup: one lookup of the policy, one of its pack.  The pack address is made uniform (both halves through
     // readfirstlane) and global explicitly: a pointer as loaded from memory is generic and not known uniform, and then the staging's
     // loads become flat loads and its batch of chunks goes to scratch (304 bytes per lane)
@@ -57,6 +58,7 @@ extern "C" int cm_rollout_chunk_multi(cm_env_t h, const cm_policy_weights *w, co
                                            actions, probs, attn);
     const ChunkArgs c = chunk_args(n_steps, *st);
     RolloutWPlan pl;
+    pl.n_act = w->n_act; pl.out = out;
     if (plan_rollout_w(a, h, false, &c, pl)) return 1;
     const mw::PolicySetW ps{ set->packs, set->wg_policy, (int)wave_pack(d), w->n_act };
     // no tape variant here: the ladder never takes that branch without a tape

@@ -91,6 +91,12 @@ class MlpWeights(C.Structure):
                 ("b", C.c_void_p * MLP_MAX_LAYERS), ("mfma_pack", C.c_void_p)]
 
 
+class MlpSetMember(C.Structure):
+    """cm_mlp_set_member: one member's rows and per-layer pointers in the table cm_mlp_policy_forward_multi reads."""
+    _fields_ = [("first_row", C.c_int32), ("n_rows", C.c_int32), ("first_env", C.c_int32), ("_pad", C.c_int32),
+                ("b", C.c_void_p * MLP_MAX_LAYERS), ("pack", C.c_void_p * MLP_MAX_LAYERS)]
+
+
 # every symbol include/commarl.h declares, with its signature
 _SIGNATURES = {
     "cm_abi_version": (C.c_int, []),
@@ -140,6 +146,11 @@ _SIGNATURES = {
     "cm_mlp_policy_forward": (C.c_int, [C.POINTER(MlpWeights), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_mlp_forward_multi_plan": (C.c_int64, [C.POINTER(MlpWeights), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]),
+    "cm_mlp_policy_forward_multi": (C.c_int, [C.POINTER(MlpWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_mlp_pack_bytes": (C.c_size_t, [C.POINTER(MlpWeights)]),
     "cm_mlp_pack": (C.c_int, [C.POINTER(MlpWeights), C.c_void_p, C.c_void_p]),
     "cm_mlp_value_forward": (C.c_int, [C.POINTER(MlpWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

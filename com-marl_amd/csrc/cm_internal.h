@@ -51,6 +51,16 @@ __device__ __forceinline__ int thread_x() {
     return t;
 }
 
+// A pointer as loaded from memory is generic and not known uniform: loads through it become flat loads and what they feed may go
+// to scratch (DESIGN.md §5 "Multi-policy rollouts").  Both halves through readfirstlane, and global explicitly.
+template <typename T>
+__device__ __forceinline__ const T *uniform_global(const T *p) {
+    const unsigned long long u = (unsigned long long)p;
+    const unsigned long long v = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(u >> 32)) << 32) |
+                                 (unsigned)__builtin_amdgcn_readfirstlane((unsigned)u);
+    return (const T *)(const __attribute__((address_space(1))) T *)v;
+}
+
 // Device-side view of one batched env set (passed to kernels by value).
 struct EnvDev {
     int scen, B, N, M, S, R, W, d, load, max_steps, mpl, L, rc2, channel, add_clock, n_empty, rng_mode, env_id_offset;

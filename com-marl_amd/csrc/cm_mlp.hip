@@ -61,173 +61,75 @@ __device__ __forceinline__ void store_tile(float *out, int sw, int rt, int ct, i
 }
 
 __global__ __launch_bounds__(TPB) void mlp_kernel(Args a) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int c = lane & 15, g = lane >> 4;
-    const int row0 = blockIdx.x * ROWS;
-    const int rows = min(ROWS, a.rows - row0);
-    const int sw = a.sw;
-    float *buf0 = smem, *buf1 = smem + (size_t)ROWS * sw;
+#define CM_MLP_ROW0 (blockIdx.x * ROWS)
+#define CM_MLP_ROWS_LEFT (a.rows - row0)
+#define CM_MLP_LAYER(l)
+#define CM_MLP_HAS_PK(l) (a.pk[l])
+#define CM_MLP_PK(l) (a.pk[l])
+#define CM_MLP_WT(l) (a.wt[l])
+#define CM_MLP_B(l) (a.b[l])
+#include "cm_mlp_body.h"
+#undef CM_MLP_ROW0
+#undef CM_MLP_ROWS_LEFT
+#undef CM_MLP_LAYER
+#undef CM_MLP_HAS_PK
+#undef CM_MLP_PK
+#undef CM_MLP_WT
+#undef CM_MLP_B
+}
 
-    // ---- layer 0: input streamed from HBM through buf1 in CHUNK-column pieces --------------------------------
-    {
-        const int K = a.in_dim, OUT = a.out_dim[0];
-        const int nct = (OUT + 15) >> 4;                     // <= 8 (host-checked: OUT <= 128)
-        const int KQ0 = (K + 15) >> 4;
-        const float *__restrict__ Wt = a.wt[0];
-        v4f acc[2][2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) { acc[t][0] = (v4f){ 0.f, 0.f, 0.f, 0.f }; acc[t][1] = (v4f){ 0.f, 0.f, 0.f, 0.f }; }
-        for (int c0 = 0; c0 < K; c0 += CHUNK) {
-            __syncthreads();                                 // previous chunk fully consumed
-            for (int i = tid; i < ROWS * CHUNK; i += TPB) {
-                const int r = i >> 7, cc = i & (CHUNK - 1);
-                const int k = c0 + cc;
-                buf1[(size_t)r * sw + cc] = (r < rows && k < K) ? a.x[(size_t)(row0 + r) * K + k] : 0.0f;
-            }
-            __syncthreads();
-            const int kc = min(CHUNK, K - c0);
-            const int k16 = (kc + 15) >> 4;
-            for (int kq = 0; kq < k16; ++kq) {
-                const float4 a0 = *reinterpret_cast<const float4 *>(buf1 + (size_t)c * sw + 16 * kq + 4 * g);
-                const float4 a1 = *reinterpret_cast<const float4 *>(buf1 + (size_t)(16 + c) * sw + 16 * kq + 4 * g);
-                const float x0[4] = { a0.x, a0.y, a0.z, a0.w }, x1[4] = { a1.x, a1.y, a1.z, a1.w };
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int ct = wave + 4 * t;
-                    if (ct >= nct) continue;                 // wave-uniform
-                    const int col = ct * 16 + c;
-                    float bw[4];
-                    if (a.pk[0]) {                           // one unconditional 16-byte load per lane
-                        const float4 v = reinterpret_cast<const float4 *>(a.pk[0])[((size_t)ct * KQ0 + (c0 >> 4) + kq) * 64 + lane];
-                        bw[0] = v.x; bw[1] = v.y; bw[2] = v.z; bw[3] = v.w;
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int k = c0 + 16 * kq + 4 * g + j;
-                            bw[j] = (k < K && col < OUT) ? Wt[(size_t)k * OUT + col] : 0.0f;
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[j], bw[j], acc[t][0], 0, 0, 0);
-                        acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[j], bw[j], acc[t][1], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        const int act = layer_act(a, 0);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int ct = wave + 4 * t;
-            if (ct >= nct) continue;
-            const int col = ct * 16 + c;
-            const float bias = (a.b[0] && col < OUT) ? a.b[0][col] : 0.0f;
-            store_tile(buf0, sw, 0, ct, lane, acc[t][0], bias, act);
-            store_tile(buf0, sw, 1, ct, lane, acc[t][1], bias, act);
-        }
-    }
-    __syncthreads();
+// ---- the same body for SEVERAL policies of one shape in one launch (cm_mlp_policy_forward_multi) ---------------------------------
+// The table's records as the kernel reads them (the ABI's cm_forward_set_wg / cm_mlp_set_member, include/commarl.h).
+struct SetWg { int32_t member, block; };
+struct SetMember {
+    int32_t first_row, n_rows, first_env, pad;
+    const float *b[MAXL];                                // biases live in the member's flat weight copy
+    const float *pk[MAXL];                               // per-layer B fragments inside the member's cm_mlp_pack output
+};
+static_assert(sizeof(SetWg) == sizeof(cm_forward_set_wg) && sizeof(SetMember) == sizeof(cm_mlp_set_member), "table records are the ABI's");
 
-    // ---- layers 1..: LDS -> LDS --------------------------------------------------------------------------------
-    float *in = buf0, *out = buf1;
-    for (int l = 1; l < a.n_layers; ++l) {
-        const int K = a.out_dim[l - 1], OUT = a.out_dim[l];
-        const int nct = (OUT + 15) >> 4, k16 = (K + 15) >> 4;
-        const float *__restrict__ Wt = a.wt[l];
-        const int act = layer_act(a, l);
-        for (int ct = wave; ct < nct; ct += 4) {
-            const int col = ct * 16 + c;
-            v4f acc0 = (v4f){ 0.f, 0.f, 0.f, 0.f }, acc1 = (v4f){ 0.f, 0.f, 0.f, 0.f };
-            for (int kq = 0; kq < k16; ++kq) {
-                const float4 a0 = *reinterpret_cast<const float4 *>(in + (size_t)c * sw + 16 * kq + 4 * g);
-                const float4 a1 = *reinterpret_cast<const float4 *>(in + (size_t)(16 + c) * sw + 16 * kq + 4 * g);
-                const float x0[4] = { a0.x, a0.y, a0.z, a0.w }, x1[4] = { a1.x, a1.y, a1.z, a1.w };
-                float bw[4];
-                if (a.pk[l]) {
-                    const float4 v = reinterpret_cast<const float4 *>(a.pk[l])[((size_t)ct * k16 + kq) * 64 + lane];
-                    bw[0] = v.x; bw[1] = v.y; bw[2] = v.z; bw[3] = v.w;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int k = 16 * kq + 4 * g + j;
-                        bw[j] = (k < K && col < OUT) ? Wt[(size_t)k * OUT + col] : 0.0f;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[j], bw[j], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[j], bw[j], acc1, 0, 0, 0);
-                }
-            }
-            const float bias = (a.b[l] && col < OUT) ? a.b[l][col] : 0.0f;
-            store_tile(out, sw, 0, ct, lane, acc0, bias, act);
-            store_tile(out, sw, 1, ct, lane, acc1, bias, act);
-        }
-        __syncthreads();
-        float *t = in; in = out; out = t;
-    }
-    // `in` now holds the last layer's output [ROWS][>= out_dim[n_layers-1]]
-
-    if (a.values) {                                          // GaussianMLPBaseline mean: one value per row
-        for (int r = tid; r < rows; r += TPB) a.values[row0 + r] = in[(size_t)r * sw];
-        return;
-    }
-
-    // ---- per-agent softmax * avail, renormalise, sample (same arithmetic order as cm_policy_mfma.hip) ------------
-    const int G = a.groups, A = a.n_act;
-    for (int it = tid; it < rows * G; it += TPB) {
-        const int r = it / G, gi = it - r * G;
-        const float *lg = in + (size_t)r * sw + gi * A;
-        float p[MAX_ACT];
-        float mx = -INFINITY, sum = 0.0f, msum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) mx = fmaxf(mx, lg[k]);
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) { p[k] = expf(lg[k] - mx); sum += p[k]; }
-        const size_t flat = (size_t)(row0 + r) * G + gi;     // global agent-row index
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) {
-            const float av = a.avail ? a.avail[flat * A + k] : 1.0f;
-            p[k] = (p[k] / sum) * av; msum += p[k];
-        }
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) p[k] = p[k] / msum;
-        if (a.probs) {
-#pragma unroll
-            for (int k = 0; k < MAX_ACT; ++k) if (k < A) a.probs[flat * A + k] = p[k];
-        }
-        if (a.actions) {
-            int act = 0;
-            if (a.greedy) {
-                float best = p[0];
-#pragma unroll
-                for (int k = 1; k < MAX_ACT; ++k) if (k < A && p[k] > best) { best = p[k]; act = k; }
-            } else {
-                const size_t e = flat / (size_t)a.agents_per_env;
-                const uint32_t i = (uint32_t)(flat - e * a.agents_per_env);
-                const u32x4 xr = philox4x32_10((uint32_t)(a.env_id_offset + (int)e),
-                                               a.policy_step + (a.step_base ? *a.step_base : 0u), SITE_ACTION, i,
-                                               a.key0, a.key1);
-                const float u = unit_f32(xr.x);
-                float acc = 0.0f;
-                int sel = -1, last = 0;
-#pragma unroll
-                for (int k = 0; k < MAX_ACT; ++k) if (k < A) { if (p[k] > 0.0f) last = k; acc += p[k]; if (sel < 0 && u < acc) sel = k; }
-                act = sel < 0 ? last : sel;
-            }
-            a.actions[flat] = act;
-        }
-    }
+// A workgroup reads whose rows it has - (member, block inside the member's rows) - and runs mlp_kernel's body on them with the
+// member's operands.  `a` is the shared shape and the whole batch's pointers and is not modified: rows are indexed in the whole
+// batch (row0 = the member's first row + 32 * block), so x / avail / outputs and the Philox env id need no rebasing - a member's
+// first row times `groups` is its first env times agents_per_env.  The per-layer pointers are read from the table by `l` where the
+// layer starts (a copy of them per workgroup would be a dynamically indexed array: scratch), each made uniform and global.  Every
+// member has a pack (the planner's condition), so there is no plain-weight gather here.
+__global__ __launch_bounds__(TPB) void mlp_set_kernel(Args a, const SetWg *__restrict__ wgs, const SetMember *__restrict__ members) {
+    const SetWg wg = wgs[blockIdx.x];
+    const int member = __builtin_amdgcn_readfirstlane(wg.member), blk = __builtin_amdgcn_readfirstlane(wg.block);
+    const SetMember &m = members[member];
+    const int first_row = __builtin_amdgcn_readfirstlane(m.first_row), n_rows = __builtin_amdgcn_readfirstlane(m.n_rows);
+#define CM_MLP_ROW0 (first_row + blk * ROWS)
+#define CM_MLP_ROWS_LEFT (n_rows - blk * ROWS)
+#define CM_MLP_LAYER(l) const float *const pk_l = uniform_global(m.pk[l]), *const b_l = uniform_global(m.b[l]);
+#define CM_MLP_HAS_PK(l) true
+#define CM_MLP_PK(l) pk_l
+#define CM_MLP_WT(l) nullptr
+#define CM_MLP_B(l) b_l
+#include "cm_mlp_body.h"
+#undef CM_MLP_ROW0
+#undef CM_MLP_ROWS_LEFT
+#undef CM_MLP_LAYER
+#undef CM_MLP_HAS_PK
+#undef CM_MLP_PK
+#undef CM_MLP_WT
+#undef CM_MLP_B
 }
 
 static size_t pack_floats(int K, int OUT) { return (size_t)((OUT + 15) >> 4) * ((K + 15) >> 4) * 256; }
 
-static int launch(Args a, void *stream) {
+// the LDS row stride of a chain (a.sw) -> the two tiles' bytes, or 0 when they exceed the 160 KB a workgroup can have
+static size_t lds_tiles(Args &a) {
     int maxw = CHUNK;
     for (int l = 0; l < a.n_layers; ++l) maxw = max(maxw, (a.out_dim[l] + 15) & ~15);
     a.sw = maxw + 4;                                         // +4 words: rows skewed across LDS banks, 16-byte aligned
     const size_t lds = 2ull * ROWS * a.sw * sizeof(float);
-    if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "mlp forward: layer too wide for the 160 KB LDS tile");
+    return lds > 160 * 1024 ? 0 : lds;
+}
+
+static int launch(Args a, void *stream) {
+    const size_t lds = lds_tiles(a);
+    if (!lds) return set_error(CM_ERR_ARG, "mlp forward: layer too wide for the 160 KB LDS tile");
     static unsigned long long attr_set = 0;
     if (cm::dev_first(attr_set)) {
         CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -261,10 +163,117 @@ static int fill(Args &a, const cm_mlp_weights *w, int32_t rows, const float *x) 
     return CM_OK;
 }
 
+static int launch_set(Args a, const SetWg *wgs, const SetMember *members, int n_wg, void *stream) {
+    const size_t lds = lds_tiles(a);
+    if (!lds) return set_error(CM_ERR_ARG, "mlp forward: layer too wide for the 160 KB LDS tile");
+    static unsigned long long attr_set = 0;
+    if (cm::dev_first(attr_set)) {
+        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   160 * 1024));
+    }
+    hipLaunchKernelGGL(mlp_set_kernel, dim3(n_wg), dim3(TPB), lds, (hipStream_t)stream, a, wgs, members);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+// what the policy entry points ask of the sampler's shape
+static int check_sampler(const char *who, const cm_mlp_weights *w, int groups, int n_act, int agents_per_env) {
+    if (groups < 1 || n_act < 1 || n_act > MAX_ACT || agents_per_env < 1)
+        return set_error(CM_ERR_ARG, std::string(who) + ": groups >= 1, 1 <= n_act <= 8, agents_per_env >= 1");
+    if (w->out_dim[w->n_layers - 1] != groups * n_act)
+        return set_error(CM_ERR_ARG, std::string(who) + ": last layer width != groups * n_act");
+    return CM_OK;
+}
+
+static bool same_shape(const cm_mlp_weights &x, const cm_mlp_weights &y) {
+    if (x.in_dim != y.in_dim || x.n_layers != y.n_layers || x.tanh_mask != y.tanh_mask || x.relu_mask != y.relu_mask) return false;
+    for (int l = 0; l < x.n_layers && l < MAXL; ++l)
+        if (x.out_dim[l] != y.out_dim[l]) return false;
+    return true;
+}
+
 }  // namespace mlp
 }  // namespace cm
 
 extern "C" {
+
+int64_t cm_mlp_forward_multi_plan(const cm_mlp_weights *members, const int32_t *group_sizes, int32_t n_policies, int32_t n_envs,
+                                  int32_t groups, int32_t n_act, int32_t agents_per_env, void *image, size_t image_bytes,
+                                  int32_t *n_wg_out) {
+    using namespace cm::mlp;
+    const std::string who = "cm_mlp_forward_multi_plan";
+    if (!members || !group_sizes || !n_wg_out) return cm::set_error(CM_ERR_ARG, who + ": null argument");
+    if (n_policies < 1) return cm::set_error(CM_ERR_ARG, who + ": a policy set has at least one member");
+    static const float no_input = 0.0f;                      // fill() wants an input pointer; the planner reads none
+    Args a{};
+    if (int rc = fill(a, &members[0], 0, &no_input)) return rc;
+    if (groups != 1 && groups != agents_per_env)
+        return cm::set_error(CM_ERR_ARG, who + ": groups is 1 (a row per agent) or agents_per_env (a row per env)");
+    if (int rc = check_sampler(who.c_str(), &members[0], groups, n_act, agents_per_env)) return rc;
+    if (!lds_tiles(a)) return cm::set_error(CM_ERR_ARG, "mlp forward: layer too wide for the 160 KB LDS tile");
+    const int rows_per_env = agents_per_env / groups;
+    long long sum = 0, n_wg = 0;
+    bool packed = true;
+    for (int k = 0; k < n_policies; ++k) {
+        if (group_sizes[k] < 1) return cm::set_error(CM_ERR_ARG, who + ": every member needs at least one env");
+        if (!same_shape(members[k], members[0])) return cm::set_error(CM_ERR_ARG, who + ": the members differ in shape");
+        packed = packed && members[k].mfma_pack;
+        sum += group_sizes[k];
+        n_wg += ((long long)group_sizes[k] * rows_per_env + ROWS - 1) / ROWS;   // a ragged last workgroup per member: none is shared with the next
+    }
+    if (sum != n_envs) return cm::set_error(CM_ERR_ARG, who + ": the group sizes must sum to n_envs");
+    if (sum * rows_per_env > INT32_MAX) return cm::set_error(CM_ERR_ARG, who + ": more than 2^31 - 1 rows in one launch");
+    if (!packed) { *n_wg_out = 0; return 0; }
+    const size_t need = (size_t)n_wg * sizeof(cm_forward_set_wg) + (size_t)n_policies * sizeof(cm_mlp_set_member);
+    *n_wg_out = (int32_t)n_wg;
+    if (!image) return (int64_t)need;
+    if (image_bytes < need) return cm::set_error(CM_ERR_ARG, who + ": image buffer too small");
+    cm_forward_set_wg *wg = reinterpret_cast<cm_forward_set_wg *>(image);
+    cm_mlp_set_member *mem = reinterpret_cast<cm_mlp_set_member *>(wg + n_wg);
+    int32_t first = 0;
+    for (int k = 0; k < n_policies; ++k) {
+        const cm_mlp_weights &w = members[k];
+        const int32_t rows = group_sizes[k] * rows_per_env;
+        for (int b = 0; b < (rows + ROWS - 1) / ROWS; ++b) *wg++ = cm_forward_set_wg{ k, b };
+        cm_mlp_set_member r{};
+        r.first_row = first * rows_per_env; r.n_rows = rows; r.first_env = first;
+        size_t off = 0;
+        for (int l = 0; l < w.n_layers; ++l) {               // the layers' fragments lie in the pack as fill() walks them
+            r.b[l] = w.b[l];
+            r.pack[l] = w.mfma_pack + off;
+            off += pack_floats(l == 0 ? w.in_dim : w.out_dim[l - 1], w.out_dim[l]);
+        }
+        mem[k] = r;
+        first += group_sizes[k];
+    }
+    return (int64_t)need;
+}
+
+int cm_mlp_policy_forward_multi(const cm_mlp_weights *shape, const void *table_dev, int32_t n_wg, int32_t n_envs, int32_t groups,
+                                int32_t n_act, int32_t agents_per_env, const float *x, const float *avail, uint64_t seed,
+                                int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy,
+                                int32_t *actions, float *probs, void *stream) {
+    using namespace cm::mlp;
+    const char *who = "cm_mlp_policy_forward_multi";
+    Args a{};
+    if (n_envs < 0) return cm::set_error(CM_ERR_ARG, std::string(who) + ": negative env count");
+    if (int rc = fill(a, shape, 0, x)) return rc;
+    if (groups != 1 && groups != agents_per_env)
+        return cm::set_error(CM_ERR_ARG, std::string(who) + ": groups is 1 (a row per agent) or agents_per_env (a row per env)");
+    if (int rc = check_sampler(who, shape, groups, n_act, agents_per_env)) return rc;
+    if (!actions && !probs) return cm::set_error(CM_ERR_ARG, std::string(who) + ": no output requested");
+    if (n_envs == 0) return CM_OK;
+    if (!shape->mfma_pack) return 1;
+    const long long rows = (long long)n_envs * (agents_per_env / groups);
+    if (!table_dev || n_wg < (rows + ROWS - 1) / ROWS || n_wg > rows || rows > INT32_MAX)
+        return cm::set_error(CM_ERR_ARG, std::string(who) + ": null table, or n_wg is not the planner's for n_envs");
+    a.rows = (int)rows;
+    a.groups = groups; a.n_act = n_act; a.agents_per_env = agents_per_env; a.avail = avail;
+    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;
+    a.env_id_offset = env_id_offset; a.greedy = greedy; a.actions = actions; a.probs = probs;
+    const SetWg *wgs = reinterpret_cast<const SetWg *>(table_dev);
+    return launch_set(a, wgs, reinterpret_cast<const SetMember *>(wgs + n_wg), n_wg, stream);
+}
 
 int cm_mlp_policy_forward(const cm_mlp_weights *w, int32_t rows, int32_t groups, int32_t n_act, int32_t agents_per_env,
                           const float *x, const float *avail, uint64_t seed, int32_t env_id_offset,
@@ -272,10 +281,7 @@ int cm_mlp_policy_forward(const cm_mlp_weights *w, int32_t rows, int32_t groups,
                           float *probs, void *stream) {
     cm::mlp::Args a{};
     if (int rc = cm::mlp::fill(a, w, rows, x)) return rc;
-    if (groups < 1 || n_act < 1 || n_act > cm::mlp::MAX_ACT || agents_per_env < 1)
-        return cm::set_error(CM_ERR_ARG, "mlp policy forward: groups >= 1, 1 <= n_act <= 8, agents_per_env >= 1");
-    if (w->out_dim[w->n_layers - 1] != groups * n_act)
-        return cm::set_error(CM_ERR_ARG, "mlp policy forward: last layer width != groups * n_act");
+    if (int rc = cm::mlp::check_sampler("mlp policy forward", w, groups, n_act, agents_per_env)) return rc;
     if (!actions && !probs) return cm::set_error(CM_ERR_ARG, "mlp policy forward: no output requested");
     a.groups = groups; a.n_act = n_act; a.agents_per_env = agents_per_env; a.avail = avail;
     a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;

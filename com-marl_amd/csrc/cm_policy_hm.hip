@@ -27,16 +27,6 @@ static_assert(sizeof(SetWg) == sizeof(cm_forward_set_wg) && sizeof(SetMember) ==
 // pack_layout_h of the shared shape, in uint4 units (enc1 sits at 0)
 struct SetOffs { unsigned enc2, attn, gcn, x1, h2, h3, h4; };
 
-// A pointer as loaded from memory is generic and not known uniform: loads through it become flat loads and what they feed may go
-// to scratch (DESIGN.md §5 "Multi-policy rollouts").  Both halves through readfirstlane, and global explicitly.
-template <typename T>
-__device__ __forceinline__ const T *uniform_global(const T *p) {
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned long long v = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(u >> 32)) << 32) |
-                                 (unsigned)__builtin_amdgcn_readfirstlane((unsigned)u);
-    return (const T *)(const __attribute__((address_space(1))) T *)v;
-}
-
 // Policy head only.  SAVES = false: the acting forward stores no activations, and the rebased copy of the argument block then has
 // no dynamically indexed member (it stays in registers).
 template <int KH, int MAXMK, int NW>

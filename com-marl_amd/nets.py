@@ -1453,8 +1453,10 @@ class PolicySet:
     """K policies of ONE architecture (class, team size, observation dim, hops, attention type, residual, hidden sizes, hidden
     nonlinearity, device) that one RolloutEngine runs side by side, each on its own contiguous range of the envs - e.g. the
     checkpoints of one run evaluated at once (evaluate.eval_models).  What the engine reads from a policy (``_n_agents``,
-    ``_action_dim``, ``comm``, ...) comes from member 0; ``sync_weights()`` refreshes every member's pack and
-    ``pack_table()`` keeps the device table of the members' pack addresses that cm_rollout_chunk_multi reads."""
+    ``_action_dim``, ``comm``, ...) comes from member 0; ``sync_weights()`` refreshes every member's pack,
+    ``pack_table()`` keeps the device table of the members' pack addresses that cm_rollout_chunk_multi reads and
+    ``forward_table()`` the one the set forward reads (cm_policy_forward_multi for Comm-DP members,
+    cm_mlp_policy_forward_multi for Obs-DP / CENT members)."""
     _SHARED = ("_n_agents", "_action_dim", "_dec_obs_dim", "_obs_dim", "_embedding_dim", "comm", "centralized", "device",
                "n_gcn_layers", "residual")
 
@@ -1511,11 +1513,13 @@ class PolicySet:
         return self._table[1]
 
     def forward_table(self, groups):
-        """(device table, workgroup count) of the set forward - cm_policy_forward_multi, every member's acting forward in one
-        launch - with member k on the next groups[k] envs; (None, 0) when the library has no set kernel for the shape or the
-        members have no operand pack.  Kept until a member's operand pack or flat weight copy was reallocated or the groups
+        """(device table, workgroup count) of the set forward - cm_policy_forward_multi (Comm-DP members) or
+        cm_mlp_policy_forward_multi (Obs-DP / CENT members), every member's acting forward in one launch - with member k on the
+        next groups[k] envs; (None, 0) when the library has no set kernel for the shape or the members have no operand pack.  Kept until a member's operand pack or flat weight copy was reallocated or the groups
         change, packing the members that have no pack yet; the weights themselves are read as they are (sync_weights()
         refreshes them in place).  A set the planner refuses (a group without envs, ...) raises."""
+        if all(hasattr(p, "_mlp_struct") for p in self.policies):
+            return self._mlp_forward_table(groups)
         if not all(hasattr(p, "_weights_struct") for p in self.policies):
             return None, 0
         if any(p._mfma is None or p._pack is None for p in self.policies):
@@ -1539,5 +1543,34 @@ class PolicySet:
                 table = torch.frombuffer(image, dtype=torch.uint8).to(self.policies[0]._mfma.device)
             if need < 0:
                 L.check(int(need), "cm_policy_forward_multi_plan")
+            self._fwd_table = (key, table, n_wg.value)
+        return self._fwd_table[1], self._fwd_table[2]
+
+    def _mlp_forward_table(self, groups):
+        """forward_table() for Obs-DP / CENT members: the table of cm_mlp_policy_forward_multi (cm_mlp_forward_multi_plan), kept
+        until a member's B-fragment pack (``_mlp_pack``) or flat weight copy was reallocated or the groups change."""
+        if any(p._mlp_pack is None or p._pack is None for p in self.policies):
+            self.sync_weights()
+            if any(p._mlp_pack is None for p in self.policies):
+                return None, 0
+        groups = tuple(int(g) for g in groups)
+        if len(groups) != len(self.policies):
+            raise ValueError(f"forward_table: {len(groups)} groups for {len(self.policies)} policies")
+        key = (groups, tuple((p._mlp_pack.data_ptr(), p._pack[0].data_ptr()) for p in self.policies))
+        if self._fwd_table is None or self._fwd_table[0] != key:
+            K, p0 = len(self.policies), self.policies[0]
+            N, A = p0._n_agents, p0._action_dim
+            ws = (L.MlpWeights * K)(*[p._mlp_struct() for p in self.policies])
+            sizes, n_wg = (C.c_int32 * K)(*groups), C.c_int32(0)
+            shape = (K, sum(groups), 1 if p0._per_agent_rows else N, A, N)
+            plan = L.lib().cm_mlp_forward_multi_plan
+            need = plan(ws, sizes, *shape, None, 0, C.byref(n_wg))
+            table = None
+            if need > 0:
+                image = bytearray(need)
+                need = plan(ws, sizes, *shape, (C.c_char * need).from_buffer(image), need, C.byref(n_wg))
+                table = torch.frombuffer(image, dtype=torch.uint8).to(p0._mlp_pack.device)
+            if need < 0:
+                L.check(int(need), "cm_mlp_forward_multi_plan")
             self._fwd_table = (key, table, n_wg.value)
         return self._fwd_table[1], self._fwd_table[2]

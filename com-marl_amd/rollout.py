@@ -60,9 +60,10 @@ class RolloutEngine:
         contiguous envs [lo_k, hi_k).  Each env plays exactly what it would play in a single-policy engine whose env batch
         starts at the same global env id.  Teams of 4 whose groups start on multiples of 16 envs run a chunk as ONE
         cm_rollout_chunk_multi launch (multi_form "wave"); every other set takes one forward + one env step over the batch per
-        step (multi_form "loop"), the forward being ONE cm_policy_forward_multi launch for all members where the library has
-        a set kernel for the shape (multi_forward "set": Comm-DP teams other than 4, up to 80 agents, one sampler seed) and one
-        cm_policy_forward per member on its envs otherwise (multi_forward "member")."""
+        step (multi_form "loop"), the forward being ONE launch for all members where the library has a set kernel for the
+        shape (multi_forward "set": cm_policy_forward_multi for Comm-DP teams other than 4, up to 80 agents, and
+        cm_mlp_policy_forward_multi for Obs-DP / CENT members of any team size; one sampler seed, production RNG) and one
+        forward launch per member on its envs otherwise (multi_forward "member")."""
         if isinstance(env, (list, tuple)):
             env = _Parts(list(env)) if len(env) > 1 else env[0]
         self.env, self.policy, self.H = env, policy, int(horizon)
@@ -148,9 +149,11 @@ class RolloutEngine:
                 and all(lo % WG_ENVS == 0 for lo, _ in self.groups) and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_form = "wave" if wave else "loop"
         self._persistent, self._fused = wave, None
-        # loop form: one forward launch for the whole set (cm_policy_forward_multi) - Comm-DP members, one sampler seed, production
-        # RNG; the library answers "not for this shape" (1) for the teams it has no set kernel for, and the engine remembers it
-        set_fwd = hasattr(ps[0], "chunk_fused") and ps.seed is not None and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX
+        # loop form: one forward launch for the whole set (cm_policy_forward_multi for Comm-DP members, cm_mlp_policy_forward_multi
+        # for Obs-DP / CENT members) - one sampler seed, production RNG; the library answers "not for this shape" (1) for the
+        # teams it has no set kernel for, and the engine remembers it
+        set_fwd = ((hasattr(ps[0], "chunk_fused") or hasattr(ps[0], "_mlp_struct")) and ps.seed is not None
+                   and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_forward = None if wave else ("set" if set_fwd else "member")
         if wave:
             n_wg = (B + WG_ENVS - 1) // WG_ENVS
@@ -180,13 +183,23 @@ class RolloutEngine:
         return True
 
     def _set_forward(self, t, greedy):
-        """Slot t's forward + sample of every member in ONE cm_policy_forward_multi launch over the batch.  False - nothing
-        launched - when the library has no set kernel for this shape (the engine launches member by member from then on).
-        The members' packs are used as they are, as in _multi_chunk."""
+        """Slot t's forward + sample of every member in ONE launch over the batch: cm_policy_forward_multi, or
+        cm_mlp_policy_forward_multi for Obs-DP / CENT members.  False - nothing launched - when the library has no set kernel
+        for this shape (the engine launches member by member from then on).  The members' packs are used as they are, as in
+        _multi_chunk."""
         ps, B = self.policy, self.env.B
         table, n_wg = ps.forward_table([hi - lo for lo, hi in self.groups])
-        rc = 1
-        if table is not None:
+        rc, what = 1, "cm_policy_forward_multi"
+        if table is not None and hasattr(ps[0], "_mlp_struct"):
+            what = "cm_mlp_policy_forward_multi"
+            w, N = ps[0]._mlp_struct(), ps._n_agents                        # the shape every member shares
+            obs, _, _, actions, probs, _ = self._slot(t, 0, B)
+            with torch.cuda.device(self.env.device):
+                rc = L.lib().cm_mlp_policy_forward_multi(
+                    C.byref(w), L.ptr(table), n_wg, B, 1 if ps[0]._per_agent_rows else N, ps._action_dim, N, L.ptr(obs), None,
+                    ps.seed, self.id0, t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs),
+                    L.current_stream())
+        elif table is not None:
             w = ps[0]._weights_struct()                                     # the shape every member shares
             obs, adj, ch, actions, probs, attn = self._slot(t, 0, B)
             with torch.cuda.device(self.env.device):
@@ -197,7 +210,7 @@ class RolloutEngine:
         if rc == 1:
             self.multi_forward = "member"
             return False
-        L.check(rc, "cm_policy_forward_multi")
+        L.check(rc, what)
         return True
 
     def _multi_step(self, t, greedy):

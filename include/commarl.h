@@ -388,6 +388,39 @@ int cm_mlp_policy_forward(const cm_mlp_weights *w, int32_t rows, int32_t groups,
                           const float *x, const float *avail, uint64_t seed, int32_t env_id_offset,
                           uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy, int32_t *actions,
                           float *probs, void *stream);
+/* cm_mlp_policy_forward for SEVERAL policies of one shape in ONE launch, each on its own contiguous range of the envs: member k acts
+ * on the group_sizes[k] envs behind those of members 0 .. k-1, i.e. on group_sizes[k] * agents_per_env / groups rows of x (agent
+ * rows with groups == 1, env rows with groups == agents_per_env; nothing else is accepted).  Every output is bit-identical to
+ * cm_mlp_policy_forward with member k's weights on its rows and env_id_offset + the group's first env (one seed for the set): a
+ * member's rows end in a ragged 32-row workgroup of their own, never shared with the next member.
+ *
+ * cm_mlp_forward_multi_plan (host only, no device work): refuses (< 0, text in cm_last_error) an empty set, a group without envs,
+ * sizes that do not sum to n_envs, members that differ in in_dim / n_layers / out_dim[] / tanh_mask / relu_mask, a shape
+ * cm_mlp_policy_forward refuses (last layer != groups * n_act wide, ...) and an `image` that is too small.  Otherwise returns the
+ * size in bytes of the table the launch reads and *n_wg = the launch's workgroup count, the sum over members of
+ * ceil(rows / 32); with `image` non-NULL the table's host image is written there: n_wg cm_forward_set_wg descriptors, then
+ * n_policies cm_mlp_set_member records.  The caller uploads the image to device memory it owns and rebuilds it when a member's
+ * pack or weight buffers move or the groups change.  Returns 0 (*n_wg = 0, nothing written) when a member has no mfma_pack: the
+ * set kernel has no plain-weight path, and the caller runs cm_mlp_policy_forward per member.
+ *
+ * cm_mlp_policy_forward_multi: the launch.  `shape` = any member's weights (dims and masks; its weight pointers are not read),
+ * table_dev = the uploaded image, n_wg / n_envs / groups / n_act / agents_per_env = the planner's; every other argument is
+ * cm_mlp_policy_forward's over the whole batch.  No allocation, copy or synchronisation: it can be captured in a hipGraph.  The
+ * kernel trusts the table.  Returns 0 when launched, < 0 on a bad argument, and 1 - nothing launched - when `shape` has no
+ * mfma_pack. */
+typedef struct cm_mlp_set_member {       /* 4 * 4 + 2 * CM_MLP_MAX_LAYERS * 8 = 112 bytes */
+    int32_t first_row, n_rows;           /* the member's rows of x */
+    int32_t first_env, _pad;             /* its first env: first_row * groups == first_env * agents_per_env */
+    const float *b[CM_MLP_MAX_LAYERS];   /* biases: in the member's flat weight copy; NULL = none / past n_layers */
+    const float *pack[CM_MLP_MAX_LAYERS];/* each layer's B fragments inside the member's cm_mlp_pack output */
+} cm_mlp_set_member;
+int64_t cm_mlp_forward_multi_plan(const cm_mlp_weights *members, const int32_t *group_sizes /* envs */, int32_t n_policies,
+                                  int32_t n_envs, int32_t groups, int32_t n_act, int32_t agents_per_env, void *image,
+                                  size_t image_bytes, int32_t *n_wg);
+int cm_mlp_policy_forward_multi(const cm_mlp_weights *shape, const void *table_dev, int32_t n_wg, int32_t n_envs,
+                                int32_t groups, int32_t n_act, int32_t agents_per_env, const float *x, const float *avail,
+                                uint64_t seed, int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base,
+                                int32_t greedy, int32_t *actions, float *probs, void *stream);
 /* GaussianMLPBaseline.forward mean (com_marl/torch/baselines/gaussian_mlp_baseline.py:100-115): the last layer has
  * one output; values [rows]. */
 int cm_mlp_value_forward(const cm_mlp_weights *w, int32_t rows, const float *x, float *values, void *stream);

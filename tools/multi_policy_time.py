@@ -6,8 +6,12 @@
   3. (`co`) the loop form on Coverage map20 (teams of 24, 2048 envs): per-step time of one policy and of a PolicySet with K in
      {1, 4, 16, 64} equal groups - every member's forward in one cm_policy_forward_multi launch where the library has it, else
      one cm_policy_forward per member - 50-step chunks, stepped eagerly and replayed from a hipGraph, the list run twice; and
-     the wall time of eval_models_co with K = 16.
-`python tools/multi_policy_time.py [pp|co]` runs one part, no argument all of them."""
+     the wall time of eval_models_co with K = 16;
+  4. (`obsdp`, `cent`) the loop form with Obs-DP / CENT policies on PP map10 (teams of 4, 4096 envs): per-step time of one policy
+     and of a PolicySet with K in {1, 4, 16, 64} equal groups - every member's forward in one cm_mlp_policy_forward_multi launch
+     where the library has it, else one cm_mlp_policy_forward per member - 50-step chunks, eager and from a hipGraph, the list
+     run twice; and the wall time of eval_models with K = 16.
+`python tools/multi_policy_time.py [pp|co|obsdp|cent]` runs one part, no argument all of them."""
 import os
 import sys
 import time
@@ -103,6 +107,37 @@ def co_main():
         print(f"[{rep}] eval_models_co K={K} x {EP} episodes ({T} steps, {K * EP} envs): {time.perf_counter() - t0:.3f} s", flush=True)
 
 
+def mlp_main(kind):
+    env = E.GridEnvBatch("pp", PARAMS, B, device="cuda:0", seed=3)
+    spec = E.EnvSpec(E._Box(np.zeros(env.N * env.d), np.ones(env.N * env.d)), E._Discrete(5))
+    cls = nets.DecCategoricalMLPPolicy if kind == "obsdp" else nets.CentralizedCategoricalMLPPolicy
+    pols = []
+    for k in range(64):
+        torch.manual_seed(k)
+        p = cls(spec, n_agents=env.N, device="cuda:0")
+        p.set_rng(3)
+        pols.append(p)
+    engines = [("one policy", RolloutEngine(env, pols[0], H))]
+    for K in (1, 4, 16, 64):
+        engines.append((f"PolicySet, K={K}", RolloutEngine(env, nets.PolicySet(pols[:K]), H, groups=[B // K] * K)))
+    for rep in range(2):
+        for name, eng in engines:
+            eager, graph = loop_step_us(eng, False), loop_step_us(eng, True)
+            print(f"[{rep}] pp_map10 {kind:5s} {name:18s} forward={getattr(eng, 'multi_forward', None) or '-':6s} eager {eager:8.2f}  "
+                  f"graph {graph:8.2f} us per step ({B} envs, {H}-step chunks)", flush=True)
+    del engines
+
+    K, EP, T = 16, B // 16, 50
+    wrap = lambda: E.PredatorPreyWrapper(True, params=PARAMS, n_envs=K * EP, device="cuda:0", seed=3)  # noqa: E731
+    eval_models(wrap(), pols[:K], 0, n_eval_episodes=EP, max_env_steps=T)                # warm-up on a wrapper of its own
+    for rep in range(2):
+        w = wrap()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eval_models(w, pols[:K], 0, n_eval_episodes=EP, max_env_steps=T)
+        print(f"[{rep}] eval_models {kind} K={K} x {EP} episodes ({T} steps, {K * EP} envs): {time.perf_counter() - t0:.3f} s", flush=True)
+
+
 def main():
     env = E.GridEnvBatch("pp", PARAMS, B, device="cuda:0", seed=3)
     pols = policies(env.d, 256)
@@ -142,3 +177,6 @@ if __name__ == "__main__":
         main()
     if part in ("co", "all"):
         co_main()
+    for kind in ("obsdp", "cent"):
+        if part in (kind, "all"):
+            mlp_main(kind)

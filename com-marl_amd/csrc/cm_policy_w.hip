@@ -27,7 +27,7 @@ template <int LHOPS, int HEADK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void train_fwd_w_kernel(FwdArgs a, WeightsW w, int n_blk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_w[];
     stage_w<LHOPS>(w, lds_w, thread_x());
-    ResidentW res{};
+    ResidentW<> res{};
     if constexpr (HEADK == 0) res.fetch<LHOPS>(w, thread_x() & 63);      // (the critic's head has no register-resident layer)
     __syncthreads();
     for (int blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {

@@ -21,10 +21,12 @@
 //     whose B operand is the lane's own coefficient row (zero off the block diagonal) and whose result is again
 //     "features 16 ct + 4 g + r of row c": bias, tanh, residual and the head follow in place.
 // Weights: all four waves of a workgroup (16 envs, ONE workgroup per CU = one wave per SIMD at 4096 envs) read their A
-// operands from LDS, where the operand pack is staged once per launch (128 KB; the last three head layers, 44 KB, overlay
-// the encoder's slots once every wave has left the encoder).  Arithmetic: the f16-split scheme of cm_policy_h_dev.h
+// operands from LDS, where the operand pack is staged once per launch and never written again (pack_w: every LDS-resident layer
+// has a slot of its own; the 128 -> 64 head layer lives in registers, ResidentW).  Arithmetic: the f16-split scheme of cm_policy_h_dev.h
 // (x = hi + 2^-12 lo, three MFMAs per block), f32-grade; pinned by the same reference fixtures at 1e-5.
 #pragma once
+#include <type_traits>
+
 #include "cm_policy_h_dev.h"
 
 namespace cm {
@@ -93,6 +95,11 @@ template <int KB> struct Act { v8h hi[KB], lo[KB]; };
 template <int KB, int CT>
 struct Frags {
     v8h h[CT][KB], l[CT][KB];
+    // TAG: nothing but a separate instance of this function for the LEAN tile (policy_tile_w).  The compiler propagates constants and
+    // ranges over ALL call sites of a helper before it inlines it, so a caller that passes other arguments (a global pointer where the
+    // others pass LDS, a lane out of a closure) changes the code of every other kernel of the unit; with an instance of their own the
+    // lean builds leave the generic builds' instruction streams exactly what they were (python -m tests.isa diff).
+    template <int TAG = 0>
     __device__ __forceinline__ void fetch(const uint4 *W, int lane) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -106,6 +113,25 @@ struct Frags {
         __builtin_amdgcn_sched_barrier(0);
     }
 };
+
+// A layer's accumulator start values (bias, features 16 ct + 4 g + r) in registers.  LDS answers in order: read next to its first MFMA,
+// a bias float4 queues behind the whole look-ahead batch of the NEXT layer's fragments; fetch() goes in front of that batch, and
+// the barrier keeps it there.  fetch<C0>() reads tiles C0 .. CT - 1 only.  ON false: nothing is read here, the layer reads its biases
+// where it always did.
+template <int CT, bool ON>
+struct BiasR {
+    v4f b[ON ? CT : 1];
+    template <int C0 = 0>
+    __device__ __forceinline__ void fetch(const float *bias, int g) {
+        if constexpr (ON) {
+#pragma unroll
+            for (int ct = C0; ct < CT; ++ct) { const float4 v = *reinterpret_cast<const float4 *>(bias + 16 * ct + 4 * g); b[ct] = (v4f){ v.x, v.y, v.z, v.w }; }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    __device__ __forceinline__ const v4f *regs() const { return ON ? b : nullptr; }
+};
+struct NoHook { __device__ __forceinline__ void operator()() const {} };
 
 // ---- epilogue arithmetic, written STAGE-WISE over small arrays: with one wave per SIMD a dependent instruction costs ~1.7x
 // an independent one (and a transcendental twice a plain one), so every stage below is N independent instructions ----------
@@ -174,19 +200,23 @@ __device__ __forceinline__ void split_stage(const float (&y)[N], h16 (&h)[N], h1
 // [CT] (the embedding E, which the residual needs again).
 // sv (may be null): this lane's row of a [rows][16 CT] f32 matrix that receives the layer's output (training forward: what the
 // backward pass reads back) - features 16 ct + 4 g .. + 3 of row c are one 16-byte store.
-template <int KB, int CT, bool TANH, bool BIAS, int SPLIT = SPLIT_DEFAULT>
+// PB0: the accumulators of tiles ct >= PB0 start from pb[ct] (BiasR, read ahead) instead of a read of `bias` here.  mid(): called once in front of the
+// MFMAs of the middle tile pair (what the caller wants requested while this layer's second half runs).
+template <int KB, int CT, bool TANH, bool BIAS, int SPLIT = SPLIT_DEFAULT, int PB0 = CT, class MID = NoHook>
 __device__ __forceinline__ void dense_act(const Frags<KB, CT> &f, const float *bias, const Act<KB> &x, Act<CT / 2> &y, v4f *keep, int lane,
-                                          float *sv = nullptr) {
+                                          float *sv = nullptr, const v4f *pb = nullptr, MID mid = MID{}) {
     const int g = lane >> 4;
     const v4f zero = (v4f){ 0.f, 0.f, 0.f, 0.f };
     v4f acc[CT];
 #pragma unroll
     for (int p = 0; p <= CT / 2; ++p) {
+        if constexpr (!std::is_same<MID, NoHook>::value) { if (p == CT / 4) mid(); }
         if (p < CT / 2) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int ct = 2 * p + t;
-                if (BIAS) { const float4 b = *reinterpret_cast<const float4 *>(bias + 16 * ct + 4 * g); acc[ct] = (v4f){ b.x, b.y, b.z, b.w }; }
+                if (BIAS && ct >= PB0) acc[ct] = pb[ct];
+                else if (BIAS) { const float4 b = *reinterpret_cast<const float4 *>(bias + 16 * ct + 4 * g); acc[ct] = (v4f){ b.x, b.y, b.z, b.w }; }
 #pragma unroll
                 for (int q = 0; q < KB; ++q) {
                     const v4f a0 = (q == 0 && !BIAS) ? zero : acc[ct];
@@ -219,14 +249,15 @@ __device__ __forceinline__ void dense_act(const Frags<KB, CT> &f, const float *b
 
 // The same product with the operands swapped (non-transposed form): out[ct][r] = row 4 g + r, feature 16 ct + c, joined f32 - H.Wg
 // for the aggregation; and the plain transposed form returning f32 (the logits).
-template <int KB, int CT, bool SWAP, bool BIAS>
-__device__ __forceinline__ void dense_f32(const Frags<KB, CT> &f, const float *bias, const Act<KB> &x, v4f (&out)[CT], int lane) {
+template <int KB, int CT, bool SWAP, bool BIAS, bool PREB = false>
+__device__ __forceinline__ void dense_f32(const Frags<KB, CT> &f, const float *bias, const Act<KB> &x, v4f (&out)[CT], int lane, const v4f *pb = nullptr) {
     const int g = lane >> 4;
     const v4f zero = (v4f){ 0.f, 0.f, 0.f, 0.f };
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
         v4f acc = zero;
-        if (BIAS) { const float4 b = *reinterpret_cast<const float4 *>(bias + 16 * ct + 4 * g); acc = (v4f){ b.x, b.y, b.z, b.w }; }
+        if constexpr (BIAS && PREB) acc = pb[ct];
+        else if (BIAS) { const float4 b = *reinterpret_cast<const float4 *>(bias + 16 * ct + 4 * g); acc = (v4f){ b.x, b.y, b.z, b.w }; }
 #pragma unroll
         for (int q = 0; q < KB; ++q) {
             if (!SWAP) {
@@ -267,12 +298,31 @@ __device__ __forceinline__ void stage_w(const WeightsW &w, unsigned char *lds, i
     }
 }
 
-// the register-resident layer (128 -> 64 of the head): fetched once per wave, from the pack in global memory
+// the register-resident layer (128 -> 64 of the head): fetched once per wave, from the pack in global memory.
+// LEAN (the map-10 rollout builds, see policy_tile_w): the two small head layers behind it (64 -> 32 -> logits) as well - 48 more
+// AGPRs for the life of the wave, 12 ds_read_b128 fewer per step, and 48 VGPRs out of the head's live set.
+template <bool LEAN = false>
 struct ResidentW {
     Frags<4, 4> h2;
+    struct None {};
+    std::conditional_t<LEAN, Frags<2, 2>, None> h3;
+    std::conditional_t<LEAN, Frags<1, 2>, None> h4;
+    // the resident copy where there is one, else the caller's own (read from LDS)
+    template <class R, class F>
+    static __device__ __forceinline__ const F &pick(const R &resident, const F &own) { if constexpr (LEAN) return resident; else return own; }
     template <int LHOPS>
     __device__ __forceinline__ void fetch(const WeightsW &w, int lane) {
-        h2.fetch(w.pack + pack_w(LHOPS).h2, lane);
+        h2.template fetch<LEAN>(w.pack + pack_w(LHOPS).h2, lane);
+        if constexpr (LEAN) {
+            h3.template fetch<LEAN>(w.pack + pack_w(LHOPS).h3, lane);
+            h4.template fetch<LEAN>(w.pack + pack_w(LHOPS).h4, lane);
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) { asm volatile("" : "+a"(h3.h[ct][q])); asm volatile("" : "+a"(h3.l[ct][q])); }
+                asm volatile("" : "+a"(h4.h[ct][0])); asm volatile("" : "+a"(h4.l[ct][0]));
+            }
+        }
         // 128 registers that live for the whole launch: the allocator parks them in AGPRs either way, and left to itself copies
         // each one back (v_accvgpr_read_b32) in front of the MFMA that takes it, every step.  Defined in AGPRs they stay there
         // and the MFMA names them directly (a gfx950 MFMA reads its A / B operands from either file).
@@ -299,10 +349,21 @@ struct ResidentW {
 struct StepOff { uint32_t actions, probs, attn; };
 template <class T>
 __device__ __forceinline__ T *at32(T *base, uint32_t elem) { return reinterpret_cast<T *>(reinterpret_cast<char *>(base) + (uint32_t)(elem * (uint32_t)sizeof(T))); }
-template <int LHOPS, bool OBS_LDS = false, bool TRAIN = false, int HEADK = 0, bool STEP32 = false>
-__device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const ResidentW &res, const unsigned char *lds, int blk,
+// LEAN (the map-10 rollout builds): the same arithmetic with a lower register peak and LDS reads that queue behind nothing they do
+// not need -
+//   * h3 / h4 come from the resident AGPRs (ResidentW<true>) instead of two more fragment batches from LDS;
+//   * the look-ahead batches of e2 and of the attention layer are requested at the MIDDLE of the layer that runs meanwhile (e1, e2)
+//     instead of in front of it: the first half's fragments are dead by then, and half a layer still covers the reads;
+//   * every layer's biases are read in front of the fragment batch that would otherwise queue ahead of them: e1 / e2 tiles of the
+//     second half in front of the batch at the layer's middle (the first half's reads have only the layer's own fragments ahead),
+//     the hop biases and b1 in front of the hop's batch, b2 / b3 / b4 (no batch left to hide behind) at the middle of x1.
+template <int LHOPS, bool OBS_LDS = false, bool TRAIN = false, int HEADK = 0, bool STEP32 = false, bool LEAN = false>
+__device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const ResidentW<LEAN> &res, const unsigned char *lds, int blk,
                                               int32_t *act_lds, int obs_row = 0, const StepOff so = StepOff{}) {
     static_assert(!STEP32 || (!TRAIN && HEADK == 0), "step offsets: the acting forward of the rollout");
+    static_assert(!LEAN || (!TRAIN && HEADK == 0), "the lean tile: the acting forward of the rollout");
+    constexpr int E1H = LEAN ? 4 : 8, E2H = LEAN ? 2 : 4;       // first e1 / e2 tile whose bias is read ahead (at the layer's middle)
+    constexpr int PB_H2 = LEAN ? 0 : 4, PB_H3 = LEAN ? 0 : 2;    // h2 / h3: every tile's bias read ahead (0), or none (the tile count)
     static_assert(HEADK == 0 || TRAIN, "the critic head exists as training forward only");
     static_assert(LHOPS >= 1 && LHOPS <= 2, "wave-owned forward: one or two hops");
     const int tid = thread_x(), wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
@@ -341,16 +402,26 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     const uint32_t draw_step = a.policy_step + (a.step_base ? *a.step_base : 0u);
 
     // ---- encoder (every layer's fragments are fetched while the layer before it runs) ----
-    Frags<1, 8> f_e1; f_e1.fetch(WL + pk.enc1, lane);
-    Frags<4, 4> f_e2; f_e2.fetch(WL + pk.enc2, lane);
+    Frags<1, 8> f_e1; f_e1.template fetch<LEAN>(WL + pk.enc1, lane);
+    BiasR<8, LEAN> r_e1;
+    Frags<4, 4> f_e2;
+    if constexpr (!LEAN) f_e2.template fetch<LEAN>(WL + pk.enc2, lane);
     auto sv_row = [&](float *base, int width) -> float * { return (TRAIN && base && rv) ? base + grow * (size_t)width : nullptr; };
     Act<4> a1;
-    dense_act<1, 8, true, true>(f_e1, BL + bm.e1, xo, a1, nullptr, lane, sv_row(a.sv_a1, EH));
-    Frags<2, 4> f_at; f_at.fetch(WL + pk.attn, lane);
+    if constexpr (LEAN)
+        dense_act<1, 8, true, true, SPLIT_DEFAULT, E1H>(f_e1, BL + bm.e1, xo, a1, nullptr, lane, nullptr, r_e1.regs(),
+                                                        [&] { r_e1.template fetch<E1H>(BL + bm.e1, g); f_e2.template fetch<LEAN>(WL + pk.enc2, lane); });
+    else dense_act<1, 8, true, true>(f_e1, BL + bm.e1, xo, a1, nullptr, lane, sv_row(a.sv_a1, EH));
+    BiasR<4, LEAN> r_e2;
+    Frags<2, 4> f_at;
+    if constexpr (!LEAN) f_at.template fetch<LEAN>(WL + pk.attn, lane);
     v4f E[4];
     Act<2> xe;
-    dense_act<4, 4, true, true>(f_e2, BL + bm.e2, a1, xe, E, lane, sv_row(a.sv_e, EMB));
-    Frags<2, 4> f_g; f_g.fetch(WL + pk.gcn, lane);
+    if constexpr (LEAN)
+        dense_act<4, 4, true, true, SPLIT_DEFAULT, E2H>(f_e2, BL + bm.e2, a1, xe, E, lane, nullptr, r_e2.regs(),
+                                                        [&] { r_e2.template fetch<E2H>(BL + bm.e2, g); f_at.template fetch<LEAN>(WL + pk.attn, lane); });
+    else dense_act<4, 4, true, true>(f_e2, BL + bm.e2, a1, xe, E, lane, sv_row(a.sv_e, EMB));
+    Frags<2, 4> f_g; f_g.template fetch<LEAN>(WL + pk.gcn, lane);
     CM_WPROBE(3);
 
     // ---- attention: Q = E.Wa^T, scores^T = E.Q^T, softmax row in the diagonal lanes ----
@@ -381,6 +452,10 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     // ---- hops: H_{l+1} = tanh(A_l.(H_l.Wg_l) + b_l), A_l = M * Range * Chan_l renormalised (comm_base_net.py:99-105) ----
     Act<2> xh = xe;
     Frags<2, HEADK == 0 ? 8 : 4> f_x1;                          // first head layer: policy 64 -> 128, critic 64 -> 64
+    BiasR<8, LEAN> r_b1;                                       // the policy head's biases (LEAN: never with the critic head)
+    BiasR<4, LEAN> r_b2;
+    BiasR<2, LEAN> r_b3;
+    BiasR<2, LEAN> r_b4;
 #pragma unroll
     for (int l = 0; l < LHOPS; ++l) {
         v4f hw[4];                                             // H.Wg_l: rows 4 g + r, feature 16 ct + c
@@ -396,8 +471,12 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
                     for (int r = 0; r < 4; ++r) dst[(size_t)r * EMB + 16 * ct] = hw[ct][r] * (1.0f / TANH_PRESCALE);
             }
         }
-        if (l + 1 < LHOPS) f_g.fetch(WL + pk.gcn + (l + 1) * frag_u4(EMB, EMB), lane);
-        else f_x1.fetch(WL + pk.x1, lane);
+        BiasR<4, LEAN> r_g; r_g.fetch(BL + bm.g + l * EMB, g);
+        if (l + 1 < LHOPS) f_g.template fetch<LEAN>(WL + pk.gcn + (l + 1) * frag_u4(EMB, EMB), lane);
+        else {
+            r_b1.fetch(BL + bm.b1, g);
+            f_x1.template fetch<LEAN>(WL + pk.x1, lane);
+        }
         float cf[4], den = 0.0f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -432,8 +511,10 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
         v4f acc[4];
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
-            const float4 b = *reinterpret_cast<const float4 *>(BL + bm.g + l * EMB + 16 * ct + 4 * g);
-            acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], bl, (v4f){ b.x, b.y, b.z, b.w }, 0, 0, 0);
+            v4f b0;
+            if constexpr (LEAN) b0 = r_g.b[ct];
+            else { const float4 b = *reinterpret_cast<const float4 *>(BL + bm.g + l * EMB + 16 * ct + 4 * g); b0 = (v4f){ b.x, b.y, b.z, b.w }; }
+            acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], bl, b0, 0, 0, 0);
             acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(al[ct], bh, acc[ct], 0, 0, 0);
             acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], bh, acc[ct], 0, 0, 0);
         }
@@ -463,7 +544,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     CM_WPROBE(6);
     if constexpr (HEADK == 1) {
         // ---- critic head: 64 -> 64 (tanh) -> 1 (comm_base_critic.py:110-112), value of row c in the lanes g == 0 ----
-        Frags<2, 1> f_d2; f_d2.fetch(WL + pk.h3, lane);
+        Frags<2, 1> f_d2; f_d2.template fetch<LEAN>(WL + pk.h3, lane);
         Act<2> xd;
         dense_act<2, 4, true, true>(f_x1, BL + bm.b1, xh, xd, nullptr, lane, sv_row(a.sv_x1, EMB));
         v4f val[1];
@@ -477,9 +558,15 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     } else {
     // ---- head: 64 -> 128 -> 64 (resident fragments) -> 32 -> logits ----
     Act<4> x1;
-    dense_act<2, 8, true, true>(f_x1, BL + bm.b1, xh, x1, nullptr, lane, sv_row(a.sv_x1, H1));
-    Frags<2, 2> f_h3; f_h3.fetch(WL + pk.h3, lane);
-    Frags<1, 2> f_h4; f_h4.fetch(WL + pk.h4, lane);
+    if constexpr (LEAN) {
+        dense_act<2, 8, true, true, SPLIT_DEFAULT, 0>(f_x1, BL + bm.b1, xh, x1, nullptr, lane, nullptr, r_b1.regs(),
+                                                      [&] { r_b2.fetch(BL + bm.b2, g); r_b3.fetch(BL + bm.b3, g); r_b4.fetch(BL + bm.b4, g); });
+    } else dense_act<2, 8, true, true>(f_x1, BL + bm.b1, xh, x1, nullptr, lane, sv_row(a.sv_x1, H1));
+    Frags<2, 2> f_h3_lds;
+    Frags<1, 2> f_h4_lds;
+    if constexpr (!LEAN) { f_h3_lds.template fetch<LEAN>(WL + pk.h3, lane); f_h4_lds.template fetch<LEAN>(WL + pk.h4, lane); }
+    const Frags<2, 2> &f_h3 = res.pick(res.h3, f_h3_lds);
+    const Frags<1, 2> &f_h4 = res.pick(res.h4, f_h4_lds);
     // the sampler's uniforms do not depend on the logits
     float u = 0.0f;
     if constexpr (!TRAIN) {
@@ -488,11 +575,11 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     }
     CM_WPROBE(7);
     Act<2> x2;
-    dense_act<4, 4, true, true>(res.h2, BL + bm.b2, x1, x2, nullptr, lane, sv_row(a.sv_x2, H2));
+    dense_act<4, 4, true, true, SPLIT_DEFAULT, PB_H2>(res.h2, BL + bm.b2, x1, x2, nullptr, lane, sv_row(a.sv_x2, H2), r_b2.regs());
     Act<1> x3;
-    dense_act<2, 2, true, true>(f_h3, BL + bm.b3, x2, x3, nullptr, lane, sv_row(a.sv_x3, H3));
+    dense_act<2, 2, true, true, SPLIT_DEFAULT, PB_H3>(f_h3, BL + bm.b3, x2, x3, nullptr, lane, sv_row(a.sv_x3, H3), r_b3.regs());
     v4f lg[2];
-    dense_f32<1, 2, false, true>(f_h4, BL + bm.b4, x3, lg, lane);    // lanes g == 0: logits 0..3 in lg[0], logit 4 in lg[1][0]
+    dense_f32<1, 2, false, true, LEAN>(f_h4, BL + bm.b4, x3, lg, lane, r_b4.regs());    // lanes g == 0: logits 0..3 in lg[0], logit 4 in lg[1][0]
 
     CM_WPROBE(9);
     // ---- softmax x avail, renormalise, sample / argmax (categorical_mlp_module.py:64-80): the 16 lanes with g == 0 ----
@@ -554,7 +641,7 @@ __device__ __forceinline__ void fwd_body_w(const FwdArgs &a, const WeightsW &w, 
     const int tid = thread_x();
     CM_WPROBE(0);
     stage_w<LHOPS>(w, lds, tid);
-    ResidentW res;
+    ResidentW<> res;
     res.fetch<LHOPS>(w, tid & 63);
     CM_WPROBE(1);
     __syncthreads();

@@ -37,8 +37,8 @@
     const bool probe = PROBES && p.stop == -2 && blockIdx.x == 0 && thread_x() == 0;
     const unsigned long long t_in = probe ? __builtin_amdgcn_s_memtime() : 0ull;
     mw::stage_w<LHOPS>(w, lds_w, thread_x());
-    mw::ResidentW res;
-    res.fetch<LHOPS>(w, thread_x() & 63);
+    mw::ResidentW<SHAPE == 1> res;
+    res.template fetch<LHOPS>(w, thread_x() & 63);
     __syncthreads();                                                     // the only workgroup barrier of the launch
     if (probe) { g_w_probe[3] = __builtin_amdgcn_s_memtime() - t_in; g_w_probe[0] = g_w_probe[1] = g_w_probe[2] = g_w_probe[4] = 0; }
     const int envs = FULLWG ? mw::WG_ENVS : min(mw::WG_ENVS, a.S - (int)blockIdx.x * mw::WG_ENVS);
@@ -90,7 +90,7 @@
         const unsigned long long t0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
         if constexpr (PRE && !CARRY) pre = env_prefetch<CM_PP, LPE>(p, b_raw, live);   // env state requested in front of the policy forward
         if constexpr (SHAPE == 1)
-            mw::policy_tile_w<LHOPS, true, false, 0, true>(at, n_act, res, lds_w, blockIdx.x, act, obs_row,
+            mw::policy_tile_w<LHOPS, true, false, 0, true, true>(at, n_act, res, lds_w, blockIdx.x, act, obs_row,
                                                            mw::StepOff{ ut * (uint32_t)c.actions, ut * (uint32_t)c.probs, ut * (uint32_t)c.attn });
         else mw::policy_tile_w<LHOPS, CARRY>(at, n_act, res, lds_w, blockIdx.x, act, obs_row);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's action words are in LDS

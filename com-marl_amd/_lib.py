@@ -55,6 +55,14 @@ class CriticWeights(C.Structure):
                                   "dec_b1", "dec_w2t", "dec_b2", "mfma_pack")]
 
 
+class NetWeights(C.Structure):
+    """cm_net_weights: a Comm-DP policy of any layer sizes (cm_policy_forward_any)."""
+    _fields_ = [(n, C.c_int32) for n in ("d", "n_agents", "n_hops", "n_act", "no_residual", "emb", "n_enc")] + [
+        ("enc_hidden", C.c_int32 * 3), ("n_head", C.c_int32), ("head_hidden", C.c_int32 * 4), ("_pad", C.c_int32),
+        ("enc_wt", C.c_void_p * 4), ("enc_b", C.c_void_p * 4), ("attn_wt", C.c_void_p), ("gcn_w", C.c_void_p),
+        ("gcn_b", C.c_void_p), ("head_wt", C.c_void_p * 5), ("head_b", C.c_void_p * 5)]
+
+
 class ChunkStrides(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("obs", "actions", "probs", "attn", "reward", "reward_f64", "done", "details",
                                          "dist_adj", "channels", "prey_alive", "success", "path_len")]
@@ -118,6 +126,9 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_critic_forward": (C.c_int, [C.POINTER(CriticWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "cm_policy_forward_any": (C.c_int, [C.POINTER(NetWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_rollout_step": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(RngTape), C.POINTER(StepOut), C.c_void_p]),

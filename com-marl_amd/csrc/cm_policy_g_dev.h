@@ -1,0 +1,273 @@
+// cm_policy_g_dev.h - device side of the run-time-sized Comm-DP policy forward (cm_policy_g.hip).
+//
+// One 256-thread workgroup owns EPB whole envs (rows = EPB * N agent rows, padded to R16 = a multiple of 16) and carries
+// them from the observation load to the sampled action.  LDS map (floats; every plane base and stride a multiple of 4):
+//   E  [R16][SE]   encoder output                      H  [R16][SE]   hop output, then the head's input x
+//   P0 [R16][SW]   ping   } as wide as the widest      P1 [R16][SW]   pong  (the staged observation starts here)
+//   M  [rows][NP]  attention softmax                   A  [rows][NP]  masked, row-renormalised attention of the hop
+// Every dense layer is v_mfma_f32_16x16x4_f32 (exact f32) with the lane maps of cm_mlp_body.h: lane group g = lane >> 4
+// supplies k = 16*kq + 4*g + j at MFMA (kq, j), so a lane's four A words are one 16-byte LDS read; B comes straight from
+// the [in,out] weights with the ragged edge zeroed by predicate.  The whole LDS tile is zeroed first, so what a padded
+// k-slot or row reads is finite and meets a zero weight.  LDS is addressed by integer offsets into one array; there is
+// no dynamically indexed local array (layer loops are unrolled over the argument block's fixed slots).
+#pragma once
+#include "cm_internal.h"
+#include "cm_rng.h"
+
+namespace cm {
+namespace pg {
+
+constexpr int TPB = 256, MAX_ENC = 3, MAX_HEAD = 4, MAX_W = 128, MAX_ACT = 8;
+constexpr size_t LDS_LIMIT = 160 * 1024;
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+struct Args {
+    int S, N, d, L, A, emb, no_residual;
+    int n_enc, enc_h[MAX_ENC];
+    int n_head, head_h[MAX_HEAD];
+    int EPB, R16, SE, SW, NP;                     // the launch plan (plan())
+    const float *enc_w[MAX_ENC], *enc_b[MAX_ENC], *enc_wo, *enc_bo;
+    const float *attn_wt, *gcn_w, *gcn_b;
+    const float *head_w[MAX_HEAD], *head_b[MAX_HEAD], *head_wo, *head_bo;
+    const float *obs, *avail, *adj, *chan;
+    uint32_t key0, key1, policy_step;
+    const uint32_t *step_base;
+    int env_id_offset, greedy;
+    int32_t *actions;
+    float *probs, *attn;
+};
+
+// The one place the LDS need is computed: the "fits" test and the launch both read it.
+struct Plan { int EPB, R16, SE, SW, NP; size_t lds_bytes; };
+
+__host__ inline int pad16(int x) { return (x + 15) & ~15; }
+
+__host__ inline Plan plan(int N, int d, int emb, int widest) {
+    Plan p;
+    // max(1, 48 / N) whole envs for EVERY team size: 25-48 rows for teams up to 24, one env per workgroup above that.  (cm_policy.hip's
+    // pick_epb gives 1 when N is no multiple of its 4-row register tile; MFMA tiles may straddle envs here, so no such rule.)
+    p.EPB = 48 / N > 0 ? 48 / N : 1;
+    p.R16 = pad16(p.EPB * N);
+    p.SE = pad16(emb) + 4;                        // +4 keeps float4 alignment and staggers the banks
+    p.SW = pad16(widest > d ? widest : d) + 4;
+    p.NP = N | 1;
+    const size_t mat = ((size_t)p.EPB * N * p.NP + 3) & ~(size_t)3;
+    p.lds_bytes = ((size_t)p.R16 * (2 * p.SE + 2 * p.SW) + 2 * mat) * sizeof(float);
+    return p;
+}
+
+__device__ __forceinline__ float fast_tanh(float x) {      // same form as cm_mlp.hip (abs err <= 2e-7)
+    const float t = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
+    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f);
+}
+
+// out[r][o] = act(sum_k in[r][k] Wt[k][o] + b[o]) for every row of the R16-row tile and every column of the 16-padded
+// width (padding columns come out as act(0) = 0).  Work items = (column tile, pair of row tiles), dealt to the 4 waves.
+template <bool TANH>
+__device__ __forceinline__ void dense(float *lds, int in, int in_s, int K, const float *__restrict__ Wt,
+                                      const float *__restrict__ bias, int OUT, int out, int out_s, int R16, int tid) {
+    const int wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+    const int nct = (OUT + 15) >> 4, k16 = (K + 15) >> 4, rtn = R16 >> 4, rp = (rtn + 1) >> 1;
+    for (int it = wave; it < nct * rp; it += 4) {
+        const int ct = it % nct, rt0 = (it / nct) * 2;
+        const bool two = rt0 + 1 < rtn;                      // wave-uniform
+        const int col = ct * 16 + c;
+        const int a0o = in + (rt0 * 16 + c) * in_s + 4 * g;
+        const int a1o = two ? a0o + 16 * in_s : a0o;
+        v4f acc0 = (v4f){ 0.f, 0.f, 0.f, 0.f }, acc1 = (v4f){ 0.f, 0.f, 0.f, 0.f };
+        for (int kq = 0; kq < k16; ++kq) {
+            const float4 x0 = *reinterpret_cast<const float4 *>(&lds[a0o + 16 * kq]);
+            const float4 x1 = *reinterpret_cast<const float4 *>(&lds[a1o + 16 * kq]);
+            const float xa[4] = { x0.x, x0.y, x0.z, x0.w }, xb[4] = { x1.x, x1.y, x1.z, x1.w };
+            float bw[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = 16 * kq + 4 * g + j;
+                bw[j] = (k < K && col < OUT) ? Wt[(size_t)k * OUT + col] : 0.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[j], bw[j], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[j], bw[j], acc1, 0, 0, 0);
+            }
+        }
+        const float bv = (bias && col < OUT) ? bias[col] : 0.0f;
+        const int o0 = out + (rt0 * 16 + 4 * g) * out_s + col;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float v = acc0[r] + bv;
+            lds[o0 + r * out_s] = TANH ? fast_tanh(v) : v;
+        }
+        if (two) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = acc1[r] + bv;
+                lds[o0 + (16 + r) * out_s] = TANH ? fast_tanh(v) : v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, N = a.N, d = a.d, L = a.L, NN = N * N, NP = a.NP, EM = a.emb;
+    const int SE = a.SE, SW = a.SW, R16 = a.R16;
+    const int s0 = blockIdx.x * a.EPB;
+    const int envs = min(a.EPB, a.S - s0);
+    const int rows = envs * N, rows_max = a.EPB * N;
+    const int mat = (rows_max * NP + 3) & ~3;
+    const int oE = 0, oH = oE + R16 * SE, oP0 = oH + R16 * SE, oP1 = oP0 + R16 * SW, oM = oP1 + R16 * SW, oA = oM + mat;
+    const int total = oA + mat;
+
+    // ---- zero the tile (16-byte stores), then stage the observations: coalesced HBM read of rows*d floats ----
+    for (int k = tid * 4; k < total; k += TPB * 4) *reinterpret_cast<float4 *>(&lds[k]) = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    {
+        const float *src = a.obs + (size_t)s0 * N * d;
+        const int n = rows * d;
+        for (int k = tid; k < n; k += TPB) { const int r = k / d, f = k - r * d; lds[oP1 + r * SW + f] = src[k]; }
+    }
+    __syncthreads();
+
+    // ---- encoder: n_enc tanh hidden layers, tanh output layer into E ----
+    int cur = oP1, nxt = oP0, K = d;
+#pragma unroll
+    for (int i = 0; i < MAX_ENC; ++i) {
+        if (i < a.n_enc) {
+            dense<true>(lds, cur, SW, K, a.enc_w[i], a.enc_b[i], a.enc_h[i], nxt, SW, R16, tid);
+            __syncthreads();
+            const int t = cur; cur = nxt; nxt = t;
+            K = a.enc_h[i];
+        }
+    }
+    dense<true>(lds, cur, SW, K, a.enc_wo, a.enc_bo, EM, oE, SE, R16, tid);
+    __syncthreads();
+
+    // ---- attention: Q = E.Wa ('general') or E ('dot'); scores = Q.E^T; softmax over j ----
+    int oQ = oE, sQ = SE;
+    if (a.attn_wt) {
+        dense<false>(lds, oE, SE, EM, a.attn_wt, nullptr, EM, oP0, SW, R16, tid);
+        __syncthreads();
+        oQ = oP0; sQ = SW;
+    }
+    for (int k = tid; k < envs * NN; k += TPB) {
+        const int e = k / NN, ij = k - e * NN, i = ij / N, j = ij - i * N;
+        const int q = oQ + (e * N + i) * sQ, kk = oE + (e * N + j) * SE;
+        float acc = 0.0f;
+        for (int x = 0; x < EM; ++x) acc = fmaf(lds[q + x], lds[kk + x], acc);
+        lds[oM + (e * N + i) * NP + j] = acc;
+    }
+    __syncthreads();
+    for (int r = tid; r < rows; r += TPB) {
+        const int m = oM + r * NP;
+        float mx = -INFINITY, sum = 0.0f;
+        for (int j = 0; j < N; ++j) mx = fmaxf(mx, lds[m + j]);
+        for (int j = 0; j < N; ++j) { const float ex = expf(lds[m + j] - mx); lds[m + j] = ex; sum += ex; }
+        for (int j = 0; j < N; ++j) lds[m + j] = lds[m + j] / sum;
+    }
+    __syncthreads();
+    if (a.attn) {                                       // attention_weights output [S,N,N]
+        float *dst = a.attn + (size_t)s0 * NN;
+        for (int k = tid; k < envs * NN; k += TPB) { const int r = k / N, j = k - r * N; dst[k] = lds[oM + r * NP + j]; }
+    }
+
+    // ---- L hops: A = M * adj * ch_l, row-renormalised; H' = tanh(A.(H.Wg_l) + b_l) ----
+    const int EP = (EM + 15) & ~15;
+    for (int l = 0; l < L; ++l) {
+        dense<false>(lds, l == 0 ? oE : oH, SE, EM, a.gcn_w + (size_t)l * EM * EM, nullptr, EM, oP0, SW, R16, tid);
+        for (int k = tid; k < envs * NN; k += TPB) {
+            const int e = k / NN, ij = k - e * NN, r = k / N, j = k - r * N;
+            float v = lds[oM + r * NP + j];
+            if (a.adj) v *= a.adj[(size_t)(s0 + e) * NN + ij];
+            if (a.chan) v *= a.chan[((size_t)(s0 + e) * L + l) * NN + ij];
+            lds[oA + r * NP + j] = v;
+        }
+        __syncthreads();
+        for (int r = tid; r < rows; r += TPB) {
+            const int ar = oA + r * NP;
+            float sum = 0.0f;
+            for (int j = 0; j < N; ++j) sum += lds[ar + j];
+            const float den = sum + 1e-12f;
+            for (int j = 0; j < N; ++j) lds[ar + j] = lds[ar + j] / den;
+        }
+        __syncthreads();
+        for (int k = tid; k < rows * EP; k += TPB) {
+            const int r = k / EP, o = k - r * EP, e = r / N;
+            const int ar = oA + r * NP, hw = oP0 + e * N * SW + o;
+            float acc = 0.0f;
+            for (int j = 0; j < N; ++j) acc = fmaf(lds[ar + j], lds[hw + j * SW], acc);
+            const float bv = (a.gcn_b && o < EM) ? a.gcn_b[(size_t)l * EM + o] : 0.0f;
+            lds[oH + r * SE + o] = o < EM ? fast_tanh(acc + bv) : 0.0f;
+        }
+        __syncthreads();
+    }
+    // ---- x = H_L (E when there are no hops) + E unless no_residual (comm_categorical_mlp_policy.py:74-77) ----
+    for (int k = tid; k < rows * EM; k += TPB) {
+        const int r = k / EM, o = k - r * EM;
+        const float ev = lds[oE + r * SE + o];
+        lds[oH + r * SE + o] = (L > 0 ? lds[oH + r * SE + o] : ev) + (a.no_residual ? 0.0f : ev);
+    }
+    __syncthreads();
+
+    // ---- head: n_head tanh hidden layers, linear logits ----
+    cur = oH; nxt = oP0; K = EM;
+    int cs = SE;
+#pragma unroll
+    for (int i = 0; i < MAX_HEAD; ++i) {
+        if (i < a.n_head) {
+            dense<true>(lds, cur, cs, K, a.head_w[i], a.head_b[i], a.head_h[i], nxt, SW, R16, tid);
+            __syncthreads();
+            cur = nxt; nxt = (nxt == oP0) ? oP1 : oP0; cs = SW;
+            K = a.head_h[i];
+        }
+    }
+    const int A = a.A;
+    dense<false>(lds, cur, cs, K, a.head_wo, a.head_bo, A, nxt, SW, R16, tid);
+    __syncthreads();
+
+    // ---- per-agent softmax * avail, renormalise, sample (same arithmetic order as cm_mlp_body.h) ----
+    for (int r = tid; r < rows; r += TPB) {
+        const int lg = nxt + r * SW;
+        float p[MAX_ACT];
+        float mx = -INFINITY, sum = 0.0f, msum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < MAX_ACT; ++k) if (k < A) mx = fmaxf(mx, lds[lg + k]);
+#pragma unroll
+        for (int k = 0; k < MAX_ACT; ++k) if (k < A) { p[k] = expf(lds[lg + k] - mx); sum += p[k]; }
+        const size_t flat = (size_t)s0 * N + r;             // global agent-row index
+#pragma unroll
+        for (int k = 0; k < MAX_ACT; ++k) if (k < A) {
+            const float av = a.avail ? a.avail[flat * A + k] : 1.0f;
+            p[k] = (p[k] / sum) * av; msum += p[k];
+        }
+#pragma unroll
+        for (int k = 0; k < MAX_ACT; ++k) if (k < A) p[k] = p[k] / msum;
+        if (a.probs) {
+#pragma unroll
+            for (int k = 0; k < MAX_ACT; ++k) if (k < A) a.probs[flat * A + k] = p[k];
+        }
+        if (a.actions) {
+            int act = 0;
+            if (a.greedy) {
+                float best = p[0];
+#pragma unroll
+                for (int k = 1; k < MAX_ACT; ++k) if (k < A && p[k] > best) { best = p[k]; act = k; }
+            } else {
+                const int e = r / N, i = r - e * N;
+                const u32x4 xr = philox4x32_10((uint32_t)(a.env_id_offset + s0 + e),
+                                               a.policy_step + (a.step_base ? *a.step_base : 0u), SITE_ACTION, (uint32_t)i,
+                                               a.key0, a.key1);
+                const float u = unit_f32(xr.x);
+                float acc = 0.0f;
+                int sel = -1, last = 0;
+#pragma unroll
+                for (int k = 0; k < MAX_ACT; ++k) if (k < A) { if (p[k] > 0.0f) last = k; acc += p[k]; if (sel < 0 && u < acc) sel = k; }
+                act = sel < 0 ? last : sel;
+            }
+            a.actions[flat] = act;
+        }
+    }
+}
+
+}  // namespace pg
+}  // namespace cm

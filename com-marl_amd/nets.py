@@ -137,7 +137,8 @@ class AttentionModule(nn.Module):
         q = self.linear_in(query) if self.attention_type == "general" else query
         if query.is_cuda and query.dim() == 3 and query.shape[-1] == 64 and query.shape[-2] <= MAX_KERNEL_AGENTS:
             return _AttentionSoftmax.apply(q, query)             # fused HIP op (cm_attention_forward/backward)
-        return torch.softmax(torch.matmul(q, query.transpose(-2, -1)), dim=-1)   # teams above 128 agents (maps >= 50): library GEMMs
+        # teams above 128 agents (maps >= 50) and embeddings other than 64 (--embedding_dim): library GEMMs, autograd backward
+        return torch.softmax(torch.matmul(q, query.transpose(-2, -1)), dim=-1)
 
 
 class GraphConvolutionModule(nn.Module):
@@ -312,9 +313,10 @@ def masked_aggregate(attn, dist_adj, channels, hop, hw, bias):
     """attn [S,N,N], dist_adj [S,N,N] or None (= ones), channels [S,L,N,N] or None, hw [S,N,E]."""
     if not hw.is_cuda:
         raise L.CommarlError("masked_aggregate is a HIP op: tensors must live on the MI355X (no CPU fallback)")
-    if hw.shape[1] > MAX_KERNEL_AGENTS:
-        # teams above 128 agents (PP map 50: N = 200): the N x N tile of one env no longer fits a workgroup's LDS - the same
-        # arithmetic (comm_base_net.py:101-103, graph_conv_module.py:63-70) on the framework's batched GEMM, still on the GPU
+    if hw.shape[1] > MAX_KERNEL_AGENTS or hw.shape[2] != 64:
+        # teams above 128 agents (PP map 50: N = 200): the N x N tile of one env no longer fits a workgroup's LDS; embeddings other
+        # than 64 (--embedding_dim): cm_masked_agg_* are built for 64 columns - the same arithmetic (comm_base_net.py:101-103,
+        # graph_conv_module.py:63-70) on the framework's batched GEMM, still on the GPU, autograd doing the backward
         A = attn
         if dist_adj is not None:
             A = A * dist_adj
@@ -369,7 +371,7 @@ def _fused_shape_ok(net, obs):
     # they keep the per-layer path.  Observations above 80 features have no matrix-core operand pack (kpad_of,
     # cm_policy_mfma_dev.h: cm_*_pack_bytes() == 0), without which the saved forward launches nothing
     return (obs.is_cuda and 1 <= net._n_agents <= MAX_FUSED_AGENTS and 1 <= len(net.gcn_layers) <= 4
-            and net._dec_obs_dim <= MAX_FUSED_OBS and len(net.encoder._layers) == 1
+            and net._dec_obs_dim <= MAX_FUSED_OBS and len(net.encoder._layers) == 1 and net._default_shape
             and os.environ.get("COMMARL_FUSED_TRAIN", "1") != "0" and os.environ.get("COMMARL_POLICY_KERNEL", "")[:1] not in ("f", "v"))
 
 
@@ -739,6 +741,27 @@ class CommBaseNet(_WeightPack, nn.Module):
         return E, H, M
 
     # -- weight pack for the fused C-ABI forward -----------------------------------------------
+    @property
+    def _default_shape(self):
+        """The reference's default layer sizes (env_uitils.py:84,140,182-192: 128 | 64 | head): the shape cm_policy_forward,
+        cm_critic_forward, the rollout kernels and the fused training forward are built for.  Every other shape
+        (--encoder_hidden_sizes, --embedding_dim, --categorical_mlp_hidden_sizes) runs on cm_policy_forward_any or layer by layer."""
+        return self._enc_hidden == (128,) and self._embedding_dim == 64 and self._head_hidden() == self._HEAD_DEFAULT
+
+    def _any_tensors(self):
+        """The flat weight copy of a net of any layer sizes (cm_net_weights): every linear weight transposed [in,out], layer by layer."""
+        t = OrderedDict()
+        for pre, mlp in (("enc", self.encoder), ("head", self._head_mlp())):
+            for i, lin in enumerate([l.linear for l in mlp._layers] + [mlp._output_layers[0].linear]):
+                t[f"{pre}_w{i}t"] = lin.weight.t()
+                t[f"{pre}_b{i}"] = lin.bias
+        # 'dot': Q = E, no weight at all (NULL)
+        t["attn_wt"] = self.attention_layer.linear_in.weight.t() if self.attention_layer.attention_type == "general" else None
+        t["gcn_w"] = _Stacked(g.weight for g in self.gcn_layers) if len(self.gcn_layers) else None
+        t["gcn_b"] = (_Stacked(g.bias for g in self.gcn_layers)
+                      if len(self.gcn_layers) and self.gcn_layers[0].bias is not None else None)
+        return t
+
     def _trunk_tensors(self):
         enc = self.encoder
         if len(enc._layers) != 1:
@@ -761,6 +784,8 @@ class CommBaseNet(_WeightPack, nn.Module):
         raise NotImplementedError
 
     def _pack_tensors(self):
+        if not self._default_shape:
+            return self._any_tensors()
         ts = self._trunk_tensors()
         ts.update(self._head_tensors())
         return ts
@@ -769,7 +794,7 @@ class CommBaseNet(_WeightPack, nn.Module):
         """(Re)build the matrix-core operand pack (cm_policy_pack / cm_critic_pack; `sections`: which parts) in its own
         persistent buffer: same address for the life of the net, so captured hipGraphs keep reading fresh weights."""
         dev = next(self.parameters()).device
-        if dev.type != "cuda":
+        if dev.type != "cuda" or not self._default_shape:    # (cm_policy_forward_any reads the plain [in,out] weights)
             return
         w = self._struct_from(ptrs)
         size_fn, pack_fn = (getattr(L.lib(), n) for n in self._mfma_fns)
@@ -797,7 +822,22 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         self._head_sizes = tuple(categorical_mlp_hidden_sizes)
         self.categorical_output_layer = MLPModule(embedding_dim, self._action_dim, categorical_mlp_hidden_sizes)
         self.seed, self.env_id_offset, self._policy_step = 1, 0, 0
+        # layer sizes other than the default: which acting forward act_device takes - "auto": one launch (cm_policy_forward_any)
+        # where it fits, else layer by layer; "layers": always layer by layer.  _last_forward says which one the last call took.
+        self._general_forward, self._last_forward = "auto", None
+        if not self._default_shape:
+            # the per-layer training path (framework GEMMs where the embedding is not 64, autograd's own adds everywhere) has not been
+            # run under the update's hipGraphs: every non-default net steps eagerly, as teams above 80 agents do
+            self._graph_capturable_update = False
         self.to(device)
+
+    _HEAD_DEFAULT = (128, 64, 32)
+
+    def _head_hidden(self):
+        return self._head_sizes
+
+    def _head_mlp(self):
+        return self.categorical_output_layer
 
     # -- autograd path (PPO update) --------------------------------------------------------------
     def _logits_flat(self, obs, adj, ch):
@@ -916,6 +956,9 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         if policy_step is None:
             policy_step = self._policy_step
             self._policy_step += 1
+        if not self._default_shape:
+            return self._act_device_any(obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
+                                        env_id_offset)
         if N > MAX_FUSED_AGENTS:
             return self._act_device_layers(obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
                                            env_id_offset)
@@ -930,12 +973,60 @@ class CommCategoricalMLPPolicy(CommBaseNet):
                 L.current_stream()), "cm_policy_forward")
         return actions, probs, attn
 
+    def _net_struct(self):
+        """cm_net_weights of this policy over its flat weight copy (any layer sizes)."""
+        if not (1 <= len(self._enc_hidden) <= 3 and 1 <= len(self._head_sizes) <= 4):
+            return None                                          # outside cm_policy_forward_any's layer counts: layer by layer
+        p = self._packed()
+        w = L.NetWeights()
+        w.d, w.n_agents, w.n_hops, w.n_act = self._dec_obs_dim, self._n_agents, len(self.gcn_layers), self._action_dim
+        w.no_residual, w.emb = 0 if self.residual else 1, self._embedding_dim
+        w.n_enc, w.n_head = len(self._enc_hidden), len(self._head_sizes)
+        for i, h in enumerate(self._enc_hidden):
+            w.enc_hidden[i] = h
+        for i, h in enumerate(self._head_sizes):
+            w.head_hidden[i] = h
+        for i in range(w.n_enc + 1):
+            w.enc_wt[i], w.enc_b[i] = p[f"enc_w{i}t"], p[f"enc_b{i}"]
+        for i in range(w.n_head + 1):
+            w.head_wt[i], w.head_b[i] = p[f"head_w{i}t"], p[f"head_b{i}"]
+        w.attn_wt, w.gcn_w, w.gcn_b = p["attn_wt"], p["gcn_w"], p["gcn_b"]
+        return w
+
+    def _act_device_any(self, obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset):
+        """Layer sizes other than the default: forward + sample in ONE launch of the run-time-sized kernel
+        (cm_policy_forward_any, csrc/cm_policy_g.hip); where it answers "not for this shape" (1: a workgroup's LDS need above
+        160 KB, more layers than it is written for) or the route is pinned (_general_forward = "layers"), layer by layer."""
+        if self._general_forward not in ("auto", "layers"):
+            raise ValueError(f"_general_forward must be 'auto' or 'layers', not {self._general_forward!r}")
+        N, d = self._n_agents, self._dec_obs_dim
+        S = obs.numel() // (N * d)
+        w = self._net_struct() if self._general_forward == "auto" else None
+        rc = 1
+        if w is not None:
+            with torch.cuda.device(obs.device):
+                rc = L.lib().cm_policy_forward_any(
+                    C.byref(w), S, L.ptr(obs), L.ptr(None if avail is None else avail.contiguous()),
+                    L.ptr(None if dist_adj is None else dist_adj.contiguous()),
+                    L.ptr(None if channels is None else channels.contiguous()), self.seed,
+                    self.env_id_offset if env_id_offset is None else int(env_id_offset),
+                    policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
+                    L.current_stream())
+        if rc == 1:
+            self._last_forward = "layers"
+            return self._act_device_layers(obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
+                                           env_id_offset)
+        L.check(rc, "cm_policy_forward_any")
+        self._last_forward = "one_launch"
+        return actions, probs, attn
+
     def _act_device_layers(self, obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset):
         """Teams above 80 agents (PP map 40: N = 128; CO map 40: N = 96): one env's activation planes plus its N x N score matrix
         exceed a workgroup's 160 KB of LDS, so the forward runs layer by layer - encoder on the library GEMM, attention softmax
         and masked aggregation on their own HIP kernels (the training path's, up to 128 agents) - and the head + softmax x avail
         + Philox sample as ONE launch of the row-MLP kernel (cm_mlp_policy_forward) over x = E + H_L.  Same Philox site as the
-        fused kernel: the sampled action is the oracle's inverse-CDF draw on the returned probabilities."""
+        fused kernel: the sampled action is the oracle's inverse-CDF draw on the returned probabilities.  Also the route of nets
+        with non-default layer sizes that cm_policy_forward_any does not take (_act_device_any)."""
         N, A, d = self._n_agents, self._action_dim, self._dec_obs_dim
         S = obs.numel() // (N * d)
         Lh = len(self.gcn_layers)
@@ -958,6 +1049,8 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         """One call of the cm_rollout_* family: what they share (handle, weights, slot pointers, sampler counters, outputs),
         with the entry point's own arguments spliced in where its signature has them.  False when the library answers
         "not for this shape" (1), having done nothing."""
+        if not self._default_shape:                          # the rollout kernels are built for the default layer sizes
+            return False
         w = self._weights_struct()
         with torch.cuda.device(obs.device):
             rc = getattr(L.lib(), name)(
@@ -1067,9 +1160,9 @@ class CommBaseCritic(CommBaseNet):
         if aggregator_type not in ("sum", "direct"):
             raise ValueError("aggregator_type must be 'sum' or 'direct' (comm_base_critic.py:46-49)")
         self.aggregator_type = aggregator_type
-        if aggregator_type != "sum" or n_agents > MAX_FUSED_AGENTS:
-            self._graph_capturable_update = False        # framework GEMMs / per-layer fallbacks in the step: eager
         self._dec_hidden = tuple(decoder_hidden_sizes)
+        if aggregator_type != "sum" or n_agents > MAX_FUSED_AGENTS or not self._default_shape:
+            self._graph_capturable_update = False        # framework GEMMs / per-layer fallbacks in the step: eager
         # 'sum': one value per agent from its embedding, summed (:110-112).  'direct': ONE value from the concatenated
         # embeddings of the whole team (:113-116) - the head is then a plain [N * 64] -> 64 -> 1 MLP on the framework's GEMMs
         # behind the fused trunk kernels (per-layer path; the fused critic kernels carry the per-agent head only)
@@ -1077,9 +1170,17 @@ class CommBaseCritic(CommBaseNet):
         self.baseline_aggregator = GaussianMLPModule(agg_in, 1, hidden_sizes=decoder_hidden_sizes)
         self.to(device)
 
+    _HEAD_DEFAULT = (64,)
+
+    def _head_hidden(self):
+        return self._dec_hidden
+
+    def _head_mlp(self):
+        return self.baseline_aggregator._mean_module
+
     def sync_weights(self):
-        if self.aggregator_type == "sum":
-            super().sync_weights()                       # 'direct' has no fused kernel, hence no weight pack to refresh
+        if self.aggregator_type == "sum" and self._default_shape:
+            super().sync_weights()                       # 'direct' / other layer sizes: no fused kernel, hence no weight pack to refresh
 
     def _head_tensors(self):
         m = self.baseline_aggregator._mean_module
@@ -1126,7 +1227,7 @@ class CommBaseCritic(CommBaseNet):
         dev = obs.device
         if dev.type != "cuda":
             raise L.CommarlError("critic forward is a HIP kernel: inputs must be CUDA tensors (no CPU fallback)")
-        if self.aggregator_type == "direct" or self._n_agents > MAX_FUSED_AGENTS:    # no one-launch kernel: layer by layer
+        if self.aggregator_type == "direct" or self._n_agents > MAX_FUSED_AGENTS or not self._default_shape:    # no one-launch kernel: layer by layer
             v = self._values_grad(obs, dist_adj, channels)[0]
             return v if out is None else out.copy_(v.reshape(out.shape))
         N = self._n_agents
@@ -1520,8 +1621,8 @@ class PolicySet:
         refreshes them in place).  A set the planner refuses (a group without envs, ...) raises."""
         if all(hasattr(p, "_mlp_struct") for p in self.policies):
             return self._mlp_forward_table(groups)
-        if not all(hasattr(p, "_weights_struct") for p in self.policies):
-            return None, 0
+        if not all(hasattr(p, "_weights_struct") and p._default_shape for p in self.policies):
+            return None, 0                                   # (the set kernel is built for the default layer sizes)
         if any(p._mfma is None or p._pack is None for p in self.policies):
             self.sync_weights()
             if any(p._mfma is None for p in self.policies):

@@ -145,14 +145,16 @@ class RolloutEngine:
         # one launch for the whole set: teams of 4 on the default (wave-owned) kernel, every member's envs in whole workgroups of
         # 16, one sampler seed; the library may still answer "not for this shape" (1), and the engine then loops from there on
         pk = os.environ.get("COMMARL_POLICY_KERNEL", "w")[:1]
-        wave = (hasattr(ps[0], "chunk_fused") and ps._n_agents == 4 and pk not in ("h", "f", "v") and ps.seed is not None
+        wave = (hasattr(ps[0], "chunk_fused") and getattr(ps[0], "_default_shape", True) and ps._n_agents == 4
+                and pk not in ("h", "f", "v") and ps.seed is not None
                 and all(lo % WG_ENVS == 0 for lo, _ in self.groups) and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_form = "wave" if wave else "loop"
         self._persistent, self._fused = wave, None
         # loop form: one forward launch for the whole set (cm_policy_forward_multi for Comm-DP members, cm_mlp_policy_forward_multi
         # for Obs-DP / CENT members) - one sampler seed, production RNG; the library answers "not for this shape" (1) for the
         # teams it has no set kernel for, and the engine remembers it
-        set_fwd = ((hasattr(ps[0], "chunk_fused") or hasattr(ps[0], "_mlp_struct")) and ps.seed is not None
+        set_fwd = ((hasattr(ps[0], "chunk_fused") or hasattr(ps[0], "_mlp_struct")) and getattr(ps[0], "_default_shape", True)
+                   and ps.seed is not None
                    and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_forward = None if wave else ("set" if set_fwd else "member")
         if wave:

@@ -228,6 +228,30 @@ int cm_policy_forward(const cm_policy_weights *w, int32_t n_samples, const float
 int cm_critic_forward(const cm_critic_weights *w, int32_t n_samples, const float *obs, const float *dist_adj,
                       const float *channels, float *values, void *stream);
 
+/* A Comm-DP policy of ANY layer sizes (the runners' --encoder_hidden_sizes, --embedding_dim and
+ * --categorical_mlp_hidden_sizes, exp_runners/env_uitils.py:83-90): n_enc = 1..3 encoder hidden layers, n_head = 1..4
+ * head hidden layers, every width, emb and d in 1..128.  Weights are plain device pointers, linear weights TRANSPOSED
+ * [in,out]; slot n_enc of enc_wt / enc_b is the encoder's output layer (-> emb), slot n_head of head_wt / head_b the
+ * logits layer (-> n_act).  attn_wt [emb,emb], NULL = 'dot' attention (Q = E).  gcn_w [L,emb,emb] stacked, gcn_b [L,emb]
+ * or NULL (gcn_bias=False). */
+typedef struct cm_net_weights {
+    int32_t d, n_agents, n_hops, n_act, no_residual, emb;
+    int32_t n_enc, enc_hidden[3];
+    int32_t n_head, head_hidden[4];
+    int32_t _pad;
+    const float *enc_wt[4], *enc_b[4];
+    const float *attn_wt, *gcn_w, *gcn_b;
+    const float *head_wt[5], *head_b[5];
+} cm_net_weights;
+/* cm_policy_forward for such a net, in one launch (csrc/cm_policy_g.hip: every dense layer on v_mfma_f32_16x16x4_f32,
+ * activations in LDS): same inputs, outputs, Philox stream and arithmetic order of the softmax x avail + draw.
+ * Returns 1 - nothing launched - when the shape is outside the bounds above or one workgroup's LDS need exceeds 160 KB
+ * (large teams of wide nets): the caller then runs layer by layer. */
+int cm_policy_forward_any(const cm_net_weights *w, int32_t n_samples, const float *obs, const float *avail,
+                          const float *dist_adj, const float *channels, uint64_t seed, int32_t env_id_offset,
+                          uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy, int32_t *actions,
+                          float *probs, float *attn, void *stream);
+
 /* Training forward (PPO update): the same fused forward, which additionally stores every activation the backward pass
  * needs ONCE, as f32 [R = S * n_agents rows, width] (the value the rest of the network saw): what torch's autograd would
  * keep layer by layer through ~20 separate kernels.  Pointers that are NULL are skipped.

@@ -56,7 +56,7 @@ class CriticWeights(C.Structure):
 
 
 class NetWeights(C.Structure):
-    """cm_net_weights: a Comm-DP policy of any layer sizes (cm_policy_forward_any)."""
+    """cm_net_weights: a Comm-DP policy or critic of any layer sizes (cm_policy_forward_any, cm_critic_forward_any)."""
     _fields_ = [(n, C.c_int32) for n in ("d", "n_agents", "n_hops", "n_act", "no_residual", "emb", "n_enc")] + [
         ("enc_hidden", C.c_int32 * 3), ("n_head", C.c_int32), ("head_hidden", C.c_int32 * 4), ("_pad", C.c_int32),
         ("enc_wt", C.c_void_p * 4), ("enc_b", C.c_void_p * 4), ("attn_wt", C.c_void_p), ("gcn_w", C.c_void_p),
@@ -129,6 +129,8 @@ _SIGNATURES = {
     "cm_policy_forward_any": (C.c_int, [C.POINTER(NetWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_critic_forward_any": (C.c_int, [C.POINTER(NetWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "cm_rollout_step": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(RngTape), C.POINTER(StepOut), C.c_void_p]),
@@ -176,6 +178,15 @@ _SIGNATURES = {
     "cm_attention_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_attention_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same four for any embedding width 1..128 (csrc/cm_graph_any.hip)
+    "cm_masked_agg_forward_any": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_masked_agg_backward_any": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "cm_attention_forward_any": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_attention_backward_any": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_linear_wgrad": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "cm_policy_forward_saved_wave": (C.c_int, [C.POINTER(PolicyWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -234,6 +245,10 @@ _SIGNATURES = {
     "cm_masked_agg_backward_det": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cm_masked_agg_backward_any_det_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cm_masked_agg_backward_any_det": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cm_linear_wgrad_det_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "cm_linear_wgrad_det": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -287,6 +302,7 @@ TWINS = {
     "cm_encoder_backward": ("cm_encoder_backward_det", "cm_encoder_backward_det_ws_bytes"),
     "cm_masked_agg_backward": ("cm_masked_agg_backward_det", "cm_masked_agg_backward_det_ws_bytes"),
     "cm_masked_agg_backward_r": ("cm_masked_agg_backward_det", "cm_masked_agg_backward_det_ws_bytes"),
+    "cm_masked_agg_backward_any": ("cm_masked_agg_backward_any_det", "cm_masked_agg_backward_any_det_ws_bytes"),
     "cm_linear_wgrad": ("cm_linear_wgrad_det", "cm_linear_wgrad_det_ws_bytes"),
     "cm_ppo_surrogate": ("cm_ppo_surrogate_det", "cm_ppo_surrogate_det_ws_bytes"),
     "cm_gauss_nll_forward": ("cm_gauss_nll_forward_det", "cm_gauss_nll_forward_det_ws_bytes"),

@@ -1,4 +1,5 @@
-// cm_policy_g_dev.h - device side of the run-time-sized Comm-DP policy forward (cm_policy_g.hip).
+// cm_policy_g_dev.h - device side of the run-time-sized Comm-DP forwards: the policy (cm_policy_g.hip) and the critic
+// (cm_critic_g.hip) are the two instantiations of one kernel, which share trunk() and head() below.
 //
 // One 256-thread workgroup owns EPB whole envs (rows = EPB * N agent rows, padded to R16 = a multiple of 16) and carries
 // them from the observation load to the sampled action.  LDS map (floats; every plane base and stride a multiple of 4):
@@ -35,6 +36,7 @@ struct Args {
     int env_id_offset, greedy;
     int32_t *actions;
     float *probs, *attn;
+    float *values;                                // the critic instantiation: [S]
 };
 
 // The one place the LDS need is computed: the "fits" test and the launch both read it.
@@ -54,6 +56,34 @@ __host__ inline Plan plan(int N, int d, int emb, int widest) {
     const size_t mat = ((size_t)p.EPB * N * p.NP + 3) & ~(size_t)3;
     p.lds_bytes = ((size_t)p.R16 * (2 * p.SE + 2 * p.SW) + 2 * mat) * sizeof(float);
     return p;
+}
+
+// cm_net_weights -> Args + Plan, for both entry points.  0: ready to launch; 1: outside the bounds the kernel is written for
+// or more than 160 KB of LDS ("not for this shape", nothing launched); < 0: a null weight pointer (cm_last_error names `fn`).
+__host__ inline bool width_ok(int w) { return w >= 1 && w <= MAX_W; }
+__host__ inline int fill(const char *fn, const cm_net_weights *w, int n_samples, Args &a, Plan &p) {
+    if (w->n_enc < 1 || w->n_enc > MAX_ENC || w->n_head < 1 || w->n_head > MAX_HEAD) return 1;
+    if (!width_ok(w->emb) || !width_ok(w->d) || w->n_act < 1 || w->n_act > MAX_ACT || w->n_agents < 1 || w->n_hops < 0) return 1;
+    int widest = w->emb;
+    for (int i = 0; i < w->n_enc; ++i) { if (!width_ok(w->enc_hidden[i])) return 1; widest = widest > w->enc_hidden[i] ? widest : w->enc_hidden[i]; }
+    for (int i = 0; i < w->n_head; ++i) { if (!width_ok(w->head_hidden[i])) return 1; widest = widest > w->head_hidden[i] ? widest : w->head_hidden[i]; }
+    p = plan(w->n_agents, w->d, w->emb, widest);
+    if (p.lds_bytes > LDS_LIMIT) return 1;
+    for (int i = 0; i <= w->n_enc; ++i)
+        if (!w->enc_wt[i]) return set_error(CM_ERR_ARG, std::string(fn) + ": null encoder weight");
+    for (int i = 0; i <= w->n_head; ++i)
+        if (!w->head_wt[i]) return set_error(CM_ERR_ARG, std::string(fn) + ": null head weight");
+    if (w->n_hops > 0 && !w->gcn_w) return set_error(CM_ERR_ARG, std::string(fn) + ": null gcn_w");
+    a.S = n_samples; a.N = w->n_agents; a.d = w->d; a.L = w->n_hops; a.A = w->n_act; a.emb = w->emb;
+    a.no_residual = w->no_residual;
+    a.n_enc = w->n_enc; a.n_head = w->n_head;
+    for (int i = 0; i < w->n_enc; ++i) { a.enc_h[i] = w->enc_hidden[i]; a.enc_w[i] = w->enc_wt[i]; a.enc_b[i] = w->enc_b[i]; }
+    a.enc_wo = w->enc_wt[w->n_enc]; a.enc_bo = w->enc_b[w->n_enc];
+    for (int i = 0; i < w->n_head; ++i) { a.head_h[i] = w->head_hidden[i]; a.head_w[i] = w->head_wt[i]; a.head_b[i] = w->head_b[i]; }
+    a.head_wo = w->head_wt[w->n_head]; a.head_bo = w->head_b[w->n_head];
+    a.attn_wt = w->attn_wt; a.gcn_w = w->gcn_w; a.gcn_b = w->gcn_b;
+    a.EPB = p.EPB; a.R16 = p.R16; a.SE = p.SE; a.SW = p.SW; a.NP = p.NP;
+    return 0;
 }
 
 __device__ __forceinline__ float fast_tanh(float x) {      // same form as cm_mlp.hip (abs err <= 2e-7)
@@ -108,9 +138,12 @@ __device__ __forceinline__ void dense(float *lds, int in, int in_s, int K, const
     }
 }
 
-__global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x, N = a.N, d = a.d, L = a.L, NN = N * N, NP = a.NP, EM = a.emb;
+// What a workgroup owns and where its planes start (float offsets into the one LDS array).
+struct Tile { int s0, envs, rows, oE, oH, oP0, oP1; };
+
+// The trunk both kernels share: zeroing, observation staging, encoder, attention + softmax, L hops, residual.  Leaves x in H.
+__device__ __forceinline__ Tile trunk(const Args &a, float *lds, int tid) {
+    const int N = a.N, d = a.d, L = a.L, NN = N * N, NP = a.NP, EM = a.emb;
     const int SE = a.SE, SW = a.SW, R16 = a.R16;
     const int s0 = blockIdx.x * a.EPB;
     const int envs = min(a.EPB, a.S - s0);
@@ -118,7 +151,6 @@ __global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
     const int mat = (rows_max * NP + 3) & ~3;
     const int oE = 0, oH = oE + R16 * SE, oP0 = oH + R16 * SE, oP1 = oP0 + R16 * SW, oM = oP1 + R16 * SW, oA = oM + mat;
     const int total = oA + mat;
-
     // ---- zero the tile (16-byte stores), then stage the observations: coalesced HBM read of rows*d floats ----
     for (int k = tid * 4; k < total; k += TPB * 4) *reinterpret_cast<float4 *>(&lds[k]) = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
@@ -209,8 +241,14 @@ __global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
     }
     __syncthreads();
 
-    // ---- head: n_head tanh hidden layers, linear logits ----
-    cur = oH; nxt = oP0; K = EM;
+    return Tile{ s0, envs, rows, oE, oH, oP0, oP1 };
+}
+
+// The head both kernels share: n_head tanh hidden layers over x (in H), then the linear output layer of a.A columns.
+// Returns the plane (stride SW) that holds the outputs.
+__device__ __forceinline__ int head(const Args &a, float *lds, const Tile &t, int tid) {
+    const int SE = a.SE, SW = a.SW, R16 = a.R16, oP0 = t.oP0, oP1 = t.oP1;
+    int cur = t.oH, nxt = oP0, K = a.emb;
     int cs = SE;
 #pragma unroll
     for (int i = 0; i < MAX_HEAD; ++i) {
@@ -221,9 +259,29 @@ __global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
             K = a.head_h[i];
         }
     }
-    const int A = a.A;
-    dense<false>(lds, cur, cs, K, a.head_wo, a.head_bo, A, nxt, SW, R16, tid);
+    dense<false>(lds, cur, cs, K, a.head_wo, a.head_bo, a.A, nxt, SW, R16, tid);
     __syncthreads();
+    return nxt;
+}
+
+// CRITIC false: the policy - per-agent softmax x avail, renormalise, sample.  CRITIC true (cm_critic_g.hip): the head is the
+// critic's decoder with ONE output column, and one thread per env sums its agents' values in agent order.
+template <bool CRITIC>
+__global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, N = a.N, SW = a.SW;
+    const Tile t = trunk(a, lds, tid);
+    const int s0 = t.s0, rows = t.rows;
+    const int nxt = head(a, lds, t, tid);
+    if constexpr (CRITIC) {
+        for (int e = tid; e < t.envs; e += TPB) {
+            float v = 0.0f;
+            for (int i = 0; i < N; ++i) v += lds[nxt + (e * N + i) * SW];
+            a.values[s0 + e] = v;
+        }
+        return;
+    }
+    const int A = a.A;
 
     // ---- per-agent softmax * avail, renormalise, sample (same arithmetic order as cm_mlp_body.h) ----
     for (int r = tid; r < rows; r += TPB) {

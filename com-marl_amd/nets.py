@@ -118,6 +118,68 @@ class _AttentionSoftmax(torch.autograd.Function):
         return d_q, d_e
 
 
+class _NotCovered(Exception):
+    """A *_any graph op answered 1: the planes of this (N, E) do not fit a workgroup's LDS - the framework path runs instead."""
+
+
+# (N, E) -> "hip" | "framework" for embeddings other than 64: what the forward ops answered (asked once per shape), or what
+# set_graph_op_route pinned
+_GRAPH_ROUTE = {}
+
+
+def graph_op_route(N, E):
+    """Which path attention and masked aggregation take for a team of N and an embedding width E other than 64: "hip" (the
+    cm_*_any kernels of csrc/cm_graph_any.hip, forward and backward) or "framework" (batched GEMMs, autograd's backward).
+    Teams above MAX_KERNEL_AGENTS and widths outside 1..128 are "framework"; so is a shape whose planes the forward op found
+    not to fit 160 KB of LDS (it answers 1 once, the answer is kept).  E = 64 has its own kernels and never asks."""
+    if N > MAX_KERNEL_AGENTS or not 1 <= E <= 128:
+        return "framework"
+    return _GRAPH_ROUTE.get((N, E), "hip")
+
+
+def set_graph_op_route(N, E, route):
+    """Pin graph_op_route(N, E) to "hip" or "framework" (None: forget the pin) - for measurements and tests."""
+    if route is None:
+        _GRAPH_ROUTE.pop((N, E), None)
+        return
+    if route not in ("hip", "framework"):
+        raise ValueError(f"route must be 'hip', 'framework' or None, not {route!r}")
+    _GRAPH_ROUTE[(N, E)] = route
+
+
+def _any_rc(rc, N, E, what):
+    if rc == 1:
+        _GRAPH_ROUTE[(N, E)] = "framework"
+        raise _NotCovered(what)
+    L.check(rc, what)
+
+
+class _AttentionSoftmaxAny(torch.autograd.Function):
+    """_AttentionSoftmax for any embedding width 1..128 (cm_attention_forward_any / _backward_any)."""
+
+    @staticmethod
+    def forward(ctx, q, e):
+        S, N, E = e.shape
+        q, e = q.contiguous(), e.contiguous()
+        m = torch.empty(S, N, N, dtype=e.dtype, device=e.device)
+        with torch.cuda.device(e.device):
+            _any_rc(L.lib().cm_attention_forward_any(S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), L.current_stream()), N, E,
+                    "cm_attention_forward_any")
+        ctx.save_for_backward(q, e, m)
+        return m
+
+    @staticmethod
+    def backward(ctx, d_m):
+        q, e, m = ctx.saved_tensors
+        S, N, E = e.shape
+        d_m = d_m.contiguous()
+        d_q, d_e = torch.empty_like(q), torch.empty_like(e)
+        with torch.cuda.device(e.device):
+            L.check(L.lib().cm_attention_backward_any(S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), L.ptr(d_m), None, None, L.ptr(d_q),
+                                                      L.ptr(d_e), L.current_stream()), "cm_attention_backward_any")
+        return d_q, d_e
+
+
 class AttentionModule(nn.Module):
     """attention_module.py:17-51: 'general' softmax_j((q W^T) . k_j) with the learned ``linear_in``, or 'dot'
     softmax_j(q . k_j) with no parameter at all (:38-41).  ('diff' creates a parameter in the reference's constructor but its
@@ -137,7 +199,13 @@ class AttentionModule(nn.Module):
         q = self.linear_in(query) if self.attention_type == "general" else query
         if query.is_cuda and query.dim() == 3 and query.shape[-1] == 64 and query.shape[-2] <= MAX_KERNEL_AGENTS:
             return _AttentionSoftmax.apply(q, query)             # fused HIP op (cm_attention_forward/backward)
-        # teams above 128 agents (maps >= 50) and embeddings other than 64 (--embedding_dim): library GEMMs, autograd backward
+        if (query.is_cuda and query.dim() == 3 and query.dtype == torch.float32
+                and graph_op_route(query.shape[-2], query.shape[-1]) == "hip"):
+            try:
+                return _AttentionSoftmaxAny.apply(q, query)      # embeddings other than 64 (--embedding_dim): cm_attention_*_any
+            except _NotCovered:
+                pass
+        # teams above 128 agents (maps >= 50), and widths whose planes do not fit the LDS: library GEMMs, autograd backward
         return torch.softmax(torch.matmul(q, query.transpose(-2, -1)), dim=-1)
 
 
@@ -309,14 +377,56 @@ class _MaskedAggregate(torch.autograd.Function):
         return d_attn, None, None, None, d_hw, d_bias
 
 
+class _MaskedAggregateAny(torch.autograd.Function):
+    """_MaskedAggregate for any embedding width 1..128 (cm_masked_agg_forward_any / _backward_any and its _det twin)."""
+
+    @staticmethod
+    def forward(ctx, attn, dist_adj, chan_all, hop, hw, bias):
+        S, N, E = hw.shape
+        attn, hw = attn.contiguous(), hw.contiguous()
+        out = torch.empty_like(hw)
+        chan_ptr, stride = None, 0
+        if chan_all is not None:
+            chan_ptr, stride = chan_all.data_ptr() + 4 * hop * N * N, chan_all.shape[1] * N * N
+        with torch.cuda.device(hw.device):
+            _any_rc(L.lib().cm_masked_agg_forward_any(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
+                                                      L.ptr(bias), L.ptr(out), L.current_stream()), N, E, "cm_masked_agg_forward_any")
+        ctx.save_for_backward(attn, dist_adj, chan_all, hw, out)
+        ctx.hop, ctx.has_bias = hop, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        attn, dist_adj, chan_all, hw, out = ctx.saved_tensors
+        S, N, E = hw.shape
+        d_out = d_out.contiguous()
+        d_attn, d_hw = torch.empty_like(attn), torch.empty_like(hw)
+        d_bias = torch.zeros(E, dtype=hw.dtype, device=hw.device) if ctx.has_bias else None
+        chan_ptr, stride = None, 0
+        if chan_all is not None:
+            chan_ptr, stride = chan_all.data_ptr() + 4 * ctx.hop * N * N, chan_all.shape[1] * N * N
+        with torch.cuda.device(hw.device):
+            L.check(L.launch("cm_masked_agg_backward_any", (S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw), L.ptr(out),
+                                                            None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias)), (S, N, E)),
+                    "cm_masked_agg_backward_any")
+        return d_attn, None, None, None, d_hw, d_bias
+
+
 def masked_aggregate(attn, dist_adj, channels, hop, hw, bias):
     """attn [S,N,N], dist_adj [S,N,N] or None (= ones), channels [S,L,N,N] or None, hw [S,N,E]."""
     if not hw.is_cuda:
         raise L.CommarlError("masked_aggregate is a HIP op: tensors must live on the MI355X (no CPU fallback)")
+    if (hw.shape[2] != 64 and hw.dim() == 3 and hw.dtype == torch.float32 and attn.dtype == torch.float32
+            and graph_op_route(hw.shape[1], hw.shape[2]) == "hip"):
+        try:                                     # embeddings other than 64 (--embedding_dim): cm_masked_agg_*_any
+            return _MaskedAggregateAny.apply(attn, dist_adj if dist_adj is None else dist_adj.contiguous(),
+                                             channels if channels is None else channels.contiguous(), hop, hw, bias)
+        except _NotCovered:
+            pass
     if hw.shape[1] > MAX_KERNEL_AGENTS or hw.shape[2] != 64:
-        # teams above 128 agents (PP map 50: N = 200): the N x N tile of one env no longer fits a workgroup's LDS; embeddings other
-        # than 64 (--embedding_dim): cm_masked_agg_* are built for 64 columns - the same arithmetic (comm_base_net.py:101-103,
-        # graph_conv_module.py:63-70) on the framework's batched GEMM, still on the GPU, autograd doing the backward
+        # teams above 128 agents (PP map 50: N = 200), and widths other than 64 whose planes do not fit: the N x N tile of one env
+        # no longer fits a workgroup's LDS - the same arithmetic (comm_base_net.py:101-103, graph_conv_module.py:63-70) on the
+        # framework's batched GEMM, still on the GPU, autograd doing the backward
         A = attn
         if dist_adj is not None:
             A = A * dist_adj
@@ -762,6 +872,29 @@ class CommBaseNet(_WeightPack, nn.Module):
                       if len(self.gcn_layers) and self.gcn_layers[0].bias is not None else None)
         return t
 
+    def _net_struct(self):
+        """cm_net_weights of this net over its flat weight copy (any layer sizes): the policy's head is its categorical MLP, the
+        'sum' critic's its decoder (one output column).  None outside the layer counts of cm_*_forward_any."""
+        head, mlp = tuple(self._head_hidden()), self._head_mlp()
+        if not (1 <= len(self._enc_hidden) <= 3 and 1 <= len(head) <= 4):
+            return None                                          # more layers than the kernel is written for: layer by layer
+        p = self._packed()
+        w = L.NetWeights()
+        w.d, w.n_agents, w.n_hops = self._dec_obs_dim, self._n_agents, len(self.gcn_layers)
+        w.n_act = mlp._output_layers[0].linear.out_features
+        w.no_residual, w.emb = 0 if self.residual else 1, self._embedding_dim
+        w.n_enc, w.n_head = len(self._enc_hidden), len(head)
+        for i, h in enumerate(self._enc_hidden):
+            w.enc_hidden[i] = h
+        for i, h in enumerate(head):
+            w.head_hidden[i] = h
+        for i in range(w.n_enc + 1):
+            w.enc_wt[i], w.enc_b[i] = p[f"enc_w{i}t"], p[f"enc_b{i}"]
+        for i in range(w.n_head + 1):
+            w.head_wt[i], w.head_b[i] = p[f"head_w{i}t"], p[f"head_b{i}"]
+        w.attn_wt, w.gcn_w, w.gcn_b = p["attn_wt"], p["gcn_w"], p["gcn_b"]
+        return w
+
     def _trunk_tensors(self):
         enc = self.encoder
         if len(enc._layers) != 1:
@@ -826,7 +959,7 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         # where it fits, else layer by layer; "layers": always layer by layer.  _last_forward says which one the last call took.
         self._general_forward, self._last_forward = "auto", None
         if not self._default_shape:
-            # the per-layer training path (framework GEMMs where the embedding is not 64, autograd's own adds everywhere) has not been
+            # the per-layer training path (the any-width graph ops where the embedding is not 64, autograd's own adds everywhere) has not been
             # run under the update's hipGraphs: every non-default net steps eagerly, as teams above 80 agents do
             self._graph_capturable_update = False
         self.to(device)
@@ -972,26 +1105,6 @@ class CommCategoricalMLPPolicy(CommBaseNet):
                 policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
                 L.current_stream()), "cm_policy_forward")
         return actions, probs, attn
-
-    def _net_struct(self):
-        """cm_net_weights of this policy over its flat weight copy (any layer sizes)."""
-        if not (1 <= len(self._enc_hidden) <= 3 and 1 <= len(self._head_sizes) <= 4):
-            return None                                          # outside cm_policy_forward_any's layer counts: layer by layer
-        p = self._packed()
-        w = L.NetWeights()
-        w.d, w.n_agents, w.n_hops, w.n_act = self._dec_obs_dim, self._n_agents, len(self.gcn_layers), self._action_dim
-        w.no_residual, w.emb = 0 if self.residual else 1, self._embedding_dim
-        w.n_enc, w.n_head = len(self._enc_hidden), len(self._head_sizes)
-        for i, h in enumerate(self._enc_hidden):
-            w.enc_hidden[i] = h
-        for i, h in enumerate(self._head_sizes):
-            w.head_hidden[i] = h
-        for i in range(w.n_enc + 1):
-            w.enc_wt[i], w.enc_b[i] = p[f"enc_w{i}t"], p[f"enc_b{i}"]
-        for i in range(w.n_head + 1):
-            w.head_wt[i], w.head_b[i] = p[f"head_w{i}t"], p[f"head_b{i}"]
-        w.attn_wt, w.gcn_w, w.gcn_b = p["attn_wt"], p["gcn_w"], p["gcn_b"]
-        return w
 
     def _act_device_any(self, obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset):
         """Layer sizes other than the default: forward + sample in ONE launch of the run-time-sized kernel
@@ -1168,6 +1281,10 @@ class CommBaseCritic(CommBaseNet):
         # behind the fused trunk kernels (per-layer path; the fused critic kernels carry the per-agent head only)
         agg_in = embedding_dim if aggregator_type == "sum" else embedding_dim * n_agents
         self.baseline_aggregator = GaussianMLPModule(agg_in, 1, hidden_sizes=decoder_hidden_sizes)
+        # 'sum' critics of layer sizes other than the default: which no-grad forward values_device takes - "auto": one launch
+        # (cm_critic_forward_any) where it fits, else layer by layer; "layers": always layer by layer.  _last_forward says which one
+        # the last call took (it stays None on the 'direct' and default-shape routes).
+        self._general_forward, self._last_forward = "auto", None
         self.to(device)
 
     _HEAD_DEFAULT = (64,)
@@ -1179,8 +1296,8 @@ class CommBaseCritic(CommBaseNet):
         return self.baseline_aggregator._mean_module
 
     def sync_weights(self):
-        if self.aggregator_type == "sum" and self._default_shape:
-            super().sync_weights()                       # 'direct' / other layer sizes: no fused kernel, hence no weight pack to refresh
+        if self.aggregator_type == "sum":
+            super().sync_weights()                       # 'direct': no fused kernel, hence no weight pack to refresh
 
     def _head_tensors(self):
         m = self.baseline_aggregator._mean_module
@@ -1223,16 +1340,35 @@ class CommBaseCritic(CommBaseNet):
 
     @torch.no_grad()
     def values_device(self, obs, dist_adj, channels, out=None):
-        """Fused no-grad forward (cm_critic_forward): obs [..., N*d] CUDA -> values [...]."""
+        """Fused no-grad forward (cm_critic_forward; cm_critic_forward_any for other layer sizes): obs [..., N*d] CUDA -> values [...]."""
         dev = obs.device
         if dev.type != "cuda":
             raise L.CommarlError("critic forward is a HIP kernel: inputs must be CUDA tensors (no CPU fallback)")
-        if self.aggregator_type == "direct" or self._n_agents > MAX_FUSED_AGENTS or not self._default_shape:    # no one-launch kernel: layer by layer
-            v = self._values_grad(obs, dist_adj, channels)[0]
-            return v if out is None else out.copy_(v.reshape(out.shape))
         N = self._n_agents
         lead = obs.shape[:-1] if obs.shape[-1] == N * self._dec_obs_dim else obs.shape[:-2]
         S = obs.numel() // (N * self._dec_obs_dim)
+        if self.aggregator_type == "sum" and not self._default_shape:
+            # layer sizes other than the default: ONE launch of the run-time-sized kernel (cm_critic_forward_any, csrc/cm_critic_g.hip);
+            # where it answers "not for this shape" (1) or the route is pinned (_general_forward = "layers"), layer by layer
+            if self._general_forward not in ("auto", "layers"):
+                raise ValueError(f"_general_forward must be 'auto' or 'layers', not {self._general_forward!r}")
+            w = self._net_struct() if self._general_forward == "auto" else None
+            rc = 1
+            if w is not None:
+                values = out if out is not None else torch.empty(S, dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    rc = L.lib().cm_critic_forward_any(C.byref(w), S, L.ptr(obs.contiguous()),
+                                                       L.ptr(None if dist_adj is None else dist_adj.contiguous()),
+                                                       L.ptr(None if channels is None else channels.contiguous()),
+                                                       L.ptr(values), L.current_stream())
+            if rc != 1:
+                L.check(rc, "cm_critic_forward_any")
+                self._last_forward = "one_launch"
+                return values.reshape(*lead) if out is None else values
+            self._last_forward = "layers"
+        if self.aggregator_type == "direct" or self._n_agents > MAX_FUSED_AGENTS or not self._default_shape:    # no one-launch kernel: layer by layer
+            v = self._values_grad(obs, dist_adj, channels)[0]
+            return v if out is None else out.copy_(v.reshape(out.shape))
         values = out if out is not None else torch.empty(S, dtype=torch.float32, device=dev)
         w = self._struct_from(self._packed())
         w.mfma_pack = None if self._mfma is None else self._mfma.data_ptr()

@@ -252,6 +252,14 @@ int cm_policy_forward_any(const cm_net_weights *w, int32_t n_samples, const floa
                           uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy, int32_t *actions,
                           float *probs, float *attn, void *stream);
 
+/* CommBaseCritic.forward with aggregator_type='sum' for such a net, in one launch (csrc/cm_critic_g.hip: the policy kernel's
+ * trunk, then the decoder): head_* carry baseline_aggregator._mean_module - n_head = 1..4 tanh hidden layers, slot n_head the
+ * [K,1] output layer - and n_act must be 1.  values[s] = sum over the env's agents of the decoder's output, summed in agent
+ * order by one thread (no atomic: the same bits on every launch).  Returns 1 - nothing launched, nothing written - where
+ * cm_policy_forward_any does. */
+int cm_critic_forward_any(const cm_net_weights *w, int32_t n_samples, const float *obs, const float *dist_adj,
+                          const float *channels, float *values, void *stream);
+
 /* Training forward (PPO update): the same fused forward, which additionally stores every activation the backward pass
  * needs ONCE, as f32 [R = S * n_agents rows, width] (the value the rest of the network saw): what torch's autograd would
  * keep layer by layer through ~20 separate kernels.  Pointers that are NULL are skipped.
@@ -478,6 +486,21 @@ int cm_attention_forward(int32_t S, int32_t N, int32_t E, const float *q, const 
 int cm_attention_backward(int32_t S, int32_t N, int32_t E, const float *q, const float *e, const float *m,
                           const float *d_m, const float *d_e_add0, const float *d_e_add1, float *d_q, float *d_e, void *stream);
 
+/* The four graph ops above for ANY embedding width E in 1..128 (--embedding_dim; csrc/cm_graph_any.hip): the argument lists and
+ * pointer semantics of their E = 64 namesakes (chan + ch_stride, out_minus, d_e_add0 / d_e_add1 and the aliasing refusal), the
+ * same arithmetic.  d_bias [E] accumulates (one row: the caller zeroes it).  Return 1 - nothing launched, nothing written -
+ * when the planes of one workgroup's envs do not fit 160 KB of LDS (N above 128, or e.g. N = 128 with E = 128): all of them
+ * answer from the SAME test, so a shape whose forward runs has its backward.  E outside 1..128 is CM_ERR_ARG. */
+int cm_masked_agg_forward_any(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                              const float *chan, int64_t ch_stride, const float *hw, const float *bias, float *out,
+                              void *stream);
+int cm_masked_agg_backward_any(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                               const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
+                               const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream);
+int cm_attention_forward_any(int32_t S, int32_t N, int32_t E, const float *q, const float *e, float *m, void *stream);
+int cm_attention_backward_any(int32_t S, int32_t N, int32_t E, const float *q, const float *e, const float *m,
+                              const float *d_m, const float *d_e_add0, const float *d_e_add1, float *d_q, float *d_e, void *stream);
+
 /* Weight gradient of a per-agent dense layer over R rows: c[p][q] += sum_r a[r][p] * b[r][q] (c [P,Q] must be
  * zeroed by the caller; accumulated with float atomics), colsum_a[p] += sum_r a[r][p] (or NULL).
  * nn.Linear backward: a = dY [R,out], b = X [R,in] -> c = dW [out,in], colsum_a = db.
@@ -616,6 +639,11 @@ size_t cm_masked_agg_backward_det_ws_bytes(int32_t S, int32_t N, int32_t E);
 int cm_masked_agg_backward_det(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
                                const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
                                const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *ws, size_t ws_bytes, void *stream);
+/* twin of cm_masked_agg_backward_any: one E-float row of d_bias per workgroup, summed in index order */
+size_t cm_masked_agg_backward_any_det_ws_bytes(int32_t S, int32_t N, int32_t E);
+int cm_masked_agg_backward_any_det(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
+                                   const float *chan, int64_t ch_stride, const float *hw, const float *out, const float *out_minus,
+                                   const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *ws, size_t ws_bytes, void *stream);
 size_t cm_linear_wgrad_det_ws_bytes(int64_t R, int32_t P, int32_t Q);
 int cm_linear_wgrad_det(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a,
                         void *ws, size_t ws_bytes, void *stream);

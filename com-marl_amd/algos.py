@@ -477,7 +477,10 @@ class CentralizedMAPPO:
             succ = e.success[paths.start + lens - 1, paths.env_idx].to(torch.float64)
             if e.dist_adj is not None:
                 deg = (e.dist_adj[t_idx, b_idx].sum(-1).mean(-1).to(torch.float64) * valid).sum(1) / lens
-                diam = torch.zeros(P, dtype=torch.float64, device=dev)               # get_graph: diameter 0 (:234)
+                if e.diameter is not None:                                           # calc_diameter: the path's mean (:314-317)
+                    diam = (e.diameter[t_idx, b_idx].to(torch.float64) * valid).sum(1) / lens
+                else:
+                    diam = torch.zeros(P, dtype=torch.float64, device=dev)           # get_graph: diameter 0 (:234)
             else:
                 deg = torch.full((P,), float(N), dtype=torch.float64, device=dev)
                 diam = deg.clone()

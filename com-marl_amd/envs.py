@@ -42,8 +42,10 @@ class EnvSpec:
 
 def make_cfg(scenario, params, n_envs, *, seed=1, env_id_offset=0, rng_mode=L.RNG_PHILOX, max_steps=None,
              max_path_length=None, channel=None):
-    """params dict -> cm_env_cfg, following predator_prey.py:52-82, coverage.py:40-96 and
-    env_communication.py:10-75 (signs: costs are stored as -abs(x))."""
+    """params dict -> (cm_env_cfg, channel type, loss probability, calc_diameter), following predator_prey.py:52-82,
+    coverage.py:40-96 and env_communication.py:10-75 (signs: costs are stored as -abs(x)).  calc_diameter
+    (env_communication.py:20) is no field of cm_env_cfg: the env step does not know the switch, the diameters are derived
+    from the dist_adj it records (graph_diameter below)."""
     p = params
     c = L.EnvCfg()
     pp = scenario == "pp"
@@ -83,7 +85,22 @@ def make_cfg(scenario, params, n_envs, *, seed=1, env_id_offset=0, rng_mode=L.RN
     c.lazy_penalty = -abs(p.get("lazy_penalty", 1))
     c.revisit_penalty = -abs(p.get("revisit_penalty", 0.5))
     c.final_reward = 100.0                                                                      # coverage.py:92
-    return c, channel, pl
+    return c, channel, pl, bool(p.get("calc_diameter"))
+
+
+def graph_diameter(dist_adj, out=None):
+    """Hop diameter of every graph of a contiguous f32 CUDA tensor [..., N, N] (cm_graph_diameter: an edge where either
+    direction is non-zero, the diagonal ignored, 0 for a disconnected graph - get_graph's calc_diameter branch,
+    env_communication.py:235-241) -> int32 [...].  One launch on the current stream; `out` receives the values when given."""
+    assert dist_adj.is_cuda and dist_adj.dtype == torch.float32 and dist_adj.dim() >= 2 and dist_adj.shape[-1] == dist_adj.shape[-2]
+    assert dist_adj.is_contiguous(), "cm_graph_diameter reads [S,N,N] through the raw pointer"
+    lead, N = dist_adj.shape[:-2], dist_adj.shape[-1]
+    if out is None:
+        out = torch.empty(lead, dtype=torch.int32, device=dist_adj.device)
+    assert out.dtype == torch.int32 and out.shape == lead and out.device == dist_adj.device and out.is_contiguous()
+    with torch.cuda.device(dist_adj.device):
+        L.check(L.lib().cm_graph_diameter(out.numel(), N, L.ptr(dist_adj), L.ptr(out), L.current_stream()), "cm_graph_diameter")
+    return out
 
 
 class GridEnvBatch:
@@ -98,7 +115,7 @@ class GridEnvBatch:
             raise L.CommarlError("GridEnvBatch runs on the MI355X only (device must be cuda:k); there is no CPU path")
         seed = int(params.get("seed", 1) if seed is None else seed)
         mode = L.RNG_TAPE if rng_mode == "tape" else L.RNG_PHILOX
-        self.cfg, self.channelType, self.pl = make_cfg(scenario, params, n_envs, seed=seed, env_id_offset=env_id_offset,
+        self.cfg, self.channelType, self.pl, calc_diameter = make_cfg(scenario, params, n_envs, seed=seed, env_id_offset=env_id_offset,
                                                        rng_mode=mode, max_steps=max_steps,
                                                        max_path_length=max_path_length, channel=channel)
         self._h = C.c_void_p()
@@ -111,6 +128,8 @@ class GridEnvBatch:
         self.n_empty_cells = L.lib().cm_env_n_empty_cells(self._h)
         self.adj_const = bool(L.lib().cm_env_adj_is_const(self._h))
         self.ch_const = bool(L.lib().cm_env_channels_are_const(self._h))
+        # params['calc_diameter'] on a range graph: engines and wrappers derive the hop diameter from dist_adj (Rcom == 0 keeps N)
+        self.calc_diameter = calc_diameter and not self.adj_const
         dev, B, N, M = self.device, self.B, self.N, max(self.M, 1)
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
         self.obs = torch.zeros(B, N, self.d, dtype=f32, device=dev)
@@ -293,7 +312,7 @@ class _WrapperBase:
         else:
             n, ne = b.N, b.n_empty_cells                                            # coverage.py:214-219
             self.bound_return = b.cfg.capture_reward * ne / n - abs(b.cfg.step_cost) * ne / n + b.cfg.final_reward
-        self.diameter = b.N if self.Rcom == 0 else 0                                # get_graph :219-223,234
+        self._diameter = b.N if self.Rcom == 0 else 0                               # get_graph :219-223,234
         self._single = (b.B == 1)
 
     # -- env attributes the sampler reads each step (sampler.py:123-131) --
@@ -315,6 +334,15 @@ class _WrapperBase:
             return self.n_agents
         v = self.batch.dist_adj.sum(-1).mean(-1).cpu().numpy()                      # :232
         return v[0] if self._single else v
+
+    @property
+    def diameter(self):
+        """get_graph's third value for the current graph: N with Rcom == 0, else 0 - or, with params['calc_diameter'], the
+        hop diameter (0 when disconnected; int for one env, int32 [B] otherwise)."""
+        if not self.batch.calc_diameter:
+            return self._diameter
+        v = graph_diameter(self.batch.dist_adj).cpu().numpy()
+        return int(v[0]) if self._single else v
 
     @property
     def success(self):

@@ -19,6 +19,7 @@ import os
 import torch
 
 from . import _lib as L
+from .envs import graph_diameter
 from .nets import PolicySet
 
 WG_ENVS = 16                 # envs per workgroup of the wave-owned kernels: a multi-policy launch gives each workgroup one policy
@@ -36,6 +37,7 @@ class _Parts:
         self.device, self.N, self.M, self.d, self.Lh = e0.device, e0.N, e0.M, e0.d, e0.Lh
         self.adj_const, self.ch_const, self.scenario = e0.adj_const, e0.ch_const, e0.scenario
         self.n_empty_cells, self.channels = e0.n_empty_cells, e0.channels
+        self.calc_diameter = getattr(e0, "calc_diameter", False)
         self.B = sum(p.B for p in parts)
         self.bounds, lo = [], 0
         for p in parts:
@@ -91,6 +93,9 @@ class RolloutEngine:
         # constant masks are never stored per step (4N^2 [adj != const] rule of SURVEY.md §8d)
         self.dist_adj = None if env.adj_const else z(H + 1, B, N, N)
         self.channels = None if env.ch_const else z(H + 1, B, Lh, N, N)
+        # params['calc_diameter'] on a range graph: the hop diameter of dist_adj[t][b], filled by ONE cm_graph_diameter launch
+        # per finished span of slots (fill_diameters) - derived data, no kernel of the step loop knows it.  None = switch off.
+        self.diameter = z(H + 1, B, dtype=i32) if self.dist_adj is not None and getattr(env, "calc_diameter", False) else None
         # device-side Philox counter base of the action sampler (uint32 bits), ONE PER SHARD: every shard bumps its own
         # copy on its own stream (all copies always hold the same value), so that the shards' chains share nothing
         self.step_bases = [torch.zeros(1, dtype=i32, device=dev) for _ in self.parts]
@@ -259,6 +264,20 @@ class RolloutEngine:
         if self.channels is not None:
             o["channels"] = self.channels[t + 1][lo:hi]
         return o
+
+    def fill_diameters(self, t0, n):
+        """diameter[t] of the n slots t0 .. t0+n-1 from dist_adj[t], in one launch on the current stream (the caller has
+        joined the shards' streams: the slots are final).  Nothing without the switch."""
+        if self.diameter is not None and n > 0:
+            graph_diameter(self.dist_adj[t0:t0 + n], out=self.diameter[t0:t0 + n])
+
+    def span_diameters(self, t0, n):
+        """Behind a span over slots t0 .. t0+n-1: the slots it wrote, t0+1 .. t0+n, and with them slot 0 (the reset's, or the
+        one a chunk's tail carried) when the span starts there."""
+        if t0 == 0:
+            self.fill_diameters(0, n + 1)
+        else:
+            self.fill_diameters(t0 + 1, n)
 
     def reset(self):
         """VecEnvExecutor.reset: every env restarts; slot 0 receives the first observation."""
@@ -458,11 +477,13 @@ class RolloutEngine:
             if not weights_synced:
                 self.policy.sync_weights()
             self._chunk(n)
+            self.span_diameters(0, n)
             return
         g = self._graphs.get((0, n, True)) or self.prepare_graph(n)
         if not weights_synced:              # in-place refresh of the weight pack the graph points at; a caller that steps
             self.policy.sync_weights()      # many chunks between optimiser steps syncs once itself (~15 us of host time)
         g.replay()
+        self.span_diameters(0, n)          # a plain launch behind the replay, not a node of the graph
 
     def run_span(self, t0, n, use_graph=True, weights_synced=True):
         """Slots t0 .. t0+n-1 -> t0+1 .. t0+n, nothing else (no carry into slot 0, no Philox bump): what obtain_samples
@@ -472,11 +493,13 @@ class RolloutEngine:
             if not weights_synced:
                 self.policy.sync_weights()
             self._chunk(n, t0, tail=False)
+            self.span_diameters(t0, n)
             return
         g = self._graphs.get((t0, n, False)) or self.prepare_graph(n, t0, tail=False)
         if not weights_synced:
             self.policy.sync_weights()
         g.replay()
+        self.span_diameters(t0, n)
 
     def invalidate_graphs(self):
         """Call after the policy weights were re-packed at a new address (never needed when

@@ -150,7 +150,7 @@ class PathBatch(Sequence):
                                    "overwritten by a later obtain_samples / reset (materialize() the paths you keep)")
             self._index()
             t = getattr(self.engine, name)
-            extra = 1 if name in ("obs", "dist_adj", "channels") else 0
+            extra = 1 if name in ("obs", "dist_adj", "channels", "diameter") else 0
             self._bufs[name] = None if t is None else t[:self._T + extra].cpu().numpy()
         return self._bufs[name]
 
@@ -204,7 +204,8 @@ class PathBatch(Sequence):
             h = self._buf("dist_adj")
             return h[sl, b].reshape(n, N, N).sum(-1).mean(-1) if h is not None else np.full(n, N)
         if key == "diameters":
-            return np.full(n, N if e.dist_adj is None else 0)
+            h = self._buf("diameter")                                      # the slots dist_adjs / ave_degs come from
+            return h[sl, b].astype(np.int64) if h is not None else np.full(n, N if e.dist_adj is None else 0)
         if key == "ave_trputs":
             return np.full(n, env.n_empty_cells if not pp else 0)
         if key == "success":
@@ -342,6 +343,7 @@ class CentralizedMAOnPolicyVectorizedSampler:
                 for k in range(t, t1):
                     eng.step(k)
                 eng.join()
+                eng.span_diameters(t, t1 - t)                     # (run_span launches it itself)
             if t1 >= t_min:
                 # stop rule on device: first step at which cumulative completed samples >= batch_size (one host read)
                 cs = eng.path_len[counted:t1].sum(dim=1, dtype=torch.int64).cumsum(0) * N + base

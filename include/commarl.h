@@ -157,6 +157,13 @@ int cm_env_agent_fault(cm_env_t h, int32_t mode, float p, float r, const float *
 int cm_comm_delays(int32_t B, int32_t L, int32_t N, const float *dist_adj, const float *link_loss, const int32_t *old_delays,
                    int32_t delay_th, int32_t init, int32_t *delays, void *stream);
 
+/* Hop diameter of S graphs of N vertices (env_communication.py:235-241: what get_graph asks networkx for with
+ * calc_diameter), a pure function of a DEVICE array: vertices i != j are joined when dist_adj[s][i][j] != 0 OR
+ * dist_adj[s][j][i] != 0 (any non-zero value is an edge, the diagonal is ignored).  diameter[s] = the largest shortest-path
+ * hop count of a connected graph (0 for N = 1), 0 for a disconnected one; exactly S ints are written.  1 <= N <= 255;
+ * anything else, or a NULL pointer with S > 0, is CM_ERR_ARG.  S = 0 launches nothing. */
+int cm_graph_diameter(int32_t S, int32_t N, const float *dist_adj, int32_t *diameter, void *stream);
+
 /* Comm-DP policy weights (device pointers), reference state_dict names in comments
  * (SURVEY.md §8 a-16).  Linear weights are passed TRANSPOSED [in,out] (contiguous over the
  * output index) - the veneer keeps a transposed device copy; GCN weights are already [in,out]. */

@@ -8,6 +8,11 @@
 // tanh, chained layers, two workgroups per CU): 1871 clk per layer against 3678, max |error| against an f64 reference
 // 3.4e-7 against 7.0e-7 for the f32 MFMA form (the f16 instruction accumulates its 32 products more accurately than a
 // chain of eight f32 MFMAs does) - far inside the 1e-5 parity bar, and pinned by the reference fixtures.
+// The 2^-25 is an ABSOLUTE floor per operand, so the bound is not scale free: a layer with small weights in front of one with large
+// weights loses more.  Emulated with exact accumulation (tests/acting_regimes.py::split2_forward, at the inputs of
+// tests/test_acting_regimes_cpu.py) on the recorded nets: encoder layers scaled 2^-4 | 2^4 stay at 3.0e-6 of a tensor's scale (the last
+// shift asserted against float64 on the GPU, tests/test_acting_forward_f64.py), 2^-6 | 2^6 reach 5.2e-6 and 2^-10 | 2^10 4.6e-5 - a
+// property of the scheme; neither of the two is a regime the kernels are held to.
 //
 // Same computation, arguments and LDS-resident structure as cm_policy_mfma_dev.h (reference:
 // comm_categorical_mlp_policy.py:48-119, comm_base_net.py:80-108, attention_module.py:26-51,

@@ -147,15 +147,53 @@ __device__ __forceinline__ void write_back(const EnvDev &p, uint32_t b, int sl, 
     }
 }
 
+// The draw stage of the carried map-10 step loop.  A step's common path needs 16 action words (site 7: env, policy step, agent)
+// and 16 prey trial blocks (site 2: env, rng_step, 2 * prey) per wave, and none of their counters depends on anything a step
+// computes (rng_step advances by one per step, reset or not): one 64-lane Philox4x32-10 call therefore serves TWO steps.  The wave
+// runs it on every even step of the loop (paired by the loop index, so a chunk draws the same whatever base it starts at) -
+//   lane >> 5 : step t / t + 1     (lane >> 4) & 1 : action / prey     lane & 15 : policy row c (env c >> 2, agent c & 3) resp.
+//   (env idx >> 2, prey idx & 3)
+// - and each lane leaves its four words in the wave's LDS buffer (`buf`: byte offset, 64 x 16 bytes, this wave's only).  LDS is in
+// order per wave: the readers (policy_tile_w: word x of an action entry; step below: a prey entry) need no barrier.  Same counters,
+// same keys, same words as the per-step calls of the generic builds.  `rng_step`: the lane's group's, at step t.  `act_step`: the
+// sampler's Philox step of step t.  Idle groups of a ragged workgroup draw for env B - 1, as their step shadows it.
+// The rounds are written out here instead of calling philox4x32_10: an instance of its own (see Frags::fetch).
+__device__ __forceinline__ void draw_stage(const EnvDev &p, uint32_t rng_step, int32_t act_gid0, uint32_t act_step, uint32_t act_k0,
+                                           uint32_t act_k1, int envs, bool all_valid, int buf) {
+    const int tx = thread_x(), lane = tx & (WAVE - 1), idx = lane & 15;
+    const bool prey = (lane & 16) != 0;
+    const uint32_t half = (uint32_t)(lane >> 5);
+    const int tgt = (tx >> 6) * 4 + (idx >> 2);                          // the entry's env inside the workgroup
+    const int b_raw = blockIdx.x * 16 + tgt;
+    const bool valid = all_valid || (tgt < envs && b_raw < p.B);
+    const int b = valid ? b_raw : p.B - 1;
+    const uint32_t rs = (uint32_t)__shfl((int)rng_step, (idx >> 2) * 16, WAVE);
+    uint32_t c0 = prey ? (uint32_t)(p.env_id_offset + b) : (uint32_t)(act_gid0 + b_raw);
+    uint32_t c1 = (prey ? rs : act_step) + half;
+    uint32_t c2 = prey ? (uint32_t)SITE_PREY : (uint32_t)SITE_ACTION;
+    uint32_t c3 = prey ? 2u * (uint32_t)(idx & 3) : (uint32_t)(idx & 3);
+    uint32_t k0 = prey ? p.key0 : act_k0, k1 = prey ? p.key1 : act_k1;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    *reinterpret_cast<uint4 *>(smem + buf + 16 * lane) = make_uint4(c0, c1, c2, c3);
+}
+
 // One env step of a 16-lane group: env_stage + env_body + env_pre_carry of the generic carried form.  `act_off`: byte offset of
 // the group's four action words in LDS; `obs_copy`: byte offset of the env's LDS observation copy.  Updates `st` and `pre`.
+// `draw`: byte offset in LDS of the wave's 16 prey entries of this step (draw_stage), 16 bytes apart.
 // `out`: the launch's bases, `off`: this step's element offsets into them.  `last`: the launch's last step - the only one whose
 // state write-back anything reads (no load of the launch reads the state arrays: the next launch and the host see what the last
 // step left), so the others keep the state in registers only.
 // Reference lines as in env_body / pp_small_step.
 __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const Emit em, int act_off, const cm_step_out &out,
                                      const StepOff &off, bool last, int grp, int b_raw, bool grp_live, int lds_base, bool all_valid,
-                                     int obs_copy) {
+                                     int obs_copy, int draw) {
     Grp<16> g;
     const int tx = thread_x();
     g.sub = (tx & (WAVE - 1)) / 16; g.sl = tx % 16;
@@ -165,9 +203,11 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
     const int b = valid ? b_raw : p.B - 1;             // idle groups shadow the last env and never commit
     const Rng rng{ (uint32_t)(p.env_id_offset + b), pre.rng_step, p.key0, p.key1 };
     const bool mine = sl < M;                          // lane j < 4: prey j's trials, agent j's watch test and write-back
-    // the prey's first four trial words depend on nothing the step computes: issued first
-    u32x4 x0 = { 0, 0, 0, 0 };
-    if (mine) x0 = rng.at(SITE_PREY, (uint32_t)(2 * sl));
+    // the prey's first four trial words come from the draw stage's buffer: requested first.  Every lane reads an entry of its own
+    // group (lanes 4-15: one of the four again, never used); two 8-byte reads, the fragment reads keep the 16-byte form to themselves
+    const uint2 *dq = reinterpret_cast<const uint2 *>(smem + draw + 16 * (4 * g.sub + (sl & 3)));
+    const uint2 d01 = dq[0], d23 = dq[1];
+    const u32x4 x0 = { d01.x, d01.y, d23.x, d23.y };
     const int4 araw = *reinterpret_cast<const int4 *>(smem + act_off);
     const int ain[4] = { araw.x, araw.y, araw.z, araw.w };
     int act[4], bad = 0;

@@ -76,6 +76,11 @@ __host__ __device__ constexpr BiasMap bias_map(int L) {
 }
 // LDS bytes of the policy part: the image (fragments | biases) | sampled actions
 __host__ __device__ inline size_t lds_policy_bytes(int L) { return (size_t)pack_w(L).lds_u4 * 16 + WG_ROWS * 4; }
+// The map-10 rollout builds (LEAN) hold h3 / h4 in AGPRs and never read those two slots of the image: they are not staged there, and
+// the room takes the Philox draws a wave computes ahead (cm_rollout_w_body.h): 64 lanes x 16 bytes per wave, touched by that wave only.
+constexpr int DRAW_WAVE_BYTES = 64 * 16;
+__host__ __device__ constexpr int draw_lds_off(int L) { return pack_w(L).h3 * 16; }
+static_assert((pack_w(1).bias - pack_w(1).h3) * 16 >= (WG_ROWS / 16) * DRAW_WAVE_BYTES, "the draw buffer lies inside the h3 / h4 slots");
 
 struct WeightsW {
     const uint4 *pack;                                   // cm_policy_pack's wave-owned section (fragments, then the bias block)
@@ -277,7 +282,8 @@ __device__ __forceinline__ void dense_f32(const Frags<KB, CT> &f, const float *b
 #define CM_WPROBE(i) do { if (a.probe && tid == 0) a.probe[(size_t)blk * mf::NPROBE + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 
 // ---- staging: the LDS image [fragments | biases], all 256 threads, once per launch (no barrier inside) ---------------------
-template <int LHOPS>
+// NO_HEAD (the LEAN builds): the h3 / h4 slots are neither loaded nor stored (their layers are resident in AGPRs, ResidentW<true>).
+template <int LHOPS, bool NO_HEAD = false>
 __device__ __forceinline__ void stage_w(const WeightsW &w, unsigned char *lds, int tid) {
     constexpr PackW pk = pack_w(LHOPS);
     uint4 *WL = reinterpret_cast<uint4 *>(lds);
@@ -288,13 +294,14 @@ __device__ __forceinline__ void stage_w(const WeightsW &w, unsigned char *lds, i
     // moment the CUs spread over the L2 channels instead of queueing on the same lines
     const int rot = (int)((blockIdx.x * 7u) % (unsigned)(2 * BATCH));
     auto chunk_of = [&](int j) { const int c = j + rot; return c >= 2 * BATCH ? c - 2 * BATCH : c; };
+    auto staged = [&](int i) { return i < pk.lds_u4 && !(NO_HEAD && i >= pk.h3 && i < pk.bias); };
 #pragma unroll
     for (int round = 0; round < 2; ++round) {
         uint4 v[BATCH];
 #pragma unroll
-        for (int k = 0; k < BATCH; ++k) { const int i = chunk_of(round * BATCH + k) * 256 + tid; v[k] = w.pack[i < pk.lds_u4 ? i : 0]; }
+        for (int k = 0; k < BATCH; ++k) { const int i = chunk_of(round * BATCH + k) * 256 + tid; v[k] = w.pack[staged(i) ? i : 0]; }
 #pragma unroll
-        for (int k = 0; k < BATCH; ++k) { const int i = chunk_of(round * BATCH + k) * 256 + tid; if (i < pk.lds_u4) WL[i] = v[k]; }
+        for (int k = 0; k < BATCH; ++k) { const int i = chunk_of(round * BATCH + k) * 256 + tid; if (staged(i)) WL[i] = v[k]; }
     }
 }
 
@@ -356,10 +363,12 @@ __device__ __forceinline__ T *at32(T *base, uint32_t elem) { return reinterpret_
 //     instead of in front of it: the first half's fragments are dead by then, and half a layer still covers the reads;
 //   * every layer's biases are read in front of the fragment batch that would otherwise queue ahead of them: e1 / e2 tiles of the
 //     second half in front of the batch at the layer's middle (the first half's reads have only the layer's own fragments ahead),
-//     the hop biases and b1 in front of the hop's batch, b2 / b3 / b4 (no batch left to hide behind) at the middle of x1.
+//     the hop biases and b1 in front of the hop's batch, b2 / b3 / b4 (no batch left to hide behind) at the middle of x1;
+//   * the sampler's Philox word is not computed here: the caller's draw stage has left it in LDS (`draw_off`: byte offset of the
+//     16 action entries of this wave and step, 16 bytes apart, row c's word first), read behind the 128 -> 64 layer.
 template <int LHOPS, bool OBS_LDS = false, bool TRAIN = false, int HEADK = 0, bool STEP32 = false, bool LEAN = false>
 __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const ResidentW<LEAN> &res, const unsigned char *lds, int blk,
-                                              int32_t *act_lds, int obs_row = 0, const StepOff so = StepOff{}) {
+                                              int32_t *act_lds, int obs_row = 0, const StepOff so = StepOff{}, int draw_off = 0) {
     static_assert(!STEP32 || (!TRAIN && HEADK == 0), "step offsets: the acting forward of the rollout");
     static_assert(!LEAN || (!TRAIN && HEADK == 0), "the lean tile: the acting forward of the rollout");
     constexpr int E1H = LEAN ? 4 : 8, E2H = LEAN ? 2 : 4;       // first e1 / e2 tile whose bias is read ahead (at the layer's middle)
@@ -399,7 +408,8 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
 #pragma unroll
         for (int e = 0; e < 8; ++e) { xo.hi[0][e] = h[e]; xo.lo[0][e] = l[e]; }
     }
-    const uint32_t draw_step = a.policy_step + (a.step_base ? *a.step_base : 0u);
+    uint32_t draw_step = 0u;
+    if constexpr (!LEAN) draw_step = a.policy_step + (a.step_base ? *a.step_base : 0u);
 
     // ---- encoder (every layer's fragments are fetched while the layer before it runs) ----
     Frags<1, 8> f_e1; f_e1.template fetch<LEAN>(WL + pk.enc1, lane);
@@ -569,7 +579,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     const Frags<1, 2> &f_h4 = res.pick(res.h4, f_h4_lds);
     // the sampler's uniforms do not depend on the logits
     float u = 0.0f;
-    if constexpr (!TRAIN) {
+    if constexpr (!TRAIN && !LEAN) {
         const u32x4 xr = philox4x32_10((uint32_t)(a.env_id_offset + (int)env_g), draw_step, SITE_ACTION, (uint32_t)agent, a.key0, a.key1);
         u = unit_f32(xr.x);
     }
@@ -579,6 +589,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     Act<1> x3;
     dense_act<2, 2, true, true, SPLIT_DEFAULT, PB_H3>(f_h3, BL + bm.b3, x2, x3, nullptr, lane, sv_row(a.sv_x3, H3), r_b3.regs());
     v4f lg[2];
+    if constexpr (LEAN) u = unit_f32(*reinterpret_cast<const uint32_t *>(lds + draw_off + 16 * c));
     dense_f32<1, 2, false, true, LEAN>(f_h4, BL + bm.b4, x3, lg, lane, r_b4.regs());    // lanes g == 0: logits 0..3 in lg[0], logit 4 in lg[1][0]
 
     CM_WPROBE(9);

@@ -13,7 +13,9 @@
 // plan_rollout_w has established for it: five actions, no avail mask, sampling (not greedy), every output the engine passes by
 // default present, every trajectory buffer below 2^31 bytes.  The sampling tail is straight-line code, a step's slot in a
 // buffer is a 32-bit element offset from the launch's base (no per-step pointer rebuild, no null test at a store), and the
-// state arrays are written by the launch's last step only.
+// state arrays are written by the launch's last step only.  The step's common Philox draws (the sampler's action word, the preys'
+// first four trial words) are computed for two steps at once on every even step of the loop (pp10::draw_stage) and handed over
+// through a per-wave LDS buffer in the image's h3 / h4 slots, which these builds do not stage.
     static_assert(SHAPE == 0 || CARRY, "shape constants are built into the carried form only");
     if constexpr (SHAPE == 1) {
         p.S = 10; p.M = 4; p.R = 1; p.W = 3; p.d = 21; p.rcp_d = 1.0f / 21.0f; p.rcp_W = 1.0f / 3.0f; p.rcp_WW = 1.0f / 9.0f;
@@ -22,6 +24,9 @@
         a.avail = nullptr; a.greedy = 0; a.adj = nullptr; a.chan = nullptr; a.probe = nullptr;
         __builtin_assume(a.actions != nullptr); __builtin_assume(a.probs != nullptr); __builtin_assume(a.attn != nullptr);
         if constexpr (!PROBES) p.stop = 0;                               // ENV_PROBE folds away
+        // the sampler's Philox base is constant for the launch (the folded tail advances it behind every wave's last read): once, here
+        a.policy_step += a.step_base ? *a.step_base : 0u;
+        a.step_base = nullptr;
     }
     const int n_act = SHAPE == 1 ? 5 : w.n_act;
     static_assert(!CARRY || (PRE && !TAPE), "the carried form is the prefetching, tape-less build");
@@ -33,10 +38,11 @@
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_w[];
     constexpr int LPE = 16;
     constexpr int ACT_OFF = mw::pack_w(LHOPS).lds_u4 * 16, ENV_BASE = ACT_OFF + mw::WG_ROWS * 4;
+    constexpr int DRAW_OFF = mw::draw_lds_off(LHOPS);                    // SHAPE 1: the draw buffers, in the image's unstaged h3 / h4 slots
     int32_t *act = reinterpret_cast<int32_t *>(lds_w + ACT_OFF);
     const bool probe = PROBES && p.stop == -2 && blockIdx.x == 0 && thread_x() == 0;
     const unsigned long long t_in = probe ? __builtin_amdgcn_s_memtime() : 0ull;
-    mw::stage_w<LHOPS>(w, lds_w, thread_x());
+    mw::stage_w<LHOPS, SHAPE == 1>(w, lds_w, thread_x());
     mw::ResidentW<SHAPE == 1> res;
     res.template fetch<LHOPS>(w, thread_x() & 63);
     __syncthreads();                                                     // the only workgroup barrier of the launch
@@ -88,10 +94,16 @@
         at.attn = a.attn ? a.attn + (size_t)t * c.attn : nullptr;
         }
         const unsigned long long t0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
+        // SHAPE 1: the Philox words of steps t and t + 1, on even t (pp10::draw_stage); entry 32 h + 16 k + i of the wave's buffer
+        const int draw = DRAW_OFF + __builtin_amdgcn_readfirstlane(tx >> 6) * mw::DRAW_WAVE_BYTES + (t & 1) * (mw::DRAW_WAVE_BYTES / 2);   // wave-uniform: a scalar
+        if constexpr (SHAPE == 1) {
+            if ((t & 1) == 0) pp10::draw_stage(p, pp.rng_step, a.env_id_offset, at.policy_step, a.key0, a.key1, envs, FULLWG, draw);
+            asm volatile("" ::: "memory");
+        }
         if constexpr (PRE && !CARRY) pre = env_prefetch<CM_PP, LPE>(p, b_raw, live);   // env state requested in front of the policy forward
         if constexpr (SHAPE == 1)
             mw::policy_tile_w<LHOPS, true, false, 0, true, true>(at, n_act, res, lds_w, blockIdx.x, act, obs_row,
-                                                           mw::StepOff{ ut * (uint32_t)c.actions, ut * (uint32_t)c.probs, ut * (uint32_t)c.attn });
+                                                           mw::StepOff{ ut * (uint32_t)c.actions, ut * (uint32_t)c.probs, ut * (uint32_t)c.attn }, draw);
         else mw::policy_tile_w<LHOPS, CARRY>(at, n_act, res, lds_w, blockIdx.x, act, obs_row);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's action words are in LDS
         const unsigned long long t1 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -113,7 +125,7 @@
             if constexpr (CARRY && SHAPE == 1) {
                 const pp10::StepOff so{ ut * (uint32_t)c.obs, ut * (uint32_t)c.reward, ut * (uint32_t)c.reward_f64, ut * (uint32_t)c.done,
                                         ut * (uint32_t)c.details, ut * (uint32_t)c.prey_alive, ut * (uint32_t)c.success, ut * (uint32_t)c.path_len };
-                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, so, t == c.n_steps - 1, grp, b_raw, live, ENV_BASE, FULLWG, obs_env);
+                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, so, t == c.n_steps - 1, grp, b_raw, live, ENV_BASE, FULLWG, obs_env, draw + mw::DRAW_WAVE_BYTES / 4);
             } else if constexpr (CARRY) {
                 const bool bad = env_stage<CM_PP, LPE>(p, pre, my_act, grp, ENV_BASE);
                 EnvCarry carry{ pre.step_count_in, pre.succ, 0 };

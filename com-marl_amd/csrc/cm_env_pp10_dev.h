@@ -202,12 +202,10 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
     const bool valid = all_valid || (grp_live && b_raw < p.B);
     const int b = valid ? b_raw : p.B - 1;             // idle groups shadow the last env and never commit
     const Rng rng{ (uint32_t)(p.env_id_offset + b), pre.rng_step, p.key0, p.key1 };
-    const bool mine = sl < M;                          // lane j < 4: prey j's trials, agent j's watch test and write-back
-    // the prey's first four trial words come from the draw stage's buffer: requested first.  Every lane reads an entry of its own
-    // group (lanes 4-15: one of the four again, never used); two 8-byte reads, the fragment reads keep the 16-byte form to themselves
-    const uint2 *dq = reinterpret_cast<const uint2 *>(smem + draw + 16 * (4 * g.sub + (sl & 3)));
-    const uint2 d01 = dq[0], d23 = dq[1];
-    const u32x4 x0 = { d01.x, d01.y, d23.x, d23.y };
+    const bool mine = sl < M;                          // lane j < 4: prey j's move, agent j's watch test and write-back
+    // the prey's first four trial words come from the draw stage's buffer: requested first.  Lane sl of a group runs trial sl >> 2
+    // of prey sl & 3 (16 lanes, 16 (prey, trial) pairs): word sl >> 2 of the prey's entry, one 4-byte read
+    const uint32_t xw = *reinterpret_cast<const uint32_t *>(smem + draw + 16 * (4 * g.sub + (sl & 3)) + 4 * (sl >> 2));
     const int4 araw = *reinterpret_cast<const int4 *>(smem + act_off);
     const int ain[4] = { araw.x, araw.y, araw.z, araw.w };
     int act[4], bad = 0;
@@ -252,14 +250,19 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
         const uint32_t my = byte_at(ppos, sl & 3);
         const int my_alive = mine & (int)((flags >> (sl & 3)) & 1u);
         const int cnt = my_alive ? agents_next(ag, my) : 0;
-        int mv = 4;
-        int found = (my_alive ^ 1) | ((p.load == 2) & (cnt >= 2));      // dead, or captured this step: no trial
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {                  // first of <= 5 draws whose target has no predator neighbour
-            const int m = prey_move_from_u32(pick(x0, t));
-            const int ok = no_agent_next(ag, my + delta_of(m)) & (found ^ 1);
-            mv = ok ? m : mv; found |= ok;
-        }
+        // first of <= 5 draws whose target has no predator neighbour.  A trial's test depends on no other trial, only "the first
+        // that passes" orders them: this lane's trial as a 3-bit code (its move, 7 = failed), and lane j takes the codes of
+        // lanes j + 4, j + 8, j + 12 of its row by row-shift DPP moves (a wave's rows of 16 are the groups, and the whole wave
+        // is active here; the old value 7 stands where a shift reaches past the row: lanes >= 4, which discard it)
+        const int m0 = prey_move_from_u32(xw);
+        const int c0 = no_agent_next(ag, my + delta_of(m0)) ? m0 : 7;
+        const int c1 = __builtin_amdgcn_update_dpp(7, c0, 0x104, 0xf, 0xf, false);   // row_shl:4
+        const int c2 = __builtin_amdgcn_update_dpp(7, c0, 0x108, 0xf, 0xf, false);   // row_shl:8
+        const int c3 = __builtin_amdgcn_update_dpp(7, c0, 0x10c, 0xf, 0xf, false);   // row_shl:12
+        const int first = c0 != 7 ? c0 : (c1 != 7 ? c1 : (c2 != 7 ? c2 : c3));
+        const int none = (my_alive ^ 1) | ((p.load == 2) & (cnt >= 2));  // dead, or captured this step: no trial
+        int mv = (none | (first == 7)) ? 4 : first;
+        const int found = none | (first != 7);
         if (!found) {                                  // fifth draw: second Philox call, rare
             const u32x4 x1 = rng.at(SITE_PREY, (uint32_t)(2 * sl + 1));
             const int m = prey_move_from_u32(x1.x);

@@ -17,10 +17,14 @@ Differences a maintainer should know (documented, not silent):
   * with a range-limited adjacency, ``nodeDeg`` of an episode's terminal step is the degree *before*
     that step (the env auto-resets on done, vec_env_executor.py:36-43, so the post-step graph of a
     finished episode is never materialised).
+
+``eval_summary`` plays the same rounds and returns only each policy's score (the CSV row of exp_runners/testing.py:329-335),
+reduced on the device by cm_episode_stats / cm_episode_means: nothing but K x 12 doubles is copied to the host.
 """
 import numpy as np
 import torch
 
+from . import _lib as L
 from .nets import PolicySet
 from .rollout import RolloutEngine
 
@@ -181,6 +185,96 @@ def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200,
     env.eval_n_epi = len(data[0])
     env.last_eval_average_reward = [(sum(r) / len(r)) / base.bound_return for r in eval_rewards]
     return [(data[k], success[k], epi_rewards[k], base.bound_return) for k in range(K)]
+
+
+SUMMARY_STATS = ['return_std', 'return_min', 'return_max']     # cm_episode_means columns behind the CM_EPI_COLS means
+
+
+def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
+                 episodes=False):
+    """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
+    eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
+    the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
+    VECTORS: the per-episode values eval_model returns as epi_success / epi_rewards); ONE cm_episode_means launch then reduces
+    the table, and its [K, 12] doubles are the only device-to-host copy of the call.
+    -> a list of K dicts (one dict for a single policy): n_episodes; success and every name of VECTORS, each the mean over the
+    episodes (the columns of exp_runners/testing.py:329, see summary_row); return_std (population), return_min, return_max of
+    the episode returns; bound_return; with episodes=True also `episodes`, the policy's [n_eval_episodes, 9] slice of the table
+    as a device tensor (column 1 is what testing.py keeps as rewMat2).  Sums are f64 in a fixed order: two calls on the same
+    episodes give the same bits; against the host loop the values agree to f64 rounding (nodeDeg to f32 rounding, the host
+    path rounds each step's degree to f32).
+    bound_return is the scalar env.bound_return for both scenarios: the Coverage twin of eval_model differs only in returning
+    it once per episode, so there is no _co entry here.  render / inspect_steps are not parameters (UI is out of scope).
+    flag[0] set returns None per policy, as eval_models returns its empty tuples.  Afterwards env.eval_n_epi and
+    env.last_eval_average_reward (a list of K for several policies) are what eval_models / eval_model leave."""
+    single = not isinstance(policies, (PolicySet, list, tuple))
+    if flag is not None and flag[0]:
+        return None if single else [None for _ in policies]
+    base = getattr(env, "env", env)
+    batch = base.batch
+    B, N = batch.B, batch.N
+    T = int(max_env_steps)
+    if single:
+        ps, K = policies, 1
+    else:
+        ps = policies if isinstance(policies, PolicySet) else PolicySet(policies)
+        K = len(ps)
+        if B % K:
+            raise ValueError(f"eval_summary: the {B} envs of the wrapper do not split evenly between {K} policies")
+    Bk = B // K
+    if T > batch.cfg.max_path_length:
+        raise ValueError(f"max_env_steps={T} exceeds the env's max_path_length={batch.cfg.max_path_length}")
+    n_epi = int(n_eval_episodes)
+    if n_epi < 1:
+        raise ValueError("eval_summary: n_eval_episodes must be at least 1")
+    env.eval_n_epi = 0
+    ps.sync_weights()
+    ps.reset([True] * Bk)
+    if single:
+        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False)
+    else:
+        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, groups=[Bk] * K)
+    lib = L.lib()
+    scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
+    table = torch.zeros(K, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
+    out = torch.empty(K, L.SUM_COLS, dtype=torch.float64, device=batch.device)
+    done = 0
+    while done < n_epi:
+        eng.reset()
+        if single or not eng.steps_fused(0, T, greedy=bool(eval_greedy)):     # eval_model steps one by one, eval_models by chunk
+            eng.fork()
+            for t in range(T):
+                eng.step(t, greedy=bool(eval_greedy))
+            eng.join()
+        eng.bump(T)
+        batch.check_status()
+        take = min(Bk, n_epi - done)
+        L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
+                                     L.ptr(eng.path_len), L.ptr(eng.dist_adj), Bk, take, n_epi, done, L.ptr(table),
+                                     L.current_stream()), "cm_episode_stats")
+        done += take
+    L.check(lib.cm_episode_means(K, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
+    host = out.cpu().numpy()
+    bound = base.bound_return
+    res = []
+    for k in range(K):
+        d = dict(n_episodes=n_epi, success=float(host[k, 0]))
+        d.update({vec: float(host[k, 1 + i]) for i, vec in enumerate(VECTORS)})
+        d.update({name: float(host[k, L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
+        d["bound_return"] = bound
+        if episodes:
+            d["episodes"] = table[k]
+        res.append(d)
+    env.eval_n_epi = n_epi
+    avg = [d["reward"] / bound for d in res]
+    env.last_eval_average_reward = avg[0] if single else avg
+    return res[0] if single else res
+
+
+def summary_row(summary):
+    """One eval_summary dict -> [success] + the VECTORS means: the list exp_runners/testing.py:329 writes between the epoch
+    columns and the time stamp of a checkpoint's CSV row."""
+    return [summary["success"]] + [summary[vec] for vec in VECTORS]
 
 
 def eval_models_co(env, policies, itr=None, **kwargs):

@@ -164,6 +164,53 @@ int cm_comm_delays(int32_t B, int32_t L, int32_t N, const float *dist_adj, const
  * anything else, or a NULL pointer with S > 0, is CM_ERR_ARG.  S = 0 launches nothing. */
 int cm_graph_diameter(int32_t S, int32_t N, const float *dist_adj, int32_t *diameter, void *stream);
 
+/* Episode statistics of an evaluation round, reduced on the device: what the reference's eval loop accumulates per episode
+ * (eval_pp.py:60-91) and exp_runners/testing.py:329-335 averages into one CSV row per checkpoint.  Pure functions of DEVICE
+ * arrays: the time-major trajectory buffers of a T-step rollout over B envs (the cm_step_out arrays, one slot per step).
+ *
+ * cm_episode_stats summarises the FIRST episode of selected envs into rows of CM_EPI_COLS doubles.  Env b belongs to group
+ * k = b / group_size and has index j = b % group_size in it; envs with j >= take are not read and nothing is written for them;
+ * every other env's row is episodes[k * episodes_per_group + row0 + j].  The episode's length n is t + 1 for the first t with
+ * path_len[t][b] > 0, or T when there is none (the step limit cut it); later episodes of an auto-reset env are ignored.
+ * Over steps 0 .. n-1, with nA = N and d = details[t][b]:
+ *   column 0 success     = success[n-1][b]
+ *          1 reward      = sum of reward_f64 (f64)
+ *          2 capture_cnt = sum d[0]        (CM_CO: / nA)
+ *          3 step_cnt    = n
+ *          4 move_cnt    = sum d[1] / nA
+ *          5 penalty_cnt = sum d[2]        (CM_CO: / nA)
+ *          6 nodeDeg     = N when dist_adj is NULL (the constant full graph); else the mean of the n entries deg[1], ...,
+ *                          deg[n-1], deg[n-1] (n = 1: the single entry deg[0]), deg[t] = (sum of the N x N floats of
+ *                          dist_adj[t][b]) / N: the graph after the step, and for the terminal step the one before it (the env
+ *                          auto-resets on done, so the post-step graph of a finished episode is never materialised)
+ *          7 variable    = sum d[4] / nA
+ *          8 vars2       = 0               (CM_CO: sum d[3] / nA)
+ * The detail columns are summed as integers and divided once; adjacency entries are 0 or 1 and summed as integers.
+ *
+ * cm_episode_means reduces each of K groups of E consecutive rows to CM_SUM_COLS doubles: the mean of every column, then for
+ * the reward column the population standard deviation sqrt(mean((x - mean)^2)) (second pass around the mean), the minimum and
+ * the maximum.
+ *
+ * Both: no atomics - every sum has one fixed order, so two launches on the same inputs write the same bits; exactly the named
+ * rows are written (B / group_size * take rows of `episodes`, K rows of `summary`).  B = 0 or take = 0 launches nothing.
+ * CM_ERR_ARG (text in cm_last_error) before anything is launched: T < 1, N outside 1..255, a scenario other than CM_PP / CM_CO,
+ * group_size < 1 or not a divisor of B, take > group_size, row0 < 0 or row0 + take > episodes_per_group, K < 1, E < 1, or a
+ * NULL pointer other than dist_adj where there is work to do. */
+#define CM_EPI_COLS 9    /* success, then the reference's VECTORS in order (testing.py:209): reward, capture_cnt, step_cnt,
+                            move_cnt, penalty_cnt, nodeDeg, variable, vars2 */
+#define CM_SUM_COLS 12   /* the 9 column means, then std (population), min, max of the reward column */
+int cm_episode_stats(int32_t T, int32_t B, int32_t N, int32_t scenario,      /* CM_PP / CM_CO */
+                     const double *reward_f64,   /* [T,B]   */
+                     const int32_t *details,     /* [T,B,6] */
+                     const int32_t *success,     /* [T,B]   */
+                     const int32_t *path_len,    /* [T,B]   */
+                     const float *dist_adj,      /* [T+1,B,N,N], or NULL = constant full graph */
+                     int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0,
+                     double *episodes,           /* [B/group_size * episodes_per_group, CM_EPI_COLS] */
+                     void *stream);
+int cm_episode_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPI_COLS] */,
+                     double *summary /* [K, CM_SUM_COLS] */, void *stream);
+
 /* Comm-DP policy weights (device pointers), reference state_dict names in comments
  * (SURVEY.md §8 a-16).  Linear weights are passed TRANSPOSED [in,out] (contiguous over the
  * output index) - the veneer keeps a transposed device copy; GCN weights are already [in,out]. */

@@ -42,6 +42,12 @@ class EnvState(C.Structure):
                                           "total_capture", "success", "ge_state", "rng_step")]
 
 
+class EnvCond(C.Structure):
+    """cm_env_cond: one env's comm condition (cm_env_set_conditions); envs.COND_DTYPE is the same record for numpy."""
+    _fields_ = [("rcom", C.c_int32), ("ploss", C.c_float), ("pgb", C.c_float), ("pbg", C.c_float), ("rng_id", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class PolicyWeights(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("d", "n_agents", "n_hops", "enc_hidden", "emb", "h1", "h2", "h3", "n_act",
                                          "no_residual")] + [
@@ -122,6 +128,8 @@ _SIGNATURES = {
     "cm_env_status": (C.c_int, [C.c_void_p]),
     "cm_env_get_state": (C.c_int, [C.c_void_p, C.POINTER(EnvState)]),
     "cm_env_set_state": (C.c_int, [C.c_void_p, C.POINTER(EnvState)]),
+    "cm_env_set_conditions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_env_has_conditions": (C.c_int, [C.c_void_p]),
     "cm_policy_forward": (C.c_int, [C.POINTER(PolicyWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -20,6 +20,7 @@
 //   * Observation windows, the range adjacency and the channel masks are emitted with the 64
 //     lanes striding the flattened [N*d] / [N*N] / [L*N*N] rows -> 256-B coalesced stores.
 // The kernel is HBM/latency bound integer work; there is nothing GEMM-shaped here.
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -240,6 +241,9 @@ extern "C" int cm_env_create(const cm_env_cfg *cfg, cm_env_t *out) {
 extern "C" int cm_env_destroy(cm_env_t h) {
     if (!h) return CM_OK;
     hipFree(h->arena);
+    if (h->cond) hipFree(h->cond);
+    if (h->cond_host) hipHostFree(h->cond_host);
+    if (h->cond_copied) hipEventDestroy(h->cond_copied);
     delete h;
     return CM_OK;
 }
@@ -281,6 +285,9 @@ static int launch(cm_env_t h, const int32_t *actions, const cm_rng_tape *tape, c
     const dim3 grid((d.B + G - 1) / G), block(WAVE);
     const hipStream_t st = (hipStream_t)stream;
     static const bool wide_on = [] { const char *e = getenv("COMMARL_ENV_WIDE"); return !(e && e[0] == '0'); }();
+    h->started = true;
+    // a handle with a condition table: the same choices below, the twins of cm_env_cond.hip launched
+    if (h->cond) return launch_env_cond(h, wide_on && d.lpe == 64 && d.B <= 1536, actions, *out, st, reset_only);
     // wide form when the narrow kernel would put at most one wave on each of the 1024 SIMDs (measured, narrow -> wide:
     // N = 72 x 1024 envs 82 -> 66 us, N = 54 x 1024 78 -> 56 us; N = 24 x 2048 is two waves per SIMD and stays narrow, 36 vs 44 us)
     const int G_ = WAVE / d.lpe;
@@ -316,6 +323,57 @@ extern "C" int cm_env_reset(cm_env_t h, const cm_rng_tape *tape, const cm_step_o
 
 extern "C" int cm_env_step(cm_env_t h, const int32_t *actions, const cm_rng_tape *tape, const cm_step_out *out, void *stream) {
     return launch(h, actions, tape, out, stream, 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// per-env comm conditions (include/commarl.h): the table the kernels of cm_env_cond.hip read
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int cm_env_has_conditions(cm_env_t h) { return h ? (h->cond ? 1 : 0) : set_error(CM_ERR_ARG, "null handle"); }
+
+extern "C" int cm_env_set_conditions(cm_env_t h, const cm_env_cond *host_table, void *stream) {
+    if (!h) return set_error(CM_ERR_ARG, "cm_env_set_conditions: null handle");
+    if (!host_table) return set_error(CM_ERR_ARG, "cm_env_set_conditions: null table");
+    if (h->cfg.rng_mode == CM_RNG_TAPE)
+        return set_error(CM_ERR_ARG, "cm_env_set_conditions: tape mode replays draws recorded under one condition; conditions need CM_RNG_PHILOX");
+    if (!h->cond && h->started)
+        return set_error(CM_ERR_ARG, "cm_env_set_conditions: the first table must be set before the handle's first reset / step "
+                                     "(callers size their dist_adj buffers by cm_env_adj_is_const)");
+    const EnvDev &d = h->dev;
+    const size_t B = (size_t)d.B, bytes = B * sizeof(EnvCondDev);
+    for (size_t b = 0; b < B; ++b) {
+        const cm_env_cond &c = host_table[b];
+        const char *bad = nullptr;
+        if (c.rcom < 0) bad = "rcom < 0";
+        else if (d.channel == CM_CH_IID && !(c.ploss >= 0.0f && c.ploss <= 1.0f)) bad = "ploss outside [0, 1]";
+        else if (d.channel == CM_CH_GE && !(c.pgb >= 0.0f && c.pgb <= 1.0f)) bad = "pgb outside [0, 1]";
+        else if (d.channel == CM_CH_GE && !(c.pbg >= 0.0f && c.pbg <= 1.0f)) bad = "pbg outside [0, 1]";
+        else if (c.reserved[0] || c.reserved[1] || c.reserved[2]) bad = "non-zero reserved word";
+        if (bad) return set_error(CM_ERR_ARG, "cm_env_set_conditions: env " + std::to_string(b) + ": " + bad);
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    CM_HIP(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_error(CM_ERR_ARG, "cm_env_set_conditions: not inside a stream capture (call it between replays: a captured graph reads the new table)");
+    if (!h->cond_host) CM_HIP(hipHostMalloc(&h->cond_host, bytes, hipHostMallocDefault));
+    if (!h->cond_copied) CM_HIP(hipEventCreateWithFlags(&h->cond_copied, hipEventDisableTiming));
+    else CM_HIP(hipEventSynchronize(h->cond_copied));                    // the previous copy has read the image
+    void *dev = h->cond;
+    if (!dev) CM_HIP(hipMalloc(&dev, bytes));
+    EnvCondDev *img = (EnvCondDev *)h->cond_host;
+    for (size_t b = 0; b < B; ++b) {
+        const cm_env_cond &c = host_table[b];
+        const bool full = c.rcom == 0 || c.rcom + 1 >= h->cfg.grid;      // env_communication.py:71-72, per env
+        img[b] = EnvCondDev{ full ? INT32_MAX : 2 * c.rcom * c.rcom, c.ploss, c.pgb, c.pbg, c.rng_id, { 0, 0, 0 } };
+    }
+    hipError_t e = hipMemcpyAsync(dev, img, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(h->cond_copied, st);
+    if (e != hipSuccess) { if (!h->cond) (void)hipFree(dev); return hip_fail(e, "cm_env_set_conditions copy"); }
+    if (!h->cond) {                                                      // first table: every env computes its own adjacency from now on
+        h->cond = dev;
+        h->dev.adj_const = 0;
+    }
+    return CM_OK;
 }
 
 extern "C" int cm_env_status(cm_env_t h) {

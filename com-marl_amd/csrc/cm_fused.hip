@@ -179,6 +179,7 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
                         float *probs, float *attn, const cm_rng_tape *tape, const cm_step_out *out, void *stream,
                         const ChunkArgs *chunk) {
     if (int rc = check_rollout_args("cm_rollout_step", h, w, obs, out)) return rc;
+    if (h->cond) return 1;                           // per-env comm conditions: only the stand-alone env step reads the table
     const EnvDev &d = h->dev;
     if (!w->mfma_pack || !policy_shape_ok(w)) return 1;
     if (int rc = check_tape(h, tape, false)) return rc;

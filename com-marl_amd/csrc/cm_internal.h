@@ -94,6 +94,16 @@ struct EnvDev {
     const double *rew_lut;    // count-indexed f64 reward terms (no f64 division on the device)
 };
 
+// Device image of one cm_env_cond record (cm_env_set_conditions): the same 32 bytes, with the range already squared
+// (EnvDev.rc2; INT32_MAX for a fully connected env) so that the kernel patches EnvDev without arithmetic.
+struct EnvCondDev {
+    int32_t rc2;
+    float ploss, pgb, pbg;
+    int32_t rng_id;
+    int32_t reserved[3];
+};
+static_assert(sizeof(EnvCondDev) == sizeof(cm_env_cond) && sizeof(EnvCondDev) == 32, "one 32-byte record per env");
+
 }  // namespace cm
 
 struct cm_env {
@@ -102,6 +112,12 @@ struct cm_env {
     size_t lds_bytes;
     void *arena;              // one hipMalloc for all state
     size_t arena_bytes;
+    // cm_env_set_conditions: the [B] device table (NULL = none: every env has the handle's comm scalars), the pinned host
+    // image later calls copy from, and the event behind the last copy (the image is not rewritten before that copy has run)
+    void *cond;
+    void *cond_host;
+    hipEvent_t cond_copied;
+    bool started;             // a reset / step was launched: the first cm_env_set_conditions comes too late
 };
 
 namespace cm {
@@ -122,6 +138,8 @@ static inline ChunkArgs chunk_args(int n_steps, const cm_chunk_strides &st) {
 }
 
 int check_tape(const cm_env *h, const cm_rng_tape *tape, bool is_reset);   // cm_env.hip: tape pointers the config needs
+// cm_env_cond.hip: the env step of a handle with a condition table; `wide` is launch()'s narrow / wide choice
+int launch_env_cond(const cm_env *h, bool wide, const int32_t *actions, const cm_step_out &out, hipStream_t st, int reset_only);
 namespace mf {
 // cm_policy_mfma.hip: one layer's weights [K,OUT] -> MFMA B fragments [out_pad/16][kpad/16][64 lanes][4], zero padded
 int pack_one(const float *Wt, int K, int OUT, int kpad, int out_pad, float *dst, void *stream);

@@ -53,6 +53,7 @@ extern "C" int cm_rollout_chunk_multi(cm_env_t h, const cm_policy_weights *w, co
     if (set->n_wg != (d.B + mw::WG_ENVS - 1) / mw::WG_ENVS)
         return set_error(CM_ERR_ARG, "cm_rollout_chunk_multi: n_wg must be ceil(B / 16) of the env handle");
     if (n_steps == 0) return CM_OK;
+    if (h->cond) return 1;                           // per-env comm conditions: only the stand-alone env step reads the table
     if (!policy_shape_ok(w) || !policy_w_enabled() || !shape_ok_rollout_w(d.N, d.d, d.L, w->n_act)) return 1;
     const mf::FwdArgs a = rollout_fwd_args(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy,
                                            actions, probs, attn);

@@ -88,6 +88,68 @@ def make_cfg(scenario, params, n_envs, *, seed=1, env_id_offset=0, rng_mode=L.RN
     return c, channel, pl, bool(p.get("calc_diameter"))
 
 
+# ---- per-env comm conditions (cm_env_set_conditions): pure numpy, no GPU ----------------------------------------------------
+COND_KEYS = ("Rcom", "pl", "Pgb", "Pbg")
+# cm_env_cond, record for record (include/commarl.h)
+COND_DTYPE = np.dtype([("rcom", "<i4"), ("ploss", "<f4"), ("pgb", "<f4"), ("pbg", "<f4"), ("rng_id", "<i4"), ("reserved", "<i4", (3,))])
+
+
+def conditions_channel(conditions, channel=None):
+    """The channel kind of a batch built with `conditions`: the explicit one; else IID if any condition has 0 < pl < 1; else
+    None - make_cfg derives it from params as it does without conditions."""
+    if channel is not None:
+        return channel
+    for c in conditions:
+        pl = c.get("pl")
+        if pl is not None and 0 < pl < 1:
+            return "IID"
+    return None
+
+
+def condition_table(scenario, params, conditions, condition_of, rng_ids=None, *, channel=None, env_id_offset=0):
+    """The [B] table cm_env_set_conditions takes (structured array, COND_DTYPE): env b gets conditions[condition_of[b]] and the
+    Philox env id rng_ids[b] (default env_id_offset + b: the id it has without a table).  A condition is a dict with optional keys
+    Rcom, pl, Pgb, Pbg (the runners' --teRcom / --tepl / --Pgb / --Pbg); a missing key takes the value make_cfg takes from
+    params.  The channel kind is one per batch (conditions_channel): ValueError for a pl given when it is not IID and for Pgb /
+    Pbg given when it is not GE - the env step would not read them - as for an index outside the list, an unknown key, a
+    negative Rcom and a probability outside [0, 1]."""
+    conditions = [dict(c) for c in conditions]
+    if not conditions:
+        raise ValueError("condition_table: at least one condition")
+    cond_of = np.asarray(condition_of)
+    if cond_of.ndim != 1 or cond_of.size == 0 or not np.issubdtype(cond_of.dtype, np.integer):
+        raise ValueError("condition_table: condition_of is an int array [B], B >= 1")
+    B = cond_of.shape[0]
+    if cond_of.min() < 0 or cond_of.max() >= len(conditions):
+        raise ValueError(f"condition_table: condition_of names a condition outside 0..{len(conditions) - 1}")
+    cfg, kind, _, _ = make_cfg(scenario, params, B, env_id_offset=env_id_offset, channel=conditions_channel(conditions, channel))
+    rows = np.zeros(len(conditions), COND_DTYPE)
+    for k, c in enumerate(conditions):
+        extra = set(c) - set(COND_KEYS)
+        if extra:
+            raise ValueError(f"condition {k}: unknown keys {sorted(extra)} (a condition has {COND_KEYS})")
+        if "pl" in c and kind != "IID":
+            raise ValueError(f"condition {k}: pl is given but the batch's channel is {kind}, not IID: the env step would ignore it")
+        if ("Pgb" in c or "Pbg" in c) and kind != "GE":
+            raise ValueError(f"condition {k}: Pgb / Pbg are given but the batch's channel is {kind}, not GE: the env step would ignore them")
+        rcom = c.get("Rcom", cfg.rcom)
+        if int(rcom) != rcom or rcom < 0:
+            raise ValueError(f"condition {k}: Rcom must be a non-negative integer, got {rcom}")
+        vals = dict(pl=c.get("pl", cfg.ploss), Pgb=c.get("Pgb", cfg.pgb), Pbg=c.get("Pbg", cfg.pbg))
+        for name, v in vals.items():
+            if not 0 <= v <= 1:
+                raise ValueError(f"condition {k}: {name}={v} is outside [0, 1]")
+        rows[k]["rcom"], rows[k]["ploss"], rows[k]["pgb"], rows[k]["pbg"] = int(rcom), vals["pl"], vals["Pgb"], vals["Pbg"]
+    ids = int(env_id_offset) + np.arange(B, dtype=np.int64) if rng_ids is None else np.asarray(rng_ids)
+    if ids.shape != (B,) or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError(f"condition_table: rng_ids is an int array [{B}]")
+    if ids.min() < -2 ** 31 or ids.max() >= 2 ** 31:
+        raise ValueError("condition_table: rng_ids are 32-bit Philox env ids")
+    table = rows[cond_of]
+    table["rng_id"] = ids
+    return np.ascontiguousarray(table)
+
+
 def graph_diameter(dist_adj, out=None):
     """Hop diameter of every graph of a contiguous f32 CUDA tensor [..., N, N] (cm_graph_diameter: an edge where either
     direction is non-zero, the diagonal ignored, 0 for a disconnected graph - get_graph's calc_diameter branch,
@@ -107,7 +169,11 @@ class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 
     def __init__(self, scenario, params, n_envs=1, *, device="cuda:0", seed=None, env_id_offset=0, rng_mode="philox",
-                 max_steps=None, max_path_length=None, channel=None):
+                 max_steps=None, max_path_length=None, channel=None, conditions=None, condition_of=None, rng_ids=None):
+        """conditions: a list of C comm conditions (condition_table) - env b steps under conditions[condition_of[b]] (default:
+        C contiguous blocks of B / C envs) and draws with the Philox env id rng_ids[b] (default: its own, env_id_offset + b).
+        Without an explicit `channel` the kind is IID if any condition has 0 < pl < 1, else what params give.  Such a batch
+        records every env's dist_adj (adj_const is off) and steps in two launches; set_conditions() replaces the values later."""
         assert scenario in ("pp", "co")
         self.scenario, self.params = scenario, dict(params)
         self.device = torch.device(device)
@@ -115,6 +181,9 @@ class GridEnvBatch:
             raise L.CommarlError("GridEnvBatch runs on the MI355X only (device must be cuda:k); there is no CPU path")
         seed = int(params.get("seed", 1) if seed is None else seed)
         mode = L.RNG_TAPE if rng_mode == "tape" else L.RNG_PHILOX
+        if conditions is not None:
+            conditions = [dict(c) for c in conditions]
+            channel = conditions_channel(conditions, channel)
         self.cfg, self.channelType, self.pl, calc_diameter = make_cfg(scenario, params, n_envs, seed=seed, env_id_offset=env_id_offset,
                                                        rng_mode=mode, max_steps=max_steps,
                                                        max_path_length=max_path_length, channel=channel)
@@ -123,6 +192,13 @@ class GridEnvBatch:
             L.check(L.lib().cm_env_create(C.byref(self.cfg), C.byref(self._h)), "cm_env_create")
         c = self.cfg
         self.B, self.N, self.M, self.Lh = c.n_envs, c.n_agents, c.n_preys, c.n_hops
+        self.conditions = self.condition_of = self.rng_ids = None
+        if conditions is not None:                          # before the const-ness queries: the first table turns adj_const off
+            if condition_of is None:
+                if self.B % len(conditions):
+                    raise ValueError(f"{self.B} envs do not split evenly between {len(conditions)} conditions: pass condition_of=")
+                condition_of = np.repeat(np.arange(len(conditions)), self.B // len(conditions))
+            self._upload_conditions(conditions, condition_of, rng_ids)
         self.S = c.grid if scenario == "pp" else c.grid + 2
         self.d = L.lib().cm_env_obs_dim(self._h)
         self.n_empty_cells = L.lib().cm_env_n_empty_cells(self._h)
@@ -154,6 +230,28 @@ class GridEnvBatch:
             except Exception:
                 pass
             self._h = None
+
+    # ---- per-env comm conditions ---------------------------------------------------------
+    def _upload_conditions(self, conditions, condition_of, rng_ids):
+        table = condition_table(self.scenario, self.params, conditions, condition_of, rng_ids, channel=self.channelType,
+                                env_id_offset=self.cfg.env_id_offset)
+        if table.shape[0] != self.B:
+            raise ValueError(f"condition_of has {table.shape[0]} entries for {self.B} envs")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().cm_env_set_conditions(self._h, table.ctypes.data, L.current_stream()), "cm_env_set_conditions")
+        self.conditions = [dict(c) for c in conditions]
+        self.condition_of = np.asarray(condition_of).astype(np.int64)
+        self.rng_ids = table["rng_id"].astype(np.int64)
+
+    def set_conditions(self, conditions, condition_of=None, rng_ids=None):
+        """New values for a batch built with conditions= (a copy ordered on the current stream into the table the kernels read:
+        captured graphs stay valid and replay with the new values - how a curriculum changes conditions between epochs).
+        condition_of / rng_ids None keep the current assignment.  The channel kind is the batch's and does not change."""
+        if self.conditions is None:
+            raise L.CommarlError("set_conditions: this batch was built without conditions= (its buffers and launch form are "
+                                 "those of a uniform batch)")
+        self._upload_conditions(list(conditions), self.condition_of if condition_of is None else condition_of,
+                                self.rng_ids if rng_ids is None else rng_ids)
 
     # ---- raw device-side API -------------------------------------------------------------
     def _out(self, over=None):
@@ -273,12 +371,14 @@ class _WrapperBase:
     _scenario = None
 
     def __init__(self, centralized, other_agent_visible=False, *args, n_envs=1, device="cuda:0", seed=None,
-                 env_id_offset=0, rng_mode="philox", max_steps=None, channel=None, **kwargs):
+                 env_id_offset=0, rng_mode="philox", max_steps=None, channel=None, conditions=None, condition_of=None,
+                 rng_ids=None, **kwargs):
         params = kwargs["params"]
         self.centralized = centralized
         self._agent_visible = other_agent_visible
         self.batch = GridEnvBatch(self._scenario, params, n_envs, device=device, seed=seed, env_id_offset=env_id_offset,
-                                  rng_mode=rng_mode, max_steps=max_steps, channel=channel)
+                                  rng_mode=rng_mode, max_steps=max_steps, channel=channel, conditions=conditions,
+                                  condition_of=condition_of, rng_ids=rng_ids)
         b = self.batch
         self.n_envs, self.n_agents = b.B, b.N
         self.n_preys = b.M
@@ -312,14 +412,31 @@ class _WrapperBase:
         else:
             n, ne = b.N, b.n_empty_cells                                            # coverage.py:214-219
             self.bound_return = b.cfg.capture_reward * ne / n - abs(b.cfg.step_cost) * ne / n + b.cfg.final_reward
-        self._diameter = b.N if self.Rcom == 0 else 0                               # get_graph :219-223,234
+        self._diameter = b.N if self._full_graph else 0                             # get_graph :219-223,234
         self._single = (b.B == 1)
+
+    # -- per-env comm conditions (GridEnvBatch(conditions=...)): Rcom / pl above stay the values params give --
+    @property
+    def _full_graph(self):
+        """Every env fully connected by the Rcom rule: without conditions only (with them each env's graph is recorded)."""
+        return self.Rcom == 0 and self.batch.conditions is None
+
+    @property
+    def conditions(self):
+        return self.batch.conditions
+
+    @property
+    def condition_of(self):
+        return self.batch.condition_of
+
+    def set_conditions(self, conditions, condition_of=None, rng_ids=None):
+        self.batch.set_conditions(conditions, condition_of, rng_ids)
 
     # -- env attributes the sampler reads each step (sampler.py:123-131) --
     @property
     def dist_adj(self):
         a = self.batch.dist_adj.cpu().numpy()
-        if self.Rcom == 0:
+        if self._full_graph:
             a = a.astype(np.float64)                                                # np.ones(...) f64 (:220)
         return a[0] if self._single else a
 
@@ -330,7 +447,7 @@ class _WrapperBase:
 
     @property
     def ave_deg(self):
-        if self.Rcom == 0:
+        if self._full_graph:
             return self.n_agents
         v = self.batch.dist_adj.sum(-1).mean(-1).cpu().numpy()                      # :232
         return v[0] if self._single else v

@@ -20,6 +20,7 @@ Differences a maintainer should know (documented, not silent):
 
 ``eval_summary`` plays the same rounds and returns only each policy's score (the CSV row of exp_runners/testing.py:329-335),
 reduced on the device by cm_episode_stats / cm_episode_means: nothing but K x 12 doubles is copied to the host.
+``eval_sweep`` does the same for K policies x C comm conditions in one rollout, on a wrapper built with ``conditions=``.
 """
 import numpy as np
 import torch
@@ -267,6 +268,106 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
         res.append(d)
     env.eval_n_epi = n_epi
     avg = [d["reward"] / bound for d in res]
+    env.last_eval_average_reward = avg[0] if single else avg
+    return res[0] if single else res
+
+
+def sweep_layout(B, K, C, env_id_offset=0, paired=True):
+    """The env layout of eval_sweep: B envs = K policies x C conditions x E envs, env b = (k*C + c)*E + e playing policy k under
+    condition c.  -> (condition_of [B], rng_ids [B]), int64 numpy.  paired: rng_id = env_id_offset + e - every (policy,
+    condition) cell sees the same spawns, prey moves and channel uniforms; else env_id_offset + b (every env its own stream)."""
+    B, K, C = int(B), int(K), int(C)
+    if K < 1 or C < 1 or B < 1 or B % (K * C):
+        raise ValueError(f"sweep_layout: {B} envs do not split evenly between {K} policies x {C} conditions")
+    E = B // (K * C)
+    b = np.arange(B, dtype=np.int64)
+    return (b // E) % C, int(env_id_offset) + (b % E if paired else b)
+
+
+def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
+               episodes=False):
+    """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
+    conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
+    policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
+    is refused) and leaves that layout on the wrapper.  Policy k's envs are one contiguous range, so the engine is eval_summary's
+    (groups of C*E envs); behind every round ONE cm_episode_stats launch with groups of E envs fills a device table
+    [K*C, n_eval_episodes, 9], ONE cm_episode_means launch reduces it, and [K*C, 12] doubles are the only copy to the host.
+    -> a [K][C] list (a [C] list for a single policy) of eval_summary's dicts, each with `condition` (the dict given) added.
+    Cell (k, c) holds exactly what eval_summary(W_c, policies[k]) returns for W_c a fresh wrapper of env's class, seed and
+    channel kind whose params carry condition c, with E envs - at env's env_id_offset when paired (under greedy evaluation the
+    points of a curve then differ only through the condition), at the cell's first env otherwise.
+    flag, episodes, the refusals and env.eval_n_epi are eval_summary's; env.last_eval_average_reward is a [K][C] list ([C] for
+    a single policy)."""
+    single = not isinstance(policies, (PolicySet, list, tuple))
+    base = getattr(env, "env", env)
+    batch = base.batch
+    conds = batch.conditions
+    if conds is None:
+        raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
+    C_ = len(conds)
+    if flag is not None and flag[0]:
+        return [None] * C_ if single else [[None] * C_ for _ in policies]
+    B, N = batch.B, batch.N
+    T = int(max_env_steps)
+    if single:
+        ps, K = policies, 1
+    else:
+        ps = policies if isinstance(policies, PolicySet) else PolicySet(policies)
+        K = len(ps)
+    if B % (K * C_):
+        raise ValueError(f"eval_sweep: the {B} envs of the wrapper do not split evenly between {K} policies x {C_} conditions")
+    E = B // (K * C_)
+    if T > batch.cfg.max_path_length:
+        raise ValueError(f"max_env_steps={T} exceeds the env's max_path_length={batch.cfg.max_path_length}")
+    n_epi = int(n_eval_episodes)
+    if n_epi < 1:
+        raise ValueError("eval_sweep: n_eval_episodes must be at least 1")
+    batch.set_conditions(conds, *sweep_layout(B, K, C_, batch.cfg.env_id_offset, paired))
+    env.eval_n_epi = 0
+    ps.sync_weights()
+    ps.reset([True] * (C_ * E))
+    if single:
+        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False)
+    else:
+        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, groups=[C_ * E] * K)
+    lib = L.lib()
+    scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
+    table = torch.zeros(K * C_, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
+    out = torch.empty(K * C_, L.SUM_COLS, dtype=torch.float64, device=batch.device)
+    done = 0
+    while done < n_epi:
+        eng.reset()
+        if single or not eng.steps_fused(0, T, greedy=bool(eval_greedy)):     # a conditions batch declines the fused forms
+            eng.fork()
+            for t in range(T):
+                eng.step(t, greedy=bool(eval_greedy))
+            eng.join()
+        eng.bump(T)
+        batch.check_status()
+        take = min(E, n_epi - done)
+        L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
+                                     L.ptr(eng.path_len), L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table),
+                                     L.current_stream()), "cm_episode_stats")
+        done += take
+    L.check(lib.cm_episode_means(K * C_, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
+    host = out.cpu().numpy()
+    bound = base.bound_return
+    res = []
+    for k in range(K):
+        row = []
+        for c in range(C_):
+            g = k * C_ + c
+            d = dict(n_episodes=n_epi, success=float(host[g, 0]))
+            d.update({vec: float(host[g, 1 + i]) for i, vec in enumerate(VECTORS)})
+            d.update({name: float(host[g, L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
+            d["bound_return"] = bound
+            d["condition"] = conds[c]
+            if episodes:
+                d["episodes"] = table[g]
+            row.append(d)
+        res.append(row)
+    env.eval_n_epi = n_epi
+    avg = [[d["reward"] / bound for d in row] for row in res]
     env.last_eval_average_reward = avg[0] if single else avg
     return res[0] if single else res
 

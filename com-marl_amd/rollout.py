@@ -41,6 +41,8 @@ class _Parts:
         self.B = sum(p.B for p in parts)
         self.bounds, lo = [], 0
         for p in parts:
+            if getattr(p, "conditions", None) is not None:
+                raise ValueError("per-env comm conditions run on one GridEnvBatch, not on shards")
             assert (p.N, p.d, p.Lh, p.scenario) == (e0.N, e0.d, e0.Lh, e0.scenario) and p.device == e0.device
             assert p.cfg.env_id_offset == e0.cfg.env_id_offset + lo, "shards must cover contiguous global env ids"
             self.bounds.append((lo, lo + p.B))

@@ -143,6 +143,34 @@ int cm_env_status(cm_env_t h);
 int cm_env_get_state(cm_env_t h, const cm_env_state *host);
 int cm_env_set_state(cm_env_t h, const cm_env_state *host);
 
+/* Per-env comm conditions: every env of the handle gets its own communication range, channel parameters and Philox env id -
+ * what the reference's runners sweep one run at a time with --teRcom / --tepl / --Pgb / --Pbg, and what a curriculum over the
+ * packet loss changes between epochs.  HOST table of n_envs records; the handle owns a device copy. */
+typedef struct cm_env_cond {      /* 32 bytes */
+    int32_t rcom;                 /* as cm_env_cfg.rcom; the rule of cm_env_create - rcom == 0 or rcom + 1 >= grid means fully
+                                     connected (env_communication.py:71-72) - is applied per env */
+    float   ploss, pgb, pbg;      /* read where the handle's channel is IID / GE; otherwise ignored */
+    int32_t rng_id;               /* the Philox env id this env draws with (without a table: cfg.env_id_offset + b) */
+    int32_t reserved[3];          /* 0 */
+} cm_env_cond;
+/* The FIRST call is allowed only before the handle's first cm_env_reset / cm_env_step (CM_ERR_ARG afterwards): it allocates the
+ * table and turns cm_env_adj_is_const off - every env's dist_adj is computed and written from then on, all ones for a fully
+ * connected env - while cm_env_channels_are_const stays what the channel kind (a property of the handle, not of a record)
+ * dictates.  Query the two once after it and size buffers by the answers.  LATER calls overwrite the same device memory with a
+ * copy ordered on `stream`: steps launched on that stream afterwards, replays of a captured hipGraph included, read the new
+ * values.  The host table may be freed on return.  Not to be called while `stream` is being captured.
+ * With a table cm_env_reset / cm_env_step launch the kernels of csrc/cm_env_cond.hip (the same narrow / wide / lanes-per-env
+ * choice): env b does exactly what env 0 of a handle created with the record's rcom / ploss / pgb / pbg and env_id_offset =
+ * rng_id would do, bit for bit.  Entry points that run the env phase inside another kernel - cm_rollout_step,
+ * cm_rollout_chunk, cm_rollout_chunk_tail, cm_rollout_chunk_multi - do not read the table: they return 1 (nothing done) for
+ * such a handle, and the caller takes the policy launch + cm_env_step.  cm_env_agent_fault and cm_comm_delays are out of
+ * scope: the fault draws stay keyed by the physical env id cfg.env_id_offset + b, whatever rng_id says.
+ * CM_ERR_ARG (text in cm_last_error) before anything is launched or copied: a NULL table, a CM_RNG_TAPE handle (a tape holds
+ * draws recorded under one condition), rcom < 0, a probability the channel kind reads outside [0, 1], a non-zero reserved
+ * word. */
+int cm_env_set_conditions(cm_env_t h, const cm_env_cond *host_table /* [n_envs] */, void *stream);
+int cm_env_has_conditions(cm_env_t h);   /* 1 once a table was set */
+
 /* PP agent_condition (predator_prey.py:74,152,258): [B,N] bytes, 0 = the agent's moves are not applied; every env reset
  * puts its row back to ones.  HOST pointers; either may be NULL.  Synchronises. */
 int cm_env_agent_condition(cm_env_t h, const uint8_t *set_host, uint8_t *get_host);

@@ -1,0 +1,126 @@
+"""Condition sweeps on one MI355X (DESIGN.md §7 "Condition sweeps"): wall time of evaluate.eval_sweep - ONE call over K policies x C
+comm conditions - against the same cells scored without per-env conditions: C evaluate.eval_summary calls on uniform wrappers of
+B / C envs, the same number of episodes per cell.  Whole calls on the host clock, each ending in a synchronise, on
+  pp_map10   PP map 10, teams of 4, 4096 envs, K = 8 policies x C = 8 conditions (IID channel: range x loss), 64 episodes per cell;
+  co_map20   CO map 20, teams of 24, 1024 envs, K = 4 x C = 4 (Gilbert-Elliott channel: range x (Pgb, Pbg)), 64 episodes per cell;
+max_env_steps = 200, greedy, one round.  Both sides are warmed up first, then alternate for three rounds; every call gets fresh
+wrappers of the same seed.  Before anything is timed the sweep's cells of policy 0 are compared (==) with eval_summary of policy 0
+on the uniform wrappers (paired ids: those cells play the same episodes).
+    python tools/eval_sweep_time.py [pp_map10|co_map20]     one workload, no argument both
+    python tools/eval_sweep_time.py kernels                 the env step alone, uniform batch then conditions batch of the same
+                                                            shape, batch and (single) condition, 300 steps each: the launches a
+                                                            `rocprofv3 --kernel-trace --stats` run of this command compares
+                                                            (env_kernel* against env_cond_kernel*)"""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import torch  # noqa: E402
+
+from com_marl_amd import envs as E, nets  # noqa: E402
+from com_marl_amd.evaluate import eval_summary, eval_sweep  # noqa: E402
+
+T, ROUNDS, SEED = 200, 3, 3
+PP = dict(load=2, max_env_steps=T, capture_reward=10, step_cost=0.1, rm=0, penalty=0, grid_size=10, Rsen=1, n_agents=4, n_preys=4,
+          n_gcn_layers=2, mode="test", teRcom=9, tepl=0)
+CO = dict(load=2, max_env_steps=T, capture_reward=2, step_cost=0, rm=0, penalty=1, revisit_penalty=0.5, lazy_penalty=1, grid_size=20,
+          Rsen=2, n_agents=24, n_preys=0, n_gcn_layers=2, mode="test", teRcom=19, tepl=0, obstComplex="Easy", add_clock=0)
+WORKLOADS = {
+    "pp_map10": dict(cls=E.PredatorPreyWrapper, params=PP, envs=4096, K=8, channel="IID",
+                     conditions=[dict(Rcom=r, pl=p) for r in (9, 3, 2, 1) for p in (0.0, 0.5)]),
+    "co_map20": dict(cls=E.CoverageWrapper, params=CO, envs=1024, K=4, channel="GE",
+                     conditions=[dict(Rcom=r, Pgb=g, Pbg=b) for r in (19, 4) for g, b in ((0.0196, 0.282), (0.3, 0.1))]),
+}
+COND_TO_PARAM = dict(Rcom="teRcom", pl="tepl", Pgb="Pgb", Pbg="Pbg")
+
+
+def with_condition(params, cond):
+    p = dict(params)
+    p.update({COND_TO_PARAM[k]: v for k, v in cond.items()})
+    return p
+
+
+def sync_time(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def run(name):
+    w = WORKLOADS[name]
+    cls, params, B, K, channel, conds = w["cls"], w["params"], w["envs"], w["K"], w["channel"], w["conditions"]
+    C_ = len(conds)
+    n_epi = B // (K * C_)
+    kw = dict(n_eval_episodes=n_epi, max_env_steps=T, eval_greedy=True)
+    sweep_wrapper = lambda: cls(True, params=params, n_envs=B, device="cuda:0", seed=SEED, channel=channel, conditions=conds)   # noqa: E731
+    uniform_wrappers = lambda n: [cls(True, params=with_condition(params, c), n_envs=n, device="cuda:0", seed=SEED,   # noqa: E731
+                                      channel=channel) for c in conds]
+    first = sweep_wrapper()
+    pols = []
+    for k in range(K):
+        torch.manual_seed(k)
+        p = nets.CommCategoricalMLPPolicy(first.spec, n_agents=params["n_agents"], device="cuda:0")
+        p.set_rng(SEED)
+        pols.append(p)
+    sweep = lambda env: eval_sweep(env, pols, 0, paired=True, **kw)                                    # noqa: E731
+    sequential = lambda envs: [eval_summary(env, pols, 0, **kw) for env in envs]                         # noqa: E731
+    # warm-up of both sides and the comparison
+    _, got = sync_time(lambda: sweep(first))
+    _, ref = sync_time(lambda: sequential(uniform_wrappers(B // C_)))
+    ref0 = [eval_summary(env, pols[0], 0, **kw) for env in uniform_wrappers(n_epi)]                     # policy 0's cells, paired ids
+    same = all({k: v for k, v in got[0][c].items() if k != "condition"} == ref0[c] for c in range(C_))
+    print(f"{name}: cells of policy 0 equal eval_summary on the uniform wrappers: {same}", flush=True)
+    for c in range(C_):
+        print(f"  {conds[c]}: success {[round(got[k][c]['success'], 3) for k in range(K)]} "
+              f"(sequential, other episodes: {[round(ref[c][k]['success'], 3) for k in range(K)]})", flush=True)
+    rounds = {"eval_sweep": [], "sequential": []}
+    for r in range(ROUNDS):
+        env = sweep_wrapper()
+        dt, _ = sync_time(lambda: sweep(env))
+        rounds["eval_sweep"].append(dt)
+        print(f"[{r}] {name} eval_sweep   1 call,  {B} envs, {K} x {C_} cells x {n_epi} episodes: {dt * 1e3:9.2f} ms", flush=True)
+        envs = uniform_wrappers(B // C_)
+        dt, _ = sync_time(lambda: sequential(envs))
+        rounds["sequential"].append(dt)
+        print(f"[{r}] {name} sequential   {C_} calls, {B // C_} envs each, {K} policies x {n_epi} episodes: {dt * 1e3:9.2f} ms", flush=True)
+    print(json.dumps({"workload": name, "envs": B, "policies": K, "conditions": C_, "episodes_per_cell": n_epi, "steps": T,
+                      "policy0_cells_equal": bool(same),
+                      "eval_sweep_ms": [round(x * 1e3, 3) for x in rounds["eval_sweep"]],
+                      "sequential_ms": [round(x * 1e3, 3) for x in rounds["sequential"]],
+                      "sweep_ahead_in_every_round_against_every_round": bool(max(rounds["eval_sweep"]) < min(rounds["sequential"]))}),
+          flush=True)
+    return same
+
+
+def kernels():
+    """300 cm_env_step launches of a uniform batch, then 300 of a conditions batch in which every env has that same condition:
+    the same work per launch, env_kernel* against env_cond_kernel*."""
+    shapes = [("pp_map10 N=4 x 4096 (16 lanes per env)", "pp", PP, 4096, "IID", dict(Rcom=3, pl=0.3)),
+              ("pp_map10 N=9 x 8192 (32 lanes per env)", "pp", dict(PP, n_agents=9), 8192, "IID", dict(Rcom=3, pl=0.3)),
+              ("pp_map10 N=9 x 2048 (64 lanes per env)", "pp", dict(PP, n_agents=9), 2048, "IID", dict(Rcom=3, pl=0.3)),
+              ("co_map20 N=24 x 1024 (wide)", "co", CO, 1024, "GE", dict(Rcom=4, Pgb=0.3, Pbg=0.1))]
+    steps = 300
+    for label, scen, params, B, channel, cond in shapes:
+        N = params["n_agents"]
+        g = torch.Generator().manual_seed(0)
+        acts = torch.randint(0, 5, (steps, B, N), generator=g, dtype=torch.int32).to("cuda:0")
+        for kind in ("uniform", "conditions", "uniform", "conditions"):
+            kw = dict(conditions=[cond]) if kind == "conditions" else {}
+            env = E.GridEnvBatch(scen, with_condition(params, cond), B, device="cuda:0", seed=SEED, channel=channel, **kw)
+            env.reset_all()
+            dt, _ = sync_time(lambda: [env.step_device(a) for a in acts])
+            env.check_status()
+            print(f"{label}: {kind:10s} {steps} steps, host clock {dt / steps * 1e6:7.2f} us per step (launch-bound where small)", flush=True)
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["kernels"]:
+        kernels()
+        sys.exit(0)
+    names = sys.argv[1:] or list(WORKLOADS)
+    ok = [run(name) for name in names]
+    sys.exit(0 if all(ok) else 1)

@@ -130,6 +130,7 @@ _SIGNATURES = {
     "cm_env_set_state": (C.c_int, [C.c_void_p, C.POINTER(EnvState)]),
     "cm_env_set_conditions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_env_has_conditions": (C.c_int, [C.c_void_p]),
+    "cm_env_fuse_conditions": (C.c_int, [C.c_void_p, C.c_int32]),
     "cm_policy_forward": (C.c_int, [C.POINTER(PolicyWeights), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -376,6 +376,12 @@ extern "C" int cm_env_set_conditions(cm_env_t h, const cm_env_cond *host_table, 
     return CM_OK;
 }
 
+extern "C" int cm_env_fuse_conditions(cm_env_t h, int32_t on) {
+    if (!h) return set_error(CM_ERR_ARG, "cm_env_fuse_conditions: null handle");
+    h->cond_fused = on != 0;
+    return CM_OK;
+}
+
 extern "C" int cm_env_status(cm_env_t h) {
     if (!h) return set_error(CM_ERR_ARG, "null handle");
     CM_HIP(hipDeviceSynchronize());

@@ -17,15 +17,9 @@
 namespace cm {
 
 // The launch's EnvDev with env b's record in place of the handle's comm scalars.  The Philox env id of env b becomes
-// rec.rng_id: the bodies compute it as env_id_offset + b.
+// rec.rng_id: the bodies compute it as env_id_offset + b (load_cond / apply_cond, cm_env_dev.h).
 __device__ __forceinline__ EnvDev with_cond(const EnvDev &p, const EnvCondDev *__restrict__ cond, int b) {
-    const int4 c = *reinterpret_cast<const int4 *>(cond + b);                   // rc2, ploss, pgb, pbg
-    const int rng_id = cond[b].rng_id;
-    EnvDev q = p;
-    q.rc2 = c.x; q.ploss = __int_as_float(c.y); q.pgb = __int_as_float(c.z); q.pbg = __int_as_float(c.w);
-    q.env_id_offset = rng_id - b;
-    q.rng_mode = CM_RNG_PHILOX;
-    return q;
+    return apply_cond(p, load_cond(cond, b));
 }
 
 template <int SCEN, int LPE>

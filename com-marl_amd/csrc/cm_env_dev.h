@@ -1200,5 +1200,27 @@ __device__ __forceinline__ void env_body(const EnvDev &p, const int32_t *__restr
     ENV_PROBE(9);
 }
 
+// ---- per-env comm conditions (cm_env_set_conditions): what a sub-wave group needs of its env's 32-byte record.  Five values per
+// group, so they live in VGPRs (with 16 lanes per env the four envs of a wave differ).  The stand-alone env step loads them per
+// launch (cm_env_cond.hip), the wave-owned rollout once ahead of its step loop (cm_rollout_wc.hip).
+struct EnvCondVals { int rc2; float ploss, pgb, pbg; int id_off; };
+
+// env b's record; id_off = rng_id - b: the bodies compute an env's Philox id as env_id_offset + b
+__device__ __forceinline__ EnvCondVals load_cond(const EnvCondDev *__restrict__ cond, int b) {
+    const int4 c = *reinterpret_cast<const int4 *>(cond + b);                   // rc2, ploss, pgb, pbg
+    const int rng_id = cond[b].rng_id;
+    return EnvCondVals{ c.x, __int_as_float(c.y), __int_as_float(c.z), __int_as_float(c.w), rng_id - b };
+}
+
+// The launch's EnvDev with a record in place of the handle's comm scalars.  Tape mode is refused for a handle with a table, so
+// rng_mode is the constant CM_RNG_PHILOX and the tape branches of the bodies fold away.
+__device__ __forceinline__ EnvDev apply_cond(const EnvDev &p, const EnvCondVals &v) {
+    EnvDev q = p;
+    q.rc2 = v.rc2; q.ploss = v.ploss; q.pgb = v.pgb; q.pbg = v.pbg;
+    q.env_id_offset = v.id_off;
+    q.rng_mode = CM_RNG_PHILOX;
+    return q;
+}
+
 
 }  // namespace cm

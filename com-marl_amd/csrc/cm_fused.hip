@@ -179,7 +179,7 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
                         float *probs, float *attn, const cm_rng_tape *tape, const cm_step_out *out, void *stream,
                         const ChunkArgs *chunk) {
     if (int rc = check_rollout_args("cm_rollout_step", h, w, obs, out)) return rc;
-    if (h->cond) return 1;                           // per-env comm conditions: only the stand-alone env step reads the table
+    if (h->cond && !h->cond_fused) return 1;         // per-env comm conditions: fused on request only (cm_env_fuse_conditions)
     const EnvDev &d = h->dev;
     if (!w->mfma_pack || !policy_shape_ok(w)) return 1;
     if (int rc = check_tape(h, tape, false)) return rc;
@@ -197,9 +197,11 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
     const bool quad = d.N == 4 && mf::pick_epb(4) * 4 <= 32;
     const int kh = mh::kh_of(d.d);
     if (policy_w_enabled() && shape_ok_rollout_w(d.N, d.d, d.L, w->n_act)) {    // teams of 4: wave-owned rows, single step or persistent chunk
-        const int rc = launch_rollout_w(a, w, reinterpret_cast<const char *>(P) + wave_pack(d), h, t, *out, stream, chunk);
+        const char *wp = reinterpret_cast<const char *>(P) + wave_pack(d);
+        const int rc = h->cond ? (tape ? 1 : launch_rollout_wc(a, w, wp, nullptr, h, *out, stream, chunk)) : launch_rollout_w(a, w, wp, h, t, *out, stream, chunk);
         if (rc != 1) return rc;
     }
+    if (h->cond) return 1;                           // the table is read by the wave-owned twins only (cm_rollout_wc.hip)
     if (policy_h_enabled() && kh) {                  // f16-split dense layers: the operand pack behind the f32 one
         const mh::PackLayoutH lh = mh::pack_layout_h(kh, d.L, true);
         const uint4 *Q = reinterpret_cast<const uint4 *>(P + lo.total);

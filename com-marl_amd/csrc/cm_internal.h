@@ -117,6 +117,7 @@ struct cm_env {
     void *cond;
     void *cond_host;
     hipEvent_t cond_copied;
+    bool cond_fused;          // cm_env_fuse_conditions: the rollout entry points run such a handle on the kernels of cm_rollout_wc.hip
     bool started;             // a reset / step was launched: the first cm_env_set_conditions comes too late
 };
 

@@ -9,6 +9,8 @@ namespace cm {
 template <int LHOPS, bool PRE, bool FULLWG, bool TAPE, bool CARRY = false, int SHAPE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_w_kernel(mf::FwdArgs a, mw::WeightsW w, EnvDev p, cm_rng_tape tape_arg, cm_step_out out, StridesW c, TailW tl) {
     constexpr bool PROBES = SHAPE != 1;                  // generic builds: gated at run time as ever; SHAPE 1: none (the entry below has them)
+    constexpr bool COND = false;                         // per-env comm conditions: the twins of cm_rollout_wc.hip
+    constexpr const EnvCondDev *cond = nullptr;
 #include "cm_rollout_w_body.h"
 }
 
@@ -17,7 +19,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // production build carries neither the s_memtime sites nor the branches around them.  Its timing is this build's, not that one's.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_w_probe_kernel(mf::FwdArgs a, mw::WeightsW w, EnvDev p, cm_rng_tape tape_arg, cm_step_out out, StridesW c, TailW tl) {
     constexpr int LHOPS = 2, SHAPE = 1;
-    constexpr bool PRE = true, FULLWG = true, TAPE = false, CARRY = true, PROBES = true;
+    constexpr bool PRE = true, FULLWG = true, TAPE = false, CARRY = true, PROBES = true, COND = false;
+    constexpr const EnvCondDev *cond = nullptr;
 #include "cm_rollout_w_body.h"
 }
 

@@ -16,6 +16,13 @@
 // state arrays are written by the launch's last step only.  The step's common Philox draws (the sampler's action word, the preys'
 // first four trial words) are computed for two steps at once on every even step of the loop (pp10::draw_stage) and handed over
 // through a per-wave LDS buffer in the image's h3 / h4 slots, which these builds do not stage.
+// constexpr bool COND (true in cm_rollout_wc.hip only; the non-carried, tape-less builds: a handle with a condition table has adj_const off): the including
+// kernel also provides  const EnvCondDev *cond  - the handle's device table (cm_env_set_conditions).  A 16-lane env group loads its
+// env's record ONCE, ahead of the step loop (the table cannot change under a running launch), and its env phase runs on a
+// by-value copy of p that carries the record's rc2, ploss, pgb, pbg and Philox env id (apply_cond, cm_env_dev.h): five VGPRs
+// per lane, everything else of p stays the scalar argument.  The policy tile is untouched.  The other kernels set COND to false
+// and cond to a constant nullptr: everything of it is behind `if constexpr`.
+    static_assert(!COND || (!CARRY && !TAPE && SHAPE == 0), "the conditions twins are the non-carried, tape-less builds");
     static_assert(SHAPE == 0 || CARRY, "shape constants are built into the carried form only");
     if constexpr (SHAPE == 1) {
         p.S = 10; p.M = 4; p.R = 1; p.W = 3; p.d = 21; p.rcp_d = 1.0f / 21.0f; p.rcp_W = 1.0f / 3.0f; p.rcp_WW = 1.0f / 9.0f;
@@ -76,6 +83,12 @@
             em = pp10::emit_codes(tx % LPE);
         } else pre = env_prefetch<CM_PP, LPE>(p, b0, live);
     }
+    EnvCondVals cv{};                                                    // COND: this group's record, for the whole launch
+    if constexpr (COND) {
+        const int grp = thread_x() / LPE;
+        const int b0 = blockIdx.x * mw::WG_ENVS + ((FULLWG || grp < envs) ? grp : 0);
+        cv = load_cond(cond, ((FULLWG || grp < envs) && b0 < p.B) ? b0 : p.B - 1);   // idle groups shadow env B - 1, as env_body
+    }
     for (int t = 0; t < c.n_steps; ++t) {
         asm volatile("" ::: "memory");                                   // keep each step's loads inside the step
         const int tx = thread_x(), grp = tx / LPE;
@@ -100,6 +113,8 @@
             if ((t & 1) == 0) pp10::draw_stage(p, pp.rng_step, a.env_id_offset, at.policy_step, a.key0, a.key1, envs, FULLWG, draw);
             asm volatile("" ::: "memory");
         }
+        if constexpr (COND) { if constexpr (PRE) pre = env_prefetch<CM_PP, LPE>(apply_cond(p, cv), b_raw, live); }
+        else
         if constexpr (PRE && !CARRY) pre = env_prefetch<CM_PP, LPE>(p, b_raw, live);   // env state requested in front of the policy forward
         if constexpr (SHAPE == 1)
             mw::policy_tile_w<LHOPS, true, false, 0, true, true>(at, n_act, res, lds_w, blockIdx.x, act, obs_row,
@@ -122,7 +137,14 @@
         }
         if (env_wave) {
             const int32_t *my_act = act + (live ? grp : 0) * 4;
-            if constexpr (CARRY && SHAPE == 1) {
+            if constexpr (COND) {                                        // the non-carried forms below, on the env's own comm scalars
+                const EnvDev q = apply_cond(p, cv);
+                if constexpr (PRE) {
+                    const bool bad = env_stage<CM_PP, LPE>(q, pre, my_act, grp, ENV_BASE);
+                    env_body<CM_PP, LPE>(q, nullptr, my_act, tape, ot, 0, grp, b_raw, live, ENV_BASE, nullptr, true, pre.rng_step, pre.step_count_in,
+                                         pre.succ, pre.t_row, pre.t_col, pre.t_step0, pre.t_step, pre.t_rew, bad, FULLWG);
+                } else env_body<CM_PP, LPE>(q, nullptr, my_act, tape, ot, 0, grp, b_raw, live, ENV_BASE);
+            } else if constexpr (CARRY && SHAPE == 1) {
                 const pp10::StepOff so{ ut * (uint32_t)c.obs, ut * (uint32_t)c.reward, ut * (uint32_t)c.reward_f64, ut * (uint32_t)c.done,
                                         ut * (uint32_t)c.details, ut * (uint32_t)c.prey_alive, ut * (uint32_t)c.success, ut * (uint32_t)c.path_len };
                 pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, so, t == c.n_steps - 1, grp, b_raw, live, ENV_BASE, FULLWG, obs_env, draw + mw::DRAW_WAVE_BYTES / 4);

@@ -1,6 +1,7 @@
 // cm_rollout_w_dev.h - what the wave-owned rollout kernels of teams of 4 share besides their step loop (cm_rollout_w_body.h):
-// rollout_w_kernel (cm_rollout_w.hip, one weight image per launch) and rollout_wm_kernel (cm_rollout_wm.hip, a workgroup picks its
-// policy's image at entry).  Both translation units are built with -fno-slp-vectorize (Makefile).
+// rollout_w_kernel (cm_rollout_w.hip, one weight image per launch), rollout_wm_kernel (cm_rollout_wm.hip, a workgroup picks its
+// policy's image at entry) and their twins for a handle with per-env comm conditions (cm_rollout_wc.hip).  The three translation
+// units are built with -fno-slp-vectorize (Makefile).
 #pragma once
 #include <stdio.h>
 
@@ -28,6 +29,17 @@ static __device__ unsigned long long g_w_probe[5];
 // the wave that takes the last one advances the sampler's Philox base - every other wave has read it for the last time
 struct TailW { float *obs_dst; uint32_t *base; unsigned int *ticket; int on; };
 struct StridesW { int n_steps, obs, actions, probs, attn, reward, reward_f64, done, details, dist_adj, channels, prey_alive, success, path_len; };
+
+namespace mw {
+// the policy set as rollout_wm_kernel / rollout_wcm_kernel see it: read at entry only, so nothing of it stays live through the step
+// loop but n_act (as WeightsW)
+struct PolicySetW {
+    const float *const *packs;                           // [K] cm_policy_pack() outputs
+    const int32_t *wg_policy;                            // [n_wg] policy of each workgroup
+    int wave_off;                                        // bytes from a pack's start to its wave-owned section (one shape: one offset)
+    int n_act;
+};
+}  // namespace mw
 
 // ---- host: what the rollout entry points share (cm_fused.hip: cm_rollout_step / _chunk / _chunk_tail; cm_rollout_wm.hip:
 // cm_rollout_chunk_multi).  The helpers defined here are static: the library exports every external symbol, and these are not ABI ----
@@ -96,6 +108,10 @@ int plan_rollout_w(const mf::FwdArgs &a, const cm_env *h, bool use_tape, const C
 // cm_rollout_w.hip: single step, or a persistent chunk; 1 = not available for this handle
 int launch_rollout_w(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pack, const cm_env *h, const cm_rng_tape &t, const cm_step_out &out,
                      void *stream, const ChunkArgs *chunk);
+// cm_rollout_wc.hip: the same for a handle with a condition table (cm_env_set_conditions) - rollout_wc_kernel with one weight image
+// (`set` NULL), rollout_wcm_kernel with a policy set; 1 = not available for this handle
+int launch_rollout_wc(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pack, const cm_policy_set *set, const cm_env *h,
+                      const cm_step_out &out, void *stream, const ChunkArgs *chunk);
 
 // The one ladder from a plan to a build of a wave-owned kernel: f(LHOPS, PRE, FULLWG, TAPE, CARRY, SHAPE), each a
 // std::integral_constant.  Per hop count: the tape variant, and {plain, env prefetch, carried, carried map10} x {ragged, full}.

@@ -8,21 +8,13 @@
 
 namespace cm {
 
-namespace mw {
-// the policy set as the kernel sees it: read at entry only, so nothing of it stays live through the step loop but n_act (as WeightsW)
-struct PolicySetW {
-    const float *const *packs;                           // [K] cm_policy_pack() outputs
-    const int32_t *wg_policy;                            // [n_wg] policy of each workgroup
-    int wave_off;                                        // bytes from a pack's start to its wave-owned section (one shape: one offset)
-    int n_act;
-};
-}  // namespace mw
-
 // No tape variant (tape mode steps one launch at a time) and no folded tail (the caller's tail is a cm_chunk_tail launch).
 template <int LHOPS, bool PRE, bool FULLWG, bool CARRY = false, int SHAPE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_wm_kernel(mf::FwdArgs a, mw::PolicySetW ps, EnvDev p, cm_step_out out, StridesW c) {
     constexpr bool TAPE = false;
     constexpr bool PROBES = SHAPE != 1;                  // the host of this entry never reads the clocks: no probe twin of its SHAPE 1 builds
+    constexpr bool COND = false;                         // per-env comm conditions: rollout_wcm_kernel (cm_rollout_wc.hip)
+    constexpr const EnvCondDev *cond = nullptr;
     // uniform per workgroup: one lookup of the policy, one of its pack.  The pack address is made uniform (both halves through
     // readfirstlane) and global explicitly: a pointer as loaded from memory is generic and not known uniform, and then the staging's
     // loads become flat loads and its batch of chunks goes to scratch (304 bytes per lane)
@@ -53,13 +45,14 @@ extern "C" int cm_rollout_chunk_multi(cm_env_t h, const cm_policy_weights *w, co
     if (set->n_wg != (d.B + mw::WG_ENVS - 1) / mw::WG_ENVS)
         return set_error(CM_ERR_ARG, "cm_rollout_chunk_multi: n_wg must be ceil(B / 16) of the env handle");
     if (n_steps == 0) return CM_OK;
-    if (h->cond) return 1;                           // per-env comm conditions: only the stand-alone env step reads the table
+    if (h->cond && !h->cond_fused) return 1;         // per-env comm conditions: fused on request only (cm_env_fuse_conditions)
     if (!policy_shape_ok(w) || !policy_w_enabled() || !shape_ok_rollout_w(d.N, d.d, d.L, w->n_act)) return 1;
     const mf::FwdArgs a = rollout_fwd_args(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy,
                                            actions, probs, attn);
     const ChunkArgs c = chunk_args(n_steps, *st);
     RolloutWPlan pl;
     pl.n_act = w->n_act; pl.out = out;
+    if (h->cond) return launch_rollout_wc(a, w, nullptr, set, h, *out, stream, &c);   // rollout_wcm_kernel, or 1
     if (plan_rollout_w(a, h, false, &c, pl)) return 1;
     const mw::PolicySetW ps{ set->packs, set->wg_policy, (int)wave_pack(d), w->n_act };
     // no tape variant here: the ladder never takes that branch without a tape

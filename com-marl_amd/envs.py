@@ -169,11 +169,13 @@ class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 
     def __init__(self, scenario, params, n_envs=1, *, device="cuda:0", seed=None, env_id_offset=0, rng_mode="philox",
-                 max_steps=None, max_path_length=None, channel=None, conditions=None, condition_of=None, rng_ids=None):
+                 max_steps=None, max_path_length=None, channel=None, conditions=None, condition_of=None, rng_ids=None,
+                 fused_conditions=False):
         """conditions: a list of C comm conditions (condition_table) - env b steps under conditions[condition_of[b]] (default:
         C contiguous blocks of B / C envs) and draws with the Philox env id rng_ids[b] (default: its own, env_id_offset + b).
         Without an explicit `channel` the kind is IID if any condition has 0 < pl < 1, else what params give.  Such a batch
-        records every env's dist_adj (adj_const is off) and steps in two launches; set_conditions() replaces the values later."""
+        records every env's dist_adj (adj_const is off) and steps in two launches; set_conditions() replaces the values later.
+        fused_conditions: fuse_conditions() at construction - teams of 4 then roll out in one launch per step / chunk."""
         assert scenario in ("pp", "co")
         self.scenario, self.params = scenario, dict(params)
         self.device = torch.device(device)
@@ -193,6 +195,9 @@ class GridEnvBatch:
         c = self.cfg
         self.B, self.N, self.M, self.Lh = c.n_envs, c.n_agents, c.n_preys, c.n_hops
         self.conditions = self.condition_of = self.rng_ids = None
+        self.fused_conditions = False
+        if fused_conditions:
+            self.fuse_conditions()
         if conditions is not None:                          # before the const-ness queries: the first table turns adj_const off
             if condition_of is None:
                 if self.B % len(conditions):
@@ -252,6 +257,15 @@ class GridEnvBatch:
                                  "those of a uniform batch)")
         self._upload_conditions(list(conditions), self.condition_of if condition_of is None else condition_of,
                                 self.rng_ids if rng_ids is None else rng_ids)
+
+    def fuse_conditions(self, on=True):
+        """Let the fused rollout entry points run this batch's conditions (cm_env_fuse_conditions): Predator-Prey teams of 4 on the
+        wave-owned kernel then step in one launch (csrc/cm_rollout_wc.hip), bit for bit what the two launches give; every other
+        shape keeps the two launches.  No effect on a batch without conditions.  A RolloutEngine asks the fused forms once and
+        remembers the answer: call this before the engine's first step."""
+        with torch.cuda.device(self.device):
+            L.check(L.lib().cm_env_fuse_conditions(self._h, int(bool(on))), "cm_env_fuse_conditions")
+        self.fused_conditions = bool(on)
 
     # ---- raw device-side API -------------------------------------------------------------
     def _out(self, over=None):
@@ -372,13 +386,13 @@ class _WrapperBase:
 
     def __init__(self, centralized, other_agent_visible=False, *args, n_envs=1, device="cuda:0", seed=None,
                  env_id_offset=0, rng_mode="philox", max_steps=None, channel=None, conditions=None, condition_of=None,
-                 rng_ids=None, **kwargs):
+                 rng_ids=None, fused_conditions=False, **kwargs):
         params = kwargs["params"]
         self.centralized = centralized
         self._agent_visible = other_agent_visible
         self.batch = GridEnvBatch(self._scenario, params, n_envs, device=device, seed=seed, env_id_offset=env_id_offset,
                                   rng_mode=rng_mode, max_steps=max_steps, channel=channel, conditions=conditions,
-                                  condition_of=condition_of, rng_ids=rng_ids)
+                                  condition_of=condition_of, rng_ids=rng_ids, fused_conditions=fused_conditions)
         b = self.batch
         self.n_envs, self.n_agents = b.B, b.N
         self.n_preys = b.M
@@ -431,6 +445,9 @@ class _WrapperBase:
 
     def set_conditions(self, conditions, condition_of=None, rng_ids=None):
         self.batch.set_conditions(conditions, condition_of, rng_ids)
+
+    def fuse_conditions(self, on=True):
+        self.batch.fuse_conditions(on)
 
     # -- env attributes the sampler reads each step (sampler.py:123-131) --
     @property

@@ -337,7 +337,9 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     done = 0
     while done < n_epi:
         eng.reset()
-        if single or not eng.steps_fused(0, T, greedy=bool(eval_greedy)):     # a conditions batch declines the fused forms
+        # a conditions batch declines the fused forms (two launches per step) unless the wrapper was built with fused_conditions=True
+        # (GridEnvBatch.fuse_conditions): then teams of 4 play the round as one launch, a single policy included
+        if not eng.steps_fused(0, T, greedy=bool(eval_greedy)):
             eng.fork()
             for t in range(T):
                 eng.step(t, greedy=bool(eval_greedy))

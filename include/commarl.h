@@ -162,14 +162,19 @@ typedef struct cm_env_cond {      /* 32 bytes */
  * With a table cm_env_reset / cm_env_step launch the kernels of csrc/cm_env_cond.hip (the same narrow / wide / lanes-per-env
  * choice): env b does exactly what env 0 of a handle created with the record's rcom / ploss / pgb / pbg and env_id_offset =
  * rng_id would do, bit for bit.  Entry points that run the env phase inside another kernel - cm_rollout_step,
- * cm_rollout_chunk, cm_rollout_chunk_tail, cm_rollout_chunk_multi - do not read the table: they return 1 (nothing done) for
- * such a handle, and the caller takes the policy launch + cm_env_step.  cm_env_agent_fault and cm_comm_delays are out of
+ * cm_rollout_chunk, cm_rollout_chunk_tail, cm_rollout_chunk_multi - return 1 (nothing done) for such a handle, and the caller
+ * takes the policy launch + cm_env_step, unless cm_env_fuse_conditions (below) switched them on.  cm_env_agent_fault and cm_comm_delays are out of
  * scope: the fault draws stay keyed by the physical env id cfg.env_id_offset + b, whatever rng_id says.
  * CM_ERR_ARG (text in cm_last_error) before anything is launched or copied: a NULL table, a CM_RNG_TAPE handle (a tape holds
  * draws recorded under one condition), rcom < 0, a probability the channel kind reads outside [0, 1], a non-zero reserved
  * word. */
 int cm_env_set_conditions(cm_env_t h, const cm_env_cond *host_table /* [n_envs] */, void *stream);
 int cm_env_has_conditions(cm_env_t h);   /* 1 once a table was set */
+/* on != 0: the four rollout entry points above run a handle with a table where the wave-owned rollout kernel covers its shape
+ * (Predator-Prey, teams of 4, 16 lanes per env, at most 16 preys, LDS within 160 KB: the kernels of csrc/cm_rollout_wc.hip, whose
+ * env phase reads the table) - bit for bit what the policy launch + cm_env_step give; every other shape still returns 1.  Off by
+ * default.  Allowed before or after the table is set; without a table it has no effect.  CM_ERR_ARG on a NULL handle. */
+int cm_env_fuse_conditions(cm_env_t h, int32_t on);
 
 /* PP agent_condition (predator_prey.py:74,152,258): [B,N] bytes, 0 = the agent's moves are not applied; every env reset
  * puts its row back to ones.  HOST pointers; either may be NULL.  Synchronises. */

@@ -3,10 +3,17 @@ comm conditions - against the same cells scored without per-env conditions: C ev
 B / C envs, the same number of episodes per cell.  Whole calls on the host clock, each ending in a synchronise, on
   pp_map10   PP map 10, teams of 4, 4096 envs, K = 8 policies x C = 8 conditions (IID channel: range x loss), 64 episodes per cell;
   co_map20   CO map 20, teams of 24, 1024 envs, K = 4 x C = 4 (Gilbert-Elliott channel: range x (Pgb, Pbg)), 64 episodes per cell;
+  pp_map10_k1  the pp_map10 batch with ONE policy: K = 1 x C = 8, 512 episodes per cell (the single-policy chunk);
 max_env_steps = 200, greedy, one round.  Both sides are warmed up first, then alternate for three rounds; every call gets fresh
 wrappers of the same seed.  Before anything is timed the sweep's cells of policy 0 are compared (==) with eval_summary of policy 0
 on the uniform wrappers (paired ids: those cells play the same episodes).
-    python tools/eval_sweep_time.py [pp_map10|co_map20]     one workload, no argument both
+Teams of 4 get a third leg, alternating with the other two: eval_sweep on a wrapper built with fused_conditions=True (the rollout in
+one launch per round, csrc/cm_rollout_wc.hip), whose cells of policy 0 are compared with the unfused sweep's as well.
+    python tools/eval_sweep_time.py [pp_map10|pp_map10_k1|co_map20]     one workload, no argument all
+    python tools/eval_sweep_time.py rollout_kernels         a 200-step chunk of RolloutEngine on a uniform IID range-3 batch (PP map 10,
+                                                            teams of 4, 4096 envs: the non-carried rollout_w_kernel), then on a fused
+                                                            conditions batch in which every env has that condition (rollout_wc_kernel),
+                                                            three times each: what a `rocprofv3 --kernel-trace --stats` run compares
     python tools/eval_sweep_time.py kernels                 the env step alone, uniform batch then conditions batch of the same
                                                             shape, batch and (single) condition, 300 steps each: the launches a
                                                             `rocprofv3 --kernel-trace --stats` run of this command compares
@@ -30,6 +37,8 @@ CO = dict(load=2, max_env_steps=T, capture_reward=2, step_cost=0, rm=0, penalty=
 WORKLOADS = {
     "pp_map10": dict(cls=E.PredatorPreyWrapper, params=PP, envs=4096, K=8, channel="IID",
                      conditions=[dict(Rcom=r, pl=p) for r in (9, 3, 2, 1) for p in (0.0, 0.5)]),
+    "pp_map10_k1": dict(cls=E.PredatorPreyWrapper, params=PP, envs=4096, K=1, channel="IID",
+                        conditions=[dict(Rcom=r, pl=p) for r in (9, 3, 2, 1) for p in (0.0, 0.5)]),
     "co_map20": dict(cls=E.CoverageWrapper, params=CO, envs=1024, K=4, channel="GE",
                      conditions=[dict(Rcom=r, Pgb=g, Pbg=b) for r in (19, 4) for g, b in ((0.0196, 0.282), (0.3, 0.1))]),
 }
@@ -56,7 +65,9 @@ def run(name):
     C_ = len(conds)
     n_epi = B // (K * C_)
     kw = dict(n_eval_episodes=n_epi, max_env_steps=T, eval_greedy=True)
-    sweep_wrapper = lambda: cls(True, params=params, n_envs=B, device="cuda:0", seed=SEED, channel=channel, conditions=conds)   # noqa: E731
+    sweep_wrapper = lambda fused=False: cls(True, params=params, n_envs=B, device="cuda:0", seed=SEED, channel=channel,   # noqa: E731
+                                            conditions=conds, fused_conditions=fused)
+    fused_leg = params["n_agents"] == 4 and cls is E.PredatorPreyWrapper    # the shapes the wave-owned rollout covers
     uniform_wrappers = lambda n: [cls(True, params=with_condition(params, c), n_envs=n, device="cuda:0", seed=SEED,   # noqa: E731
                                       channel=channel) for c in conds]
     first = sweep_wrapper()
@@ -66,19 +77,30 @@ def run(name):
         p = nets.CommCategoricalMLPPolicy(first.spec, n_agents=params["n_agents"], device="cuda:0")
         p.set_rng(SEED)
         pols.append(p)
-    sweep = lambda env: eval_sweep(env, pols, 0, paired=True, **kw)                                    # noqa: E731
-    sequential = lambda envs: [eval_summary(env, pols, 0, **kw) for env in envs]                         # noqa: E731
+    who = pols if K > 1 else pols[0]                                        # one policy: the single-policy engine, not a set of one
+    as_grid = lambda res: res if K > 1 else [res]                           # noqa: E731
+    sweep = lambda env: as_grid(eval_sweep(env, who, 0, paired=True, **kw))                             # noqa: E731
+    sequential = lambda envs: [as_grid(eval_summary(env, who, 0, **kw)) for env in envs]                # noqa: E731
     # warm-up of both sides and the comparison
     _, got = sync_time(lambda: sweep(first))
     _, ref = sync_time(lambda: sequential(uniform_wrappers(B // C_)))
+    if fused_leg:
+        _, got_f = sync_time(lambda: sweep(sweep_wrapper(True)))
+        same_f = all(got_f[0][c] == got[0][c] for c in range(C_))
+        print(f"{name}: cells of policy 0 on the fused wrapper equal the unfused sweep's: {same_f}", flush=True)
     ref0 = [eval_summary(env, pols[0], 0, **kw) for env in uniform_wrappers(n_epi)]                     # policy 0's cells, paired ids
     same = all({k: v for k, v in got[0][c].items() if k != "condition"} == ref0[c] for c in range(C_))
     print(f"{name}: cells of policy 0 equal eval_summary on the uniform wrappers: {same}", flush=True)
     for c in range(C_):
         print(f"  {conds[c]}: success {[round(got[k][c]['success'], 3) for k in range(K)]} "
               f"(sequential, other episodes: {[round(ref[c][k]['success'], 3) for k in range(K)]})", flush=True)
-    rounds = {"eval_sweep": [], "sequential": []}
+    rounds = {"eval_sweep_fused": [], "eval_sweep": [], "sequential": []}
     for r in range(ROUNDS):
+        if fused_leg:
+            env = sweep_wrapper(True)
+            dt, _ = sync_time(lambda: sweep(env))
+            rounds["eval_sweep_fused"].append(dt)
+            print(f"[{r}] {name} eval_sweep, fused wrapper   1 call,  {B} envs, {K} x {C_} cells x {n_epi} episodes: {dt * 1e3:9.2f} ms", flush=True)
         env = sweep_wrapper()
         dt, _ = sync_time(lambda: sweep(env))
         rounds["eval_sweep"].append(dt)
@@ -89,11 +111,17 @@ def run(name):
         print(f"[{r}] {name} sequential   {C_} calls, {B // C_} envs each, {K} policies x {n_epi} episodes: {dt * 1e3:9.2f} ms", flush=True)
     print(json.dumps({"workload": name, "envs": B, "policies": K, "conditions": C_, "episodes_per_cell": n_epi, "steps": T,
                       "policy0_cells_equal": bool(same),
+                      **({"fused_policy0_cells_equal": bool(same_f),
+                          "eval_sweep_fused_ms": [round(x * 1e3, 3) for x in rounds["eval_sweep_fused"]],
+                          "fused_ahead_of_unfused_in_every_round_against_every_round":
+                              bool(max(rounds["eval_sweep_fused"]) < min(rounds["eval_sweep"])),
+                          "fused_ahead_of_sequential_in_every_round_against_every_round":
+                              bool(max(rounds["eval_sweep_fused"]) < min(rounds["sequential"]))} if fused_leg else {}),
                       "eval_sweep_ms": [round(x * 1e3, 3) for x in rounds["eval_sweep"]],
                       "sequential_ms": [round(x * 1e3, 3) for x in rounds["sequential"]],
                       "sweep_ahead_in_every_round_against_every_round": bool(max(rounds["eval_sweep"]) < min(rounds["sequential"]))}),
           flush=True)
-    return same
+    return same and (not fused_leg or same_f)
 
 
 def kernels():
@@ -117,9 +145,35 @@ def kernels():
             print(f"{label}: {kind:10s} {steps} steps, host clock {dt / steps * 1e6:7.2f} us per step (launch-bound where small)", flush=True)
 
 
+def rollout_kernels():
+    """A 200-step chunk, three times, on a uniform IID range-3 batch - adjacency and channels change every step: the non-carried
+    rollout_w_kernel - and on a fused conditions batch of the same shape whose every env has that condition (rollout_wc_kernel)."""
+    from com_marl_amd.rollout import RolloutEngine
+    cond, B = dict(Rcom=3, pl=0.3), 4096
+    for kind in ("uniform", "conditions", "uniform", "conditions"):
+        kw = dict(conditions=[cond], fused_conditions=True) if kind == "conditions" else {}
+        env = E.GridEnvBatch("pp", with_condition(PP, cond), B, device="cuda:0", seed=SEED, channel="IID", **kw)
+        spec = E.EnvSpec(E._Box([0.0] * (env.d * env.N), [1.0] * (env.d * env.N)), E._Discrete(5))
+        torch.manual_seed(0)
+        pol = nets.CommCategoricalMLPPolicy(spec, n_agents=4, device="cuda:0")
+        pol.set_rng(SEED)
+        eng = RolloutEngine(env, pol, T)
+        pol.sync_weights()
+        for r in range(3):
+            eng.reset()
+            dt, ok = sync_time(lambda: eng.steps_fused(0, T))
+            assert ok, "the chunk was not one launch"
+            eng.bump(T)
+            env.check_status()
+            print(f"rollout chunk, {kind:10s} [{r}] {T} steps x {B} envs in one launch: {dt / T * 1e6:7.2f} us per step (host clock)", flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["kernels"]:
         kernels()
+        sys.exit(0)
+    if sys.argv[1:] == ["rollout_kernels"]:
+        rollout_kernels()
         sys.exit(0)
     names = sys.argv[1:] or list(WORKLOADS)
     ok = [run(name) for name in names]

@@ -16,6 +16,7 @@ CHANNELS = {"FC": 0, "FL": 1, "IID": 2, "GE": 3}
 RNG_PHILOX, RNG_TAPE = 0, 1
 ENT_ADD, ENT_SOFTPLUS, ENT_STOP_GRAD = 1, 2, 4                              # cm_ppo_surrogate's add_entropy bits
 EPI_COLS, SUM_COLS = 9, 12                                                  # cm_episode_stats / cm_episode_means row widths
+COMM_COLS, EPC_COLS = 4, 4                                                  # cm_comm_stats / cm_episode_comm, cm_comm_means row widths
 
 
 class EnvCfg(C.Structure):
@@ -215,6 +216,11 @@ _SIGNATURES = {
     "cm_episode_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "cm_episode_means": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_comm_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                C.c_void_p]),
+    "cm_episode_comm": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "cm_comm_means": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_chunk_tail": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cm_linear_act_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

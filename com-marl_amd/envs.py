@@ -165,6 +165,32 @@ def graph_diameter(dist_adj, out=None):
     return out
 
 
+def comm_stats(dist_adj, channels, n_hops, out=None):
+    """Link delivery and L-hop reach of every graph (cm_comm_stats, include/commarl.h): contiguous f32 CUDA tensors dist_adj
+    [..., N, N] and channels [..., L, N, N] with the same leading shape, either None = all ones (not both: the team size comes
+    from the tensors) -> int32 [..., 4]: in_range, delivered (summed over the n_hops hops), reach, range_reach.  An entry is set
+    when it is != 0, the diagonals are ignored.  One launch on the current stream; `out` receives the values when given."""
+    ref = dist_adj if dist_adj is not None else channels
+    assert ref is not None, "comm_stats: dist_adj and channels cannot both be None"
+    n_hops = int(n_hops)
+    for t, tail in ((dist_adj, 2), (channels, 3)):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.dim() >= tail and t.shape[-1] == t.shape[-2])
+        assert t is None or t.is_contiguous(), "cm_comm_stats reads the blocks through the raw pointer"
+    N = ref.shape[-1]
+    lead = dist_adj.shape[:-2] if dist_adj is not None else channels.shape[:-3]
+    if channels is not None:
+        assert channels.shape[-3] == n_hops and channels.shape[-1] == N and channels.shape[:-3] == lead
+        assert channels.device == ref.device
+    if out is None:
+        out = torch.empty(*lead, L.COMM_COLS, dtype=torch.int32, device=ref.device)
+    assert out.dtype == torch.int32 and out.shape == (*lead, L.COMM_COLS) and out.device == ref.device and out.is_contiguous()
+    S = out.numel() // L.COMM_COLS
+    with torch.cuda.device(ref.device):
+        L.check(L.lib().cm_comm_stats(S, N, n_hops, L.ptr(dist_adj), N * N, L.ptr(channels), n_hops * N * N, L.ptr(out),
+                                      L.current_stream()), "cm_comm_stats")
+    return out
+
+
 class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 

@@ -21,6 +21,8 @@ Differences a maintainer should know (documented, not silent):
 ``eval_summary`` plays the same rounds and returns only each policy's score (the CSV row of exp_runners/testing.py:329-335),
 reduced on the device by cm_episode_stats / cm_episode_means: nothing but K x 12 doubles is copied to the host.
 ``eval_sweep`` does the same for K policies x C comm conditions in one rollout, on a wrapper built with ``conditions=``.
+Both take ``comm_stats=True``: how much of the offered communication was delivered and how much of the team an agent can hear
+through the net's hops (cm_comm_stats on the engine's dist_adj / channels, COMM_KEYS in every dict).
 """
 import numpy as np
 import torch
@@ -189,10 +191,56 @@ def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200,
 
 
 SUMMARY_STATS = ['return_std', 'return_min', 'return_max']     # cm_episode_means columns behind the CM_EPI_COLS means
+COMM_STATS = ['range_degree', 'heard_degree', 'reach', 'range_reach']   # cm_episode_comm / cm_comm_means columns
+COMM_KEYS = COMM_STATS + ['delivery']                          # what comm_stats=True adds to a summary dict
+
+
+class _CommStats:
+    """The comm_stats=True side of eval_summary / eval_sweep: behind every round ONE cm_comm_stats launch on the engine's
+    dist_adj / channels (all T + 1 slots of all B envs) and ONE cm_episode_comm launch into a device table [cells, n_epi, 4];
+    after the last round ONE cm_comm_means launch into `self.out`, a view of the tail of the buffer the caller copies to the host.
+    A constant fully connected adjacency and a constant FC channel are passed as NULL (ones), a constant FL channel as the
+    batch's constant block with stride 0."""
+
+    def __init__(self, eng, batch, T, cells, n_epi, out):
+        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out = eng, batch, T, cells, n_epi, out
+        self.stats = torch.empty(T + 1, batch.B, L.COMM_COLS, dtype=torch.int32, device=batch.device)
+        self.table = torch.zeros(cells, n_epi, L.EPC_COLS, dtype=torch.float64, device=batch.device)
+
+    def round(self, group_size, take, row0):
+        eng, batch, lib = self.eng, self.batch, L.lib()
+        B, N, Lh = batch.B, batch.N, batch.Lh
+        if eng.channels is not None:
+            chan, chan_stride = eng.channels, Lh * N * N
+        elif batch.channelType == "FC":
+            chan, chan_stride = None, 0
+        else:
+            chan, chan_stride = batch.channels, 0                      # FL: one constant block (the identity) for every graph
+        L.check(lib.cm_comm_stats((self.T + 1) * B, N, Lh, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride,
+                                  L.ptr(self.stats), L.current_stream()), "cm_comm_stats")
+        L.check(lib.cm_episode_comm(self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
+                                    L.ptr(self.table), L.current_stream()), "cm_episode_comm")
+
+    def means(self):
+        L.check(L.lib().cm_comm_means(self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out), L.current_stream()),
+                "cm_comm_means")
+
+    @staticmethod
+    def keys(row):
+        d = {name: float(row[i]) for i, name in enumerate(COMM_STATS)}
+        d["delivery"] = d["heard_degree"] / d["range_degree"] if d["range_degree"] != 0 else 1.0
+        return d
+
+
+def _summary_buffers(cells, comm_stats, device):
+    """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None)."""
+    n = cells * L.SUM_COLS
+    flat = torch.empty(n + (cells * L.EPC_COLS if comm_stats else 0), dtype=torch.float64, device=device)
+    return flat, flat[:n].view(cells, L.SUM_COLS), (flat[n:].view(cells, L.EPC_COLS) if comm_stats else None)
 
 
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
-                 episodes=False):
+                 episodes=False, comm_stats=False):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
     eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
     the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
@@ -207,7 +255,15 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     bound_return is the scalar env.bound_return for both scenarios: the Coverage twin of eval_model differs only in returning
     it once per episode, so there is no _co entry here.  render / inspect_steps are not parameters (UI is out of scope).
     flag[0] set returns None per policy, as eval_models returns its empty tuples.  Afterwards env.eval_n_epi and
-    env.last_eval_average_reward (a list of K for several policies) are what eval_models / eval_model leave."""
+    env.last_eval_average_reward (a list of K for several policies) are what eval_models / eval_model leave.
+    comm_stats=True adds the communication statistics of the graphs the policy acted through (slots 0 .. n-1 of each episode;
+    include/commarl.h, cm_comm_stats): behind every round ONE cm_comm_stats launch on the engine's dist_adj / channels and ONE
+    cm_episode_comm launch, after the last round ONE cm_comm_means launch whose [K, 4] doubles ride in the same device-to-host
+    copy as the summary.  Every dict gains range_degree (mean number of agents in range), heard_degree (mean number heard per
+    hop), reach (mean number of team mates whose information can arrive within the net's hops), range_reach (the same without
+    channel loss) and delivery = heard_degree / range_degree (1.0 when nobody is in range); with episodes=True also
+    `comm_episodes`, the [n_eval_episodes, 4] device table behind the first four.  Off (the default), nothing is launched,
+    allocated or returned beyond the above and the results are bit for bit the same."""
     single = not isinstance(policies, (PolicySet, list, tuple))
     if flag is not None and flag[0]:
         return None if single else [None for _ in policies]
@@ -238,7 +294,8 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     lib = L.lib()
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(K, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    out = torch.empty(K, L.SUM_COLS, dtype=torch.float64, device=batch.device)
+    flat, out, comm_out = _summary_buffers(K, comm_stats, batch.device)
+    comm = _CommStats(eng, batch, T, K, n_epi, comm_out) if comm_stats else None
     done = 0
     while done < n_epi:
         eng.reset()
@@ -253,9 +310,15 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
         L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
                                      L.ptr(eng.path_len), L.ptr(eng.dist_adj), Bk, take, n_epi, done, L.ptr(table),
                                      L.current_stream()), "cm_episode_stats")
+        if comm:
+            comm.round(Bk, take, done)
         done += take
     L.check(lib.cm_episode_means(K, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
-    host = out.cpu().numpy()
+    if comm:
+        comm.means()
+    host_all = flat.cpu().numpy()
+    host = host_all[:K * L.SUM_COLS].reshape(K, L.SUM_COLS)
+    host_comm = host_all[K * L.SUM_COLS:].reshape(K, L.EPC_COLS) if comm else None
     bound = base.bound_return
     res = []
     for k in range(K):
@@ -265,6 +328,10 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
         d["bound_return"] = bound
         if episodes:
             d["episodes"] = table[k]
+        if comm:
+            d.update(comm.keys(host_comm[k]))
+            if episodes:
+                d["comm_episodes"] = comm.table[k]
         res.append(d)
     env.eval_n_epi = n_epi
     avg = [d["reward"] / bound for d in res]
@@ -285,7 +352,7 @@ def sweep_layout(B, K, C, env_id_offset=0, paired=True):
 
 
 def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
-               episodes=False):
+               episodes=False, comm_stats=False):
     """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
     conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
     policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
@@ -296,8 +363,10 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     Cell (k, c) holds exactly what eval_summary(W_c, policies[k]) returns for W_c a fresh wrapper of env's class, seed and
     channel kind whose params carry condition c, with E envs - at env's env_id_offset when paired (under greedy evaluation the
     points of a curve then differ only through the condition), at the cell's first env otherwise.
-    flag, episodes, the refusals and env.eval_n_epi are eval_summary's; env.last_eval_average_reward is a [K][C] list ([C] for
-    a single policy)."""
+    flag, episodes, comm_stats, the refusals and env.eval_n_epi are eval_summary's; env.last_eval_average_reward is a [K][C] list
+    ([C] for a single policy).  With comm_stats=True every cell carries eval_summary's communication keys (one cm_comm_stats and
+    one cm_episode_comm launch more per round, one cm_comm_means at the end, [K*C, 4] doubles more in the same copy): a robustness
+    curve can then be plotted against what was delivered (delivery, reach), not only against the knob that was turned."""
     single = not isinstance(policies, (PolicySet, list, tuple))
     base = getattr(env, "env", env)
     batch = base.batch
@@ -333,7 +402,8 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     lib = L.lib()
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(K * C_, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    out = torch.empty(K * C_, L.SUM_COLS, dtype=torch.float64, device=batch.device)
+    flat, out, comm_out = _summary_buffers(K * C_, comm_stats, batch.device)
+    comm = _CommStats(eng, batch, T, K * C_, n_epi, comm_out) if comm_stats else None
     done = 0
     while done < n_epi:
         eng.reset()
@@ -350,9 +420,15 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
         L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
                                      L.ptr(eng.path_len), L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table),
                                      L.current_stream()), "cm_episode_stats")
+        if comm:
+            comm.round(E, take, done)
         done += take
     L.check(lib.cm_episode_means(K * C_, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
-    host = out.cpu().numpy()
+    if comm:
+        comm.means()
+    host_all = flat.cpu().numpy()
+    host = host_all[:K * C_ * L.SUM_COLS].reshape(K * C_, L.SUM_COLS)
+    host_comm = host_all[K * C_ * L.SUM_COLS:].reshape(K * C_, L.EPC_COLS) if comm else None
     bound = base.bound_return
     res = []
     for k in range(K):
@@ -366,6 +442,10 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
             d["condition"] = conds[c]
             if episodes:
                 d["episodes"] = table[g]
+            if comm:
+                d.update(comm.keys(host_comm[g]))
+                if episodes:
+                    d["comm_episodes"] = comm.table[g]
             row.append(d)
         res.append(row)
     env.eval_n_epi = n_epi

@@ -244,6 +244,53 @@ int cm_episode_stats(int32_t T, int32_t B, int32_t N, int32_t scenario,      /* 
 int cm_episode_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPI_COLS] */,
                      double *summary /* [K, CM_SUM_COLS] */, void *stream);
 
+/* Communication statistics: how much of the offered communication was delivered, and how much of the team an agent can hear
+ * through the L hops of the Comm-DP net.  At hop l agent i hears j iff dist_adj[i][j] * channels[l][i][j] != 0
+ * (comm_base_net.py:101-103).  Pure functions of DEVICE arrays.
+ *
+ * cm_comm_stats turns S graphs into rows of CM_COMM_COLS int32.  Graph s reads the N*N floats at dist_adj + s*adj_stride and the
+ * L*N*N floats at channels + s*chan_stride (strides in floats).  A NULL array means all ones.  A stride of 0 means every graph
+ * reads the same block (a constant FL channel - the identity - is passed this way); any other stride must be at least the block
+ * size (N*N, L*N*N).  An entry is "set" when it is != 0.0f (-0.0 is not set).  The diagonal of both inputs is ignored and taken
+ * as set.  With a[i][j] = (dist_adj[i][j] set) and m_l[i][j] = a[i][j] && (channels[l][i][j] set), for i != j:
+ *   column 0 in_range    = #{(i,j), i != j : a[i][j]}
+ *          1 delivered   = sum over l of #{(i,j), i != j : m_l[i][j]}
+ *          2 reach       = #{(i,k), i != k : X_L[i][k]},  X_0 = I,  X_{l+1}[i] = X_l[i] OR (OR over j with m_l[i][j] of X_l[j]):
+ *                          hop 0 is applied first, and the order matters
+ *          3 range_reach = reach with every channel taken as ones (the geometry's share alone)
+ * Integer arithmetic, no atomics: two launches on the same inputs write the same bits.  Exactly S rows are written; S = 0 launches
+ * nothing.  CM_ERR_ARG (text in cm_last_error) before anything is launched: S < 0, N outside 1..255, L outside 1..8, a stride of a
+ * non-NULL array that is neither 0 nor at least the block size, or NULL stats with S > 0.
+ *
+ * cm_episode_comm sums the rows of the slots an episode's policy acted through into one row of CM_EPC_COLS doubles per episode.
+ * The env-to-row mapping (group_size, take, episodes_per_group, row0), the first-episode rule and the episode length n are
+ * cm_episode_stats's; the slots summed are 0 .. n-1 (the forward of step t reads slot t).  With c = the int64 column sums:
+ *   column 0 range_degree = c[in_range]    / (n N)      mean number of agents in range
+ *          1 heard_degree = c[delivered]   / (n N L)    mean number of agents heard per hop
+ *          2 reach        = c[reach]       / (n N)      mean number of team mates whose information can arrive within L hops
+ *          3 range_reach  = c[range_reach] / (n N)      the same on loss-free channels
+ * each sum divided once.  Refusals as cm_episode_stats (T < 1, N outside 1..255, group_size < 1 or not a divisor of B,
+ * take > group_size, row0 < 0 or row0 + take > episodes_per_group, a NULL pointer where there is work to do), and L outside 1..8.
+ * B = 0 or take = 0 launches nothing.
+ *
+ * cm_comm_means reduces each of K groups of E consecutive rows to their CM_EPC_COLS column means, summed in one fixed order
+ * (the order of cm_episode_means).  K < 1, E < 1 or a NULL pointer is CM_ERR_ARG. */
+#define CM_COMM_COLS 4   /* in_range, delivered, reach, range_reach */
+#define CM_EPC_COLS 4    /* range_degree, heard_degree, reach, range_reach */
+int cm_comm_stats(int32_t S, int32_t N, int32_t L,
+                  const float *dist_adj, int64_t adj_stride,     /* graph s: dist_adj + s*adj_stride, N*N floats; NULL = ones */
+                  const float *channels, int64_t chan_stride,    /* graph s: channels + s*chan_stride, L*N*N floats; NULL = ones */
+                  int32_t *stats,                                /* [S, CM_COMM_COLS] */
+                  void *stream);
+int cm_episode_comm(int32_t T, int32_t B, int32_t N, int32_t L,
+                    const int32_t *path_len,    /* [T,B] */
+                    const int32_t *stats,       /* [T+1,B,CM_COMM_COLS] */
+                    int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0,
+                    double *episodes,           /* [B/group_size * episodes_per_group, CM_EPC_COLS] */
+                    void *stream);
+int cm_comm_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPC_COLS] */,
+                  double *summary /* [K, CM_EPC_COLS] */, void *stream);
+
 /* Comm-DP policy weights (device pointers), reference state_dict names in comments
  * (SURVEY.md §8 a-16).  Linear weights are passed TRANSPOSED [in,out] (contiguous over the
  * output index) - the veneer keeps a transposed device copy; GCN weights are already [in,out]. */

@@ -92,6 +92,16 @@ class ForwardSetMember(C.Structure):
         (n, C.c_void_p) for n in ("pack", "enc_b1", "enc_b2", "gcn_b", "hd_b1", "hd_b2", "hd_b3", "hd_b4")]
 
 
+class AnySetMember(C.Structure):
+    """cm_any_set_member: one member's group, layer sizes, plane strides and weight pointers in the table
+    cm_policy_forward_any_multi reads."""
+    _fields_ = [(n, C.c_int32) for n in ("first_env", "n_envs", "emb", "no_residual", "n_enc")] + [
+        ("enc_h", C.c_int32 * 3), ("n_head", C.c_int32), ("head_h", C.c_int32 * 4), ("SE", C.c_int32), ("SW", C.c_int32),
+        ("_pad", C.c_int32), ("enc_w", C.c_void_p * 3), ("enc_b", C.c_void_p * 3), ("enc_wo", C.c_void_p), ("enc_bo", C.c_void_p),
+        ("attn_wt", C.c_void_p), ("gcn_w", C.c_void_p), ("gcn_b", C.c_void_p), ("head_w", C.c_void_p * 4),
+        ("head_b", C.c_void_p * 4), ("head_wo", C.c_void_p), ("head_bo", C.c_void_p)]
+
+
 MLP_MAX_LAYERS = 6
 
 
@@ -157,6 +167,11 @@ _SIGNATURES = {
     "cm_policy_forward_multi": (C.c_int, [C.POINTER(PolicyWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_policy_forward_any_multi_plan": (C.c_int64, [C.POINTER(NetWeights), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p,
+                                                     C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
+    "cm_policy_forward_any_multi": (C.c_int, [C.POINTER(NetWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_rollout_chunk_tail": (C.c_int, [C.c_void_p, C.POINTER(PolicyWeights), C.c_int32, C.POINTER(ChunkStrides), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StepOut), C.c_void_p, C.c_void_p, C.c_void_p,

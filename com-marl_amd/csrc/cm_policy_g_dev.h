@@ -1,5 +1,7 @@
 // cm_policy_g_dev.h - device side of the run-time-sized Comm-DP forwards: the policy (cm_policy_g.hip) and the critic
-// (cm_critic_g.hip) are the two instantiations of one kernel, which share trunk() and head() below.
+// (cm_critic_g.hip) are the two instantiations of one kernel, which share trunk() and head() below; the policy-set kernel
+// (cm_policy_gm.hip: every workgroup runs the net its table record names) calls the same two and includes the same sampler
+// tail (cm_policy_g_tail.h).
 //
 // One 256-thread workgroup owns EPB whole envs (rows = EPB * N agent rows, padded to R16 = a multiple of 16) and carries
 // them from the observation load to the sampled action.  LDS map (floats; every plane base and stride a multiple of 4):
@@ -142,10 +144,11 @@ __device__ __forceinline__ void dense(float *lds, int in, int in_s, int K, const
 struct Tile { int s0, envs, rows, oE, oH, oP0, oP1; };
 
 // The trunk both kernels share: zeroing, observation staging, encoder, attention + softmax, L hops, residual.  Leaves x in H.
-__device__ __forceinline__ Tile trunk(const Args &a, float *lds, int tid) {
+// `blk`: the workgroup's block index in the batch `a` describes (blockIdx.x, or the block inside a set member's group).
+__device__ __forceinline__ Tile trunk(const Args &a, float *lds, int tid, unsigned blk) {
     const int N = a.N, d = a.d, L = a.L, NN = N * N, NP = a.NP, EM = a.emb;
     const int SE = a.SE, SW = a.SW, R16 = a.R16;
-    const int s0 = blockIdx.x * a.EPB;
+    const int s0 = blk * a.EPB;
     const int envs = min(a.EPB, a.S - s0);
     const int rows = envs * N, rows_max = a.EPB * N;
     const int mat = (rows_max * NP + 3) & ~3;
@@ -270,7 +273,7 @@ template <bool CRITIC>
 __global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, N = a.N, SW = a.SW;
-    const Tile t = trunk(a, lds, tid);
+    const Tile t = trunk(a, lds, tid, blockIdx.x);
     const int s0 = t.s0, rows = t.rows;
     const int nxt = head(a, lds, t, tid);
     if constexpr (CRITIC) {
@@ -281,50 +284,7 @@ __global__ __launch_bounds__(TPB) void fwd_any_kernel(Args a) {
         }
         return;
     }
-    const int A = a.A;
-
-    // ---- per-agent softmax * avail, renormalise, sample (same arithmetic order as cm_mlp_body.h) ----
-    for (int r = tid; r < rows; r += TPB) {
-        const int lg = nxt + r * SW;
-        float p[MAX_ACT];
-        float mx = -INFINITY, sum = 0.0f, msum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) mx = fmaxf(mx, lds[lg + k]);
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) { p[k] = expf(lds[lg + k] - mx); sum += p[k]; }
-        const size_t flat = (size_t)s0 * N + r;             // global agent-row index
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) {
-            const float av = a.avail ? a.avail[flat * A + k] : 1.0f;
-            p[k] = (p[k] / sum) * av; msum += p[k];
-        }
-#pragma unroll
-        for (int k = 0; k < MAX_ACT; ++k) if (k < A) p[k] = p[k] / msum;
-        if (a.probs) {
-#pragma unroll
-            for (int k = 0; k < MAX_ACT; ++k) if (k < A) a.probs[flat * A + k] = p[k];
-        }
-        if (a.actions) {
-            int act = 0;
-            if (a.greedy) {
-                float best = p[0];
-#pragma unroll
-                for (int k = 1; k < MAX_ACT; ++k) if (k < A && p[k] > best) { best = p[k]; act = k; }
-            } else {
-                const int e = r / N, i = r - e * N;
-                const u32x4 xr = philox4x32_10((uint32_t)(a.env_id_offset + s0 + e),
-                                               a.policy_step + (a.step_base ? *a.step_base : 0u), SITE_ACTION, (uint32_t)i,
-                                               a.key0, a.key1);
-                const float u = unit_f32(xr.x);
-                float acc = 0.0f;
-                int sel = -1, last = 0;
-#pragma unroll
-                for (int k = 0; k < MAX_ACT; ++k) if (k < A) { if (p[k] > 0.0f) last = k; acc += p[k]; if (sel < 0 && u < acc) sel = k; }
-                act = sel < 0 ? last : sel;
-            }
-            a.actions[flat] = act;
-        }
-    }
+#include "cm_policy_g_tail.h"
 }
 
 }  // namespace pg

@@ -149,7 +149,9 @@ def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200,
     into K contiguous groups of B / K, policy k playing on group k, all K in the same rollout (one launch per round's chunk
     on the wave-owned kernel of teams of 4, nets.PolicySet).  -> list of K tuples (episode_data, epi_success, epi_rewards,
     bound_return); tuple k is exactly eval_model(W_k, policies[k], ...) for W_k a fresh wrapper of env's class, params and seed
-    with n_envs = B / K and env_id_offset = env's + k B / K.  Afterwards env.eval_n_epi is the episode count of one policy and
+    with n_envs = B / K and env_id_offset = env's + k B / K.  Comm-DP nets of other than the default layer sizes, also of
+    different sizes, take one forward launch per step when passed as nets.PolicySet(policies, any_sizes=True) (the same holds
+    for eval_summary and eval_sweep); as a list they step member by member.  Afterwards env.eval_n_epi is the episode count of one policy and
     env.last_eval_average_reward the list of the K policies' averages."""
     if render or inspect_steps:
         raise NotImplementedError("rendering is outside the MI355X path")

@@ -1686,6 +1686,21 @@ def _architecture(p):
             ("device", next(p.parameters()).device)]
 
 
+# what the members of a PolicySet(any_sizes=True) of Comm-DP policies may differ in: the layer sizes (encoder, embedding, head),
+# 'general' / 'dot' attention, the residual and the GCN bias (the last is part of "hidden sizes": a parameter more or less)
+_ANY_SIZES_FREE = ("attention type", "residual", "hidden sizes")
+
+
+def _differences(policies, skip=()):
+    """(member index, field, value, member 0's value) of the first disagreement with member 0 in a field not in `skip`, or None."""
+    ref = _architecture(policies[0])
+    for i, p in enumerate(policies[1:], 1):
+        for (name, v0), (_, v) in zip(ref, _architecture(p)):
+            if v != v0 and name not in skip:
+                return i, name, v, v0
+    return None
+
+
 class PolicySet:
     """K policies of ONE architecture (class, team size, observation dim, hops, attention type, residual, hidden sizes, hidden
     nonlinearity, device) that one RolloutEngine runs side by side, each on its own contiguous range of the envs - e.g. the
@@ -1693,22 +1708,35 @@ class PolicySet:
     ``_action_dim``, ``comm``, ...) comes from member 0; ``sync_weights()`` refreshes every member's pack,
     ``pack_table()`` keeps the device table of the members' pack addresses that cm_rollout_chunk_multi reads and
     ``forward_table()`` the one the set forward reads (cm_policy_forward_multi for Comm-DP members,
-    cm_mlp_policy_forward_multi for Obs-DP / CENT members)."""
-    _SHARED = ("_n_agents", "_action_dim", "_dec_obs_dim", "_obs_dim", "_embedding_dim", "comm", "centralized", "device",
-               "n_gcn_layers", "residual")
+    cm_mlp_policy_forward_multi for Obs-DP / CENT members).
 
-    def __init__(self, policies):
+    any_sizes=True (Comm-DP members only; Obs-DP / CENT members keep the whole check): the members may differ in their layer
+    sizes - encoder hidden sizes, embedding dim, head hidden sizes -, in 'general' / 'dot' attention, the residual and the GCN
+    bias (an architecture ablation in one rollout); class, team size, observation dim, action dim, hops, hidden nonlinearity and
+    device still agree.  Such a set of non-default nets - mixed or K checkpoints of one non-default shape - takes its forward as
+    ONE cm_policy_forward_any_multi launch per step (``set_kernel == "any"``); with a member of the default layer sizes in it, it
+    runs member by member.  A set whose members pass the whole check and have the default sizes behaves as without the keyword.
+    ``uniform`` says whether the members pass the whole check (always true without the keyword)."""
+    _SHARED = ("_n_agents", "_action_dim", "_dec_obs_dim", "_obs_dim", "comm", "centralized", "device", "n_gcn_layers")
+
+    def __init__(self, policies, any_sizes=False):
         policies = list(policies)
         if not policies:
             raise ValueError("PolicySet needs at least one policy")
-        ref = _architecture(policies[0])
-        for i, p in enumerate(policies[1:], 1):
-            for (name, v0), (_, v) in zip(ref, _architecture(p)):
-                if v != v0:
-                    raise ValueError(f"PolicySet: policies[{i}] differs from policies[0] in {name}: {v!r} != {v0!r}")
+        comm = all(isinstance(p, CommBaseNet) for p in policies)
+        self.any_sizes = bool(any_sizes)
+        bad = _differences(policies, skip=_ANY_SIZES_FREE if (self.any_sizes and comm) else ())
+        if bad is not None:
+            i, name, v, v0 = bad
+            raise ValueError(f"PolicySet: policies[{i}] differs from policies[0] in {name}: {v!r} != {v0!r}")
+        self.uniform = not (self.any_sizes and comm) or _differences(policies) is None
+        # the route of the run-time-sized set kernel: opted into, and not the set the default kernels already serve
+        default = self.uniform and all(getattr(p, "_default_shape", True) for p in policies)
+        self.set_kernel = "any" if (self.any_sizes and comm and not default) else "default"
         self.policies = policies
         self._table = None                      # (pack addresses, int64 device tensor of them)
         self._fwd_table = None                  # (key, device image | None, workgroup count): forward_table()
+        self.forward_lds = 0                    # set_kernel "any": the launch's dynamic LDS bytes, with _fwd_table
 
     def __getattr__(self, name):
         if name in PolicySet._SHARED:
@@ -1757,6 +1785,8 @@ class PolicySet:
         refreshes them in place).  A set the planner refuses (a group without envs, ...) raises."""
         if all(hasattr(p, "_mlp_struct") for p in self.policies):
             return self._mlp_forward_table(groups)
+        if self.set_kernel == "any":
+            return self._any_forward_table(groups)
         if not all(hasattr(p, "_weights_struct") and p._default_shape for p in self.policies):
             return None, 0                                   # (the set kernel is built for the default layer sizes)
         if any(p._mfma is None or p._pack is None for p in self.policies):
@@ -1781,6 +1811,40 @@ class PolicySet:
             if need < 0:
                 L.check(int(need), "cm_policy_forward_multi_plan")
             self._fwd_table = (key, table, n_wg.value)
+        return self._fwd_table[1], self._fwd_table[2]
+
+    def _any_forward_table(self, groups):
+        """forward_table() of a PolicySet(any_sizes=True) of non-default Comm-DP nets: the table of cm_policy_forward_any_multi
+        (cm_policy_forward_any_multi_plan over every member's cm_net_weights), kept until a member's flat weight copy was
+        reallocated or the groups change; ``forward_lds`` is the launch's LDS need.  (None, 0) when a member has more layers than
+        cm_policy_forward_any takes, the planner declines the set (a member above 160 KB of LDS), or a member has the default
+        layer sizes: its own forward is the f16-split cm_policy_forward, which the f32 set kernel would not equal bit for bit."""
+        if any(p._default_shape for p in self.policies):
+            return None, 0
+        groups = tuple(int(g) for g in groups)
+        if len(groups) != len(self.policies):
+            raise ValueError(f"forward_table: {len(groups)} groups for {len(self.policies)} policies")
+        if any(p._pack is None for p in self.policies):
+            self.sync_weights()
+        key = (groups, tuple(p._pack[0].data_ptr() for p in self.policies))
+        if self._fwd_table is None or self._fwd_table[0] != key:
+            K = len(self.policies)
+            structs = [p._net_struct() for p in self.policies]
+            if any(w is None for w in structs):
+                self._fwd_table, self.forward_lds = (key, None, 0), 0
+                return None, 0
+            ws = (L.NetWeights * K)(*structs)
+            sizes, n_wg, lds = (C.c_int32 * K)(*groups), C.c_int32(0), C.c_size_t(0)
+            plan = L.lib().cm_policy_forward_any_multi_plan
+            need = plan(ws, sizes, K, sum(groups), None, 0, C.byref(n_wg), C.byref(lds))
+            table = None
+            if need > 0:
+                image = bytearray(need)
+                need = plan(ws, sizes, K, sum(groups), (C.c_char * need).from_buffer(image), need, C.byref(n_wg), C.byref(lds))
+                table = torch.frombuffer(image, dtype=torch.uint8).to(self.policies[0]._pack[0].device)
+            if need < 0:
+                L.check(int(need), "cm_policy_forward_any_multi_plan")
+            self._fwd_table, self.forward_lds = (key, table, n_wg.value), (lds.value if table is not None else 0)
         return self._fwd_table[1], self._fwd_table[2]
 
     def _mlp_forward_table(self, groups):

@@ -65,8 +65,9 @@ class RolloutEngine:
         starts at the same global env id.  Teams of 4 whose groups start on multiples of 16 envs run a chunk as ONE
         cm_rollout_chunk_multi launch (multi_form "wave"); every other set takes one forward + one env step over the batch per
         step (multi_form "loop"), the forward being ONE launch for all members where the library has a set kernel for the
-        shape (multi_forward "set": cm_policy_forward_multi for Comm-DP teams other than 4, up to 80 agents, and
-        cm_mlp_policy_forward_multi for Obs-DP / CENT members of any team size; one sampler seed, production RNG) and one
+        shape (multi_forward "set": cm_policy_forward_multi for Comm-DP teams other than 4, up to 80 agents,
+        cm_mlp_policy_forward_multi for Obs-DP / CENT members of any team size, and cm_policy_forward_any_multi for a
+        PolicySet(any_sizes=True) of Comm-DP nets with non-default - also mixed - layer sizes; one sampler seed, production RNG) and one
         forward launch per member on its envs otherwise (multi_forward "member")."""
         if isinstance(env, (list, tuple)):
             env = _Parts(list(env)) if len(env) > 1 else env[0]
@@ -152,15 +153,19 @@ class RolloutEngine:
         # one launch for the whole set: teams of 4 on the default (wave-owned) kernel, every member's envs in whole workgroups of
         # 16, one sampler seed; the library may still answer "not for this shape" (1), and the engine then loops from there on
         pk = os.environ.get("COMMARL_POLICY_KERNEL", "w")[:1]
-        wave = (hasattr(ps[0], "chunk_fused") and getattr(ps[0], "_default_shape", True) and ps._n_agents == 4
+        # (member 0 speaks for the set only where the members pass the whole architecture check: ps.uniform)
+        wave = (hasattr(ps[0], "chunk_fused") and getattr(ps[0], "_default_shape", True) and ps.uniform and ps._n_agents == 4
                 and pk not in ("h", "f", "v") and ps.seed is not None
                 and all(lo % WG_ENVS == 0 for lo, _ in self.groups) and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_form = "wave" if wave else "loop"
         self._persistent, self._fused = wave, None
         # loop form: one forward launch for the whole set (cm_policy_forward_multi for Comm-DP members, cm_mlp_policy_forward_multi
         # for Obs-DP / CENT members) - one sampler seed, production RNG; the library answers "not for this shape" (1) for the
-        # teams it has no set kernel for, and the engine remembers it
-        set_fwd = ((hasattr(ps[0], "chunk_fused") or hasattr(ps[0], "_mlp_struct")) and getattr(ps[0], "_default_shape", True)
+        # teams it has no set kernel for, and the engine remembers it.  PolicySet(any_sizes=True) of non-default Comm-DP nets:
+        # cm_policy_forward_any_multi, whatever the members' layer sizes
+        set_fwd = ((ps.set_kernel == "any"
+                    or ((hasattr(ps[0], "chunk_fused") or hasattr(ps[0], "_mlp_struct")) and getattr(ps[0], "_default_shape", True)
+                        and ps.uniform))
                    and ps.seed is not None
                    and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_forward = None if wave else ("set" if set_fwd else "member")
@@ -192,8 +197,9 @@ class RolloutEngine:
         return True
 
     def _set_forward(self, t, greedy):
-        """Slot t's forward + sample of every member in ONE launch over the batch: cm_policy_forward_multi, or
-        cm_mlp_policy_forward_multi for Obs-DP / CENT members.  False - nothing launched - when the library has no set kernel
+        """Slot t's forward + sample of every member in ONE launch over the batch: cm_policy_forward_multi,
+        cm_mlp_policy_forward_multi for Obs-DP / CENT members, or cm_policy_forward_any_multi for a PolicySet(any_sizes=True) of
+        non-default Comm-DP nets.  False - nothing launched - when the library has no set kernel
         for this shape (the engine launches member by member from then on).  The members' packs are used as they are, as in
         _multi_chunk."""
         ps, B = self.policy, self.env.B
@@ -207,6 +213,15 @@ class RolloutEngine:
                 rc = L.lib().cm_mlp_policy_forward_multi(
                     C.byref(w), L.ptr(table), n_wg, B, 1 if ps[0]._per_agent_rows else N, ps._action_dim, N, L.ptr(obs), None,
                     ps.seed, self.id0, t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs),
+                    L.current_stream())
+        elif table is not None and ps.set_kernel == "any":
+            what = "cm_policy_forward_any_multi"
+            w = ps[0]._net_struct()                                         # the team, observation, hops and actions every member shares
+            obs, adj, ch, actions, probs, attn = self._slot(t, 0, B)
+            with torch.cuda.device(self.env.device):
+                rc = L.lib().cm_policy_forward_any_multi(
+                    C.byref(w), L.ptr(table), n_wg, B, ps.forward_lds, L.ptr(obs), None, L.ptr(adj), L.ptr(ch), ps.seed, self.id0,
+                    t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
                     L.current_stream())
         elif table is not None:
             w = ps[0]._weights_struct()                                     # the shape every member shares

@@ -503,6 +503,52 @@ int cm_policy_forward_multi(const cm_policy_weights *shape, const void *table_de
                             int32_t env_id_offset, uint32_t policy_step, const uint32_t *policy_step_base, int32_t greedy,
                             int32_t *actions, float *probs, float *attn, void *stream);
 
+/* cm_policy_forward_any for SEVERAL Comm-DP policies in ONE launch, each on its own contiguous range of the envs - and the members
+ * may differ in their layer sizes: encoder hidden sizes, embedding, head hidden sizes, 'general' / 'dot' attention (attn_wt NULL),
+ * residual, GCN bias (gcn_b NULL).  They share n_agents, d, n_hops and n_act.  A workgroup owns whole envs of ONE member, reads
+ * that member's sizes and weight pointers from the table and runs cm_policy_forward_any's body on them (csrc/cm_policy_gm.hip):
+ * every output is bit-identical to cm_policy_forward_any with member k's weights on its group's rows and env_id_offset + the
+ * group's first env (one seed for the set).
+ *
+ * cm_policy_forward_any_multi_plan (host only, no device work): checks the set and returns the size in bytes of the table the
+ * launch reads, *n_wg = the launch's workgroup count = sum over k of ceil(group_sizes[k] / EPB), EPB = max(1, 48 / n_agents) (a
+ * group ends in a ragged workgroup of its own, never shared with the next member), *lds_bytes = the launch's dynamic LDS (the
+ * largest member's need; every workgroup zeroes and uses its own member's map only).  With `image` non-NULL (image_bytes >= that
+ * size) the table's host image is written there: n_wg cm_forward_set_wg descriptors, then n_policies cm_any_set_member records.
+ * The caller uploads the image to device memory it owns and rebuilds it when a member's weight buffers move or the groups change;
+ * the weights themselves are read at launch time.  Returns
+ *   0 (*n_wg = 0, nothing written: no set kernel) when a member is outside cm_policy_forward_any's bounds or needs more than
+ *     160 KB of LDS (*lds_bytes = the largest need found, 0 when a member is out of bounds);
+ *   CM_ERR_ARG (< 0, cm_last_error set) for a null argument, n_policies < 1, members that differ in n_agents, d, n_hops or
+ *     n_act, a group of fewer than 1 env, group sizes that do not sum to n_envs, a null weight cm_policy_forward_any requires, or
+ *     an image buffer that is too small.
+ *
+ * cm_policy_forward_any_multi: the launch.  `shape` = any member's weights (n_agents, d, n_hops, n_act are read, and its layer sizes
+ * only to answer 1), table_dev = the uploaded image, n_wg / n_envs / lds_bytes = the planner's; every argument from `obs` on is
+ * cm_policy_forward_any's over the whole batch.  No allocation, copy or synchronisation: it can be captured in a hipGraph.  The
+ * kernel trusts the table.  Returns 0 when launched; 1 - nothing launched, nothing written - when `shape` is a net
+ * cm_policy_forward_any answers 1 for, or lds_bytes is 0 or above 160 KB (the planner's answer for a set it declines): the caller
+ * then runs cm_policy_forward_any (or layer by layer) per member; CM_ERR_ARG for a null shape / obs / table, an n_wg outside
+ * [ceil(n_envs / EPB), n_envs], or an lds_bytes below `shape`'s own need. */
+typedef struct cm_any_set_member {
+    int32_t first_env, n_envs;       /* the member's group */
+    int32_t emb, no_residual;
+    int32_t n_enc, enc_h[3];
+    int32_t n_head, head_h[4];
+    int32_t SE, SW;                  /* LDS row strides of the member's planes: pad16(emb) + 4, pad16(max(widest layer, d)) + 4 */
+    int32_t _pad;
+    const float *enc_w[3], *enc_b[3], *enc_wo, *enc_bo;     /* hidden layers (slots >= n_enc NULL), then the output layer (-> emb) */
+    const float *attn_wt, *gcn_w, *gcn_b;                   /* attn_wt NULL = 'dot'; gcn_b NULL = no GCN bias */
+    const float *head_w[4], *head_b[4], *head_wo, *head_bo; /* hidden layers (slots >= n_head NULL), then the logits layer */
+} cm_any_set_member;
+int64_t cm_policy_forward_any_multi_plan(const cm_net_weights *members, const int32_t *group_sizes, int32_t n_policies,
+                                         int32_t n_envs, void *image, size_t image_bytes, int32_t *n_wg, size_t *lds_bytes);
+int cm_policy_forward_any_multi(const cm_net_weights *shape, const void *table_dev, int32_t n_wg, int32_t n_envs,
+                                size_t lds_bytes, const float *obs, const float *avail, const float *dist_adj,
+                                const float *channels, uint64_t seed, int32_t env_id_offset, uint32_t policy_step,
+                                const uint32_t *policy_step_base, int32_t greedy, int32_t *actions, float *probs, float *attn,
+                                void *stream);
+
 /* cm_rollout_chunk followed by cm_chunk_tail (below) for the same chunk: the observation (and masks, where the env produces
  * them) the last step wrote - out->obs + (n_steps - 1) * strides->obs, ... - carried into obs_next / dist_adj_next /
  * channels_next (slot 0 of the caller's ring; the mask pointers may be NULL) and *policy_step_base += n_steps.  Where the wave-owned

@@ -34,13 +34,12 @@ from .rollout import RolloutEngine
 VECTORS = ['reward', 'capture_cnt', 'step_cnt', 'move_cnt', 'penalty_cnt', 'nodeDeg', 'variable', 'vars2']   # testing.py:209
 
 
-def _first_episodes(eng, base, T, greedy):
-    """reset + T steps; returns host arrays for every env's first episode."""
+def _first_episodes(eng, base, T, greedy, chunk=False):
+    """reset + T steps; returns host arrays for every env's first episode.  chunk: the T steps as chunk launches where the
+    engine has them (one launch for every member of a PolicySet on the wave-owned kernel); bit-identical to stepping them one
+    by one."""
     eng.reset()
-    eng.fork()
-    for t in range(T):
-        eng.step(t, greedy=greedy)
-    eng.join()
+    eng.play(0, T, greedy=greedy, chunk=chunk)
     eng.bump(T)
     base.batch.check_status()
     pl = eng.path_len[:T]                                                  # [T,B]
@@ -75,38 +74,17 @@ def eval_model(env, policy, itr, n_eval_episodes=100, max_env_steps=200, eval_gr
     episode_data, epi_success = [], []
     epi_rewards = {vec: [] for vec in VECTORS}
     eval_rewards = []
-    nA = float(N)
     while len(episode_data) < n_eval_episodes:
-        h = _first_episodes(eng, base, T, bool(eval_greedy))
+        h = _first_episodes(eng, base, T, bool(eval_greedy))               # (a single policy steps one by one)
         for b in range(min(B, n_eval_episodes - len(episode_data))):
-            n = int(h["first"][b]) + 1
-            det = h["details"][:n, b].astype(np.float64)
-            rew = h["reward"][:n, b]
-            if "deg" in h:
-                deg = np.concatenate([h["deg"][1:n, b], h["deg"][n - 1:n, b]])
-            else:
-                deg = np.full(n, N)
-            if pp:                                                          # predator_prey.py:440-448
-                cols = dict(capture_cnt=det[:, 0], move_cnt=det[:, 1] / nA, penalty_cnt=det[:, 2],
-                            variable=det[:, 4] / nA, vars2=np.zeros(n))
-            else:                                                           # coverage.py:308-315
-                cols = dict(capture_cnt=det[:, 0] / nA, move_cnt=det[:, 1] / nA, penalty_cnt=det[:, 2] / nA,
-                            variable=det[:, 4] / nA, vars2=det[:, 3] / nA)
-            cols.update(reward=rew, step_cnt=np.ones(n), nodeDeg=deg)
-            step_data = {vec: cols[vec].tolist() for vec in VECTORS}
-            step_success = h["success"][:n, b].tolist()
-            episode_data.append((step_success, step_data))
-            epi_success.append(int(h["success"][n - 1, b]))
-            for vec in VECTORS:
-                epi_rewards[vec].append(float(np.mean(cols[vec]) if vec == 'nodeDeg' else np.sum(cols[vec])))
-            eval_rewards.append(float(rew.sum()))
+            _append_episode(h, b, N, pp, episode_data, epi_success, epi_rewards, eval_rewards)
     env.eval_n_epi = len(episode_data)
     env.last_eval_average_reward = (sum(eval_rewards) / len(eval_rewards)) / base.bound_return    # eval_pp.py:95
     return episode_data, epi_success, epi_rewards, base.bound_return
 
 
 def _episode(h, b, N, pp):
-    """Env b's first episode of a round (host arrays of _first_episodes / _rounds) -> what eval_model appends for it."""
+    """Env b's first episode of a round (host arrays of _first_episodes) -> what eval_model appends for it."""
     n = int(h["first"][b]) + 1
     det = h["details"][:n, b].astype(np.float64)
     rew = h["reward"][:n, b]
@@ -122,25 +100,16 @@ def _episode(h, b, N, pp):
     return n, cols, rew
 
 
-def _rounds(eng, base, T, greedy):
-    """_first_episodes with the T steps as chunk launches where the engine has them (one launch for every member of a
-    PolicySet on the wave-owned kernel); bit-identical to stepping them one by one."""
-    eng.reset()
-    if not eng.steps_fused(0, T, greedy=greedy):
-        eng.fork()
-        for t in range(T):
-            eng.step(t, greedy=greedy)
-        eng.join()
-    eng.bump(T)
-    base.batch.check_status()
-    pl = eng.path_len[:T]
-    ended = pl > 0
-    first = torch.where(ended.any(0), ended.to(torch.int32).argmax(0), torch.full_like(pl[0], T - 1)).long()
-    h = dict(first=first.cpu().numpy(), reward=eng.reward64[:T].cpu().numpy(), details=eng.details[:T].cpu().numpy(),
-             success=eng.success[:T].cpu().numpy(), done=eng.done[:T].cpu().numpy())
-    if eng.dist_adj is not None:
-        h["deg"] = eng.dist_adj[:T + 1].sum(-1).mean(-1).cpu().numpy()
-    return h
+def _append_episode(h, b, N, pp, episode_data, epi_success, epi_rewards, eval_rewards):
+    """Env b's first episode of a round onto one policy's lists: what eval_model returns per episode (the per-step success and
+    VECTORS lists, the final success, per vector the episode's sum - mean for nodeDeg) and the return behind
+    last_eval_average_reward."""
+    n, cols, rew = _episode(h, b, N, pp)
+    episode_data.append((h["success"][:n, b].tolist(), {vec: cols[vec].tolist() for vec in VECTORS}))
+    epi_success.append(int(h["success"][n - 1, b]))
+    for vec in VECTORS:
+        epi_rewards[vec].append(float(np.mean(cols[vec]) if vec == 'nodeDeg' else np.sum(cols[vec])))
+    eval_rewards.append(float(rew.sum()))
 
 
 def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, render=False,
@@ -177,16 +146,11 @@ def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200,
     epi_rewards = [{vec: [] for vec in VECTORS} for _ in range(K)]
     eval_rewards = [[] for _ in range(K)]
     while len(data[0]) < n_eval_episodes:                 # every group has Bk envs: the same number of rounds for each
-        h = _rounds(eng, base, T, bool(eval_greedy))
+        h = _first_episodes(eng, base, T, bool(eval_greedy), chunk=True)
         take = min(Bk, n_eval_episodes - len(data[0]))
         for k, (lo, _) in enumerate(eng.groups):
             for b in range(lo, lo + take):
-                n, cols, rew = _episode(h, b, N, pp)
-                data[k].append((h["success"][:n, b].tolist(), {vec: cols[vec].tolist() for vec in VECTORS}))
-                success[k].append(int(h["success"][n - 1, b]))
-                for vec in VECTORS:
-                    epi_rewards[k][vec].append(float(np.mean(cols[vec]) if vec == 'nodeDeg' else np.sum(cols[vec])))
-                eval_rewards[k].append(float(rew.sum()))
+                _append_episode(h, b, N, pp, data[k], success[k], epi_rewards[k], eval_rewards[k])
     env.eval_n_epi = len(data[0])
     env.last_eval_average_reward = [(sum(r) / len(r)) / base.bound_return for r in eval_rewards]
     return [(data[k], success[k], epi_rewards[k], base.bound_return) for k in range(K)]
@@ -241,6 +205,97 @@ def _summary_buffers(cells, comm_stats, device):
     return flat, flat[:n].view(cells, L.SUM_COLS), (flat[n:].view(cells, L.EPC_COLS) if comm_stats else None)
 
 
+def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True):
+    """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
+    refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
+    [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  Per round reset, play, bump, check_status, the
+    episode rows of groups of E envs into the device table [K*C, n_eval_episodes, 9] (and _CommStats.round); then the table's
+    reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer."""
+    single = not isinstance(policies, (PolicySet, list, tuple))
+    C_ = 1 if conds is None else len(conds)
+
+    def shaped(cells):
+        """K*C values in cell order -> the caller's [K] (eval_summary) or [K][C] (eval_sweep); a single policy: its entry."""
+        per = cells if conds is None else [cells[i:i + C_] for i in range(0, len(cells), C_)]
+        return per[0] if single else per
+
+    if flag is not None and flag[0]:
+        return shaped([None] * ((1 if single else len(policies)) * C_))
+    base = getattr(env, "env", env)
+    batch = base.batch
+    B, N = batch.B, batch.N
+    T = int(max_env_steps)
+    if single:
+        ps, K = policies, 1
+    else:
+        ps = policies if isinstance(policies, PolicySet) else PolicySet(policies)
+        K = len(ps)
+    cells = K * C_
+    if B % cells:
+        raise ValueError(f"{who}: the {B} envs of the wrapper do not split evenly between {K} policies"
+                         + ("" if conds is None else f" x {C_} conditions"))
+    E = B // cells
+    if T > batch.cfg.max_path_length:
+        raise ValueError(f"max_env_steps={T} exceeds the env's max_path_length={batch.cfg.max_path_length}")
+    n_epi = int(n_eval_episodes)
+    if n_epi < 1:
+        raise ValueError(f"{who}: n_eval_episodes must be at least 1")
+    if conds is not None:
+        batch.set_conditions(conds, *sweep_layout(B, K, C_, batch.cfg.env_id_offset, paired))
+    env.eval_n_epi = 0
+    ps.sync_weights()
+    ps.reset([True] * (C_ * E))
+    eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, **({} if single else dict(groups=[C_ * E] * K)))
+    # eval_summary of a single policy plays eval_model's rounds, which step one by one; every other call asks for the chunk
+    # launch, as eval_models does.  A conditions batch declines the fused forms (two launches per step) unless the wrapper was
+    # built with fused_conditions=True (GridEnvBatch.fuse_conditions): then teams of 4 play the round as one launch, a single
+    # policy included
+    chunk = conds is not None or not single
+    lib = L.lib()
+    scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
+    table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
+    flat, out, comm_out = _summary_buffers(cells, comm_stats, batch.device)
+    comm = _CommStats(eng, batch, T, cells, n_epi, comm_out) if comm_stats else None
+    done = 0
+    while done < n_epi:
+        eng.reset()
+        eng.play(0, T, greedy=bool(eval_greedy), chunk=chunk)
+        eng.bump(T)
+        batch.check_status()
+        take = min(E, n_epi - done)
+        L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
+                                     L.ptr(eng.path_len), L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table),
+                                     L.current_stream()), "cm_episode_stats")
+        if comm:
+            comm.round(E, take, done)
+        done += take
+    L.check(lib.cm_episode_means(cells, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
+    if comm:
+        comm.means()
+    host_all = flat.cpu().numpy()
+    host = host_all[:cells * L.SUM_COLS].reshape(cells, L.SUM_COLS)
+    host_comm = host_all[cells * L.SUM_COLS:].reshape(cells, L.EPC_COLS) if comm else None
+    bound = base.bound_return
+    res = []
+    for g in range(cells):
+        d = dict(n_episodes=n_epi, success=float(host[g, 0]))
+        d.update({vec: float(host[g, 1 + i]) for i, vec in enumerate(VECTORS)})
+        d.update({name: float(host[g, L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
+        d["bound_return"] = bound
+        if conds is not None:
+            d["condition"] = conds[g % C_]
+        if episodes:
+            d["episodes"] = table[g]
+        if comm:
+            d.update(comm.keys(host_comm[g]))
+            if episodes:
+                d["comm_episodes"] = comm.table[g]
+        res.append(d)
+    env.eval_n_epi = n_epi
+    env.last_eval_average_reward = shaped([d["reward"] / bound for d in res])
+    return shaped(res)
+
+
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
                  episodes=False, comm_stats=False):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
@@ -266,79 +321,7 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     channel loss) and delivery = heard_degree / range_degree (1.0 when nobody is in range); with episodes=True also
     `comm_episodes`, the [n_eval_episodes, 4] device table behind the first four.  Off (the default), nothing is launched,
     allocated or returned beyond the above and the results are bit for bit the same."""
-    single = not isinstance(policies, (PolicySet, list, tuple))
-    if flag is not None and flag[0]:
-        return None if single else [None for _ in policies]
-    base = getattr(env, "env", env)
-    batch = base.batch
-    B, N = batch.B, batch.N
-    T = int(max_env_steps)
-    if single:
-        ps, K = policies, 1
-    else:
-        ps = policies if isinstance(policies, PolicySet) else PolicySet(policies)
-        K = len(ps)
-        if B % K:
-            raise ValueError(f"eval_summary: the {B} envs of the wrapper do not split evenly between {K} policies")
-    Bk = B // K
-    if T > batch.cfg.max_path_length:
-        raise ValueError(f"max_env_steps={T} exceeds the env's max_path_length={batch.cfg.max_path_length}")
-    n_epi = int(n_eval_episodes)
-    if n_epi < 1:
-        raise ValueError("eval_summary: n_eval_episodes must be at least 1")
-    env.eval_n_epi = 0
-    ps.sync_weights()
-    ps.reset([True] * Bk)
-    if single:
-        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False)
-    else:
-        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, groups=[Bk] * K)
-    lib = L.lib()
-    scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
-    table = torch.zeros(K, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    flat, out, comm_out = _summary_buffers(K, comm_stats, batch.device)
-    comm = _CommStats(eng, batch, T, K, n_epi, comm_out) if comm_stats else None
-    done = 0
-    while done < n_epi:
-        eng.reset()
-        if single or not eng.steps_fused(0, T, greedy=bool(eval_greedy)):     # eval_model steps one by one, eval_models by chunk
-            eng.fork()
-            for t in range(T):
-                eng.step(t, greedy=bool(eval_greedy))
-            eng.join()
-        eng.bump(T)
-        batch.check_status()
-        take = min(Bk, n_epi - done)
-        L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
-                                     L.ptr(eng.path_len), L.ptr(eng.dist_adj), Bk, take, n_epi, done, L.ptr(table),
-                                     L.current_stream()), "cm_episode_stats")
-        if comm:
-            comm.round(Bk, take, done)
-        done += take
-    L.check(lib.cm_episode_means(K, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
-    if comm:
-        comm.means()
-    host_all = flat.cpu().numpy()
-    host = host_all[:K * L.SUM_COLS].reshape(K, L.SUM_COLS)
-    host_comm = host_all[K * L.SUM_COLS:].reshape(K, L.EPC_COLS) if comm else None
-    bound = base.bound_return
-    res = []
-    for k in range(K):
-        d = dict(n_episodes=n_epi, success=float(host[k, 0]))
-        d.update({vec: float(host[k, 1 + i]) for i, vec in enumerate(VECTORS)})
-        d.update({name: float(host[k, L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
-        d["bound_return"] = bound
-        if episodes:
-            d["episodes"] = table[k]
-        if comm:
-            d.update(comm.keys(host_comm[k]))
-            if episodes:
-                d["comm_episodes"] = comm.table[k]
-        res.append(d)
-    env.eval_n_epi = n_epi
-    avg = [d["reward"] / bound for d in res]
-    env.last_eval_average_reward = avg[0] if single else avg
-    return res[0] if single else res
+    return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats)
 
 
 def sweep_layout(B, K, C, env_id_offset=0, paired=True):
@@ -369,91 +352,11 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     ([C] for a single policy).  With comm_stats=True every cell carries eval_summary's communication keys (one cm_comm_stats and
     one cm_episode_comm launch more per round, one cm_comm_means at the end, [K*C, 4] doubles more in the same copy): a robustness
     curve can then be plotted against what was delivered (delivery, reach), not only against the knob that was turned."""
-    single = not isinstance(policies, (PolicySet, list, tuple))
-    base = getattr(env, "env", env)
-    batch = base.batch
-    conds = batch.conditions
+    conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
-    C_ = len(conds)
-    if flag is not None and flag[0]:
-        return [None] * C_ if single else [[None] * C_ for _ in policies]
-    B, N = batch.B, batch.N
-    T = int(max_env_steps)
-    if single:
-        ps, K = policies, 1
-    else:
-        ps = policies if isinstance(policies, PolicySet) else PolicySet(policies)
-        K = len(ps)
-    if B % (K * C_):
-        raise ValueError(f"eval_sweep: the {B} envs of the wrapper do not split evenly between {K} policies x {C_} conditions")
-    E = B // (K * C_)
-    if T > batch.cfg.max_path_length:
-        raise ValueError(f"max_env_steps={T} exceeds the env's max_path_length={batch.cfg.max_path_length}")
-    n_epi = int(n_eval_episodes)
-    if n_epi < 1:
-        raise ValueError("eval_sweep: n_eval_episodes must be at least 1")
-    batch.set_conditions(conds, *sweep_layout(B, K, C_, batch.cfg.env_id_offset, paired))
-    env.eval_n_epi = 0
-    ps.sync_weights()
-    ps.reset([True] * (C_ * E))
-    if single:
-        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False)
-    else:
-        eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, groups=[C_ * E] * K)
-    lib = L.lib()
-    scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
-    table = torch.zeros(K * C_, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    flat, out, comm_out = _summary_buffers(K * C_, comm_stats, batch.device)
-    comm = _CommStats(eng, batch, T, K * C_, n_epi, comm_out) if comm_stats else None
-    done = 0
-    while done < n_epi:
-        eng.reset()
-        # a conditions batch declines the fused forms (two launches per step) unless the wrapper was built with fused_conditions=True
-        # (GridEnvBatch.fuse_conditions): then teams of 4 play the round as one launch, a single policy included
-        if not eng.steps_fused(0, T, greedy=bool(eval_greedy)):
-            eng.fork()
-            for t in range(T):
-                eng.step(t, greedy=bool(eval_greedy))
-            eng.join()
-        eng.bump(T)
-        batch.check_status()
-        take = min(E, n_epi - done)
-        L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
-                                     L.ptr(eng.path_len), L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table),
-                                     L.current_stream()), "cm_episode_stats")
-        if comm:
-            comm.round(E, take, done)
-        done += take
-    L.check(lib.cm_episode_means(K * C_, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
-    if comm:
-        comm.means()
-    host_all = flat.cpu().numpy()
-    host = host_all[:K * C_ * L.SUM_COLS].reshape(K * C_, L.SUM_COLS)
-    host_comm = host_all[K * C_ * L.SUM_COLS:].reshape(K * C_, L.EPC_COLS) if comm else None
-    bound = base.bound_return
-    res = []
-    for k in range(K):
-        row = []
-        for c in range(C_):
-            g = k * C_ + c
-            d = dict(n_episodes=n_epi, success=float(host[g, 0]))
-            d.update({vec: float(host[g, 1 + i]) for i, vec in enumerate(VECTORS)})
-            d.update({name: float(host[g, L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
-            d["bound_return"] = bound
-            d["condition"] = conds[c]
-            if episodes:
-                d["episodes"] = table[g]
-            if comm:
-                d.update(comm.keys(host_comm[g]))
-                if episodes:
-                    d["comm_episodes"] = comm.table[g]
-            row.append(d)
-        res.append(row)
-    env.eval_n_epi = n_epi
-    avg = [[d["reward"] / bound for d in row] for row in res]
-    env.last_eval_average_reward = avg[0] if single else avg
-    return res[0] if single else res
+    return _score("eval_sweep", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
+                  conds=conds, paired=paired)
 
 
 def summary_row(summary):

@@ -153,8 +153,8 @@ class RolloutEngine:
         # one launch for the whole set: teams of 4 on the default (wave-owned) kernel, every member's envs in whole workgroups of
         # 16, one sampler seed; the library may still answer "not for this shape" (1), and the engine then loops from there on
         pk = os.environ.get("COMMARL_POLICY_KERNEL", "w")[:1]
-        # (member 0 speaks for the set only where the members pass the whole architecture check: ps.uniform)
-        wave = (hasattr(ps[0], "chunk_fused") and getattr(ps[0], "_default_shape", True) and ps.uniform and ps._n_agents == 4
+        # (ps.forward_kind "default": Comm-DP policies that pass the whole architecture check and have the default layer sizes)
+        wave = (ps.forward_kind == "default" and ps._n_agents == 4
                 and pk not in ("h", "f", "v") and ps.seed is not None
                 and all(lo % WG_ENVS == 0 for lo, _ in self.groups) and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_form = "wave" if wave else "loop"
@@ -163,10 +163,7 @@ class RolloutEngine:
         # for Obs-DP / CENT members) - one sampler seed, production RNG; the library answers "not for this shape" (1) for the
         # teams it has no set kernel for, and the engine remembers it.  PolicySet(any_sizes=True) of non-default Comm-DP nets:
         # cm_policy_forward_any_multi, whatever the members' layer sizes
-        set_fwd = ((ps.set_kernel == "any"
-                    or ((hasattr(ps[0], "chunk_fused") or hasattr(ps[0], "_mlp_struct")) and getattr(ps[0], "_default_shape", True)
-                        and ps.uniform))
-                   and ps.seed is not None
+        set_fwd = (ps.forward_kind is not None and ps.seed is not None
                    and getattr(self.env.cfg, "rng_mode", 0) == L.RNG_PHILOX)
         self.multi_forward = None if wave else ("set" if set_fwd else "member")
         if wave:
@@ -199,38 +196,22 @@ class RolloutEngine:
     def _set_forward(self, t, greedy):
         """Slot t's forward + sample of every member in ONE launch over the batch: cm_policy_forward_multi,
         cm_mlp_policy_forward_multi for Obs-DP / CENT members, or cm_policy_forward_any_multi for a PolicySet(any_sizes=True) of
-        non-default Comm-DP nets.  False - nothing launched - when the library has no set kernel
+        non-default Comm-DP nets.  The set names the entry point and the arguments it begins with (PolicySet.forward_call); the
+        rest is the same for every kind.  False - nothing launched - when the library has no set kernel
         for this shape (the engine launches member by member from then on).  The members' packs are used as they are, as in
         _multi_chunk."""
         ps, B = self.policy, self.env.B
-        table, n_wg = ps.forward_table([hi - lo for lo, hi in self.groups])
-        rc, what = 1, "cm_policy_forward_multi"
-        if table is not None and hasattr(ps[0], "_mlp_struct"):
-            what = "cm_mlp_policy_forward_multi"
-            w, N = ps[0]._mlp_struct(), ps._n_agents                        # the shape every member shares
-            obs, _, _, actions, probs, _ = self._slot(t, 0, B)
-            with torch.cuda.device(self.env.device):
-                rc = L.lib().cm_mlp_policy_forward_multi(
-                    C.byref(w), L.ptr(table), n_wg, B, 1 if ps[0]._per_agent_rows else N, ps._action_dim, N, L.ptr(obs), None,
-                    ps.seed, self.id0, t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs),
-                    L.current_stream())
-        elif table is not None and ps.set_kernel == "any":
-            what = "cm_policy_forward_any_multi"
-            w = ps[0]._net_struct()                                         # the team, observation, hops and actions every member shares
+        call = ps.forward_call([hi - lo for lo, hi in self.groups], B)
+        rc = 1                                                              # no table: as the library's "not for this shape"
+        if call is not None:
+            what, lead = call
             obs, adj, ch, actions, probs, attn = self._slot(t, 0, B)
+            # the Obs-DP / CENT entry point has no adjacency, channel or attention argument
+            graph, attn = ((), ()) if ps.forward_kind == "mlp" else ((L.ptr(adj), L.ptr(ch)), (L.ptr(attn),))
             with torch.cuda.device(self.env.device):
-                rc = L.lib().cm_policy_forward_any_multi(
-                    C.byref(w), L.ptr(table), n_wg, B, ps.forward_lds, L.ptr(obs), None, L.ptr(adj), L.ptr(ch), ps.seed, self.id0,
-                    t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
-                    L.current_stream())
-        elif table is not None:
-            w = ps[0]._weights_struct()                                     # the shape every member shares
-            obs, adj, ch, actions, probs, attn = self._slot(t, 0, B)
-            with torch.cuda.device(self.env.device):
-                rc = L.lib().cm_policy_forward_multi(
-                    C.byref(w), L.ptr(table), n_wg, B, L.ptr(obs), None, L.ptr(adj), L.ptr(ch), ps.seed, self.id0,
-                    t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
-                    L.current_stream())
+                rc = getattr(L.lib(), what)(
+                    *lead, L.ptr(obs), None, *graph, ps.seed, self.id0, t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy),
+                    L.ptr(actions), L.ptr(probs), *attn, L.current_stream())
         if rc == 1:
             self.multi_forward = "member"
             return False
@@ -350,6 +331,17 @@ class RolloutEngine:
         for st in self.streams:
             if st is not None:
                 cur.wait_stream(st)
+
+    def play(self, t0, n, greedy=False, chunk=True):
+        """Slots t0 .. t0+n-1, joined (a round of an evaluation): with `chunk` as steps_fused's launch where the library has
+        one, else - and where it has none - step by step between fork() and join().  Bit-identical either way; neither resets
+        nor bumps the sampler's Philox base."""
+        if chunk and self.steps_fused(t0, n, greedy=greedy):
+            return
+        self.fork()
+        for t in range(t0, t0 + n):
+            self.step(t, greedy=greedy)
+        self.join()
 
     def _wrap_part(self, k, n):
         """Carry the last slot written by an n-step chunk into slot 0 for shard k (what `obses = next_obses` does)."""

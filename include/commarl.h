@@ -574,7 +574,8 @@ int cm_chunk_tail(uint32_t *policy_step_base, uint32_t n_steps, const void *src0
  * runners.  Layer l:  y = x . wt[l] + b[l]  (wt TRANSPOSED [in,out] as above), followed by tanh
  * when bit l of tanh_mask is set, by ReLU (torch.relu: y < 0 ? 0 : y, NaN passes) when bit l of relu_mask is set
  * (hidden_nonlinearity=F.relu); a layer with both bits set is refused (CM_ERR_ARG).  First layer at most 128 outputs;
- * any layer at most 1024. */
+ * any layer at most 624: the two 32-row LDS tiles of max(128, width padded to 16) + 4 words a row must fit a workgroup's
+ * 160 KB (2 * 32 * 628 * 4 = 160768 bytes; at 640 + 4 words they do not), and a wider layer is refused (CM_ERR_ARG). */
 #define CM_MLP_MAX_LAYERS 6
 typedef struct cm_mlp_weights {
     int32_t in_dim, n_layers;

@@ -344,17 +344,34 @@ TWINS = {
 }
 
 
-def launch(name, args, ws_args):
-    """Entry point `name` with `args` (all but the stream) on the current stream -> its return code.  In deterministic mode
-    its twin instead (TWINS), with a slab of twin_ws_bytes(*ws_args) bytes on the current device."""
+def run(name, *args, device=None, maybe=False):
+    """Entry point `name` with `args` on the current stream (of `device`, made current for the call, when given), its return
+    code checked -> True.  maybe: a return of 1 ("not for this shape, nothing done") -> False instead of raising."""
+    if device is None:
+        rc = getattr(lib(), name)(*args, current_stream())
+    else:
+        import torch
+        with torch.cuda.device(device):
+            rc = getattr(lib(), name)(*args, current_stream())
+    if rc == 0:
+        return True
+    if maybe and rc == 1:
+        return False
+    check(rc, name)
+
+
+def launch(name, args, ws_args, device=None, maybe=False):
+    """run(name, *args) - or, in deterministic mode, of its twin instead (TWINS), with a slab of twin_ws_bytes(*ws_args) bytes on
+    the current device."""
     from . import deterministic
-    L = lib()
     if not deterministic():
-        return getattr(L, name)(*args, current_stream())
+        return run(name, *args, device=device, maybe=maybe)
+    import torch
     twin, ws_bytes = TWINS[name]
-    nb = getattr(L, ws_bytes)(*ws_args)
-    n = len(_SIGNATURES[twin][1]) - 3
-    return getattr(L, twin)(*args[:n], ptr(slab(nb, "cuda")), nb, current_stream())
+    with torch.cuda.device(device):
+        nb = getattr(lib(), ws_bytes)(*ws_args)
+        n = len(_SIGNATURES[twin][1]) - 3
+        return run(twin, *args[:n], ptr(slab(nb, "cuda")), nb, maybe=maybe)
 
 
 def check(rc, what=""):
@@ -369,6 +386,11 @@ def ptr(t):
         return None
     assert t.is_contiguous(), "C ABI takes contiguous buffers"
     return t.data_ptr()
+
+
+def cptr(t):
+    """ptr() of `t` made contiguous (None for None)."""
+    return None if t is None else t.contiguous().data_ptr()
 
 
 def current_stream():

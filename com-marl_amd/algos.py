@@ -44,10 +44,9 @@ class _SurrogateFn(torch.autograd.Function):
         dl = torch.empty_like(lg) if need else None
         total = torch.empty((), dtype=torch.float64, device=dev)
         count = torch.empty((), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):                         # (deterministic mode: block sums summed in a fixed order, no f64 atomics)
-            L.check(L.launch("cm_ppo_surrogate", (P, T, N, A, L.ptr(lg), L.ptr(actions.contiguous()), L.ptr(old_ll.contiguous()),
-                                                  L.ptr(adv.contiguous()), L.ptr(valids), float(clip), float(ent_coeff), int(add_entropy),
-                                                  L.ptr(total), L.ptr(count), L.ptr(dl)), (P, T)), "cm_ppo_surrogate")
+        # (deterministic mode: block sums summed in a fixed order, no f64 atomics)
+        L.launch("cm_ppo_surrogate", (P, T, N, A, L.ptr(lg), L.cptr(actions), L.cptr(old_ll), L.cptr(adv), L.ptr(valids), float(clip),
+                                      float(ent_coeff), int(add_entropy), L.ptr(total), L.ptr(count), L.ptr(dl)), (P, T), device=dev)
         ctx.dl = dl
         ctx.mark_non_differentiable(count)
         return total.to(torch.float32), count
@@ -310,9 +309,7 @@ class CentralizedMAPPO:
         self.temp_max_path_length = T
         rewards = rew64.to(torch.float32).contiguous()                              # torch.Tensor(path['rewards']) (:645)
         returns = torch.empty(P, T, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_discount_returns(P, T, L.ptr(rew64.contiguous()), L.ptr(valids), float(self.discount),
-                                                L.ptr(returns), L.current_stream()), "cm_discount_returns")
+        L.run("cm_discount_returns", P, T, L.cptr(rew64), L.ptr(valids), float(self.discount), L.ptr(returns), device=dev)
         with torch.no_grad():                                                       # :653-657
             baselines = self._baseline_forward(obs, dist_adjs, channels)
         return obs, None, actions, rewards, valids, baselines, returns, dist_adjs, channels
@@ -335,10 +332,8 @@ class CentralizedMAPPO:
         """compute_advantages + per-path normalisation (:418-426) in one scan kernel."""
         P, T = rewards.shape
         adv = torch.empty_like(rewards)
-        with torch.cuda.device(rewards.device):
-            L.check(L.lib().cm_gae(P, T, L.ptr(rewards.contiguous()), L.ptr(baselines.contiguous()), L.ptr(valids),
-                                   float(self.discount), float(self._gae_lambda), int(self._center_adv), self._eps,
-                                   L.ptr(adv), L.current_stream()), "cm_gae")
+        L.run("cm_gae", P, T, L.cptr(rewards), L.cptr(baselines), L.ptr(valids), float(self.discount), float(self._gae_lambda),
+              int(self._center_adv), self._eps, L.ptr(adv), device=rewards.device)
         if self._positive_adv:
             adv = adv - adv.min()
         return adv
@@ -354,11 +349,9 @@ class CentralizedMAPPO:
         N, A = logits.shape[-2:]
         lg = logits.detach().contiguous()
         adv = torch.empty_like(rewards)
-        with torch.cuda.device(rewards.device):
-            L.check(L.lib().cm_entropy_gae(P, T, N, A, L.ptr(lg), L.ptr(rewards), L.ptr(baselines.contiguous()),
-                                           float(self.discount), float(self._gae_lambda), float(self._policy_ent_coeff),
-                                           int(self._use_softplus_entropy), L.ptr(rewards) if in_place else None, None,
-                                           L.ptr(adv), L.current_stream()), "cm_entropy_gae")
+        L.run("cm_entropy_gae", P, T, N, A, L.ptr(lg), L.ptr(rewards), L.cptr(baselines), float(self.discount),
+              float(self._gae_lambda), float(self._policy_ent_coeff), int(self._use_softplus_entropy),
+              L.ptr(rewards) if in_place else None, None, L.ptr(adv), device=rewards.device)
         if self._positive_adv:
             adv = adv - adv.min()
         return adv

@@ -160,8 +160,7 @@ def graph_diameter(dist_adj, out=None):
     if out is None:
         out = torch.empty(lead, dtype=torch.int32, device=dist_adj.device)
     assert out.dtype == torch.int32 and out.shape == lead and out.device == dist_adj.device and out.is_contiguous()
-    with torch.cuda.device(dist_adj.device):
-        L.check(L.lib().cm_graph_diameter(out.numel(), N, L.ptr(dist_adj), L.ptr(out), L.current_stream()), "cm_graph_diameter")
+    L.run("cm_graph_diameter", out.numel(), N, L.ptr(dist_adj), L.ptr(out), device=dist_adj.device)
     return out
 
 
@@ -185,9 +184,7 @@ def comm_stats(dist_adj, channels, n_hops, out=None):
         out = torch.empty(*lead, L.COMM_COLS, dtype=torch.int32, device=ref.device)
     assert out.dtype == torch.int32 and out.shape == (*lead, L.COMM_COLS) and out.device == ref.device and out.is_contiguous()
     S = out.numel() // L.COMM_COLS
-    with torch.cuda.device(ref.device):
-        L.check(L.lib().cm_comm_stats(S, N, n_hops, L.ptr(dist_adj), N * N, L.ptr(channels), n_hops * N * N, L.ptr(out),
-                                      L.current_stream()), "cm_comm_stats")
+    L.run("cm_comm_stats", S, N, n_hops, L.ptr(dist_adj), N * N, L.ptr(channels), n_hops * N * N, L.ptr(out), device=ref.device)
     return out
 
 
@@ -248,9 +245,7 @@ class GridEnvBatch:
         self.channels = torch.ones(B, self.Lh, N, N, dtype=f32, device=dev)
         self.prey_alive = torch.ones(B, M, dtype=u8, device=dev)
         self.success_t = torch.zeros(B, dtype=i32, device=dev)
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_env_fill_constants(self._h, L.ptr(self.dist_adj), L.ptr(self.channels),
-                                                  L.current_stream()), "cm_env_fill_constants")
+        L.run("cm_env_fill_constants", self._h, L.ptr(self.dist_adj), L.ptr(self.channels), device=dev)
         self._keep = None
 
     def __del__(self):
@@ -268,8 +263,7 @@ class GridEnvBatch:
                                 env_id_offset=self.cfg.env_id_offset)
         if table.shape[0] != self.B:
             raise ValueError(f"condition_of has {table.shape[0]} entries for {self.B} envs")
-        with torch.cuda.device(self.device):
-            L.check(L.lib().cm_env_set_conditions(self._h, table.ctypes.data, L.current_stream()), "cm_env_set_conditions")
+        L.run("cm_env_set_conditions", self._h, table.ctypes.data, device=self.device)
         self.conditions = [dict(c) for c in conditions]
         self.condition_of = np.asarray(condition_of).astype(np.int64)
         self.rng_ids = table["rng_id"].astype(np.int64)
@@ -321,22 +315,18 @@ class GridEnvBatch:
     def reset_all(self, tape=None, out=None):
         t = self._tape(tape)
         so = self._out(out)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().cm_env_reset(self._h, C.byref(t) if t else None, C.byref(so), L.current_stream()),
-                    "cm_env_reset")
+        L.run("cm_env_reset", self._h, C.byref(t) if t else None, C.byref(so), device=self.device)
 
     def step_device(self, actions, tape=None, out=None):
         """actions: int32 CUDA tensor [B,N].  Asynchronous; results land in self.* (or `out` overrides)."""
         assert actions.dtype == torch.int32 and actions.shape == (self.B, self.N) and actions.is_cuda
         t = self._tape(tape)
         so = self._out(out)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().cm_env_step(self._h, L.ptr(actions), C.byref(t) if t else None, C.byref(so),
-                                        L.current_stream()), "cm_env_step")
+        L.run("cm_env_step", self._h, L.ptr(actions), C.byref(t) if t else None, C.byref(so), device=self.device)
 
     def check_status(self):
         with torch.cuda.device(self.device):
-            L.check(L.lib().cm_env_status(self._h), "env kernel")
+            L.check(L.lib().cm_env_status(self._h), "cm_env_status")
 
     def get_state(self):
         B, N, M, S = self.B, self.N, max(self.M, 1), self.S
@@ -376,8 +366,7 @@ class GridEnvBatch:
         mode = {"iid": 1, "GE": 2}[kind]
         keep = None if tape_u is None else torch.as_tensor(np.ascontiguousarray(tape_u, np.float32)).to(self.device)
         with torch.cuda.device(self.device):
-            L.check(L.lib().cm_env_agent_fault(self._h, mode, float(p), float(r), L.ptr(keep), int(fault_step) & 0xFFFFFFFF,
-                                               L.current_stream()), "cm_env_agent_fault")
+            L.run("cm_env_agent_fault", self._h, mode, float(p), float(r), L.ptr(keep), int(fault_step) & 0xFFFFFFFF)
             torch.cuda.current_stream().synchronize()
 
     def comm_delays(self, dist_adj, link_loss, delay_th=None, old_delays=None):
@@ -385,12 +374,8 @@ class GridEnvBatch:
         old_delays) (:271-286).  CUDA tensors [B,N,N] / [B,L,N,N] / [B,N,N] int32 -> delays [B,L,N,N] int32."""
         Lh = link_loss.shape[1]
         out = torch.empty(self.B, Lh, self.N, self.N, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().cm_comm_delays(self.B, Lh, self.N, L.ptr(None if dist_adj is None else dist_adj.contiguous()),
-                                           L.ptr(link_loss.contiguous()),
-                                           L.ptr(None if old_delays is None else old_delays.contiguous()),
-                                           int(delay_th or 0), int(old_delays is None), L.ptr(out), L.current_stream()),
-                    "cm_comm_delays")
+        L.run("cm_comm_delays", self.B, Lh, self.N, L.cptr(dist_adj), L.cptr(link_loss), L.cptr(old_delays), int(delay_th or 0),
+              int(old_delays is None), L.ptr(out), device=self.device)
         return out
 
     def set_state(self, **arrays):

@@ -174,7 +174,7 @@ class _CommStats:
         self.table = torch.zeros(cells, n_epi, L.EPC_COLS, dtype=torch.float64, device=batch.device)
 
     def round(self, group_size, take, row0):
-        eng, batch, lib = self.eng, self.batch, L.lib()
+        eng, batch = self.eng, self.batch
         B, N, Lh = batch.B, batch.N, batch.Lh
         if eng.channels is not None:
             chan, chan_stride = eng.channels, Lh * N * N
@@ -182,14 +182,12 @@ class _CommStats:
             chan, chan_stride = None, 0
         else:
             chan, chan_stride = batch.channels, 0                      # FL: one constant block (the identity) for every graph
-        L.check(lib.cm_comm_stats((self.T + 1) * B, N, Lh, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride,
-                                  L.ptr(self.stats), L.current_stream()), "cm_comm_stats")
-        L.check(lib.cm_episode_comm(self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
-                                    L.ptr(self.table), L.current_stream()), "cm_episode_comm")
+        L.run("cm_comm_stats", (self.T + 1) * B, N, Lh, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride, L.ptr(self.stats))
+        L.run("cm_episode_comm", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
+              L.ptr(self.table))
 
     def means(self):
-        L.check(L.lib().cm_comm_means(self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out), L.current_stream()),
-                "cm_comm_means")
+        L.run("cm_comm_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
 
     @staticmethod
     def keys(row):
@@ -251,7 +249,6 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     # built with fused_conditions=True (GridEnvBatch.fuse_conditions): then teams of 4 play the round as one launch, a single
     # policy included
     chunk = conds is not None or not single
-    lib = L.lib()
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
     flat, out, comm_out = _summary_buffers(cells, comm_stats, batch.device)
@@ -263,13 +260,12 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
         eng.bump(T)
         batch.check_status()
         take = min(E, n_epi - done)
-        L.check(lib.cm_episode_stats(T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
-                                     L.ptr(eng.path_len), L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table),
-                                     L.current_stream()), "cm_episode_stats")
+        L.run("cm_episode_stats", T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success), L.ptr(eng.path_len),
+              L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table))
         if comm:
             comm.round(E, take, done)
         done += take
-    L.check(lib.cm_episode_means(cells, n_epi, L.ptr(table), L.ptr(out), L.current_stream()), "cm_episode_means")
+    L.run("cm_episode_means", cells, n_epi, L.ptr(table), L.ptr(out))
     if comm:
         comm.means()
     host_all = flat.cpu().numpy()

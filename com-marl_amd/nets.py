@@ -92,32 +92,6 @@ class MLPModule(nn.Module):
         return hip_linear(x, out.linear, act=1 if len(out) > 1 else 0)
 
 
-class _AttentionSoftmax(torch.autograd.Function):
-    """M = softmax_j(q_i . e_j) per sample, one HIP kernel each way instead of three batched N x N GEMMs."""
-
-    @staticmethod
-    def forward(ctx, q, e):
-        S, N, E = e.shape
-        q, e = q.contiguous(), e.contiguous()
-        m = torch.empty(S, N, N, dtype=e.dtype, device=e.device)
-        with torch.cuda.device(e.device):
-            L.check(L.lib().cm_attention_forward(S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), L.current_stream()),
-                    "cm_attention_forward")
-        ctx.save_for_backward(q, e, m)
-        return m
-
-    @staticmethod
-    def backward(ctx, d_m):
-        q, e, m = ctx.saved_tensors
-        S, N, E = e.shape
-        d_m = d_m.contiguous()
-        d_q, d_e = torch.empty_like(q), torch.empty_like(e)
-        with torch.cuda.device(e.device):
-            L.check(L.lib().cm_attention_backward(S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), L.ptr(d_m), None, None, L.ptr(d_q),
-                                                  L.ptr(d_e), L.current_stream()), "cm_attention_backward")
-        return d_q, d_e
-
-
 class _NotCovered(Exception):
     """A *_any graph op answered 1: the planes of this (N, E) do not fit a workgroup's LDS - the framework path runs instead."""
 
@@ -147,25 +121,34 @@ def set_graph_op_route(N, E, route):
     _GRAPH_ROUTE[(N, E)] = route
 
 
-def _any_rc(rc, N, E, what):
-    if rc == 1:
+def _graph_forward(name, any_width, N, E, *args, device):
+    """The forward of a graph op: `name` (E = 64), or `name`_any, whose answer 1 sends the shape to the framework path."""
+    if not any_width:
+        L.run(name, *args, device=device)
+    elif not L.run(name + "_any", *args, device=device, maybe=True):
         _GRAPH_ROUTE[(N, E)] = "framework"
-        raise _NotCovered(what)
-    L.check(rc, what)
+        raise _NotCovered(name + "_any")
 
 
-class _AttentionSoftmaxAny(torch.autograd.Function):
-    """_AttentionSoftmax for any embedding width 1..128 (cm_attention_forward_any / _backward_any)."""
+def _hop_channels(chan_all, hop, N):
+    """(pointer | None, per-sample stride in floats) of hop `hop`'s N x N planes in channels [S,L,N,N] (contiguous f32)."""
+    if chan_all is None:
+        return None, 0
+    return chan_all.data_ptr() + 4 * hop * N * N, chan_all.shape[1] * N * N
+
+
+class _AttentionSoftmax(torch.autograd.Function):
+    """M = softmax_j(q_i . e_j) per sample, one HIP kernel each way instead of three batched N x N GEMMs: cm_attention_forward /
+    _backward for E = 64, with `any_width` their _any forms (widths 1..128; _NotCovered where the forward answers 1)."""
 
     @staticmethod
-    def forward(ctx, q, e):
+    def forward(ctx, q, e, any_width=False):
         S, N, E = e.shape
         q, e = q.contiguous(), e.contiguous()
         m = torch.empty(S, N, N, dtype=e.dtype, device=e.device)
-        with torch.cuda.device(e.device):
-            _any_rc(L.lib().cm_attention_forward_any(S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), L.current_stream()), N, E,
-                    "cm_attention_forward_any")
+        _graph_forward("cm_attention_forward", any_width, N, E, S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), device=e.device)
         ctx.save_for_backward(q, e, m)
+        ctx.any_width = any_width
         return m
 
     @staticmethod
@@ -174,10 +157,9 @@ class _AttentionSoftmaxAny(torch.autograd.Function):
         S, N, E = e.shape
         d_m = d_m.contiguous()
         d_q, d_e = torch.empty_like(q), torch.empty_like(e)
-        with torch.cuda.device(e.device):
-            L.check(L.lib().cm_attention_backward_any(S, N, E, L.ptr(q), L.ptr(e), L.ptr(m), L.ptr(d_m), None, None, L.ptr(d_q),
-                                                      L.ptr(d_e), L.current_stream()), "cm_attention_backward_any")
-        return d_q, d_e
+        L.run("cm_attention_backward_any" if ctx.any_width else "cm_attention_backward", S, N, E, L.ptr(q), L.ptr(e), L.ptr(m),
+              L.ptr(d_m), None, None, L.ptr(d_q), L.ptr(d_e), device=e.device)
+        return d_q, d_e, None
 
 
 class AttentionModule(nn.Module):
@@ -202,7 +184,7 @@ class AttentionModule(nn.Module):
         if (query.is_cuda and query.dim() == 3 and query.dtype == torch.float32
                 and graph_op_route(query.shape[-2], query.shape[-1]) == "hip"):
             try:
-                return _AttentionSoftmaxAny.apply(q, query)      # embeddings other than 64 (--embedding_dim): cm_attention_*_any
+                return _AttentionSoftmax.apply(q, query, True)   # embeddings other than 64 (--embedding_dim): cm_attention_*_any
             except _NotCovered:
                 pass
         # teams above 128 agents (maps >= 50), and widths whose planes do not fit the LDS: library GEMMs, autograd backward
@@ -230,17 +212,16 @@ def _wgrad(a2d, b2d, want_colsum):
     Q = b2d.shape[1]
     c = torch.zeros(P, Q, dtype=torch.float32, device=a2d.device)
     cs = torch.zeros(P, dtype=torch.float32, device=a2d.device) if want_colsum else None
-    with torch.cuda.device(a2d.device):
-        L.check(L.launch("cm_linear_wgrad", (R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs)), (R, P, Q)), "cm_linear_wgrad")
+    L.launch("cm_linear_wgrad", (R, P, Q, L.ptr(a2d), L.ptr(b2d), L.ptr(c), L.ptr(cs)), (R, P, Q), device=a2d.device)
     return c, cs
 
 
 def _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y, dx, dw, db, act=None):
     """cm_linear_act_backward (y given = tanh layer), or with ``act`` (0 / 1 / 2) cm_linear_act_backward_ex (their slab twins
-    in deterministic mode)."""
+    in deterministic mode), on w's device."""
     name = "cm_linear_act_backward" if act is None else "cm_linear_act_backward_ex"
     args = (R, K, O, L.ptr(x2), L.ptr(w), layout, L.ptr(dy2), L.ptr(dy_add), L.ptr(y)) + (() if act is None else (int(act),))
-    L.check(L.launch(name, args + (L.ptr(dx), L.ptr(dw), L.ptr(db)), (R, K, O)), name)
+    L.launch(name, args + (L.ptr(dx), L.ptr(dw), L.ptr(db)), (R, K, O), device=w.device)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -292,10 +273,8 @@ class _LinearActFn(torch.autograd.Function):
         x2 = x.reshape(-1, K).contiguous()
         w = weight.contiguous()
         y = torch.empty(x2.shape[0], O, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            L.check(L.lib().cm_linear_act_forward(x2.shape[0], K, O, L.ptr(x2), L.ptr(w), layout,
-                                                  L.ptr(None if bias is None else bias.contiguous()), int(act), L.ptr(y),
-                                                  L.current_stream()), "cm_linear_act_forward")
+        L.run("cm_linear_act_forward", x2.shape[0], K, O, L.ptr(x2), L.ptr(w), layout, L.cptr(bias), int(act), L.ptr(y),
+              device=x.device)
         ctx.save_for_backward(x2, w, y if act else None)
         ctx.meta = (tuple(x.shape), K, O, int(act), layout, bias is not None)
         return y.reshape(*x.shape[:-1], O)
@@ -308,10 +287,8 @@ class _LinearActFn(torch.autograd.Function):
         dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         dw = torch.zeros_like(w)
         db = torch.zeros(O, dtype=torch.float32, device=w.device) if has_bias else None
-        with torch.cuda.device(w.device):
-            # ReLU names its activation (cm_linear_act_backward_ex); tanh / identity keep the entry points they always used
-            _linear_act_backward(x2.shape[0], K, O, x2, w, layout, dy2, None, y, dx, dw, db,
-                                 act=act if act == ACT_RELU else None)
+        # ReLU names its activation (cm_linear_act_backward_ex); tanh / identity keep the entry points they always used
+        _linear_act_backward(x2.shape[0], K, O, x2, w, layout, dy2, None, y, dx, dw, db, act=act if act == ACT_RELU else None)
         return (None if dx is None else dx.reshape(shape)), dw, db, None, None
 
 
@@ -341,23 +318,19 @@ class HipLinear(nn.Linear):
 
 
 class _MaskedAggregate(torch.autograd.Function):
-    """out = tanh(A.(HW) + b), A = M*R*C row-renormalised (comm_base_net.py:101-103,
-    graph_conv_module.py:63-70) as one HIP kernel each way."""
+    """out = tanh(A.(HW) + b), A = M*R*C row-renormalised (comm_base_net.py:101-103, graph_conv_module.py:63-70) as one HIP
+    kernel each way: cm_masked_agg_forward / _backward for E = 64, with `any_width` their _any forms (widths 1..128;
+    _NotCovered where the forward answers 1).  Either backward has its _det twin."""
 
     @staticmethod
-    def forward(ctx, attn, dist_adj, chan_all, hop, hw, bias):
+    def forward(ctx, attn, dist_adj, chan_all, hop, hw, bias, any_width=False):
         S, N, E = hw.shape
         attn, hw = attn.contiguous(), hw.contiguous()
         out = torch.empty_like(hw)
-        chan_ptr, stride = None, 0
-        if chan_all is not None:
-            Lh = chan_all.shape[1]
-            chan_ptr, stride = chan_all.data_ptr() + 4 * hop * N * N, Lh * N * N
-        with torch.cuda.device(hw.device):
-            L.check(L.lib().cm_masked_agg_forward(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
-                                                  L.ptr(bias), L.ptr(out), L.current_stream()), "cm_masked_agg_forward")
+        _graph_forward("cm_masked_agg_forward", any_width, N, E, S, N, E, L.ptr(attn), L.ptr(dist_adj),
+                       *_hop_channels(chan_all, hop, N), L.ptr(hw), L.ptr(bias), L.ptr(out), device=hw.device)
         ctx.save_for_backward(attn, dist_adj, chan_all, hw, out)
-        ctx.hop, ctx.has_bias = hop, bias is not None
+        ctx.hop, ctx.has_bias, ctx.any_width = hop, bias is not None, any_width
         return out
 
     @staticmethod
@@ -367,49 +340,10 @@ class _MaskedAggregate(torch.autograd.Function):
         d_out = d_out.contiguous()
         d_attn, d_hw = torch.empty_like(attn), torch.empty_like(hw)
         d_bias = torch.zeros(E, dtype=hw.dtype, device=hw.device) if ctx.has_bias else None
-        chan_ptr, stride = None, 0
-        if chan_all is not None:
-            chan_ptr, stride = chan_all.data_ptr() + 4 * ctx.hop * N * N, chan_all.shape[1] * N * N
-        with torch.cuda.device(hw.device):
-            L.check(L.launch("cm_masked_agg_backward", (S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw), L.ptr(out), None,
-                                                        L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias)), (S, N, E)),
-                    "cm_masked_agg_backward")
-        return d_attn, None, None, None, d_hw, d_bias
-
-
-class _MaskedAggregateAny(torch.autograd.Function):
-    """_MaskedAggregate for any embedding width 1..128 (cm_masked_agg_forward_any / _backward_any and its _det twin)."""
-
-    @staticmethod
-    def forward(ctx, attn, dist_adj, chan_all, hop, hw, bias):
-        S, N, E = hw.shape
-        attn, hw = attn.contiguous(), hw.contiguous()
-        out = torch.empty_like(hw)
-        chan_ptr, stride = None, 0
-        if chan_all is not None:
-            chan_ptr, stride = chan_all.data_ptr() + 4 * hop * N * N, chan_all.shape[1] * N * N
-        with torch.cuda.device(hw.device):
-            _any_rc(L.lib().cm_masked_agg_forward_any(S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw),
-                                                      L.ptr(bias), L.ptr(out), L.current_stream()), N, E, "cm_masked_agg_forward_any")
-        ctx.save_for_backward(attn, dist_adj, chan_all, hw, out)
-        ctx.hop, ctx.has_bias = hop, bias is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        attn, dist_adj, chan_all, hw, out = ctx.saved_tensors
-        S, N, E = hw.shape
-        d_out = d_out.contiguous()
-        d_attn, d_hw = torch.empty_like(attn), torch.empty_like(hw)
-        d_bias = torch.zeros(E, dtype=hw.dtype, device=hw.device) if ctx.has_bias else None
-        chan_ptr, stride = None, 0
-        if chan_all is not None:
-            chan_ptr, stride = chan_all.data_ptr() + 4 * ctx.hop * N * N, chan_all.shape[1] * N * N
-        with torch.cuda.device(hw.device):
-            L.check(L.launch("cm_masked_agg_backward_any", (S, N, E, L.ptr(attn), L.ptr(dist_adj), chan_ptr, stride, L.ptr(hw), L.ptr(out),
-                                                            None, L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias)), (S, N, E)),
-                    "cm_masked_agg_backward_any")
-        return d_attn, None, None, None, d_hw, d_bias
+        L.launch("cm_masked_agg_backward_any" if ctx.any_width else "cm_masked_agg_backward",
+                 (S, N, E, L.ptr(attn), L.ptr(dist_adj), *_hop_channels(chan_all, ctx.hop, N), L.ptr(hw), L.ptr(out), None,
+                  L.ptr(d_out), L.ptr(d_attn), L.ptr(d_hw), L.ptr(d_bias)), (S, N, E), device=hw.device)
+        return d_attn, None, None, None, d_hw, d_bias, None
 
 
 def masked_aggregate(attn, dist_adj, channels, hop, hw, bias):
@@ -419,8 +353,8 @@ def masked_aggregate(attn, dist_adj, channels, hop, hw, bias):
     if (hw.shape[2] != 64 and hw.dim() == 3 and hw.dtype == torch.float32 and attn.dtype == torch.float32
             and graph_op_route(hw.shape[1], hw.shape[2]) == "hip"):
         try:                                     # embeddings other than 64 (--embedding_dim): cm_masked_agg_*_any
-            return _MaskedAggregateAny.apply(attn, dist_adj if dist_adj is None else dist_adj.contiguous(),
-                                             channels if channels is None else channels.contiguous(), hop, hw, bias)
+            return _MaskedAggregate.apply(attn, dist_adj if dist_adj is None else dist_adj.contiguous(),
+                                          channels if channels is None else channels.contiguous(), hop, hw, bias, True)
         except _NotCovered:
             pass
     if hw.shape[1] > MAX_KERNEL_AGENTS or hw.shape[2] != 64:
@@ -470,8 +404,7 @@ def _lin_bwd(x2, w, layout, dy2, y2, want_dx, has_bias, dy_add=None, pool=None):
     dx = torch.empty_like(x2) if want_dx else None
     dw = pool.take(w.shape) if pool is not None else torch.zeros_like(w)
     db = (pool.take((O,)) if pool is not None else torch.zeros(O, dtype=torch.float32, device=w.device)) if has_bias else None
-    with torch.cuda.device(w.device):
-        _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y2, dx, dw, db)
+    _linear_act_backward(R, K, O, x2, w, layout, dy2, dy_add, y2, dx, dw, db)
     return dx, dw, db
 
 
@@ -497,13 +430,13 @@ def _fwd_wave_ok(N, S):
             and (os.environ.get("COMMARL_POLICY_KERNEL") or "w")[0] not in "hfv")
 
 
-def _forward_saved(name, wave, *args):
+def _forward_saved(name, wave, *args, device):
     """`name` (cm_policy_forward_saved / cm_critic_forward_saved) on the current stream, preceded by its _wave form when
-    `wave`: the wave kernel's return of 1 (shape not covered) falls back to `name` -> the return code."""
-    rc = getattr(L.lib(), name + "_wave")(*args, L.current_stream()) if wave else 1
-    if rc == 1:
-        rc = getattr(L.lib(), name)(*args, L.current_stream())
-    return rc
+    `wave`: the wave kernel's return of 1 (shape not covered) falls back to `name`, whose return of 1 raises."""
+    if wave and L.run(name + "_wave", *args, device=device, maybe=True):
+        return
+    if not L.run(name, *args, device=device, maybe=True):
+        raise L.CommarlError(f"{name}: no saved-forward instantiation for this shape (callers check _fused_shape_ok)")
 
 
 class _FusedNetFn(torch.autograd.Function):
@@ -520,7 +453,7 @@ class _FusedNetFn(torch.autograd.Function):
         S = obs.shape[0]
         R = S * N
         dev = obs.device
-        policy = hasattr(net, "categorical_output_layer")
+        policy = net._is_policy
         z = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)   # noqa: E731
         obs2 = obs.reshape(R, d).contiguous()
         t = dict(a1=z(R, 128), e=z(R, 64), q=z(R, 64), hw=[z(R, 64) for _ in range(Lh)], h=[z(R, 64) for _ in range(Lh)])
@@ -541,23 +474,13 @@ class _FusedNetFn(torch.autograd.Function):
         net._train_fwd = True                          # the weight pack refreshes the f16-split section only (_WeightPack._packed)
         # ... and the CM_PACK_WAVE section with it when the wave-owned kernel runs (its fragments)
         wave = net._train_fwd_wave = _fwd_wave_ok(N, S)
+        vals = () if policy else (z(S),)               # the critic's entry point also writes the summed values
         try:
-            with torch.cuda.device(dev):
-                if policy:
-                    w = net._weights_struct()
-                    rc = _forward_saved("cm_policy_forward_saved", wave, C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
-                                        C.byref(sv))
-                else:
-                    w = net._struct_from(net._packed())
-                    w.mfma_pack = None if net._mfma is None else net._mfma.data_ptr()
-                    vals = z(S)
-                    rc = _forward_saved("cm_critic_forward_saved", wave, C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn),
-                                        L.ptr(vals), C.byref(sv))
+            w = net._weights_struct()
+            _forward_saved("cm_policy_forward_saved" if policy else "cm_critic_forward_saved", wave, C.byref(w), S, L.ptr(obs2),
+                           L.ptr(adj_c), L.ptr(ch_c), L.ptr(attn), *map(L.ptr, vals), C.byref(sv), device=dev)
         finally:
             net._train_fwd = net._train_fwd_wave = False
-        if rc == 1:
-            raise L.CommarlError("no saved-forward instantiation for this shape (caller should have checked _fused_train_ok)")
-        L.check(rc, "cm_*_forward_saved")
         ctx.net, ctx.t, ctx.obs2, ctx.adj, ctx.ch, ctx.attn, ctx.policy = net, t, obs2, adj_c, ch_c, attn, policy
         ctx.names = [n for n, _ in net.named_parameters()]
         ctx.mark_non_differentiable(attn)
@@ -594,39 +517,35 @@ class _FusedNetFn(torch.autograd.Function):
         e, q = t["e"], t["q"]
         d_res = d if net.residual else None                              # residual: the same gradient flows into E
         dH, d_attn, dhin0 = d, None, None
-        with torch.cuda.device(obs2.device):
-            for l in reversed(range(Lh)):
-                gl = net.gcn_layers[l]
-                minus = e if (l == Lh - 1 and net.residual) else None       # saved x = E + H_L: the hop's tanh output is x - E
-                da, dhw = torch.empty_like(attn), torch.empty_like(e)
-                # large batches of teams of 4: the bias gradient over 32 rows summed afterwards (cm_masked_agg_backward_r)
-                reps = 32 if (N == 4 and S > 16 * 512 and not det) else 1
-                dgb = pool.take((reps, 64)) if gl.bias is not None else None
-                chan_ptr, stride = None, 0
-                if ch is not None:
-                    chan_ptr, stride = ch.data_ptr() + 4 * l * N * N, ch.shape[1] * N * N
-                # (deterministic mode: one bias row, merged in a fixed order)
-                L.check(L.launch("cm_masked_agg_backward_r", (S, N, 64, L.ptr(attn), L.ptr(adj), chan_ptr, stride, L.ptr(t["hw"][l]),
-                                                              L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb), reps),
-                                 (S, N, 64)), "cm_masked_agg_backward_r")
-                if dgb is not None:
-                    dgb = dgb.sum(0) if reps > 1 else dgb[0]
-                d_attn = da if d_attn is None else d_attn.add_(da)
-                hin = t["h"][l - 1] if l > 0 else e
-                dhin, g["gcn_layers.%d.weight" % l], _ = _lin_bwd(hin, gl.weight, 1, dhw, None, True, False, pool=pool)
-                if gl.bias is not None:
-                    g["gcn_layers.%d.bias" % l] = dgb
-                if l > 0:
-                    dH = dhin
-                else:
-                    dhin0 = dhin
-            # gradient wrt E = residual term + hop 0's input gradient + attention key side (summed by the attention kernel)
-            # + linear_in's input gradient (summed by the encoder layer's backward): no accumulation passes
-            if Lh == 0:
-                raise L.CommarlError("fused training path needs at least one hop")
-            dq, dE = torch.empty_like(q), torch.empty_like(e)
-            L.check(L.lib().cm_attention_backward(S, N, 64, L.ptr(q), L.ptr(e), L.ptr(attn), L.ptr(d_attn), L.ptr(d_res), L.ptr(dhin0),
-                                                  L.ptr(dq), L.ptr(dE), L.current_stream()), "cm_attention_backward")
+        for l in reversed(range(Lh)):
+            gl = net.gcn_layers[l]
+            minus = e if (l == Lh - 1 and net.residual) else None       # saved x = E + H_L: the hop's tanh output is x - E
+            da, dhw = torch.empty_like(attn), torch.empty_like(e)
+            # large batches of teams of 4: the bias gradient over 32 rows summed afterwards (cm_masked_agg_backward_r)
+            reps = 32 if (N == 4 and S > 16 * 512 and not det) else 1
+            dgb = pool.take((reps, 64)) if gl.bias is not None else None
+            # (deterministic mode: one bias row, merged in a fixed order)
+            L.launch("cm_masked_agg_backward_r", (S, N, 64, L.ptr(attn), L.ptr(adj), *_hop_channels(ch, l, N), L.ptr(t["hw"][l]),
+                                                  L.ptr(t["h"][l]), L.ptr(minus), L.ptr(dH), L.ptr(da), L.ptr(dhw), L.ptr(dgb), reps),
+                     (S, N, 64), device=obs2.device)
+            if dgb is not None:
+                dgb = dgb.sum(0) if reps > 1 else dgb[0]
+            d_attn = da if d_attn is None else d_attn.add_(da)
+            hin = t["h"][l - 1] if l > 0 else e
+            dhin, g["gcn_layers.%d.weight" % l], _ = _lin_bwd(hin, gl.weight, 1, dhw, None, True, False, pool=pool)
+            if gl.bias is not None:
+                g["gcn_layers.%d.bias" % l] = dgb
+            if l > 0:
+                dH = dhin
+            else:
+                dhin0 = dhin
+        # gradient wrt E = residual term + hop 0's input gradient + attention key side (summed by the attention kernel)
+        # + linear_in's input gradient (summed by the encoder layer's backward): no accumulation passes
+        if Lh == 0:
+            raise L.CommarlError("fused training path needs at least one hop")
+        dq, dE = torch.empty_like(q), torch.empty_like(e)
+        L.run("cm_attention_backward", S, N, 64, L.ptr(q), L.ptr(e), L.ptr(attn), L.ptr(d_attn), L.ptr(d_res), L.ptr(dhin0),
+              L.ptr(dq), L.ptr(dE), device=obs2.device)
         if net.attention_layer.attention_type == "general":
             deq, g["attention_layer.linear_in.weight"], _ = _lin_bwd(e, net.attention_layer.linear_in.weight, 0, dq, None, True, False, pool=pool)
         else:
@@ -636,14 +555,11 @@ class _FusedNetFn(torch.autograd.Function):
         # (d > 64) take the two layers one by one
         dw2, db2 = pool.take(enc2.weight.shape), pool.take(enc2.bias.shape)
         dw1, db1 = pool.take(enc1.weight.shape), pool.take(enc1.bias.shape)
-        with torch.cuda.device(obs2.device):
-            rc = L.launch("cm_encoder_backward", (R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE),
-                                                  L.ptr(deq), L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1)), (R, obs2.shape[1]))
-        if rc == 1:
+        if not L.launch("cm_encoder_backward", (R, obs2.shape[1], L.ptr(obs2), L.ptr(t["a1"]), L.ptr(e), L.ptr(enc2.weight), L.ptr(dE),
+                                                L.ptr(deq), L.ptr(dw2), L.ptr(db2), L.ptr(dw1), L.ptr(db1)), (R, obs2.shape[1]),
+                        device=obs2.device, maybe=True):
             da1, dw2, db2 = _lin_bwd(t["a1"], enc2.weight, 0, dE, e, True, True, dy_add=deq)     # (dw2 .. db1 taken above stay zero, unused)
             _, dw1, db1 = _lin_bwd(obs2, enc1.weight, 0, da1, t["a1"], False, True)
-        else:
-            L.check(rc, "cm_encoder_backward")
         g["encoder._output_layers.0.linear.weight"], g["encoder._output_layers.0.linear.bias"] = dw2, db2
         g["encoder._layers.0.linear.weight"], g["encoder._layers.0.linear.bias"] = dw1, db1
         ctx.t = None                                                     # free the saved activations
@@ -667,14 +583,10 @@ def _fused_logits_nograd(net, obs, adj, ch, want_probs=False):
         sv.probs = probs.data_ptr()
     adj_c = None if adj is None else adj.contiguous()
     ch_c = None if ch is None else ch.contiguous()
-    with torch.cuda.device(obs.device):
-        w = net._weights_struct()                            # (no-grad user: every section of the pack is current)
-        # large batches of teams of 4: the same kernel the training forward takes (both sides of the PPO ratio from one arithmetic)
-        rc = _forward_saved("cm_policy_forward_saved", _fwd_wave_ok(N, S), C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c),
-                            L.ptr(attn), C.byref(sv))
-    if rc == 1:
-        raise L.CommarlError("no saved-forward instantiation for this shape")
-    L.check(rc, "cm_policy_forward_saved")
+    w = net._weights_struct()                                # (no-grad user: every section of the pack is current)
+    # large batches of teams of 4: the same kernel the training forward takes (both sides of the PPO ratio from one arithmetic)
+    _forward_saved("cm_policy_forward_saved", _fwd_wave_ok(N, S), C.byref(w), S, L.ptr(obs2), L.ptr(adj_c), L.ptr(ch_c),
+                   L.ptr(attn), C.byref(sv), device=obs.device)
     return (out.view(S, N, A), probs) if want_probs else (out.view(S, N, A), attn)
 
 
@@ -763,8 +675,7 @@ class _WeightPack:
             rows = (C.c_int32 * m)(*[t[2] for t in plain])
             cols = (C.c_int32 * m)(*[t[3] for t in plain])
             tr = (C.c_int32 * m)(*[t[4] for t in plain])
-            with torch.cuda.device(buf.device):
-                L.check(L.lib().cm_multi_copy_t(m, src, dstp, rows, cols, tr, L.current_stream()), "cm_multi_copy_t")
+            L.run("cm_multi_copy_t", m, src, dstp, rows, cols, tr, device=buf.device)
 
     @staticmethod
     def _flat_copy_one(v, dst, n, plain, buf):
@@ -858,6 +769,14 @@ class CommBaseNet(_WeightPack, nn.Module):
         (--encoder_hidden_sizes, --embedding_dim, --categorical_mlp_hidden_sizes) runs on cm_policy_forward_any or layer by layer."""
         return self._enc_hidden == (128,) and self._embedding_dim == 64 and self._head_hidden() == self._HEAD_DEFAULT
 
+    _is_policy = False                   # which saved forward and head _FusedNetFn runs (the policy class says True)
+
+    def _gcn_tensors(self):
+        """The hops' weights [in,out] and biases, each stacked hop by hop (None: no hop / no bias)."""
+        gs = self.gcn_layers
+        return OrderedDict(gcn_w=_Stacked(g.weight for g in gs) if len(gs) else None,
+                           gcn_b=_Stacked(g.bias for g in gs) if len(gs) and gs[0].bias is not None else None)
+
     def _any_tensors(self):
         """The flat weight copy of a net of any layer sizes (cm_net_weights): every linear weight transposed [in,out], layer by layer."""
         t = OrderedDict()
@@ -867,9 +786,7 @@ class CommBaseNet(_WeightPack, nn.Module):
                 t[f"{pre}_b{i}"] = lin.bias
         # 'dot': Q = E, no weight at all (NULL)
         t["attn_wt"] = self.attention_layer.linear_in.weight.t() if self.attention_layer.attention_type == "general" else None
-        t["gcn_w"] = _Stacked(g.weight for g in self.gcn_layers) if len(self.gcn_layers) else None
-        t["gcn_b"] = (_Stacked(g.bias for g in self.gcn_layers)
-                      if len(self.gcn_layers) and self.gcn_layers[0].bias is not None else None)
+        t.update(self._gcn_tensors())
         return t
 
     def _net_struct(self):
@@ -908,9 +825,7 @@ class CommBaseNet(_WeightPack, nn.Module):
             t["attn_wt"] = self.attention_layer.linear_in.weight.t()
         else:                                   # 'dot': Q = E, i.e. the fused kernels' linear_in is the identity (a constant)
             t["attn_wt"] = torch.eye(self._embedding_dim, dtype=torch.float32, device=next(self.parameters()).device)
-        t["gcn_w"] = _Stacked(g.weight for g in self.gcn_layers) if len(self.gcn_layers) else None
-        t["gcn_b"] = (_Stacked(g.bias for g in self.gcn_layers)
-                      if len(self.gcn_layers) and self.gcn_layers[0].bias is not None else None)
+        t.update(self._gcn_tensors())
         return t
 
     def _head_tensors(self):
@@ -930,19 +845,64 @@ class CommBaseNet(_WeightPack, nn.Module):
         if dev.type != "cuda" or not self._default_shape:    # (cm_policy_forward_any reads the plain [in,out] weights)
             return
         w = self._struct_from(ptrs)
-        size_fn, pack_fn = (getattr(L.lib(), n) for n in self._mfma_fns)
+        size_fn, pack_fn = self._mfma_fns
         if self._mfma is None or self._mfma.device != dev:
-            nbytes = size_fn(C.byref(w))
+            nbytes = getattr(L.lib(), size_fn)(C.byref(w))
             self._mfma = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
         if self._mfma is not None:
-            with torch.cuda.device(dev):
-                L.check(pack_fn(C.byref(w), L.ptr(self._mfma), int(sections), L.current_stream()), self._mfma_fns[1])
+            L.run(pack_fn, C.byref(w), L.ptr(self._mfma), int(sections), device=dev)
+
+    def _weights_struct(self):
+        """The net's cm_policy_weights / cm_critic_weights over its current flat weight copy and operand pack."""
+        w = self._struct_from(self._packed())
+        w.mfma_pack = None if self._mfma is None else self._mfma.data_ptr()
+        return w
+
+    def _general_route(self, launch):
+        """Which no-grad forward a net of non-default layer sizes takes, recorded in _last_forward.  launch(w) starts the
+        one-launch kernel (cm_policy_forward_any / cm_critic_forward_any) over w = _net_struct() and says whether it ran.
+        -> True ("one_launch"), or False ("layers": the caller runs layer by layer) where the route is pinned (_general_forward =
+        "layers"), the net has more layers than the kernel is written for (no struct) or the kernel answered "not for this
+        shape" (1: a workgroup's LDS need above 160 KB)."""
+        if self._general_forward not in ("auto", "layers"):
+            raise ValueError(f"_general_forward must be 'auto' or 'layers', not {self._general_forward!r}")
+        w = self._net_struct() if self._general_forward == "auto" else None
+        done = w is not None and launch(w)
+        self._last_forward = "one_launch" if done else "layers"
+        return done
+
+
+class _Acting:
+    """What the acting forwards (act_device) of the Comm-DP policy and the row-MLP policies share: the sampler's Philox stream,
+    the policy-step counter and the output buffers."""
+
+    def set_rng(self, seed, env_id_offset=0):
+        """Philox stream of the action sampler: counter (env id, policy step, site 7, agent)."""
+        self.seed, self.env_id_offset = int(seed), int(env_id_offset)
+
+    def _next_step(self):
+        """This policy's own step counter (what act_device uses when it is given no policy_step), which then advances."""
+        self._policy_step += 1
+        return self._policy_step - 1
+
+    def _act_outputs(self, S, dev, want_actions, want_probs, want_attn, out_actions, out_probs, out_attn):
+        """(actions int32 [S,N], probs [S,N,A], attn [S,N,N]) on `dev`: the caller's buffer, else a new one where wanted, else None."""
+        if dev.type != "cuda":
+            raise L.CommarlError("the rollout forward is a HIP kernel: inputs must be CUDA tensors (no CPU fallback)")
+        N = self._n_agents
+        if out_actions is None and want_actions:
+            out_actions = torch.empty(S, N, dtype=torch.int32, device=dev)
+        if out_probs is None and want_probs:
+            out_probs = torch.empty(S, N, self._action_dim, dtype=torch.float32, device=dev)
+        if out_attn is None and want_attn:
+            out_attn = torch.empty(S, N, N, dtype=torch.float32, device=dev)
+        return out_actions, out_probs, out_attn
 
 
 # ---------------------------------------------------------------------------------------------
 # policy
 # ---------------------------------------------------------------------------------------------
-class CommCategoricalMLPPolicy(CommBaseNet):
+class CommCategoricalMLPPolicy(_Acting, CommBaseNet):
     """comm_categorical_mlp_policy.py:8-141 (same ctor kwargs as runner_pp_commDP.py:49-61)."""
 
     def __init__(self, env_spec, n_agents, encoder_hidden_sizes=(128,), embedding_dim=64, attention_type="general",
@@ -965,6 +925,7 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         self.to(device)
 
     _HEAD_DEFAULT = (128, 64, 32)
+    _is_policy = True
 
     def _head_hidden(self):
         return self._head_sizes
@@ -1057,16 +1018,7 @@ class CommCategoricalMLPPolicy(CommBaseNet):
             setattr(w, k, v)
         return w
 
-    def _weights_struct(self):
-        w = self._struct_from(self._packed())
-        w.mfma_pack = None if self._mfma is None else self._mfma.data_ptr()
-        return w
-
     _mfma, _mfma_fns = None, ("cm_policy_pack_bytes", "cm_policy_pack_sections")
-
-    def set_rng(self, seed, env_id_offset=0):
-        """Philox stream of the action sampler: counter (env id, policy step, site 7, agent)."""
-        self.seed, self.env_id_offset = int(seed), int(env_id_offset)
 
     @torch.no_grad()
     def act_device(self, obs, avail, dist_adj, channels, greedy=False, want_actions=True, want_probs=True,
@@ -1074,64 +1026,42 @@ class CommCategoricalMLPPolicy(CommBaseNet):
                    env_id_offset=None):
         """Fused forward on device tensors: obs [S,N*d]|[S,N,d]; avail/dist_adj/channels may be None
         (= all ones).  Returns (actions int32 [S,N], probs [S,N,A], attn [S,N,N]) as CUDA tensors."""
-        dev = obs.device
-        if dev.type != "cuda":
-            raise L.CommarlError("the rollout forward is a HIP kernel: inputs must be CUDA tensors (no CPU fallback)")
-        N, A = self._n_agents, self._action_dim
-        S = obs.numel() // (N * self._dec_obs_dim)
-        obs = obs.contiguous()
-        actions = out_actions if out_actions is not None else (
-            torch.empty(S, N, dtype=torch.int32, device=dev) if want_actions else None)
-        probs = out_probs if out_probs is not None else (
-            torch.empty(S, N, A, dtype=torch.float32, device=dev) if want_probs else None)
-        attn = out_attn if out_attn is not None else (
-            torch.empty(S, N, N, dtype=torch.float32, device=dev) if want_attn else None)
+        S = obs.numel() // (self._n_agents * self._dec_obs_dim)
+        actions, probs, attn = self._act_outputs(S, obs.device, want_actions, want_probs, want_attn, out_actions, out_probs, out_attn)
         if policy_step is None:
-            policy_step = self._policy_step
-            self._policy_step += 1
+            policy_step = self._next_step()
+        rest = (obs.contiguous(), avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset)
         if not self._default_shape:
-            return self._act_device_any(obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
-                                        env_id_offset)
-        if N > MAX_FUSED_AGENTS:
-            return self._act_device_layers(obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
-                                           env_id_offset)
-        w = self._weights_struct()
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_policy_forward(
-                C.byref(w), S, L.ptr(obs), L.ptr(None if avail is None else avail.contiguous()),
-                L.ptr(None if dist_adj is None else dist_adj.contiguous()),
-                L.ptr(None if channels is None else channels.contiguous()), self.seed,
-                self.env_id_offset if env_id_offset is None else int(env_id_offset),
-                policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
-                L.current_stream()), "cm_policy_forward")
+            return self._act_device_any(*rest)
+        if self._n_agents > MAX_FUSED_AGENTS:
+            return self._act_device_layers(*rest)
+        self._forward_launch("cm_policy_forward", self._weights_struct(), *rest)
         return actions, probs, attn
+
+    def _forward_launch(self, name, w, obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
+                        env_id_offset, maybe=False):
+        """cm_policy_forward / cm_policy_forward_any (`name`) over the weights struct `w`: forward + sample of S env states in one
+        launch -> as L.run answers.  The call is written out instead of going through L.run: this is the per-step launch of an
+        eager rollout, where the helper's extra Python frame showed (+1 us on 34 us per step)."""
+        S = obs.numel() // (self._n_agents * self._dec_obs_dim)
+        with torch.cuda.device(obs.device):
+            rc = getattr(L.lib(), name)(
+                C.byref(w), S, L.ptr(obs), L.cptr(avail), L.cptr(dist_adj), L.cptr(channels), self.seed,
+                self.env_id_offset if env_id_offset is None else int(env_id_offset), policy_step & 0xFFFFFFFF,
+                L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn), L.current_stream())
+        if maybe and rc == 1:
+            return False
+        L.check(rc, name)
+        return True
 
     def _act_device_any(self, obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset):
         """Layer sizes other than the default: forward + sample in ONE launch of the run-time-sized kernel
         (cm_policy_forward_any, csrc/cm_policy_g.hip); where it answers "not for this shape" (1: a workgroup's LDS need above
         160 KB, more layers than it is written for) or the route is pinned (_general_forward = "layers"), layer by layer."""
-        if self._general_forward not in ("auto", "layers"):
-            raise ValueError(f"_general_forward must be 'auto' or 'layers', not {self._general_forward!r}")
-        N, d = self._n_agents, self._dec_obs_dim
-        S = obs.numel() // (N * d)
-        w = self._net_struct() if self._general_forward == "auto" else None
-        rc = 1
-        if w is not None:
-            with torch.cuda.device(obs.device):
-                rc = L.lib().cm_policy_forward_any(
-                    C.byref(w), S, L.ptr(obs), L.ptr(None if avail is None else avail.contiguous()),
-                    L.ptr(None if dist_adj is None else dist_adj.contiguous()),
-                    L.ptr(None if channels is None else channels.contiguous()), self.seed,
-                    self.env_id_offset if env_id_offset is None else int(env_id_offset),
-                    policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
-                    L.current_stream())
-        if rc == 1:
-            self._last_forward = "layers"
-            return self._act_device_layers(obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base,
-                                           env_id_offset)
-        L.check(rc, "cm_policy_forward_any")
-        self._last_forward = "one_launch"
-        return actions, probs, attn
+        rest = (obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset)
+        if self._general_route(lambda w: self._forward_launch("cm_policy_forward_any", w, *rest, maybe=True)):
+            return actions, probs, attn
+        return self._act_device_layers(*rest)
 
     def _act_device_layers(self, obs, avail, dist_adj, channels, greedy, actions, probs, attn, policy_step, step_base, env_id_offset):
         """Teams above 80 agents (PP map 40: N = 128; CO map 40: N = 96): one env's activation planes plus its N x N score matrix
@@ -1165,16 +1095,10 @@ class CommCategoricalMLPPolicy(CommBaseNet):
         if not self._default_shape:                          # the rollout kernels are built for the default layer sizes
             return False
         w = self._weights_struct()
-        with torch.cuda.device(obs.device):
-            rc = getattr(L.lib(), name)(
-                env_batch._h, C.byref(w), *head, L.ptr(obs), *after_obs, L.ptr(dist_adj), L.ptr(channels), self.seed,
-                self.env_id_offset if env_id_offset is None else int(env_id_offset), policy_step & 0xFFFFFFFF,
-                L.ptr(step_base), int(greedy), L.ptr(out_actions), L.ptr(out_probs), L.ptr(out_attn), *before_out,
-                C.byref(step_out), *after_out, L.current_stream())
-        if rc == 1:
-            return False
-        L.check(rc, name)
-        return True
+        return L.run(name, env_batch._h, C.byref(w), *head, L.ptr(obs), *after_obs, L.ptr(dist_adj), L.ptr(channels), self.seed,
+                     self.env_id_offset if env_id_offset is None else int(env_id_offset), policy_step & 0xFFFFFFFF,
+                     L.ptr(step_base), int(greedy), L.ptr(out_actions), L.ptr(out_probs), L.ptr(out_attn), *before_out,
+                     C.byref(step_out), *after_out, device=obs.device, maybe=True)
 
     @torch.no_grad()
     def step_fused(self, env_batch, obs, dist_adj, channels, step_out, greedy=False, out_actions=None, out_probs=None,
@@ -1240,9 +1164,9 @@ class _GaussNLLFn(torch.autograd.Function):
         pa, r = per_agent.contiguous(), returns.contiguous()
         out = torch.empty(2, dtype=torch.float32, device=pa.device)
         has_min = 0 if min_log_std is None else 1
-        with torch.cuda.device(pa.device):                   # (deterministic mode: block sums summed in a fixed order, no f64 atomics)
-            L.check(L.launch("cm_gauss_nll_forward", (S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
-                                                      L.ptr(out), L.ptr(ws)), (S,)), "cm_gauss_nll_forward")
+        # (deterministic mode: block sums summed in a fixed order, no f64 atomics)
+        L.launch("cm_gauss_nll_forward", (S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(min_log_std or 0.0), has_min,
+                                          L.ptr(out), L.ptr(ws)), (S,), device=pa.device)
         ctx.save_for_backward(pa, r, log_std, out)
         ctx.min_log_std = min_log_std
         return out[0]
@@ -1253,10 +1177,8 @@ class _GaussNLLFn(torch.autograd.Function):
         S, N = pa.shape
         d_pa, d_ls = torch.empty_like(pa), torch.empty_like(log_std)
         g = g.to(torch.float32).contiguous()
-        with torch.cuda.device(pa.device):
-            L.check(L.lib().cm_gauss_nll_backward(S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(ctx.min_log_std or 0.0),
-                                                  0 if ctx.min_log_std is None else 1, L.ptr(out), L.ptr(g), L.ptr(d_pa), L.ptr(d_ls),
-                                                  L.current_stream()), "cm_gauss_nll_backward")
+        L.run("cm_gauss_nll_backward", S, N, L.ptr(pa), L.ptr(r), L.ptr(log_std), float(ctx.min_log_std or 0.0),
+              0 if ctx.min_log_std is None else 1, L.ptr(out), L.ptr(g), L.ptr(d_pa), L.ptr(d_ls), device=pa.device)
         return d_pa, None, d_ls, None, None
 
 
@@ -1347,36 +1269,24 @@ class CommBaseCritic(CommBaseNet):
         N = self._n_agents
         lead = obs.shape[:-1] if obs.shape[-1] == N * self._dec_obs_dim else obs.shape[:-2]
         S = obs.numel() // (N * self._dec_obs_dim)
+        values = None
+
+        def launch(name, w, maybe=False):
+            nonlocal values
+            values = out if out is not None else torch.empty(S, dtype=torch.float32, device=dev)
+            return L.run(name, C.byref(w), S, L.cptr(obs), L.cptr(dist_adj), L.cptr(channels), L.ptr(values), device=dev, maybe=maybe)
+
         if self.aggregator_type == "sum" and not self._default_shape:
             # layer sizes other than the default: ONE launch of the run-time-sized kernel (cm_critic_forward_any, csrc/cm_critic_g.hip);
             # where it answers "not for this shape" (1) or the route is pinned (_general_forward = "layers"), layer by layer
-            if self._general_forward not in ("auto", "layers"):
-                raise ValueError(f"_general_forward must be 'auto' or 'layers', not {self._general_forward!r}")
-            w = self._net_struct() if self._general_forward == "auto" else None
-            rc = 1
-            if w is not None:
-                values = out if out is not None else torch.empty(S, dtype=torch.float32, device=dev)
-                with torch.cuda.device(dev):
-                    rc = L.lib().cm_critic_forward_any(C.byref(w), S, L.ptr(obs.contiguous()),
-                                                       L.ptr(None if dist_adj is None else dist_adj.contiguous()),
-                                                       L.ptr(None if channels is None else channels.contiguous()),
-                                                       L.ptr(values), L.current_stream())
-            if rc != 1:
-                L.check(rc, "cm_critic_forward_any")
-                self._last_forward = "one_launch"
-                return values.reshape(*lead) if out is None else values
-            self._last_forward = "layers"
-        if self.aggregator_type == "direct" or self._n_agents > MAX_FUSED_AGENTS or not self._default_shape:    # no one-launch kernel: layer by layer
+            one_launch = self._general_route(lambda w: launch("cm_critic_forward_any", w, maybe=True))
+        elif self.aggregator_type == "sum" and N <= MAX_FUSED_AGENTS:
+            one_launch = launch("cm_critic_forward", self._weights_struct())
+        else:
+            one_launch = False
+        if not one_launch:                                   # 'direct', teams above 80 agents, sizes the kernel refuses: layer by layer
             v = self._values_grad(obs, dist_adj, channels)[0]
             return v if out is None else out.copy_(v.reshape(out.shape))
-        values = out if out is not None else torch.empty(S, dtype=torch.float32, device=dev)
-        w = self._struct_from(self._packed())
-        w.mfma_pack = None if self._mfma is None else self._mfma.data_ptr()
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_critic_forward(C.byref(w), S, L.ptr(obs.contiguous()),
-                                              L.ptr(None if dist_adj is None else dist_adj.contiguous()),
-                                              L.ptr(None if channels is None else channels.contiguous()),
-                                              L.ptr(values), L.current_stream()), "cm_critic_forward")
         return values.reshape(*lead) if out is None else values
 
     def forward(self, obs_n, avail_actions_n, dist_adj, channels, get_actions=False):
@@ -1408,7 +1318,7 @@ class CommBaseCritic(CommBaseNet):
 # ---------------------------------------------------------------------------------------------
 # Obs-DP / CENT variants: no communication, plain row-wise MLPs
 # ---------------------------------------------------------------------------------------------
-class _RowMLPPolicy(_WeightPack):
+class _RowMLPPolicy(_Acting, _WeightPack):
     """Shared rollout path of the two non-communicating policies: one fused HIP launch
     (cm_mlp_policy_forward, csrc/cm_mlp.hip) over the layer chain listed by ``_chain()``."""
 
@@ -1433,8 +1343,7 @@ class _RowMLPPolicy(_WeightPack):
         w = self._struct_from(ptrs)
         if self._mlp_pack is None or self._mlp_pack.device != dev:
             self._mlp_pack = torch.zeros(L.lib().cm_mlp_pack_bytes(C.byref(w)) // 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_mlp_pack(C.byref(w), L.ptr(self._mlp_pack), L.current_stream()), "cm_mlp_pack")
+        L.run("cm_mlp_pack", C.byref(w), L.ptr(self._mlp_pack), device=dev)
 
     def _mlp_struct(self):
         w = self._struct_from(self._packed())
@@ -1454,37 +1363,22 @@ class _RowMLPPolicy(_WeightPack):
             w.relu_mask |= int(int(act) == ACT_RELU) << i
         return w
 
-    def set_rng(self, seed, env_id_offset=0):
-        """Philox stream of the action sampler: counter (env id, policy step, site 7, agent)."""
-        self.seed, self.env_id_offset = int(seed), int(env_id_offset)
-
     @torch.no_grad()
     def act_device(self, obs, avail=None, dist_adj=None, channels=None, greedy=False, want_actions=True,
                    want_probs=True, want_attn=False, out_actions=None, out_probs=None, out_attn=None,
                    policy_step=None, step_base=None, env_id_offset=None):
         """obs [S,N*d] (CUDA) -> (actions int32 [S,N], probs [S,N,A], None).  dist_adj / channels are accepted
         and ignored so the rollout engine drives every policy through one call shape."""
-        dev = obs.device
-        if dev.type != "cuda":
-            raise L.CommarlError("the rollout forward is a HIP kernel: inputs must be CUDA tensors (no CPU fallback)")
         N, A = self._n_agents, self._action_dim
         S = obs.numel() // (N * self._dec_obs_dim)
-        obs = obs.contiguous()
-        actions = out_actions if out_actions is not None else (
-            torch.empty(S, N, dtype=torch.int32, device=dev) if want_actions else None)
-        probs = out_probs if out_probs is not None else (
-            torch.empty(S, N, A, dtype=torch.float32, device=dev) if want_probs else None)
+        actions, probs, _ = self._act_outputs(S, obs.device, want_actions, want_probs, False, out_actions, out_probs, None)
         if policy_step is None:
-            policy_step = self._policy_step
-            self._policy_step += 1
+            policy_step = self._next_step()
         rows, groups = (S * N, 1) if self._per_agent_rows else (S, N)
-        w = self._mlp_struct()
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_mlp_policy_forward(
-                C.byref(w), rows, groups, A, N, L.ptr(obs), L.ptr(None if avail is None else avail.contiguous()),
-                self.seed, self.env_id_offset if env_id_offset is None else int(env_id_offset),
-                policy_step & 0xFFFFFFFF, L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs),
-                L.current_stream()), "cm_mlp_policy_forward")
+        obs, w = obs.contiguous(), self._mlp_struct()
+        L.run("cm_mlp_policy_forward", C.byref(w), rows, groups, A, N, L.ptr(obs), L.cptr(avail), self.seed,
+              self.env_id_offset if env_id_offset is None else int(env_id_offset), policy_step & 0xFFFFFFFF,
+              L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), device=obs.device)
         return actions, probs, None
 
     def get_actions(self, observations, avail_actions, greedy=False):
@@ -1650,9 +1544,7 @@ class GaussianMLPBaseline(_WeightPack, nn.Module):
         rows = obs.numel() // self.input_dim
         values = torch.empty(rows, dtype=torch.float32, device=dev)
         w = self._mlp_struct()
-        with torch.cuda.device(dev):
-            L.check(L.lib().cm_mlp_value_forward(C.byref(w), rows, L.ptr(obs.contiguous()), L.ptr(values),
-                                                 L.current_stream()), "cm_mlp_value_forward")
+        L.run("cm_mlp_value_forward", C.byref(w), rows, L.cptr(obs), L.ptr(values), device=dev)
         return values.reshape(*lead)
 
     def forward(self, obs):

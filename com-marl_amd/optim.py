@@ -102,21 +102,16 @@ class Adam(torch.optim.Optimizer):
                 out = self._norm[0]
             if n > 40:
                 raise L.CommarlError("cm_multi_adam_step takes at most 40 tensors per parameter group")
-            with torch.cuda.device(dev):
-                if ds is not None:
-                    L.check(L.lib().cm_multi_adam_step_dev(
-                        n, arr(ps), arr(grads), arr([self.state[p]["exp_avg"] for p in ps]),
-                        arr([self.state[p]["exp_avg_sq"] for p in ps]), sizes, norm_ptr,
-                        float(max_norm if max_norm is not None else 0.0), float(group["lr"]), float(b1), float(b2),
-                        float(group["eps"]), ds["table"].data_ptr(), ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY, L.current_stream()),
-                        "cm_multi_adam_step_dev")
-                    ds["cursor"].add_(1)
-                else:
-                    L.check(L.lib().cm_multi_adam_step(
-                        n, arr(ps), arr(grads), arr([self.state[p]["exp_avg"] for p in ps]),
-                        arr([self.state[p]["exp_avg_sq"] for p in ps]), sizes, norm_ptr,
-                        float(max_norm if max_norm is not None else 0.0), float(group["lr"]), float(b1), float(b2),
-                        float(group["eps"]), step, L.current_stream()), "cm_multi_adam_step")
+            # what both entry points take before their step number (host value, or the device table and its cursor)
+            args = (n, arr(ps), arr(grads), arr([self.state[p]["exp_avg"] for p in ps]),
+                    arr([self.state[p]["exp_avg_sq"] for p in ps]), sizes, norm_ptr,
+                    float(max_norm if max_norm is not None else 0.0), float(group["lr"]), float(b1), float(b2), float(group["eps"]))
+            if ds is not None:
+                L.run("cm_multi_adam_step_dev", *args, ds["table"].data_ptr(), ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY,
+                      device=dev)
+                ds["cursor"].add_(1)
+            else:
+                L.run("cm_multi_adam_step", *args, step, device=dev)
             # the kernel wrote through raw pointers: tell torch (and the nets' weight-pack cache, which keys on the version
             # counters) that the parameters changed
             for p in ps:

@@ -182,15 +182,11 @@ class RolloutEngine:
         w = ps[0]._weights_struct()                                         # the shape every member shares
         st = L.PolicySetT(len(ps), self._wg_policy.numel(), L.ptr(ps.pack_table()), L.ptr(self._wg_policy))
         obs, adj, ch, actions, probs, attn = self._slot(t0, 0, B)
-        with torch.cuda.device(env.device):
-            rc = L.lib().cm_rollout_chunk_multi(
-                env._h, C.byref(w), C.byref(st), int(n), C.byref(self._strides()), L.ptr(obs), L.ptr(adj), L.ptr(ch), ps.seed,
-                self.id0, t0 & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions), L.ptr(probs), L.ptr(attn),
-                C.byref(env._out(self._out(t0, 0, B))), L.current_stream())
-        if rc == 1:
+        if not L.run("cm_rollout_chunk_multi", env._h, C.byref(w), C.byref(st), int(n), C.byref(self._strides()), L.ptr(obs),
+                     L.ptr(adj), L.ptr(ch), ps.seed, self.id0, t0 & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy), L.ptr(actions),
+                     L.ptr(probs), L.ptr(attn), C.byref(env._out(self._out(t0, 0, B))), device=env.device, maybe=True):
             self.multi_form, self._persistent, self.multi_forward = "loop", False, "member"     # (teams of 4: no set forward)
             return False
-        L.check(rc, "cm_rollout_chunk_multi")
         return True
 
     def _set_forward(self, t, greedy):
@@ -202,21 +198,17 @@ class RolloutEngine:
         _multi_chunk."""
         ps, B = self.policy, self.env.B
         call = ps.forward_call([hi - lo for lo, hi in self.groups], B)
-        rc = 1                                                              # no table: as the library's "not for this shape"
+        done = False                                                        # no table: as the library's "not for this shape"
         if call is not None:
             what, lead = call
             obs, adj, ch, actions, probs, attn = self._slot(t, 0, B)
             # the Obs-DP / CENT entry point has no adjacency, channel or attention argument
             graph, attn = ((), ()) if ps.forward_kind == "mlp" else ((L.ptr(adj), L.ptr(ch)), (L.ptr(attn),))
-            with torch.cuda.device(self.env.device):
-                rc = getattr(L.lib(), what)(
-                    *lead, L.ptr(obs), None, *graph, ps.seed, self.id0, t & 0xFFFFFFFF, L.ptr(self.step_bases[0]), int(greedy),
-                    L.ptr(actions), L.ptr(probs), *attn, L.current_stream())
-        if rc == 1:
+            done = L.run(what, *lead, L.ptr(obs), None, *graph, ps.seed, self.id0, t & 0xFFFFFFFF, L.ptr(self.step_bases[0]),
+                         int(greedy), L.ptr(actions), L.ptr(probs), *attn, device=self.env.device, maybe=True)
+        if not done:
             self.multi_forward = "member"
-            return False
-        L.check(rc, what)
-        return True
+        return done
 
     def _multi_step(self, t, greedy):
         """Slot t -> t+1 for every member: one launch (a chunk of one step) where the set has the multi-policy kernel, else the
@@ -359,8 +351,7 @@ class RolloutEngine:
         args = []
         for src, dst in pairs + [(None, None)] * (3 - len(pairs)):
             args += [L.ptr(src), L.ptr(dst), 0 if src is None else src.numel() * src.element_size()]
-        with torch.cuda.device(self.env.device):
-            L.check(L.lib().cm_chunk_tail(L.ptr(self.step_bases[k]), n, *args, L.current_stream()), "cm_chunk_tail")
+        L.run("cm_chunk_tail", L.ptr(self.step_bases[k]), n, *args, device=self.env.device)
 
     def _strides(self):
         e = self.env

@@ -44,6 +44,7 @@ from oracle import oracle as O
 from tests import acting_regimes as G
 from tests import any_shapes as AS
 from tests import f64_commnet as R
+from tests.lib_spy import spy  # noqa: F401  (the fixture: a recording proxy around _lib.lib())
 from tests.test_oracle_golden import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -51,31 +52,6 @@ pytestmark = pytest.mark.gpu
 TAU = 1e-5
 DEV = "cuda:0"
 F64 = torch.float64
-
-
-class _Spy:
-    """Stands in for the loaded library: records the name of every cm_* call, then makes it."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if not name.startswith("cm_") or name == "cm_last_error":
-            return fn
-
-        def call(*a):
-            self.calls.append(name)
-            return fn(*a)
-        return call
-
-
-@pytest.fixture
-def spy(monkeypatch):
-    from com_marl_amd import _lib as L
-    s = _Spy(L.lib())
-    monkeypatch.setattr(L, "lib", lambda: s)
-    return s
 
 
 LAYER_OPS = {"cm_attention_forward", "cm_masked_agg_forward", "cm_mlp_policy_forward"}

@@ -1,5 +1,6 @@
 """The training path of Comm-DP nets whose embedding is not 64, now on the any-width graph ops (cm_attention_*_any,
-cm_masked_agg_*_any through nets._AttentionSoftmaxAny / _MaskedAggregateAny): which route nets.graph_op_route gives, every
+cm_masked_agg_*_any through the any-width family of nets._AttentionSoftmax / _MaskedAggregate): which route nets.graph_op_route
+gives and which entry points then run (recorded by the proxy of tests/lib_spy.py around com_marl_amd._lib.lib()), every
 parameter gradient of policy and critic at shapes A and C (tests/any_shapes.py) against float64 autograd of
 tests/f64_commnet.py - the bound of tests/test_any_shape_training.py:121-123, rtol 1e-4 plus 1e-5 of the tensor's scale -
 and bit-identical gradients of two backward passes in deterministic mode."""
@@ -8,6 +9,7 @@ import pytest
 
 from tests import any_shapes as G
 from tests import f64_commnet as R
+from tests.lib_spy import spy  # noqa: F401  (the fixture: a recording proxy around _lib.lib())
 from tests.test_any_shape_critic import C_KW
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +34,11 @@ def _nets(shape, torch):
     return pol, crit
 
 
-def test_graph_op_routes(torch_cuda, monkeypatch):
+def _any_calls(spy):
+    return [c for c in spy.calls if c.endswith("_any")]
+
+
+def test_graph_op_routes(torch_cuda, spy):
     torch = torch_cuda
     from com_marl_amd import nets
     for N, E in ((4, 32), (24, 32), (5, 16)):
@@ -45,39 +51,38 @@ def test_graph_op_routes(torch_cuda, monkeypatch):
     e = torch.tanh(torch.randn(S, N, E, device=DEV))
     try:
         m = att(e)
+        assert _any_calls(spy) == ["cm_attention_forward_any"]               # asked once: the refusal
         assert nets.graph_op_route(N, E) == "framework"
-        np.testing.assert_allclose(m.cpu().numpy(), torch.softmax(e @ e.transpose(-2, -1), -1).cpu().numpy(), rtol=1e-5, atol=1e-7)
-        calls = []
-        monkeypatch.setattr(nets._AttentionSoftmaxAny, "apply", lambda *a: calls.append(a))
-        monkeypatch.setattr(nets._MaskedAggregateAny, "apply", lambda *a: calls.append(a))
-        att(e)
+        want = torch.softmax(e @ e.transpose(-2, -1), -1).cpu().numpy()
+        np.testing.assert_allclose(m.cpu().numpy(), want, rtol=1e-5, atol=1e-7)
+        spy.calls.clear()
+        m2 = att(e)
         out = nets.masked_aggregate(m, None, None, 0, e, None)
-        assert not calls                                                     # not probed again
+        assert not _any_calls(spy), spy.calls                                # not probed again
+        np.testing.assert_allclose(m2.cpu().numpy(), want, rtol=1e-5, atol=1e-7)
         assert tuple(out.shape) == (S, N, E)
     finally:
         nets.set_graph_op_route(N, E, None)
 
 
-def test_width_64_never_asks_for_a_route(torch_cuda, monkeypatch):
+def test_width_64_never_asks_for_a_route(torch_cuda, monkeypatch, spy):
     torch = torch_cuda
     from com_marl_amd import nets
 
     def boom(*a):
         raise AssertionError("graph_op_route consulted for E = 64")
     monkeypatch.setattr(nets, "graph_op_route", boom)
-    monkeypatch.setattr(nets._AttentionSoftmaxAny, "apply", boom)
-    monkeypatch.setattr(nets._MaskedAggregateAny, "apply", boom)
     S, N = 3, 4
     e = torch.tanh(torch.randn(S, N, 64, device=DEV))
     m = nets.AttentionModule(64, "dot").to(DEV)(e)
     out = nets.masked_aggregate(m, None, None, 0, e, None)
     assert tuple(out.shape) == (S, N, 64)
+    assert spy.calls == ["cm_attention_forward", "cm_masked_agg_forward"]    # and no _any entry point
 
 
 @pytest.mark.parametrize("shape", ["A", "C"])
-def test_parameter_gradients_match_float64(shape, torch_cuda, monkeypatch):
+def test_parameter_gradients_match_float64(shape, torch_cuda, spy):
     torch = torch_cuda
-    from com_marl_amd import nets
     s = G.SHAPES[shape]
     N, hops = s["N"], s["hops"]
     residual = s["pol"].get("residual", True)
@@ -88,10 +93,7 @@ def test_parameter_gradients_match_float64(shape, torch_cuda, monkeypatch):
     t64 = lambda a: torch.as_tensor(a, dtype=R.F64)                          # noqa: E731
     g = torch.Generator().manual_seed(11)
     w_p, w_v = torch.randn(S, N, 5, generator=g), torch.randn(S, generator=g)
-    taken = []
-    for cls in (nets._AttentionSoftmaxAny, nets._MaskedAggregateAny):       # the new ops carry these gradients
-        orig = cls.apply
-        monkeypatch.setattr(cls, "apply", lambda *a, _o=orig, _n=cls.__name__: (taken.append(_n), _o(*a))[1])
+    spy.calls.clear()
 
     probs, _ = pol._probs(dobs, dav, dadj, dch)
     pol.zero_grad()
@@ -99,7 +101,10 @@ def test_parameter_gradients_match_float64(shape, torch_cuda, monkeypatch):
     values, _ = crit._values_grad(dobs, dadj, dch)
     crit.zero_grad()
     (values * w_v.to(DEV)).sum().backward()
-    assert taken.count("_AttentionSoftmaxAny") == 2 and taken.count("_MaskedAggregateAny") == 2 * hops
+    # the any-width ops carry these gradients: policy + critic, each backward as often as its forward, no E = 64 entry point
+    for op, n in (("cm_attention", 2), ("cm_masked_agg", 2 * hops)):
+        assert spy.count(op + "_forward_any") == n and spy.count(op + "_backward_any") == n, (op, spy.calls)
+        assert spy.count(op + "_forward") == 0 and spy.count(op + "_backward") == 0, (op, spy.calls)
 
     p64 = R.params(dict(pol.state_dict()))
     _, probs64, _ = R.policy_forward(p64, t64(obs), t64(avail), t64(adj), t64(ch), N, residual)

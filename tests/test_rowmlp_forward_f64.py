@@ -37,7 +37,7 @@ import torch
 
 from oracle import oracle as O
 from tests import f64_rowmlp as M
-from tests.test_acting_forward_f64 import spy  # noqa: F401  (the fixture: a recording proxy around _lib.lib())
+from tests.lib_spy import spy  # noqa: F401  (the fixture: a recording proxy around _lib.lib())
 
 pytestmark = pytest.mark.gpu
 

@@ -16,43 +16,13 @@ import pytest
 import torch
 
 from tests import f64_commnet as R
+from tests.lib_spy import spy  # noqa: F401  (the fixture: a recording proxy around _lib.lib())
 
 pytestmark = pytest.mark.gpu
 
 TAU = 1e-5
 DEV = "cuda:0"
 F64 = torch.float64
-
-
-class _Spy:
-    """Stands in for the loaded library: records (entry point, bias_replicas) of every cm_* call, then makes it."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if not name.startswith("cm_") or name == "cm_last_error":
-            return fn
-
-        def call(*a):
-            self.calls.append((name, a[14] if name == "cm_masked_agg_backward_r" else None))
-            return fn(*a)
-        return call
-
-    def names(self):
-        return {n for n, _ in self.calls}
-
-    def replicas(self):
-        return {r for n, r in self.calls if n == "cm_masked_agg_backward_r"}
-
-
-@pytest.fixture
-def spy(monkeypatch):
-    from com_marl_amd import _lib as L
-    s = _Spy(L.lib())
-    monkeypatch.setattr(L, "lib", lambda: s)
-    return s
 
 
 # path -> (entry points that must run, entry points that must not)

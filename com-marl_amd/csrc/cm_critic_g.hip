@@ -18,12 +18,5 @@ extern "C" int cm_critic_forward_any(const cm_net_weights *w, int32_t n_samples,
     a.obs = obs; a.adj = dist_adj; a.chan = channels;
     a.values = values;
 
-    static unsigned long long attr_set = 0;
-    if (dev_first(attr_set))
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pg::fwd_any_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)pg::LDS_LIMIT));
-    const int blocks = (a.S + a.EPB - 1) / a.EPB;
-    hipLaunchKernelGGL(pg::fwd_any_kernel<true>, dim3(blocks), dim3(pg::TPB), p.lds_bytes, (hipStream_t)stream, a);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&pg::fwd_any_kernel<true>>(dim3((a.S + a.EPB - 1) / a.EPB), dim3(pg::TPB), p.lds_bytes, stream, a);
 }

@@ -16,8 +16,6 @@
 
 namespace cm {
 
-bool policy_h_enabled();                                 // cm_policy_h.hip: f16-split dense layers (default) or the all-f32 body
-
 // POL selects the policy body: 0 = cm_policy_mfma_dev.h (all f32), 1 = cm_policy_h_dev.h (f16-split dense layers).  Both
 // forms take the workgroup's dynamic LDS block; `act` = the sampled actions behind the policy tiles.
 template <int POL, int KPAD, int MAXMK, bool FULL = false>
@@ -126,47 +124,19 @@ static int launch_fused(mf::FwdArgs a, const mf::TrunkW &tw, const mf::PolHead &
     if (env_bytes > pol_floats * sizeof(float)) return 1;                // env area would reach into the action array
     const size_t lds = (pol_floats + (size_t)a.EPB * a.N) * sizeof(float);
     if (lds > 160 * 1024) return 1;
-    static unsigned long long attr_set = 0;
-    if (cm::dev_first(attr_set)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    const int blocks = (a.S + a.EPB - 1) / a.EPB;
-    if (chunk) {
-        static unsigned long long attr_set_c = 0;
-        if (cm::dev_first(attr_set_c)) {
-            CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_chunk_kernel<SCEN, LPE, KPAD, MAXMK, POL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        }
-        hipLaunchKernelGGL((rollout_chunk_kernel<SCEN, LPE, KPAD, MAXMK, POL>), dim3(blocks), dim3(mf::TPB), lds, (hipStream_t)stream, a,
-                           tw, ph, twh, phh, d, out, *chunk, (int)pol_floats);
-        CM_HIP(hipGetLastError());
-        return CM_OK;
-    }
+    const dim3 grid((a.S + a.EPB - 1) / a.EPB), block(mf::TPB);
+    if (chunk)
+        return launch_lds<&rollout_chunk_kernel<SCEN, LPE, KPAD, MAXMK, POL>>(grid, block, lds, stream, a, tw, ph, twh, phh, d, out, *chunk, (int)pol_floats);
     if constexpr (MAXMK < 0 && POL == 1) {
-        if (a.EPB == 8 && a.S % 8 == 0) {
-#define CM_FULL_LAUNCH(PRE)                                                                                                       \
-    do {                                                                                                                          \
-        static unsigned long long attr_set_f = 0;                                                                                           \
-        if (cm::dev_first(attr_set_f)) {                                                                                                        \
-            CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL, true, PRE>), \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                  \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL, true, PRE>), dim3(blocks), dim3(mf::TPB), lds,       \
-                           (hipStream_t)stream, a, tw, ph, twh, phh, d, t, out, (int)pol_floats);                                 \
-        CM_HIP(hipGetLastError());                                                                                                \
-        if (d.stop < 0) env_probe_dump("fused", HIP_SYMBOL(g_env_probe), stream);                                                 \
-        return CM_OK;                                                                                                             \
-    } while (0)
-            if (env_prefetch_ok<SCEN, LPE>(d)) CM_FULL_LAUNCH(true);
-            CM_FULL_LAUNCH(false);
-#undef CM_FULL_LAUNCH
+        if (a.EPB == 8 && a.S % 8 == 0) {                                // every workgroup full: the constant-shape build
+            const int rc = env_prefetch_ok<SCEN, LPE>(d)
+                ? launch_lds<&rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL, true, true>>(grid, block, lds, stream, a, tw, ph, twh, phh, d, t, out, (int)pol_floats)
+                : launch_lds<&rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL, true, false>>(grid, block, lds, stream, a, tw, ph, twh, phh, d, t, out, (int)pol_floats);
+            if (rc == CM_OK && d.stop < 0) env_probe_dump("fused", HIP_SYMBOL(g_env_probe), stream);
+            return rc;
         }
     }
-    hipLaunchKernelGGL((rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL>), dim3(blocks), dim3(mf::TPB), lds, (hipStream_t)stream, a, tw,
-                       ph, twh, phh, d, t, out, (int)pol_floats);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&rollout_step_kernel<SCEN, LPE, KPAD, MAXMK, POL>>(grid, block, lds, stream, a, tw, ph, twh, phh, d, t, out, (int)pol_floats);
 }
 
 }  // namespace cm
@@ -185,28 +155,27 @@ static int rollout_impl(cm_env_t h, const cm_policy_weights *w, const float *obs
     if (int rc = check_tape(h, tape, false)) return rc;
     cm_rng_tape t{};
     if (tape) t = *tape;
-    const mf::FwdArgs a = rollout_fwd_args(h, w, obs, avail, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy,
-                                           actions, probs, attn);
-    const int kpad = mf::kpad_of(d.d);
-    const mf::PackLayout lo = mf::pack_layout(kpad, d.L, true);
-    const float *P = w->mfma_pack;
-    const mf::TrunkW tw{ P + lo.enc1, w->enc_b1, P + lo.enc2, w->enc_b2, P + lo.attn, P + lo.gcn, w->gcn_b };
-    const mf::PolHead ph{ P + lo.x1, w->hd_b1, P + lo.h2, w->hd_b2, P + lo.h3, w->hd_b3, P + lo.h4, w->hd_b4, w->n_act };
-    const int mk = d.N < 16 ? 0 : (d.N <= 80 ? 25 : 64);                    // as mf::dispatch
+    // the policy forward's arguments: shape from the env handle, the rest as the entry point received it
+    const mf::FwdArgs a = fwd_args(FwdShape{ d.B, d.N, d.d, d.L, w->no_residual }, obs, dist_adj, channels, attn,
+                                   FwdSampler{ avail, seed, env_id_offset, policy_step, policy_step_base, greedy, actions, probs });
+    const int kpad = mf::kpad_of(d.d), kh = mh::kh_of(d.d);
+    const PackSections s = pack_sections(w);
+    const mf::PackLayout lo = layout_f32(w);
+    const mf::TrunkW tw = trunk_w(s.f32(), lo, w);
+    const mf::PolHead ph = pol_head(s.f32(), lo, w);
     // instantiations: the four BASELINE shapes (PP sen1 small teams; CO sen2 mid teams; PP / CO sen2 large teams)
-    const bool quad = d.N == 4 && mf::pick_epb(4) * 4 <= 32;
-    const int kh = mh::kh_of(d.d);
+    const FwdTile ft = fwd_tile(d.N);
+    const int mk = ft.mk;
+    const bool quad = ft.quad;
     if (policy_w_enabled() && shape_ok_rollout_w(d.N, d.d, d.L, w->n_act)) {    // teams of 4: wave-owned rows, single step or persistent chunk
-        const char *wp = reinterpret_cast<const char *>(P) + wave_pack(d);
-        const int rc = h->cond ? (tape ? 1 : launch_rollout_wc(a, w, wp, nullptr, h, *out, stream, chunk)) : launch_rollout_w(a, w, wp, h, t, *out, stream, chunk);
+        const int rc = h->cond ? (tape ? 1 : launch_rollout_wc(a, w, s.w(), nullptr, h, *out, stream, chunk)) : launch_rollout_w(a, w, s.w(), h, t, *out, stream, chunk);
         if (rc != 1) return rc;
     }
     if (h->cond) return 1;                           // the table is read by the wave-owned twins only (cm_rollout_wc.hip)
     if (policy_h_enabled() && kh) {                  // f16-split dense layers: the operand pack behind the f32 one
-        const mh::PackLayoutH lh = mh::pack_layout_h(kh, d.L, true);
-        const uint4 *Q = reinterpret_cast<const uint4 *>(P + lo.total);
-        const mh::TrunkH twh{ Q + lh.enc1, w->enc_b1, Q + lh.enc2, w->enc_b2, Q + lh.attn, Q + lh.gcn, w->gcn_b };
-        const mh::PolHeadH phh{ Q + lh.x1, w->hd_b1, Q + lh.h2, w->hd_b2, Q + lh.h3, w->hd_b3, Q + lh.h4, w->hd_b4, w->n_act };
+        const mh::PackLayoutH lh = layout_h(w);
+        const mh::TrunkH twh = trunk_h(s.h(), lh, w);
+        const mh::PolHeadH phh = pol_head_h(s.h(), lh, w);
         // teams of 4: 8 envs per workgroup.  With 32 lanes per env the env phase occupies all four waves (16 lanes leave two of
         // them idle): its lane-parallel loops (observation emission, tile rebuild) halve - 28.5 -> 27.4 us per step at the
         // headline config.  The stand-alone env kernel keeps the handle's own choice (16: more envs per wave); the env body

@@ -363,15 +363,10 @@ static int masked_agg_backward_any(const char *fn, int32_t S, int32_t N, int32_t
                                               nullptr, 0, stream);
     const hipStream_t st = (hipStream_t)stream;
     float *const slab = static_cast<float *>(ws);
-    static unsigned long long once = 0;
-    if (dev_first(once))
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_any_kernel<DET>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)LDS_LIMIT));
     const int vec = E % 4 == 0 && aligned16({ hw, out, out_minus, d_out });
     const int grid = grid_of(S, p.EPB, GRID_CAP_AGG_BWD);
-    hipLaunchKernelGGL((agg_bwd_any_kernel<DET>), dim3(grid), dim3(TPB), p.agg_bwd, st, S, N, E, p.EPB, vec, attn, dist_adj, chan,
-                       (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, DET ? slab : d_bias);
-    CM_HIP(hipGetLastError());
+    if (int rc = launch_lds<&agg_bwd_any_kernel<DET>>(dim3(grid), dim3(TPB), p.agg_bwd, st, S, N, E, p.EPB, vec, attn, dist_adj, chan,
+                                                     (long)ch_stride, hw, out, out_minus, d_out, d_attn, d_hw, DET ? slab : d_bias)) return rc;
     if (!DET) return CM_OK;
     SlabSegs segs{};
     segs.s[0] = { d_bias, 0, E };
@@ -391,15 +386,9 @@ extern "C" int cm_masked_agg_forward_any(int32_t S, int32_t N, int32_t E, const 
     ga::Plan p;
     if (const int rc = ga::shape_rc(__func__, N, E, p)) return rc;
     if (S <= 0) return CM_OK;
-    static unsigned long long once = 0;
-    if (dev_first(once))
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ga::agg_fwd_any_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)ga::LDS_LIMIT));
     const int vec = E % 4 == 0 && ga::aligned16({ hw });
-    hipLaunchKernelGGL(ga::agg_fwd_any_kernel, dim3(ga::grid_of(S, p.EPB, ga::GRID_CAP)), dim3(ga::TPB), p.agg_fwd, (hipStream_t)stream, S, N,
-                       E, p.EPB, vec, attn, dist_adj, chan, (long)ch_stride, hw, bias, out);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&ga::agg_fwd_any_kernel>(dim3(ga::grid_of(S, p.EPB, ga::GRID_CAP)), dim3(ga::TPB), p.agg_fwd, stream, S, N, E, p.EPB, vec, attn,
+                                               dist_adj, chan, (long)ch_stride, hw, bias, out);
 }
 
 extern "C" int cm_masked_agg_backward_any(int32_t S, int32_t N, int32_t E, const float *attn, const float *dist_adj,
@@ -427,15 +416,8 @@ extern "C" int cm_attention_forward_any(int32_t S, int32_t N, int32_t E, const f
     ga::Plan p;
     if (const int rc = ga::shape_rc(__func__, N, E, p)) return rc;
     if (S <= 0) return CM_OK;
-    static unsigned long long once = 0;
-    if (dev_first(once))
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ga::attn_fwd_any_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)ga::LDS_LIMIT));
     const int vec = E % 4 == 0 && ga::aligned16({ q, e });
-    hipLaunchKernelGGL(ga::attn_fwd_any_kernel, dim3(ga::grid_of(S, p.EPB, ga::GRID_CAP)), dim3(ga::TPB), p.attn_fwd, (hipStream_t)stream, S,
-                       N, E, p.EPB, vec, q, e, m);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&ga::attn_fwd_any_kernel>(dim3(ga::grid_of(S, p.EPB, ga::GRID_CAP)), dim3(ga::TPB), p.attn_fwd, stream, S, N, E, p.EPB, vec, q, e, m);
 }
 
 extern "C" int cm_attention_backward_any(int32_t S, int32_t N, int32_t E, const float *q, const float *e, const float *m,
@@ -446,13 +428,7 @@ extern "C" int cm_attention_backward_any(int32_t S, int32_t N, int32_t E, const 
     ga::Plan p;
     if (const int rc = ga::shape_rc(__func__, N, E, p)) return rc;
     if (S <= 0) return CM_OK;
-    static unsigned long long once = 0;
-    if (dev_first(once))
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ga::attn_bwd_any_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)ga::LDS_LIMIT));
     const int vec = E % 4 == 0 && ga::aligned16({ q, e });
-    hipLaunchKernelGGL(ga::attn_bwd_any_kernel, dim3(ga::grid_of(S, p.EPB, ga::GRID_CAP)), dim3(ga::TPB), p.attn_bwd, (hipStream_t)stream, S,
-                       N, E, p.EPB, vec, q, e, m, d_m, d_e_add0, d_e_add1, d_q, d_e);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&ga::attn_bwd_any_kernel>(dim3(ga::grid_of(S, p.EPB, ga::GRID_CAP)), dim3(ga::TPB), p.attn_bwd, stream, S, N, E, p.EPB, vec, q, e, m,
+                                                d_m, d_e_add0, d_e_add1, d_q, d_e);
 }

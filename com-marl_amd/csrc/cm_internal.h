@@ -29,6 +29,16 @@ inline bool dev_first(unsigned long long &done) {
     done |= bit;
     return true;
 }
+// A launch with dynamic LDS: the 160 KB attribute on KERN once per device, the launch, its error.  (CM_HIP is defined above;
+// the static is per kernel and argument types - a kernel launched from two sites sets its attribute at most twice.)
+template <auto KERN, class... A>
+static inline int launch_lds(dim3 grid, dim3 block, size_t lds_bytes, void *stream, const A &...args) {
+    static unsigned long long done = 0;
+    if (dev_first(done)) CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(KERN, grid, block, lds_bytes, (hipStream_t)stream, args...);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
 inline int cu_count() {
     static int cached[64] = { 0 };
     int dev = 0;

@@ -130,16 +130,8 @@ static size_t lds_tiles(Args &a) {
 static int launch(Args a, void *stream) {
     const size_t lds = lds_tiles(a);
     if (!lds) return set_error(CM_ERR_ARG, "mlp forward: layer too wide for the 160 KB LDS tile");
-    static unsigned long long attr_set = 0;
-    if (cm::dev_first(attr_set)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-    }
     if (a.rows == 0) return CM_OK;
-    const int blocks = (a.rows + ROWS - 1) / ROWS;
-    hipLaunchKernelGGL(mlp_kernel, dim3(blocks), dim3(TPB), lds, (hipStream_t)stream, a);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&mlp_kernel>(dim3((a.rows + ROWS - 1) / ROWS), dim3(TPB), lds, stream, a);
 }
 
 static int fill(Args &a, const cm_mlp_weights *w, int32_t rows, const float *x) {
@@ -166,14 +158,7 @@ static int fill(Args &a, const cm_mlp_weights *w, int32_t rows, const float *x) 
 static int launch_set(Args a, const SetWg *wgs, const SetMember *members, int n_wg, void *stream) {
     const size_t lds = lds_tiles(a);
     if (!lds) return set_error(CM_ERR_ARG, "mlp forward: layer too wide for the 160 KB LDS tile");
-    static unsigned long long attr_set = 0;
-    if (cm::dev_first(attr_set)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-    }
-    hipLaunchKernelGGL(mlp_set_kernel, dim3(n_wg), dim3(TPB), lds, (hipStream_t)stream, a, wgs, members);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&mlp_set_kernel>(dim3(n_wg), dim3(TPB), lds, stream, a, wgs, members);
 }
 
 // what the policy entry points ask of the sampler's shape

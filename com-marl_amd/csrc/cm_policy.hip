@@ -19,6 +19,7 @@
 
 #include "cm_internal.h"
 #include "cm_rng.h"
+#include "cm_policy_host.h"
 
 namespace cm {
 
@@ -256,34 +257,26 @@ static int launch_fwd(FwdArgs a, const TrunkW &tw, const PolHead &ph, const Crit
     a.EPB = pick_epb(a.N);
     const size_t lds = fwd_lds_floats(a.EPB * a.N, a.EPB, a.N) * sizeof(float);
     if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "policy forward: n_agents too large for the 160 KB LDS tile");
-    static unsigned long long attr_set[2] = { 0, 0 };
-    if (cm::dev_first(attr_set[HEAD])) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_kernel<HEAD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    const int blocks = (a.S + a.EPB - 1) / a.EPB;
-    hipLaunchKernelGGL(fwd_kernel<HEAD>, dim3(blocks), dim3(TPB), lds, (hipStream_t)stream, a, tw, ph, chd);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&fwd_kernel<HEAD>>(dim3((a.S + a.EPB - 1) / a.EPB), dim3(TPB), lds, stream, a, tw, ph, chd);
+}
+
+// the switch of cm_policy_host.h (truth table there): parsed on first use, once per process
+PolicyKernel policy_kernel() {
+    static const PolicyKernel v = [] {
+        const char *e = getenv("COMMARL_POLICY_KERNEL");
+        switch (e ? e[0] : 0) {
+        case 'h': return PolicyKernel::h;
+        case 'f': return PolicyKernel::f32;
+        case 'v': return PolicyKernel::valu;
+        default: return PolicyKernel::wave;
+        }
+    }();
+    return v;
 }
 
 }  // namespace cm
 
 using namespace cm;
-
-namespace cm {
-int policy_forward_mfma(const cm_policy_weights *w, int32_t S, const float *obs, const float *avail, const float *adj,
-                        const float *chan, uint64_t seed, int32_t env_id_offset, uint32_t policy_step,
-                        const uint32_t *step_base, int32_t greedy, int32_t *actions, float *probs, float *attn,
-                        void *stream);
-int critic_forward_mfma(const cm_critic_weights *w, int32_t S, const float *obs, const float *adj, const float *chan,
-                        float *values, void *stream);
-}
-
-// COMMARL_POLICY_KERNEL=valu forces the generic VALU kernel (A/B timing, obs dims without an MFMA build)
-static bool use_mfma() {
-    static const bool v = [] { const char *e = getenv("COMMARL_POLICY_KERNEL"); return !(e && e[0] == 'v'); }();
-    return v;
-}
 
 extern "C" int cm_policy_forward(const cm_policy_weights *w, int32_t n_samples, const float *obs, const float *avail,
                                  const float *dist_adj, const float *channels, uint64_t seed, int32_t env_id_offset,
@@ -295,17 +288,12 @@ extern "C" int cm_policy_forward(const cm_policy_weights *w, int32_t n_samples, 
         return set_error(CM_ERR_ARG, "cm_policy_forward: only the reference layer sizes (128 | 64 | 128,64,32) are built");
     if (w->n_act < 1 || w->n_act > MAX_ACT || w->d < 1 || w->d > 2 * SE - 4 || w->n_agents < 1 || w->n_hops < 0)
         return set_error(CM_ERR_ARG, "cm_policy_forward: bad dims");
-    if (use_mfma()) {
-        const int rc = policy_forward_mfma(w, n_samples, obs, avail, dist_adj, channels, seed, env_id_offset, policy_step,
-                                           policy_step_base, greedy, actions, probs, attn, stream);
+    const FwdSampler sm{ avail, seed, env_id_offset, policy_step, policy_step_base, greedy, actions, probs };
+    if (policy_mfma_enabled()) {                             // 1: no matrix-core instantiation or no operand pack - the VALU kernel runs
+        const int rc = policy_forward_mfma(w, fwd_args(fwd_shape(w, n_samples), obs, dist_adj, channels, attn, sm), stream);
         if (rc <= 0) return rc;
     }
-    FwdArgs a{};
-    a.S = n_samples; a.N = w->n_agents; a.d = w->d; a.L = w->n_hops;
-    a.obs = obs; a.avail = avail; a.adj = dist_adj; a.chan = channels;
-    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;
-    a.env_id_offset = env_id_offset; a.greedy = greedy; a.no_residual = w->no_residual;
-    a.actions = actions; a.probs = probs; a.attn = attn;
+    const FwdArgs a = fwd_args<FwdArgs>(fwd_shape(w, n_samples), obs, dist_adj, channels, attn, sm);
     TrunkW tw{ w->enc_w1t, w->enc_b1, w->enc_w2t, w->enc_b2, w->attn_wt, w->gcn_w, w->gcn_b };
     PolHead ph{ w->hd_w1t, w->hd_b1, w->hd_w2t, w->hd_b2, w->hd_w3t, w->hd_b3, w->hd_w4t, w->hd_b4, w->n_act };
     return launch_fwd<0>(a, tw, ph, CritHead{}, stream);
@@ -318,13 +306,11 @@ extern "C" int cm_critic_forward(const cm_critic_weights *w, int32_t n_samples, 
     if (w->enc_hidden != EH || w->emb != EMB || w->dec_hidden != DH)
         return set_error(CM_ERR_ARG, "cm_critic_forward: only the reference layer sizes (128 | 64 | 64) are built");
     if (w->d < 1 || w->d > 2 * SE - 4 || w->n_agents < 1 || w->n_hops < 0) return set_error(CM_ERR_ARG, "cm_critic_forward: bad dims");
-    if (use_mfma()) {
-        const int rc = critic_forward_mfma(w, n_samples, obs, dist_adj, channels, values, stream);
+    if (policy_mfma_enabled()) {
+        const int rc = critic_forward_mfma(w, fwd_args(fwd_shape(w, n_samples), obs, dist_adj, channels, nullptr, values), stream);
         if (rc <= 0) return rc;
     }
-    FwdArgs a{};
-    a.S = n_samples; a.N = w->n_agents; a.d = w->d; a.L = w->n_hops;
-    a.obs = obs; a.adj = dist_adj; a.chan = channels; a.values = values; a.no_residual = w->no_residual;
+    const FwdArgs a = fwd_args<FwdArgs>(fwd_shape(w, n_samples), obs, dist_adj, channels, nullptr, values);
     TrunkW tw{ w->enc_w1t, w->enc_b1, w->enc_w2t, w->enc_b2, w->attn_wt, w->gcn_w, w->gcn_b };
     CritHead chd{ w->dec_w1t, w->dec_b1, w->dec_w2t, w->dec_b2 };
     return launch_fwd<1>(a, tw, PolHead{}, chd, stream);

@@ -165,13 +165,6 @@ extern "C" int cm_policy_forward_any_multi(const cm_net_weights *shape, const vo
     a.env_id_offset = env_id_offset; a.greedy = greedy;
     a.actions = actions; a.probs = probs; a.attn = attn;
 
-    static unsigned long long attr_set = 0;
-    if (dev_first(attr_set))
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pgm::fwd_any_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)pg::LDS_LIMIT));
     const pgm::SetWg *wgs = reinterpret_cast<const pgm::SetWg *>(table_dev);
-    hipLaunchKernelGGL(pgm::fwd_any_set_kernel, dim3(n_wg), dim3(pg::TPB), lds_bytes, (hipStream_t)stream, a, wgs,
-                       reinterpret_cast<const pgm::SetMember *>(wgs + n_wg));
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&pgm::fwd_any_set_kernel>(dim3(n_wg), dim3(pg::TPB), lds_bytes, stream, a, wgs, reinterpret_cast<const pgm::SetMember *>(wgs + n_wg));
 }

@@ -9,7 +9,7 @@
 
 #include "cm_internal.h"
 #include "cm_rng.h"
-#include "cm_policy_h_dev.h"
+#include "cm_policy_host.h"
 
 namespace cm {
 namespace mh {
@@ -36,60 +36,23 @@ __global__ __launch_bounds__(256, 3) void fwd_h_occ3_kernel(FwdArgs a, TrunkH tw
     fwd_body_h<HEAD, KH, -1, 4, true, true>(a, tw, ph, chd, lds_h, blockIdx.x, nullptr);
 }
 
-template <int HEAD, int KH, int MAXMK, int NW = 4>
+template <int HEAD, int KH, int MAXMK, int NW>
 static int launch_h(FwdArgs a, const TrunkH &tw, const PolHeadH &ph, const CritHeadH &chd, void *stream) {
     a.EPB = mf::pick_epb(a.N);
     const int rows_cap = (a.EPB * a.N + 15) & ~15;
     const size_t lds = lds_map(rows_cap, a.EPB, a.N, MAXMK < 0 ? -1 : (MAXMK > 0 ? 1 : 0)).total;
     if (lds > 160 * 1024) return 1;                      // caller falls back (and reports the size limit there)
-    static unsigned long long attr_set = 0;
-    if (cm::dev_first(attr_set)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_h_kernel<HEAD, KH, MAXMK, NW>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
     const int blocks = (a.S + a.EPB - 1) / a.EPB;
     if constexpr (MAXMK < 0 && NW == 4) {
-        if (blocks >= 4096) {
-            static unsigned long long attr3 = 0;
-            if (cm::dev_first(attr3)) {
-                CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_h_occ3_kernel<HEAD, KH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            hipLaunchKernelGGL((fwd_h_occ3_kernel<HEAD, KH>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, a, tw, ph, chd);
-            CM_HIP(hipGetLastError());
-            return CM_OK;
-        }
-        if (a.EPB == 8 && a.S % 8 == 0) {
-            static unsigned long long attrf = 0;
-            if (cm::dev_first(attrf)) {
-                CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_h_full_kernel<HEAD, KH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-            hipLaunchKernelGGL((fwd_h_full_kernel<HEAD, KH>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, a, tw, ph, chd);
-            CM_HIP(hipGetLastError());
-            return CM_OK;
-        }
+        if (blocks >= 4096) return launch_lds<&fwd_h_occ3_kernel<HEAD, KH>>(dim3(blocks), dim3(256), lds, stream, a, tw, ph, chd);
+        if (a.EPB == 8 && a.S % 8 == 0) return launch_lds<&fwd_h_full_kernel<HEAD, KH>>(dim3(blocks), dim3(256), lds, stream, a, tw, ph, chd);
     }
-    hipLaunchKernelGGL((fwd_h_kernel<HEAD, KH, MAXMK, NW>), dim3(blocks), dim3(64 * NW), lds, (hipStream_t)stream, a, tw, ph, chd);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&fwd_h_kernel<HEAD, KH, MAXMK, NW>>(dim3(blocks), dim3(64 * NW), lds, stream, a, tw, ph, chd);
 }
 
 template <int HEAD>
 static int dispatch_h(const FwdArgs &a, const TrunkH &tw, const PolHeadH &ph, const CritHeadH &chd, void *stream) {
-    const int kh = kh_of(a.d);
-    if (!kh || a.N > 128) return 1;
-    const int mk = a.N < 16 ? 0 : (a.N <= 80 ? 25 : 64);   // as mf::dispatch
-    const bool quad = a.N == 4 && mf::pick_epb(4) * 4 <= 32;
-    const bool w8 = a.N >= 32;                               // 8-wave workgroups (every team with mk == 64)
-#define CM_FWH(K) (quad ? launch_h<HEAD, K, -1>(a, tw, ph, chd, stream) : mk == 0 ? launch_h<HEAD, K, 0>(a, tw, ph, chd, stream) \
-                   : mk == 25 ? (w8 ? launch_h<HEAD, K, 15, 8>(a, tw, ph, chd, stream) : launch_h<HEAD, K, 25>(a, tw, ph, chd, stream)) \
-                              : launch_h<HEAD, K, 32, 8>(a, tw, ph, chd, stream))
-    switch (kh) {
-    case 32: return CM_FWH(32);
-    case 64: return CM_FWH(64);
-    case 96: return CM_FWH(96);
-    default: return 1;
-    }
-#undef CM_FWH
+    return for_fwd_variant<96>(kh_of(a.d), a.N, [&](auto K, auto MK, auto NW) { return launch_h<HEAD, K.value, MK.value, NW.value>(a, tw, ph, chd, stream); });
 }
 
 // ---- operand pack: Wt [K][OUT] f32 (the ABI's transposed weights) -> A fragments of the transposed layer ----------
@@ -198,23 +161,21 @@ static int pack_trunk_h(PackJobsH &t, int d, int L, const float *w1t, const floa
 
 }  // namespace mh
 
-// COMMARL_POLICY_KERNEL=f32: the round-1 all-f32 MFMA kernel; anything else (default): the f16-split kernel
-bool policy_h_enabled() {
-    static const bool v = [] { const char *e = getenv("COMMARL_POLICY_KERNEL"); return !(e && e[0] == 'f'); }();
-    return v;
-}
-
-int policy_pack_w(const cm_policy_weights *w, void *dst, void *stream, int *bad);   // cm_policy_w.hip
-
 size_t policy_pack_h_bytes(int d, int L, bool policy) {
     const int kh = mh::kh_of(d);
     return kh ? mh::pack_layout_h(kh, L, policy).total * sizeof(uint4) : 0;
 }
 
+// dst = the f16-split section of the caller's pack buffer; the wave-owned one (teams of 4: another k order, cm_policy_w.hip) lies behind it
+template <class W>
+static char *wave_section(const W *w, void *dst) {
+    return reinterpret_cast<char *>(dst) + pack_sections(w, nullptr).h_bytes;
+}
+
 int policy_pack_h(const cm_policy_weights *w, void *dst, int sections, void *stream) {
     const int kh = mh::kh_of(w->d);
     if (!kh) return CM_OK;                               // no f16 instantiation for this obs dim: nothing to pack
-    const mh::PackLayoutH lo = mh::pack_layout_h(kh, w->n_hops, true);
+    const mh::PackLayoutH lo = layout_h(w);
     uint4 *pack = reinterpret_cast<uint4 *>(dst);
     int *bad = (sections & CM_PACK_CHECK) ? mh::range_check_begin(stream) : nullptr;
     if (sections & CM_PACK_F16) {
@@ -226,18 +187,15 @@ int policy_pack_h(const cm_policy_weights *w, void *dst, int sections, void *str
         if (int rc = mh::pack_one_h(t, w->hd_w4t, mf::H3, w->n_act, mf::H3, 16, pack + lo.h4, stream, bad)) return rc;
         if (int rc = mh::pack_flush_h(t, stream, bad)) return rc;
     }
-    // teams of 4: the wave-owned kernel's fragments (another k order, cm_policy_w.hip), behind this section
     if (sections & CM_PACK_WAVE)
-        if (int rc = policy_pack_w(w, reinterpret_cast<char *>(dst) + lo.total * sizeof(uint4), stream, bad)) return rc;
+        if (int rc = policy_pack_w(w, wave_section(w, dst), stream, bad)) return rc;
     return mh::range_check_end(bad, stream, "cm_policy_pack");
 }
-
-int critic_pack_w(const cm_critic_weights *w, void *dst, void *stream, int *bad);   // cm_policy_w.hip
 
 int critic_pack_h(const cm_critic_weights *w, void *dst, int sections, void *stream) {
     const int kh = mh::kh_of(w->d);
     if (!kh || !(sections & (CM_PACK_F16 | CM_PACK_WAVE))) return CM_OK;
-    const mh::PackLayoutH lo = mh::pack_layout_h(kh, w->n_hops, false);
+    const mh::PackLayoutH lo = layout_h(w);
     uint4 *pack = reinterpret_cast<uint4 *>(dst);
     int *bad = (sections & CM_PACK_CHECK) ? mh::range_check_begin(stream) : nullptr;
     if (sections & CM_PACK_F16) {
@@ -246,32 +204,26 @@ int critic_pack_h(const cm_critic_weights *w, void *dst, int sections, void *str
         if (int rc = mh::pack_one_h(t, w->dec_w1t, mf::EMB, mf::DH, mf::EMB, mf::DH, pack + lo.x1, stream, bad)) return rc;
         if (int rc = mh::pack_flush_h(t, stream, bad)) return rc;
     }
-    // teams of 4: the wave-owned training forward's fragments (cm_critic_forward_saved_wave), behind this section
+    // the wave-owned training forward's fragments (cm_critic_forward_saved_wave)
     if (sections & CM_PACK_WAVE)
-        if (int rc = critic_pack_w(w, reinterpret_cast<char *>(dst) + lo.total * sizeof(uint4), stream, bad)) return rc;
+        if (int rc = critic_pack_w(w, wave_section(w, dst), stream, bad)) return rc;
     return mh::range_check_end(bad, stream, "cm_critic_pack");
 }
 
 // h_pack = the f16 operand pack (behind the f32 one in the caller's pack buffer).  Returns 1 when this shape has no
 // f16 instantiation (the caller then runs the f32 kernel).
 int policy_forward_h(const cm_policy_weights *w, const void *h_pack, mf::FwdArgs a, void *stream) {
-    const int kh = mh::kh_of(w->d);
-    if (!kh || !h_pack) return 1;
-    const mh::PackLayoutH lo = mh::pack_layout_h(kh, w->n_hops, true);
+    if (!mh::kh_of(w->d) || !h_pack) return 1;
+    const mh::PackLayoutH lo = layout_h(w);
     const uint4 *P = reinterpret_cast<const uint4 *>(h_pack);
-    const mh::TrunkH tw{ P + lo.enc1, w->enc_b1, P + lo.enc2, w->enc_b2, P + lo.attn, P + lo.gcn, w->gcn_b };
-    const mh::PolHeadH ph{ P + lo.x1, w->hd_b1, P + lo.h2, w->hd_b2, P + lo.h3, w->hd_b3, P + lo.h4, w->hd_b4, w->n_act };
-    return mh::dispatch_h<0>(a, tw, ph, mh::CritHeadH{}, stream);
+    return mh::dispatch_h<0>(a, trunk_h(P, lo, w), pol_head_h(P, lo, w), mh::CritHeadH{}, stream);
 }
 
 int critic_forward_h(const cm_critic_weights *w, const void *h_pack, mf::FwdArgs a, void *stream) {
-    const int kh = mh::kh_of(w->d);
-    if (!kh || !h_pack) return 1;
-    const mh::PackLayoutH lo = mh::pack_layout_h(kh, w->n_hops, false);
+    if (!mh::kh_of(w->d) || !h_pack) return 1;
+    const mh::PackLayoutH lo = layout_h(w);
     const uint4 *P = reinterpret_cast<const uint4 *>(h_pack);
-    const mh::TrunkH tw{ P + lo.enc1, w->enc_b1, P + lo.enc2, w->enc_b2, P + lo.attn, P + lo.gcn, w->gcn_b };
-    const mh::CritHeadH chd{ P + lo.x1, w->dec_b1, w->dec_w2t, w->dec_b2 };
-    return mh::dispatch_h<1>(a, tw, mh::PolHeadH{}, chd, stream);
+    return mh::dispatch_h<1>(a, trunk_h(P, lo, w), mh::PolHeadH{}, crit_head_h(P, lo, w), stream);
 }
 
 }  // namespace cm

@@ -4,16 +4,11 @@
 // from a device table, points the argument block at the group and the weight pointers at the member's operand pack, and from there
 // runs fwd_h_kernel's body unchanged - every env's arithmetic and Philox draws are those of a cm_policy_forward launch on the
 // group's rows with env_id_offset + the group's first env.  Teams of 4 keep cm_rollout_chunk_multi (cm_rollout_wm.hip).
-#include <stdlib.h>
-
 #include "cm_internal.h"
 #include "cm_rng.h"
-#include "cm_policy_h_dev.h"
+#include "cm_policy_host.h"
 
 namespace cm {
-
-bool policy_h_enabled();                                 // cm_policy_h.hip
-
 namespace mh {
 
 // the table's records as the kernel reads them (the ABI's cm_forward_set_wg / cm_forward_set_member, include/commarl.h)
@@ -55,35 +50,12 @@ __global__ __launch_bounds__(64 * NW) void fwd_h_set_kernel(FwdArgs a, const Set
     fwd_body_h<0, KH, MAXMK, NW, false>(a, tw, ph, CritHeadH{}, lds_h, blk, nullptr);
 }
 
-template <int KH, int MAXMK, int NW = 4>
-static int launch_set(const FwdArgs &a, const SetWg *wgs, const SetMember *members, int n_wg, const SetOffs &o, int n_act, size_t lds,
-                      void *stream) {
-    static unsigned long long attr_set = 0;
-    if (cm::dev_first(attr_set)) {
-        CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fwd_h_set_kernel<KH, MAXMK, NW>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL((fwd_h_set_kernel<KH, MAXMK, NW>), dim3(n_wg), dim3(64 * NW), lds, (hipStream_t)stream, a, wgs, members, o, n_act);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
 // the families dispatch_h (cm_policy_h.hip) selects for teams that are not 4, policy head
 static int dispatch_set(const FwdArgs &a, const SetWg *wgs, const SetMember *members, int n_wg, const SetOffs &o, int n_act, size_t lds,
                         void *stream) {
-    const int mk = a.N < 16 ? 0 : (a.N <= 80 ? 25 : 64);
-    const bool w8 = a.N >= 32;
-#define CM_FWS(K) (mk == 0 ? launch_set<K, 0>(a, wgs, members, n_wg, o, n_act, lds, stream)                                              \
-                   : mk == 25 ? (w8 ? launch_set<K, 15, 8>(a, wgs, members, n_wg, o, n_act, lds, stream)                                 \
-                                    : launch_set<K, 25>(a, wgs, members, n_wg, o, n_act, lds, stream))                                   \
-                              : launch_set<K, 32, 8>(a, wgs, members, n_wg, o, n_act, lds, stream))
-    switch (kh_of(a.d)) {
-    case 32: return CM_FWS(32);
-    case 64: return CM_FWS(64);
-    case 96: return CM_FWS(96);
-    default: return 1;
-    }
-#undef CM_FWS
+    return for_fwd_variant<96, false>(kh_of(a.d), a.N, [&](auto K, auto MK, auto NW) {
+        return launch_lds<&fwd_h_set_kernel<K.value, MK.value, NW.value>>(dim3(n_wg), dim3(64 * NW.value), lds, stream, a, wgs, members, o, n_act);
+    });
 }
 
 }  // namespace mh
@@ -92,8 +64,7 @@ static int dispatch_set(const FwdArgs &a, const SetWg *wgs, const SetMember *mem
 // the ones a host runs layer by layer (nets.py: one env's planes and scores exceed the LDS tile from 84 agents on), so a set launch
 // would have no member-by-member twin to equal there.  0 = no set kernel; else the LDS bytes of a workgroup.
 static size_t forward_set_lds(const cm_policy_weights *w) {
-    static const bool valu = [] { const char *e = getenv("COMMARL_POLICY_KERNEL"); return e && e[0] == 'v'; }();
-    if (valu || !policy_h_enabled() || !policy_shape_ok(w) || !mh::kh_of(w->d)) return 0;
+    if (!policy_set_enabled() || !policy_shape_ok(w) || !mh::kh_of(w->d)) return 0;
     const int N = w->n_agents;
     if (N == 4 || N > 80) return 0;
     const int epb = mf::pick_epb(N), rows_cap = (epb * N + 15) & ~15;
@@ -134,13 +105,12 @@ extern "C" int64_t cm_policy_forward_multi_plan(const cm_policy_weights *members
     if (image_bytes < need) return set_error(CM_ERR_ARG, std::string(who) + ": image buffer too small");
     cm_forward_set_wg *wg = reinterpret_cast<cm_forward_set_wg *>(image);
     cm_forward_set_member *mem = reinterpret_cast<cm_forward_set_member *>(wg + n_wg);
-    const size_t f32_floats = mf::pack_layout(mf::kpad_of(members[0].d), members[0].n_hops, true).total;   // the f16 section sits behind the f32 one
     int32_t first = 0;
     for (int k = 0; k < n_policies; ++k) {
         const cm_policy_weights &w = members[k];
         const int blocks = (group_sizes[k] + epb - 1) / epb;
         for (int b = 0; b < blocks; ++b) *wg++ = cm_forward_set_wg{ k, b };
-        mem[k] = cm_forward_set_member{ first, group_sizes[k], w.mfma_pack + f32_floats, w.enc_b1, w.enc_b2, w.gcn_b, w.hd_b1, w.hd_b2, w.hd_b3, w.hd_b4 };
+        mem[k] = cm_forward_set_member{ first, group_sizes[k], pack_sections(&w).h(), w.enc_b1, w.enc_b2, w.gcn_b, w.hd_b1, w.hd_b2, w.hd_b3, w.hd_b4 };
         first += group_sizes[k];
     }
     return (int64_t)need;
@@ -158,13 +128,10 @@ extern "C" int cm_policy_forward_multi(const cm_policy_weights *shape, const voi
     const int epb = mf::pick_epb(shape->n_agents);
     if (!table_dev || n_wg < (n_envs + epb - 1) / epb || n_wg > n_envs)
         return set_error(CM_ERR_ARG, "cm_policy_forward_multi: null table, or n_wg is not the planner's for n_envs");
-    mf::FwdArgs a{};
-    a.S = n_envs; a.N = shape->n_agents; a.d = shape->d; a.L = shape->n_hops; a.EPB = epb;
-    a.obs = obs; a.avail = avail; a.adj = dist_adj; a.chan = channels;
-    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;
-    a.env_id_offset = env_id_offset; a.greedy = greedy; a.no_residual = shape->no_residual;
-    a.actions = actions; a.probs = probs; a.attn = attn;
-    const mh::PackLayoutH lo = mh::pack_layout_h(mh::kh_of(shape->d), shape->n_hops, true);
+    mf::FwdArgs a = fwd_args(fwd_shape(shape, n_envs), obs, dist_adj, channels, attn,
+                             FwdSampler{ avail, seed, env_id_offset, policy_step, policy_step_base, greedy, actions, probs });
+    a.EPB = epb;
+    const mh::PackLayoutH lo = layout_h(shape);
     const mh::SetOffs o{ (unsigned)lo.enc2, (unsigned)lo.attn, (unsigned)lo.gcn, (unsigned)lo.x1, (unsigned)lo.h2, (unsigned)lo.h3, (unsigned)lo.h4 };
     const mh::SetWg *wgs = reinterpret_cast<const mh::SetWg *>(table_dev);
     return mh::dispatch_set(a, wgs, reinterpret_cast<const mh::SetMember *>(wgs + n_wg), n_wg, o, shape->n_act, lds, stream);

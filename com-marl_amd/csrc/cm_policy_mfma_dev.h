@@ -808,7 +808,4 @@ inline PackLayout pack_layout(int kpad, int L, bool policy) {
 }
 
 }  // namespace mf
-
-bool policy_shape_ok(const cm_policy_weights *w);   // cm_policy_mfma.hip
-
 }  // namespace cm

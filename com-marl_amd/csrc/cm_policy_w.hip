@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "cm_internal.h"
-#include "cm_policy_w_dev.h"
+#include "cm_policy_host.h"
 
 namespace cm {
 namespace mw {
@@ -106,12 +106,6 @@ static int pack_one_w(const float *Wt, int K, int OUT, int kp, int out_pad, bool
 
 }  // namespace mw
 
-// COMMARL_POLICY_KERNEL: unset / "w" = wave-owned kernel where the shape allows; "h" / "f32" / "valu" = the older kernels
-bool policy_w_enabled() {
-    static const bool v = [] { const char *e = getenv("COMMARL_POLICY_KERNEL"); return !(e && (e[0] == 'h' || e[0] == 'f' || e[0] == 'v')); }();
-    return v;
-}
-
 size_t policy_pack_w_bytes(const cm_policy_weights *w) {
     return mw::shape_ok_w(w->n_agents, w->d, w->n_hops, w->n_act) ? (size_t)mw::pack_w(w->n_hops).total * sizeof(uint4) : 0;
 }
@@ -139,23 +133,19 @@ int policy_pack_w(const cm_policy_weights *w, void *dst, void *stream, int *bad)
     return CM_OK;
 }
 
+// The training forward's launch, HEADK 0 = policy, 1 = critic: a persistent workgroup per CU walks the 64-row blocks
+template <int HEADK>
+static int launch_train_w(int L, const mf::FwdArgs &a, const mw::WeightsW &ww, void *stream) {
+    const size_t lds = mw::lds_policy_bytes(L);
+    const int n_blk = (a.S + mw::WG_ENVS - 1) / mw::WG_ENVS, blocks = std::min(n_blk, cm::cu_count());
+    return L == 1 ? launch_lds<&mw::train_fwd_w_kernel<1, HEADK>>(dim3(blocks), dim3(256), lds, stream, a, ww, n_blk)
+                  : launch_lds<&mw::train_fwd_w_kernel<2, HEADK>>(dim3(blocks), dim3(256), lds, stream, a, ww, n_blk);
+}
+
 // cm_policy_forward_saved_wave: 1 = no wave-owned instantiation for the shape (nothing launched)
 int policy_forward_w_train(const cm_policy_weights *w, const void *w_pack, mf::FwdArgs a, void *stream) {
     if (!policy_w_enabled() || !mw::shape_ok_w(w->n_agents, w->d, w->n_hops, w->n_act) || a.avail) return 1;
-    const mw::WeightsW ww{ reinterpret_cast<const uint4 *>(w_pack), w->n_act };
-    const size_t lds = mw::lds_policy_bytes(w->n_hops);
-    const int n_blk = (a.S + mw::WG_ENVS - 1) / mw::WG_ENVS, blocks = std::min(n_blk, cm::cu_count());
-#define CM_TW(LH, HK)                                                                                                          \
-    do {                                                                                                                       \
-        static unsigned long long done = 0;                                                                                    \
-        if (cm::dev_first(done))                                                                                               \
-            CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mw::train_fwd_w_kernel<LH, HK>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       160 * 1024));                                                                           \
-        hipLaunchKernelGGL((mw::train_fwd_w_kernel<LH, HK>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, a, ww, n_blk); \
-    } while (0)
-    if (w->n_hops == 1) CM_TW(1, 0); else CM_TW(2, 0);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_train_w<0>(w->n_hops, a, weights_w(w, w_pack), stream);
 }
 
 // ---- the critic on the same kernel (training forward only): its fragments in the policy's image layout ----
@@ -188,17 +178,7 @@ int critic_pack_w(const cm_critic_weights *w, void *dst, void *stream, int *bad)
 // cm_critic_forward_saved_wave: 1 = no wave-owned instantiation for the shape (nothing launched)
 int critic_forward_w_train(const cm_critic_weights *w, const void *w_pack, mf::FwdArgs a, void *stream) {
     if (!critic_w_ok(w)) return 1;
-    const mw::WeightsW ww{ reinterpret_cast<const uint4 *>(w_pack), 0 };
-    const size_t lds = mw::lds_policy_bytes(w->n_hops);
-    const int n_blk = (a.S + mw::WG_ENVS - 1) / mw::WG_ENVS, blocks = std::min(n_blk, cm::cu_count());
-    if (w->n_hops == 1) CM_TW(1, 1); else CM_TW(2, 1);
-#undef CM_TW
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-mw::WeightsW weights_w(const cm_policy_weights *w, const void *w_pack) {
-    return mw::WeightsW{ reinterpret_cast<const uint4 *>(w_pack), w->n_act };
+    return launch_train_w<1>(w->n_hops, a, mw::WeightsW{ reinterpret_cast<const uint4 *>(w_pack), 0 }, stream);
 }
 
 // Returns 1 when the shape has no wave-owned instantiation (the caller runs the workgroup-tiled kernel).
@@ -207,42 +187,34 @@ int policy_forward_w(const cm_policy_weights *w, const void *w_pack, mf::FwdArgs
     const mw::WeightsW ww = weights_w(w, w_pack);
     const size_t lds = mw::lds_policy_bytes(w->n_hops);
     const int blocks = (a.S + mw::WG_ENVS - 1) / mw::WG_ENVS;
-#define CM_FW(LH)                                                                                                              \
-    do {                                                                                                                       \
-        static unsigned long long done = 0;                                                                                    \
-        if (cm::dev_first(done))                                                                                               \
-            CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mw::fwd_w_kernel<LH>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       160 * 1024));                                                                           \
-        hipLaunchKernelGGL((mw::fwd_w_kernel<LH>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, a, ww);                  \
-    } while (0)
+    auto launch = [&] {
+        return w->n_hops == 1 ? launch_lds<&mw::fwd_w_kernel<1>>(dim3(blocks), dim3(256), lds, stream, a, ww)
+                              : launch_lds<&mw::fwd_w_kernel<2>>(dim3(blocks), dim3(256), lds, stream, a, ww);
+    };
     static const bool want_probe = getenv("COMMARL_FWD_PROBE") != nullptr;
+    if (!want_probe) return launch();
+    // diagnostic: per-phase shader clocks of thread 0 of every workgroup
     unsigned long long *dbuf = nullptr;
-    if (want_probe) {                                    // diagnostic: per-phase shader clocks of thread 0 of every workgroup
-        CM_HIP(hipMalloc(&dbuf, (size_t)blocks * mf::NPROBE * sizeof(unsigned long long)));
-        CM_HIP(hipMemset(dbuf, 0, (size_t)blocks * mf::NPROBE * sizeof(unsigned long long)));
-        a.probe = dbuf;
-        if (w->n_hops == 1) CM_FW(1); else CM_FW(2);     // warm (instruction cache, L2)
+    CM_HIP(hipMalloc(&dbuf, (size_t)blocks * mf::NPROBE * sizeof(unsigned long long)));
+    CM_HIP(hipMemset(dbuf, 0, (size_t)blocks * mf::NPROBE * sizeof(unsigned long long)));
+    a.probe = dbuf;
+    if (int rc = launch()) return rc;                    // warm (instruction cache, L2)
+    if (int rc = launch()) return rc;
+    CM_HIP(hipDeviceSynchronize());
+    std::vector<unsigned long long> h((size_t)blocks * mf::NPROBE);
+    CM_HIP(hipMemcpy(h.data(), dbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    CM_HIP(hipFree(dbuf));
+    double sum[mf::NPROBE] = { 0 };
+    unsigned long long tmin = ~0ull, tmax = 0;
+    for (int b = 0; b < blocks; ++b) {
+        tmin = std::min(tmin, h[(size_t)b * mf::NPROBE]);
+        for (int i = 1; i <= 10; ++i) { sum[i] += (double)(h[(size_t)b * mf::NPROBE + i] - h[(size_t)b * mf::NPROBE]); tmax = std::max(tmax, h[(size_t)b * mf::NPROBE + i]); }
     }
-    if (w->n_hops == 1) CM_FW(1); else CM_FW(2);
-    if (want_probe) {
-        CM_HIP(hipDeviceSynchronize());
-        std::vector<unsigned long long> h((size_t)blocks * mf::NPROBE);
-        CM_HIP(hipMemcpy(h.data(), dbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        CM_HIP(hipFree(dbuf));
-        double sum[mf::NPROBE] = { 0 };
-        unsigned long long tmin = ~0ull, tmax = 0;
-        for (int b = 0; b < blocks; ++b) {
-            tmin = std::min(tmin, h[(size_t)b * mf::NPROBE]);
-            for (int i = 1; i <= 10; ++i) { sum[i] += (double)(h[(size_t)b * mf::NPROBE + i] - h[(size_t)b * mf::NPROBE]); tmax = std::max(tmax, h[(size_t)b * mf::NPROBE + i]); }
-        }
-        fprintf(stderr, "[fwd_w probe] blocks=%d span=%llu ticks; mean ticks since entry:", blocks, tmax - tmin);
-        for (int i = 1; i <= 10; ++i) fprintf(stderr, " p%d=%.0f", i, sum[i] / blocks);
-        fprintf(stderr, "  (block 0:");
-        for (int i = 1; i <= 10; ++i) fprintf(stderr, " %llu", h[i] - h[0]);
-        fprintf(stderr, ")\n");
-    }
-#undef CM_FW
-    CM_HIP(hipGetLastError());
+    fprintf(stderr, "[fwd_w probe] blocks=%d span=%llu ticks; mean ticks since entry:", blocks, tmax - tmin);
+    for (int i = 1; i <= 10; ++i) fprintf(stderr, " p%d=%.0f", i, sum[i] / blocks);
+    fprintf(stderr, "  (block 0:");
+    for (int i = 1; i <= 10; ++i) fprintf(stderr, " %llu", h[i] - h[0]);
+    fprintf(stderr, ")\n");
     return CM_OK;
 }
 

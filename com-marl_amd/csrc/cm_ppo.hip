@@ -1033,13 +1033,9 @@ extern "C" int cm_masked_agg_forward(int32_t S, int32_t N, int32_t E, const floa
     if (S <= 0) return CM_OK;
     const size_t lds = agg_lds_fwd(N, E);
     if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "cm_masked_agg_forward: n_agents too large");
-    static unsigned long long once = 0;
-    if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_fwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
     const int epb = agg_epb(N);
     const int blocks = (int)std::min<long>((S + epb - 1) / epb, 256 * 8);
-    hipLaunchKernelGGL(agg_fwd_kernel<64>, dim3(blocks), dim3(TPB), lds, (hipStream_t)stream, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, bias, out);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&agg_fwd_kernel<64>>(dim3(blocks), dim3(TPB), lds, stream, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, bias, out);
 }
 
 extern "C" size_t cm_masked_agg_backward_det_ws_bytes(int32_t S, int32_t N, int32_t E) {
@@ -1078,13 +1074,10 @@ static int masked_agg_backward(const char *fn, int32_t S, int32_t N, int32_t E, 
     } else {
         const size_t lds = agg_lds_bwd(N, E);
         if (lds > 160 * 1024) return set_error(CM_ERR_ARG, std::string(fn) + ": n_agents too large");
-        static unsigned long long once = 0;
-        if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_bwd_kernel<64, DET>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
         const int epb = agg_epb(N);
         grid = (int)std::min<long>((S + epb - 1) / epb, 256 * 4);
-        hipLaunchKernelGGL((agg_bwd_kernel<64, DET>), dim3(grid), dim3(TPB), lds, st, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, out,
-                           out_minus, d_out, d_attn, d_hw, gb);
-        CM_HIP(hipGetLastError());
+        if (int rc = launch_lds<&agg_bwd_kernel<64, DET>>(dim3(grid), dim3(TPB), lds, st, S, N, epb, attn, dist_adj, chan, (long)ch_stride, hw, out,
+                                                         out_minus, d_out, d_attn, d_hw, gb)) return rc;
     }
     if (!DET) return CM_OK;
     SlabSegs segs{};
@@ -1176,13 +1169,9 @@ extern "C" int cm_attention_forward(int32_t S, int32_t N, int32_t E, const float
     if (S <= 0) return CM_OK;
     const size_t lds = attn_lds(N, E);
     if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "cm_attention_forward: n_agents too large");
-    static unsigned long long once = 0;
-    if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_fwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
     const int epb = agg_epb(N);
     const int blocks = (int)std::min<long>((S + epb - 1) / epb, 256 * 8);
-    hipLaunchKernelGGL(attn_fwd_kernel<64>, dim3(blocks), dim3(TPB), lds, (hipStream_t)stream, S, N, epb, q, e, m);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&attn_fwd_kernel<64>>(dim3(blocks), dim3(TPB), lds, stream, S, N, epb, q, e, m);
 }
 
 extern "C" int cm_attention_backward(int32_t S, int32_t N, int32_t E, const float *q, const float *e, const float *m,
@@ -1201,13 +1190,9 @@ extern "C" int cm_attention_backward(int32_t S, int32_t N, int32_t E, const floa
     if (const int rc = attn_bwd_mfma(S, N, q, e, m, d_m, d_e_add0, d_e_add1, d_q, d_e, stream); rc != 1) return rc;
     const size_t lds = attn_lds(N, E);
     if (lds > 160 * 1024) return set_error(CM_ERR_ARG, "cm_attention_backward: n_agents too large");
-    static unsigned long long once = 0;
-    if (cm::dev_first(once)) { CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); }
     const int epb = agg_epb(N);
     const int blocks = (int)std::min<long>((S + epb - 1) / epb, 256 * 8);
-    hipLaunchKernelGGL(attn_bwd_kernel<64>, dim3(blocks), dim3(TPB), lds, (hipStream_t)stream, S, N, epb, q, e, m, d_m, d_e_add0, d_e_add1, d_q, d_e);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return launch_lds<&attn_bwd_kernel<64>>(dim3(blocks), dim3(TPB), lds, stream, S, N, epb, q, e, m, d_m, d_e_add0, d_e_add1, d_q, d_e);
 }
 
 extern "C" int cm_discount_returns(int32_t P, int32_t T, const double *rewards, const int32_t *lens, double gamma,

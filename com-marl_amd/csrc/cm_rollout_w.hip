@@ -81,9 +81,9 @@ int launch_rollout_w(mf::FwdArgs a, const cm_policy_weights *w, const void *w_pa
     RolloutWPlan pl;
     pl.n_act = w->n_act; pl.out = &out;
     if (plan_rollout_w(a, h, use_tape, chunk, pl)) return 1;
-    const mw::WeightsW ww{ reinterpret_cast<const uint4 *>(w_pack), w->n_act };
-    const int rc = pl.probes ? launch_rollout_w_variant<&rollout_w_probe_kernel>(pl, stream, a, ww, d, t, out, pl.c, pl.tl) : for_rollout_w_variant(d.L, use_tape, pl, [&](auto LH, auto PR, auto FU, auto TP, auto CA, auto SH) {
-        return launch_rollout_w_variant<&rollout_w_kernel<LH.value, PR.value, FU.value, TP.value, CA.value, SH.value>>(pl, stream, a, ww, d, t, out, pl.c, pl.tl);
+    const mw::WeightsW ww = weights_w(w, w_pack);
+    const int rc = pl.probes ? launch_lds<&rollout_w_probe_kernel>(dim3(pl.blocks), dim3(256), pl.lds, stream, a, ww, d, t, out, pl.c, pl.tl) : for_rollout_w_variant(d.L, use_tape, pl, [&](auto LH, auto PR, auto FU, auto TP, auto CA, auto SH) {
+        return launch_lds<&rollout_w_kernel<LH.value, PR.value, FU.value, TP.value, CA.value, SH.value>>(dim3(pl.blocks), dim3(256), pl.lds, stream, a, ww, d, t, out, pl.c, pl.tl);
     });
     if (rc != CM_OK) return rc;
     if (pl.map10 && !pl.probes) return CM_OK;                            // a SHAPE 1 build without the clocks: nothing to print

@@ -9,7 +9,7 @@
 
 #include "cm_env_dev.h"
 #include "cm_env_pp10_dev.h"
-#include "cm_policy_w_dev.h"
+#include "cm_policy_host.h"
 
 namespace cm {
 
@@ -42,11 +42,8 @@ struct PolicySetW {
 }  // namespace mw
 
 // ---- host: what the rollout entry points share (cm_fused.hip: cm_rollout_step / _chunk / _chunk_tail; cm_rollout_wm.hip:
-// cm_rollout_chunk_multi).  The helpers defined here are static: the library exports every external symbol, and these are not ABI ----
-bool policy_w_enabled();                                 // cm_policy_w.hip: wave-owned teams-of-4 kernel (default where the shape allows)
-size_t policy_pack_h_bytes(int d, int L, bool policy);   // cm_policy_h.hip: size of the f16 pack the wave-owned fragments sit behind
-bool shape_ok_rollout_w(int N, int d, int L, int n_act);   // cm_rollout_w.hip: teams of 4 on the wave-owned kernel, where enabled
-
+// cm_rollout_chunk_multi), besides cm_policy_host.h.  The helpers defined here are static: the library exports every external symbol,
+// and these are not ABI ----
 // handle, weights and buffers are there and of one shape; `who` (the entry point) opens the error text
 static inline int check_rollout_args(const char *who, const cm_env *h, const cm_policy_weights *w, const void *obs, const cm_step_out *out) {
     if (!h || !w || !obs || !out) return set_error(CM_ERR_ARG, std::string(who) + ": null argument");
@@ -60,25 +57,6 @@ static inline int check_chunk_args(const char *who, const cm_env *h, const cm_ch
     if (n_steps < min_steps) return set_error(CM_ERR_ARG, std::string(who) + (min_steps ? ": at least one step" : ": negative step count"));
     if (h && h->cfg.rng_mode == CM_RNG_TAPE) return set_error(CM_ERR_ARG, std::string(who) + ": tape mode steps one launch at a time");
     return CM_OK;
-}
-
-// the policy forward's arguments of a rollout launch: shape from the env handle, the rest as the entry point received it
-static inline mf::FwdArgs rollout_fwd_args(const cm_env *h, const cm_policy_weights *w, const float *obs, const float *avail, const float *dist_adj,
-                                           const float *channels, uint64_t seed, int32_t env_id_offset, uint32_t policy_step,
-                                           const uint32_t *policy_step_base, int32_t greedy, int32_t *actions, float *probs, float *attn) {
-    const EnvDev &d = h->dev;
-    mf::FwdArgs a{};
-    a.S = d.B; a.N = d.N; a.d = d.d; a.L = d.L;
-    a.obs = obs; a.avail = avail; a.adj = dist_adj; a.chan = channels;
-    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.policy_step = policy_step; a.step_base = policy_step_base;
-    a.env_id_offset = env_id_offset; a.greedy = greedy; a.no_residual = w->no_residual;
-    a.actions = actions; a.probs = probs; a.attn = attn;
-    return a;
-}
-
-// bytes from the start of a cm_policy_pack() output to its wave-owned section: behind the all-f32 fragments and the f16-split pack
-static inline size_t wave_pack(const EnvDev &d) {
-    return mf::pack_layout(mf::kpad_of(d.d), d.L, true).total * sizeof(float) + policy_pack_h_bytes(d.d, d.L, true);
 }
 
 // diagnostic (COMMARL_ENV_STOP < 0): phase clocks of workgroup 0's env phase (ENV_PROBE, cm_env_dev.h).  The caller passes
@@ -115,6 +93,7 @@ int launch_rollout_wc(mf::FwdArgs a, const cm_policy_weights *w, const void *w_p
 
 // The one ladder from a plan to a build of a wave-owned kernel: f(LHOPS, PRE, FULLWG, TAPE, CARRY, SHAPE), each a
 // std::integral_constant.  Per hop count: the tape variant, and {plain, env prefetch, carried, carried map10} x {ragged, full}.
+// What f does with its kernel: launch_lds (cm_internal.h) on pl.blocks workgroups of 256 lanes with pl.lds bytes of LDS.
 template <class F>
 static int for_rollout_w_variant(int L, bool use_tape, const RolloutWPlan &pl, F &&f) {
     using T = std::true_type;
@@ -127,15 +106,6 @@ static int for_rollout_w_variant(int L, bool use_tape, const RolloutWPlan &pl, F
         return pl.pre ? fill(T{}, N{}, S0{}) : fill(N{}, N{}, S0{});
     };
     return L == 1 ? hops(std::integral_constant<int, 1>{}) : hops(std::integral_constant<int, 2>{});
-}
-// what f does with its kernel: the 160 KB dynamic-LDS attribute once per device, then the launch
-template <auto KERN, class... A>
-static int launch_rollout_w_variant(const RolloutWPlan &pl, void *stream, const A &...args) {
-    static unsigned long long done = 0;
-    if (dev_first(done)) CM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(KERN, dim3(pl.blocks), dim3(256), pl.lds, (hipStream_t)stream, args...);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
 }
 
 }  // namespace cm

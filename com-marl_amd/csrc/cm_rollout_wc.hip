@@ -52,16 +52,16 @@ int launch_rollout_wc(mf::FwdArgs a, const cm_policy_weights *w, const void *w_p
     pl.n_act = w->n_act; pl.out = &out;
     if (!cond || plan_rollout_w(a, h, false, chunk, pl) || pl.carry) return 1;
     if (set) {
-        const mw::PolicySetW ps{ set->packs, set->wg_policy, (int)wave_pack(d), w->n_act };
+        const mw::PolicySetW ps{ set->packs, set->wg_policy, (int)pack_sections(w).w_off, w->n_act };
         return for_rollout_w_variant(d.L, false, pl, [&](auto LH, auto PR, auto FU, auto, auto, auto) {
             if constexpr (LH.value == 2 && !PR.value) return 1;          // two hops, plain: not built (header)
-            else return launch_rollout_w_variant<&rollout_wcm_kernel<LH.value, PR.value, FU.value>>(pl, stream, a, ps, d, cond, out, pl.c);
+            else return launch_lds<&rollout_wcm_kernel<LH.value, PR.value, FU.value>>(dim3(pl.blocks), dim3(256), pl.lds, stream, a, ps, d, cond, out, pl.c);
         });
     }
-    const mw::WeightsW ww{ reinterpret_cast<const uint4 *>(w_pack), w->n_act };
+    const mw::WeightsW ww = weights_w(w, w_pack);
     return for_rollout_w_variant(d.L, false, pl, [&](auto LH, auto PR, auto FU, auto, auto, auto) {
         if constexpr (LH.value == 2 && !PR.value) return 1;
-        else return launch_rollout_w_variant<&rollout_wc_kernel<LH.value, PR.value, FU.value>>(pl, stream, a, ww, d, cond, out, pl.c);
+        else return launch_lds<&rollout_wc_kernel<LH.value, PR.value, FU.value>>(dim3(pl.blocks), dim3(256), pl.lds, stream, a, ww, d, cond, out, pl.c);
     });
 }
 

@@ -47,16 +47,17 @@ extern "C" int cm_rollout_chunk_multi(cm_env_t h, const cm_policy_weights *w, co
     if (n_steps == 0) return CM_OK;
     if (h->cond && !h->cond_fused) return 1;         // per-env comm conditions: fused on request only (cm_env_fuse_conditions)
     if (!policy_shape_ok(w) || !policy_w_enabled() || !shape_ok_rollout_w(d.N, d.d, d.L, w->n_act)) return 1;
-    const mf::FwdArgs a = rollout_fwd_args(h, w, obs, nullptr, dist_adj, channels, seed, env_id_offset, policy_step, policy_step_base, greedy,
-                                           actions, probs, attn);
+    // the policy forward's arguments: shape from the env handle, the rest as the entry point received it
+    const mf::FwdArgs a = fwd_args(FwdShape{ d.B, d.N, d.d, d.L, w->no_residual }, obs, dist_adj, channels, attn,
+                                   FwdSampler{ nullptr, seed, env_id_offset, policy_step, policy_step_base, greedy, actions, probs });
     const ChunkArgs c = chunk_args(n_steps, *st);
     RolloutWPlan pl;
     pl.n_act = w->n_act; pl.out = out;
     if (h->cond) return launch_rollout_wc(a, w, nullptr, set, h, *out, stream, &c);   // rollout_wcm_kernel, or 1
     if (plan_rollout_w(a, h, false, &c, pl)) return 1;
-    const mw::PolicySetW ps{ set->packs, set->wg_policy, (int)wave_pack(d), w->n_act };
+    const mw::PolicySetW ps{ set->packs, set->wg_policy, (int)pack_sections(w).w_off, w->n_act };
     // no tape variant here: the ladder never takes that branch without a tape
     return for_rollout_w_variant(d.L, false, pl, [&](auto LH, auto PR, auto FU, auto, auto CA, auto SH) {
-        return launch_rollout_w_variant<&rollout_wm_kernel<LH.value, PR.value, FU.value, CA.value, SH.value>>(pl, stream, a, ps, d, *out, pl.c);
+        return launch_lds<&rollout_wm_kernel<LH.value, PR.value, FU.value, CA.value, SH.value>>(dim3(pl.blocks), dim3(256), pl.lds, stream, a, ps, d, *out, pl.c);
     });
 }

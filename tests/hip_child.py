@@ -1,5 +1,5 @@
 """Child-process cases of the -m gpu suite: things that need a FRESH process because the library reads the knob once
-(COMMARL_ENV_LPE, COMMARL_ENV_WIDE), selects another build (COMMARL_LIB = the CM_BOUNDS debug library) or needs several
+(COMMARL_ENV_LPE, COMMARL_ENV_WIDE, COMMARL_POLICY_KERNEL), selects another build (COMMARL_LIB = the CM_BOUNDS debug library) or needs several
 ranks (gloo, all on GPU 0).  tests/conftest.py starts them one after the other BEFORE the pytest process itself touches
 the GPU and keeps their reports; the tests only assert on the reports.
 
@@ -24,6 +24,11 @@ CASES = {
                                   "range-checked (-DCM_BOUNDS) build: env goldens + Philox lock-step"),
     "bench_two_rank_rehearsal": (dict(COMMARL_DIST_BACKEND="gloo"),
                                  "bench.py --gpus 2 started without a launcher (self-launch), two gloo ranks on GPU 0: weak and --scaling strong"),
+    # COMMARL_POLICY_KERNEL (csrc/cm_policy_host.h has the truth table): the acting forward under each setting
+    "policy_kernel_unset": ({}, "default: teams of 4 act through the wave-owned kernel, every other team through the f16-split one"),
+    "policy_kernel_h": (dict(COMMARL_POLICY_KERNEL="h"), "workgroup-tiled f16-split kernel for every team size"),
+    "policy_kernel_f32": (dict(COMMARL_POLICY_KERNEL="f32"), "all-f32 matrix-core kernel"),
+    "policy_kernel_valu": (dict(COMMARL_POLICY_KERNEL="valu"), "generic VALU kernel"),
     "two_rank_train_once": ({}, "CentralizedMAPPO.train_once on 2 gloo ranks (both on GPU 0) == 1 process on the union (2 clipped steps; 5 steps without the ratio clip)"),
 }
 
@@ -108,6 +113,59 @@ def bench_two_rank_rehearsal():
         assert "cpu_baseline" not in d and "configs" not in d                   # single-GPU extras stay out of multi-rank lines
         out[scaling] = dict(value=d["value"], train_loop=tl["value"])
     return out
+
+
+def _policy_kernel_case():
+    """The acting forward (cm_policy_forward through act_device) at the two smallest rungs of the ladder - teams of 4 (the wave-owned
+    kernel or the quad build, ragged last workgroup) and teams of 8 - against the torch module, and against evaluate_nograd, with
+    the comparisons and tolerances of tests/test_hip_policy_parity.py."""
+    import numpy as np
+    import torch
+    from com_marl_amd import nets
+    from com_marl_amd.envs import EnvSpec, _Box, _Discrete
+    from tests.test_hip_policy_parity import TOL
+    setting = os.environ.get("COMMARL_POLICY_KERNEL", "w")[:1]
+    shapes = []
+    for N, d, hops, S in ((4, 21, 1, 19), (8, 29, 2, 7)):
+        torch.manual_seed(d + N)
+        spec = EnvSpec(_Box(np.zeros(d * N), np.ones(d * N)), _Discrete(5))
+        pol = nets.CommCategoricalMLPPolicy(spec, n_agents=N, n_gcn_layers=hops, device="cuda:0")
+        obs = torch.rand(S, N * d, device="cuda:0")
+        adj = (torch.rand(S, N, N, device="cuda:0") < 0.6).float()
+        adj[:, range(N), range(N)] = 1
+        ch = (torch.rand(S, hops, N, N, device="cuda:0") < 0.7).float()
+        ch[:, :, range(N), range(N)] = 1
+        _, probs, attn = pol.act_device(obs, None, adj, ch, policy_step=0)
+        with torch.no_grad():
+            p_ref, a_ref = pol._probs(obs, None, adj, ch)                 # the torch module: GEMMs + masked_aggregate
+        np.testing.assert_allclose(probs.cpu().numpy(), p_ref.cpu().numpy(), **TOL)
+        np.testing.assert_allclose(attn.cpu().numpy(), a_ref.cpu().numpy(), **TOL)
+        # test_evaluate_nograd_shares_one_forward: the training forward's kernel (f16-split whatever the switch says; act_device
+        # itself under f32 / valu) against the acting one - bit for bit unless teams of 4 act through the wave-owned kernel
+        _, p_eval = pol.evaluate_nograd(obs.reshape(1, S, -1), adj.reshape(1, S, N, N), ch.reshape(1, S, hops, N, N))
+        if N == 4 and setting not in ("h", "f", "v"):
+            np.testing.assert_allclose(p_eval.reshape(S, N, 5).cpu().numpy(), probs.cpu().numpy(), rtol=3e-6, atol=3e-7)
+        else:
+            assert torch.equal(p_eval.reshape(S, N, 5), probs)
+        shapes.append([N, d, hops, S])
+    return dict(setting=setting, shapes=shapes)
+
+
+def policy_kernel_unset():
+    os.environ.pop("COMMARL_POLICY_KERNEL", None)                        # before the library's first (and only) read of it
+    return _policy_kernel_case()
+
+
+def policy_kernel_h():
+    return _policy_kernel_case()
+
+
+def policy_kernel_f32():
+    return _policy_kernel_case()
+
+
+def policy_kernel_valu():
+    return _policy_kernel_case()
 
 
 def two_rank_train_once():

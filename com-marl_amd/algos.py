@@ -15,7 +15,9 @@ entropy and the new log-likelihood (the reference runs it twice); multi-GPU adds
 all-reduce of the flat (policy ‖ critic ‖ counts) gradient bucket per optimiser step.
 """
 import collections
+import contextlib
 import copy
+import functools
 import os
 import time
 
@@ -62,9 +64,26 @@ def _fused_loss_ok(policy, obs, avail_actions, actions, valids):
             and actions.dtype == torch.int32 and valids.dtype == torch.int32 and os.environ.get("COMMARL_FUSED_LOSS", "1") != "0")
 
 
-def _dist_ready():
-    from .dist import is_distributed
-    return is_distributed()
+@contextlib.contextmanager
+def _torch_deterministic():
+    """Deterministic update mode: the framework / library operations of the update (the input-gradient GEMMs of nets._LinearFn and
+    _MatmulWFn, the wide first layers, the layer-by-layer path) with torch's deterministic setting on - the library GEMMs then
+    take no atomic split-K kernels - and no NaN fill of every torch.empty (nothing here reads one unwritten); the caller's three
+    settings come back afterwards."""
+    import torch.utils.deterministic as tud
+    was = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(), tud.fill_uninitialized_memory
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    tud.fill_uninitialized_memory = False
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(was[0], warn_only=was[1])
+        tud.fill_uninitialized_memory = was[2]
+
+
+# One minibatch: its paths' rows of process_samples' tensors (None where the batch has none), of the epoch's advantages and old
+# log-likelihoods, and n_crit, the critic's count of padded steps (device scalar): to _UpdateGraphs the tuple of a step's inputs.
+_Minibatch = collections.namedtuple("_Minibatch", "obs actions rewards valids baselines dist_adjs channels advantages old_ll returns n_crit")
 
 
 class _UpdateGraphs:
@@ -85,14 +104,14 @@ class _UpdateGraphs:
     def maybe(cls, algo, minibatches, T, distributed):
         mode = os.environ.get("COMMARL_UPDATE_GRAPH", "auto")
         E = algo._optimization_mini_epochs
-        obs = minibatches[0][0]
+        obs = minibatches[0].obs
         if (mode == "0" or distributed or not obs.is_cuda or E < 3
                 or not all(hasattr(o, "begin_device_steps") for o in (algo._optimizer, algo._baseline_optimizer))
                 or E * len(minibatches) > algo._optimizer.DEV_STEP_CAPACITY
-                or not _fused_loss_ok(algo.policy, obs, None, minibatches[0][1], minibatches[0][3])    # (the framework's Categorical
+                or not _fused_loss_ok(algo.policy, obs, None, minibatches[0].actions, minibatches[0].valids)   # (the framework's Categorical
                 or not all(getattr(n, "_graph_capturable_update", False) for n in (algo.policy, algo.baseline))):   # validates on the host)
             return None                                      # only the nets whose whole step is this library's launches (CommBaseNet)
-        rows = max(mb[0].shape[0] for mb in minibatches) * T * getattr(algo.policy, "_n_agents", 1)
+        rows = max(mb.obs.shape[0] for mb in minibatches) * T * getattr(algo.policy, "_n_agents", 1)
         if mode != "1" and rows > cls.MAX_ROWS:
             return None
         self = getattr(algo, "_update_graphs", None)
@@ -127,12 +146,12 @@ class _UpdateGraphs:
         return (i, self.hyper) + tuple(None if t is None else (tuple(t.shape), t.dtype) for t in inputs)
 
     def step(self, i, inputs, fn):
-        """Step of minibatch i on `inputs` (its tensors: fn(*inputs) issues the step): replayed from its graph -> the step's
+        """Step of minibatch i on `inputs` (the tuple of its tensors: fn(inputs) issues the step): replayed from its graph -> the step's
         gradient-norm output.  First time this epoch: the graph of an earlier epoch with the same shapes gets the tensors copied
         into its input buffers, else the step is captured with these tensors as its input buffers.  A capture that fails
         switches the rest of the epoch back to eager steps."""
         if self.broken:
-            return fn(*inputs)
+            return fn(inputs)
         if not self.armed:                                   # the moments exist, the step counts are known
             self.algo._optimizer.begin_device_steps(self.n_steps)
             self.algo._baseline_optimizer.begin_device_steps(self.n_steps)
@@ -149,14 +168,14 @@ class _UpdateGraphs:
                 self.reused += 1
             else:
                 try:
-                    g, out = self._capture(lambda: fn(*inputs))
+                    g, out = self._capture(lambda: fn(inputs))
                 except Exception as e:                       # noqa: BLE001 - whatever the capture tripped over, the step itself is fine
                     import warnings
                     warnings.warn(f"PPO update: hipGraph capture of the optimiser step failed ({type(e).__name__}: {e}); eager steps from here")
                     torch.cuda.synchronize()
                     self.close()
                     self.broken = True
-                    return fn(*inputs)
+                    return fn(inputs)
                 ent = self.cache[key] = [g, out, list(inputs)]
                 self.captured += 1
                 while len(self.cache) > self.MAX_CACHED:
@@ -271,23 +290,13 @@ class CentralizedMAPPO:
         dev = self._dev()
         if isinstance(paths, PathBatch):
             e = paths.engine
-            lens = paths.length
-            P, T = lens.numel(), int(lens.max().item())
-            tau = torch.arange(T, device=dev)
-            valid = tau[None, :] < lens[:, None]                                  # [P,T]
-            t_idx = (paths.start[:, None] + tau[None, :]).clamp_(max=e.obs.shape[0] - 2)
-            b_idx = paths.env_idx[:, None].expand(P, T)
-
-            def gather(buf, pad):
-                x = buf[t_idx, b_idx]                                              # [P,T,...]
-                m = valid.reshape(P, T, *([1] * (x.dim() - 2)))
-                return torch.where(m, x, torch.full((), pad, dtype=x.dtype, device=dev))
-            obs = gather(e.obs, 0).reshape(P, T, -1)
-            actions = gather(e.actions, 0)
-            rew64 = gather(e.reward64, 0)
-            dist_adjs = None if e.dist_adj is None else gather(e.dist_adj, 1)
-            channels = None if e.channels is None else gather(e.channels, 1)
-            valids = lens.to(torch.int32)
+            P, T = paths.gather_index()[:2]
+            obs = paths.padded("obs", 0).reshape(P, T, -1)
+            actions = paths.padded("actions", 0)
+            rew64 = paths.padded("reward64", 0)
+            dist_adjs = None if e.dist_adj is None else paths.padded("dist_adj", 1)
+            channels = None if e.channels is None else paths.padded("channels", 1)
+            valids = paths.length.to(torch.int32)
         else:                                                                       # reference list-of-dicts
             P = len(paths)
             T = max(len(p['rewards']) for p in paths)
@@ -334,17 +343,17 @@ class CentralizedMAPPO:
         adv = torch.empty_like(rewards)
         L.run("cm_gae", P, T, L.cptr(rewards), L.cptr(baselines), L.ptr(valids), float(self.discount), float(self._gae_lambda),
               int(self._center_adv), self._eps, L.ptr(adv), device=rewards.device)
-        if self._positive_adv:
-            adv = adv - adv.min()
-        return adv
+        return self._positive(adv)
+
+    def _positive(self, adv):                                  # positive_adv (:428-429): minus the min of this call's advantages
+        return adv - adv.min() if self._positive_adv else adv
 
     def _max_entropy_advantages(self, logits, rewards, baselines, in_place):
         """entropy_method 'max' (:415-418): r' = r + c * H of the current policy, then compute_advantages, in one
         cm_entropy_gae launch on the detached logits [P,T,N,A] (the entropy carries no gradient in this mode: the ctor
         demands stop_entropy_gradient).  in_place writes r' back into `rewards`, as the reference's `rewards +=` does to the
         epoch's full-batch tensor (the two quirks of the in-place add); a minibatch step leaves its rewards
-        buffer alone (the reference adds to a copy, and a replayed update graph would add c * H again every mini-epoch).
-        positive_adv subtracts the min of this call's advantages (:428-429)."""
+        buffer alone (the reference adds to a copy, and a replayed update graph would add c * H again every mini-epoch)."""
         P, T = rewards.shape
         N, A = logits.shape[-2:]
         lg = logits.detach().contiguous()
@@ -352,9 +361,7 @@ class CentralizedMAPPO:
         L.run("cm_entropy_gae", P, T, N, A, L.ptr(lg), L.ptr(rewards), L.cptr(baselines), float(self.discount),
               float(self._gae_lambda), float(self._policy_ent_coeff), int(self._use_softplus_entropy),
               L.ptr(rewards) if in_place else None, None, L.ptr(adv), device=rewards.device)
-        if self._positive_adv:
-            adv = adv - adv.min()
-        return adv
+        return self._positive(adv)
 
     def _entropy_flags(self):
         """cm_ppo_surrogate's add_entropy bits: the 'regularized' term and its two switches (:434-435, :509-536)."""
@@ -363,27 +370,23 @@ class CentralizedMAPPO:
         return (L.ENT_ADD | (L.ENT_SOFTPLUS if self._use_softplus_entropy else 0)
                 | (L.ENT_STOP_GRAD if self._stop_entropy_gradient else 0))
 
-    def _entropy_column(self, p):
-        """The logged Entropy (:366): mean over all padded steps of the per-step entropy (mean over agents), softplus per step
-        first when use_softplus_entropy is set (it goes through _compute_policy_entropy, :499-538)."""
-        h = -(p * torch.log(p)).sum(-1).mean(-1)
-        if self._use_softplus_entropy:
-            h = F.softplus(h)
-        return h.mean()
-
     @torch.no_grad()
-    def _old_log_likelihood(self, obs, actions, dist_adjs, channels):
-        """old_policy.log_likelihood (:561-566): one fused no-grad launch."""
-        P, T = obs.shape[:2]
-        N = self.policy._n_agents
-        flat = lambda x: None if x is None else x.reshape(P * T, *x.shape[2:])      # noqa: E731
-        _, probs, _ = self._old_policy.act_device(flat(obs), None, flat(dist_adjs), flat(channels), want_actions=False,
-                                                  want_attn=False, policy_step=0)
-        lp = torch.log(probs.gather(-1, actions.reshape(P * T, N, 1).long())).squeeze(-1)
-        return lp.sum(-1).reshape(P, T)
+    def _act_probs(self, policy, obs, dist_adjs, channels):
+        """Action probabilities [P,T,N,A] of `policy` over the padded batch from its act_device: one fused no-grad launch."""
+        flat = lambda x: None if x is None else x.reshape(-1, *x.shape[2:])         # noqa: E731  ([P,T,...] -> [P*T,...])
+        _, probs, _ = policy.act_device(flat(obs), None, flat(dist_adjs), flat(channels), want_actions=False, want_attn=False, policy_step=0)
+        return probs.reshape(*obs.shape[:2], self.policy._n_agents, -1)
 
-    def _valid_mask(self, valids, T):
-        return torch.arange(T, device=valids.device)[None, :] < valids[:, None]
+    def _evaluate(self, policy, obs, dist_adjs, channels):
+        """One no-grad forward over the full batch -> (logits or None, probs [P,T,N,A]): the policy's evaluate_nograd, or, of a
+        policy object without one, act_device's probabilities and no logits."""
+        if hasattr(policy, "evaluate_nograd"):
+            return policy.evaluate_nograd(obs, dist_adjs, channels)
+        return None, self._act_probs(policy, obs, dist_adjs, channels)
+
+    def _old_log_likelihood(self, obs, actions, dist_adjs, channels):
+        """old_policy.log_likelihood (:561-566)."""
+        return self._ll_from_probs(self._act_probs(self._old_policy, obs, dist_adjs, channels), actions)
 
     @staticmethod
     def _ll_from_probs(probs, actions):
@@ -391,9 +394,14 @@ class CentralizedMAPPO:
         return torch.log(probs.gather(-1, actions.long().unsqueeze(-1))).squeeze(-1).sum(-1)
 
     def _kl_entropy(self, p_old, p_new):
-        """KL(old || new) mean and entropy mean of `p_new` over ALL padded steps (:440-538) from two probability tensors."""
+        """KL(old || new) mean and the logged Entropy of `p_new` (:366), both over ALL padded steps (:440-538), from two
+        probability tensors.  Entropy: the per-step entropy (mean over agents), softplus per step first when
+        use_softplus_entropy is set (it goes through _compute_policy_entropy, :499-538)."""
         kl = (p_old * (torch.log(p_old) - torch.log(p_new))).sum(-1).mean()
-        return float(kl), float(self._entropy_column(p_new))
+        h = -(p_new * torch.log(p_new)).sum(-1).mean(-1)
+        if self._use_softplus_entropy:
+            h = F.softplus(h)
+        return float(kl), float(h.mean())
 
     def _compute_loss(self, itr, obs, avail_actions, actions, rewards, valids, baselines, dist_adjs, channels,
                       advantages=None, old_ll=None, reduce=True, logits=None, rewards_in_place=False):
@@ -401,7 +409,6 @@ class CentralizedMAPPO:
         reduce=False returns (sum, count) for the count-weighted multi-GPU reduction.
         entropy_method 'max' ignores `advantages`: they come from this call's entropy (_max_entropy_advantages), and
         rewards_in_place says whether r + c * H is written back into `rewards` (the full-batch calls of train_once)."""
-        T = obs.shape[1]
         maxent = self._maximum_entropy
         if advantages is None and not maxent:
             advantages = self._advantages(rewards, baselines, valids)
@@ -433,39 +440,18 @@ class CentralizedMAPPO:
         objective = torch.min(surrogate, clipped)                                    # :540-589
         if self._entropy_regularzied:
             objective = objective + self._policy_ent_coeff * entropies               # :434-435
-        mask = self._valid_mask(valids, T)
-        total = -(objective * mask).sum()
-        count = mask.sum()
-        if not reduce:
-            return total, count
-        return total / count
-
-    @torch.no_grad()
-    def _diagnostics(self, obs, actions, valids, dist_adjs, channels):
-        """KL(old || new) mean and policy entropy mean over ALL padded steps, as :440-538 compute them."""
-        P, T = obs.shape[:2]
-        flat = lambda x: None if x is None else x.reshape(P * T, *x.shape[2:])      # noqa: E731
-        _, p_new, _ = self.policy.act_device(flat(obs), None, flat(dist_adjs), flat(channels), want_actions=False,
-                                             want_attn=False, policy_step=0)
-        _, p_old, _ = self._old_policy.act_device(flat(obs), None, flat(dist_adjs), flat(channels),
-                                                  want_actions=False, want_attn=False, policy_step=0)
-        kl = (p_old * (torch.log(p_old) - torch.log(p_new))).sum(-1).mean()
-        return float(kl), float(self._entropy_column(p_new))
+        mask = torch.arange(obs.shape[1], device=valids.device)[None, :] < valids[:, None]
+        total, count = -(objective * mask).sum(), mask.sum()
+        return (total, count) if not reduce else total / count
 
     def _log_performance(self, itr, paths, returns, valids):
         """The progress.csv columns of centralized_ma_ppo.py:286-366 (per-path sums -> means over paths).
         With a PathBatch everything is reduced on the device and one small vector comes to the host."""
         N = self.policy._n_agents
         if isinstance(paths, PathBatch):
-            e, dev = paths.engine, self._dev()
-            lens = paths.length
-            P, T = lens.numel(), int(lens.max().item())
-            tau = torch.arange(T, device=dev)
-            valid = tau[None, :] < lens[:, None]
-            t_idx = (paths.start[:, None] + tau[None, :]).clamp_(max=e.reward64.shape[0] - 1)
-            b_idx = paths.env_idx[:, None].expand(P, T)
-            rew = torch.where(valid, e.reward64[t_idx, b_idx], torch.zeros((), dtype=torch.float64, device=dev))
-            undisc = rew.sum(1)                                                      # np.sum(path_rewards), f64
+            e, dev, lens = paths.engine, self._dev(), paths.length
+            P, T, valid, t_idx, b_idx = paths.gather_index()
+            undisc = paths.padded("reward64", 0).sum(1)                              # np.sum(path_rewards), f64
             det = (e.details[t_idx, b_idx].to(torch.float64) * valid[..., None]).sum(1)   # [P,6]
             succ = e.success[paths.start + lens - 1, paths.env_idx].to(torch.float64)
             if e.dist_adj is not None:
@@ -522,6 +508,9 @@ class CentralizedMAPPO:
             b = self._bucket = GradBucket(pol, cri)
         b.allreduce(n_valid, n_crit)
 
+    def _max_norm(self):
+        return float("inf") if self._clip_grad_norm is None else float(self._clip_grad_norm)
+
     def _mean_grad_norm(self, grad_norm, dev):
         """Mean over the epoch's optimiser steps of the norm the reference records AFTER the clip (:256):
         |g| * min(1, max / (|g| + 1e-6)); optim.Adam hands over |g|^2 per step on the device, the rest is done once here."""
@@ -530,165 +519,144 @@ class CentralizedMAPPO:
         if not torch.is_tensor(grad_norm[0]):
             return float(np.mean(grad_norm))
         pre = torch.stack(grad_norm).to(torch.float32).sqrt()
-        mx = float("inf") if self._clip_grad_norm is None else float(self._clip_grad_norm)
-        return float((pre * torch.clamp(mx / (pre + 1e-6), max=1.0)).mean())
+        return float((pre * torch.clamp(self._max_norm() / (pre + 1e-6), max=1.0)).mean())
 
     # ------------------------------------------------------------------------------------------
     # train_once (:175-388)
     # ------------------------------------------------------------------------------------------
     def train_once(self, runner=None, itr=None, paths=None):
-        if not deterministic():
+        with _torch_deterministic() if deterministic() else contextlib.nullcontext():
             return self._train_once(runner, itr, paths)
-        # deterministic mode: the framework / library operations of the update (the input-gradient GEMMs of nets._LinearFn and
-        # _MatmulWFn, the wide first layers, the layer-by-layer path) with torch's deterministic setting on - the library GEMMs
-        # then take no atomic split-K kernels; the caller's settings come back afterwards
-        import torch.utils.deterministic as tud
-        was_on, was_warn, was_fill = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(),
-                                      tud.fill_uninitialized_memory)
-        torch.use_deterministic_algorithms(True, warn_only=True)
-        tud.fill_uninitialized_memory = False                # (no NaN fill of every torch.empty: nothing here reads one unwritten)
-        try:
-            return self._train_once(runner, itr, paths)
-        finally:
-            torch.use_deterministic_algorithms(was_on, warn_only=was_warn)
-            tud.fill_uninitialized_memory = was_fill
 
-    def _train_once(self, runner=None, itr=None, paths=None):
-        if runner is not None:
-            itr, paths = runner.step_itr, runner.step_path
-        t_start = time.time()
-        obs, avail, actions, rewards, valids, baselines, returns, dist_adjs, channels = self.process_samples(itr, paths)
+    def _minibatches(self, batch, advantages, old_ll, distributed):
+        """The epoch's minibatches (:209-215).  The permutation is drawn once, so the minibatches are the same path subsets in
+        every mini-epoch: gather them once instead of 10 times (each gather copies ~1/3 of the padded batch)."""
+        obs, _, actions, rewards, valids, baselines, returns, dist_adjs, channels = batch
         P, T = rewards.shape
-        distributed = _dist_ready()
-        # entropy_method 'max': no epoch-wide advantages - every loss evaluation derives its own from the current policy's
-        # entropy (_max_entropy_advantages), and the full-batch evaluations before / after the update add c * H into `rewards`
-        # in place as the reference does (its minibatches are sliced from the tensor loss_before left behind)
-        maxent = self._maximum_entropy
-        advantages = None if maxent else self._advantages(rewards, baselines, valids)
-        # The reference evaluates the two policies over the full batch eight times per epoch (old log-likelihood twice,
-        # loss before / after, KL + entropy before / after with both nets each).  Only three distinct (weights, batch)
-        # pairs are involved - last epoch's pre-update weights, this epoch's pre-update weights (which the old policy
-        # becomes at :204) and the post-update weights - so three forwards are run and their outputs shared.
-        shared = avail is None and all(hasattr(p, "evaluate_nograd") for p in (self.policy, self._old_policy))
-        if shared:
-            with torch.no_grad():
-                _, p_old0 = self._old_policy.evaluate_nograd(obs, dist_adjs, channels)
-                lg_new, p_new = self.policy.evaluate_nograd(obs, dist_adjs, channels)
-                old_ll0 = self._ll_from_probs(p_old0, actions)
-                loss_before = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                       channels, advantages, old_ll0, logits=lg_new, rewards_in_place=maxent))
-                kl_before, _ = self._kl_entropy(p_old0, p_new)
-                del p_old0, lg_new
-            self._old_policy.load_state_dict(self.policy.state_dict())              # :204
-            with torch.no_grad():
-                old_ll = self._ll_from_probs(p_new, actions)                         # the old policy now IS the policy
-        else:
-            with torch.no_grad():
-                old_ll0 = self._old_log_likelihood(obs, actions, dist_adjs, channels)
-                loss_before = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                       channels, advantages, old_ll0, rewards_in_place=maxent))
-                kl_before, _ = self._diagnostics(obs, actions, valids, dist_adjs, channels)
-            self._old_policy.load_state_dict(self.policy.state_dict())              # :204
-            with torch.no_grad():
-                old_ll = self._old_log_likelihood(obs, actions, dist_adjs, channels)
-
         step_size = int(np.ceil(P / self._optimization_n_minibatches))
         if distributed and P < 2 * self._optimization_n_minibatches:
             raise RuntimeError("distributed update needs >= 2 paths per minibatch on every rank (equal optimiser-step counts)")
         shuffled_ids = np.random.permutation(P)                                      # :209
-        grad_norm = []
-        sl = lambda x, ids: None if x is None else x[ids]                            # noqa: E731
-        t_opt = time.time()
-        # the permutation is drawn once (:209), so the minibatches are the same path subsets in every mini-epoch:
-        # gather them once instead of 10 times (each gather copies ~1/3 of the padded batch)
+        cols = (obs, actions, rewards, valids, baselines, dist_adjs, channels, advantages, old_ll, returns)
         minibatches = []
         for start in range(0, P, step_size):
-            ids = torch.as_tensor(shuffled_ids[start:min(start + step_size, P)], device=obs.device)
-            minibatches.append((obs[ids], actions[ids], rewards[ids], valids[ids], baselines[ids], sl(dist_adjs, ids),
-                                sl(channels, ids), sl(advantages, ids), old_ll[ids], returns[ids]))
+            ids = torch.as_tensor(shuffled_ids[start:start + step_size], device=obs.device)
+            minibatches.append(_Minibatch(*(None if x is None else x[ids] for x in cols),
+                                          n_crit=torch.tensor(float(len(ids) * T), device=obs.device)))
+        return minibatches
+
+    def _critic_step(self, mb, side, distributed):
+        """The critic's half of a step, on stream `side`: Gaussian NLL, mean over padded steps (comm_base_critic.py:88-89)."""
+        with torch.cuda.stream(side):
+            bl_loss = self._baseline_loss(mb.obs, mb.returns, mb.dist_adjs, mb.channels)
+            (bl_loss * mb.n_crit if distributed else bl_loss).backward()
+            if not distributed:
+                self._baseline_optimizer.step()
+
+    def _optimiser_step(self, mb, distributed=False, two_streams=False):
+        """One optimiser step of both nets on one minibatch (:211-268) -> the squared pre-clip gradient norm (device scalar,
+        optim.Adam) or the post-clip norm (host float, any other optimiser)."""
+        main = torch.cuda.current_stream(mb.obs.device)
+        side = self._side_stream if two_streams else main
+        self._baseline_optimizer.zero_grad()
+        self._optimizer.zero_grad()
+        side.wait_stream(main)                                               # fork: both nets see the minibatch, nothing else
+        # Issue order: the policy's chain is the longer one, and a captured graph submits its nodes in capture order - with the
+        # critic first the policy's first kernel of a replayed step started ~110 us late (kernel trace of the reference-batch
+        # step).  The distributed step keeps the critic first: its gradients must be there when the bucket is reduced.
+        if distributed:
+            self._critic_step(mb, side, distributed)
+        loss_sum, n_valid = self._compute_loss(None, mb.obs, None, mb.actions, mb.rewards, mb.valids, mb.baselines, mb.dist_adjs,
+                                               mb.channels, mb.advantages, mb.old_ll, reduce=False)
+        if distributed:
+            loss_sum.backward()
+            main.wait_stream(side)
+            self._allreduce_grads(n_valid, mb.n_crit)
+        else:
+            (loss_sum / n_valid).backward()
+        if hasattr(self._optimizer, "_norm"):                               # optim.Adam: clip + update in two launches
+            self._optimizer.step(max_norm=self._max_norm(), return_norm=False)   # policy only (:253-255)
+            gn = self._optimizer.norm_sq                                     # a view of the optimiser's workspace
+        else:
+            if self._clip_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self._clip_grad_norm)
+            gn = self.policy.grad_norm()
+            self._optimizer.step()                                           # _optimize (:606-610)
+        if distributed:
+            self._baseline_optimizer.step()
+        else:
+            self._critic_step(mb, side, distributed)
+        main.wait_stream(side)
+        return gn
+
+    def _run_steps(self, minibatches, T, distributed):
+        """optimization_mini_epochs passes over the minibatches (:209-268) -> the gradient norm of every step, in order."""
+        dev = minibatches[0].obs.device
         # The critic has its own trunk (a-17): its forward / backward (/ optimiser step) share nothing with the policy's
         # but the minibatch, so they run on a second HIP stream and fill the gaps of the policy's launch chain.
-        two_streams = obs.is_cuda and os.environ.get("COMMARL_CRITIC_STREAM", "1") != "0"
-        if two_streams and (getattr(self, "_side_stream", None) is None or self._side_stream.device != obs.device):
-            self._side_stream = torch.cuda.Stream(device=obs.device)
-        n_crits = [torch.tensor(float(mb[0].shape[0] * T), device=obs.device) for mb in minibatches]
-
-        def one_step(o, a, r, v, bl, da, ch, adv_mb, oll_mb, ret_mb, n_crit):
-            """One optimiser step of both nets on one minibatch (:211-268) -> the squared pre-clip gradient norm (device scalar,
-            optim.Adam) or the post-clip norm (host float, any other optimiser)."""
-            main = torch.cuda.current_stream(obs.device)
-            side = self._side_stream if two_streams else main
-            self._baseline_optimizer.zero_grad()
-            self._optimizer.zero_grad()
-            side.wait_stream(main)                                               # fork: both nets see the minibatch, nothing else
-
-            def critic():                                                        # Gaussian NLL, mean over padded steps (comm_base_critic.py:88-89)
-                with torch.cuda.stream(side):
-                    bl_loss = self._baseline_loss(o, ret_mb, da, ch)
-                    (bl_loss * n_crit if distributed else bl_loss).backward()
-                    if not distributed:
-                        self._baseline_optimizer.step()
-            # Issue order: the policy's chain is the longer one, and a captured graph submits its nodes in capture order - with the
-            # critic first the policy's first kernel of a replayed step started ~110 us late (kernel trace of the reference-batch
-            # step).  The distributed step keeps the critic first: its gradients must be there when the bucket is reduced.
-            if distributed:
-                critic()
-            loss_sum, n_valid = self._compute_loss(itr, o, None, a, r, v, bl, da, ch, adv_mb, oll_mb, reduce=False)
-            if distributed:
-                loss_sum.backward()
-                main.wait_stream(side)
-                self._allreduce_grads(n_valid, n_crit)
-            else:
-                (loss_sum / n_valid).backward()
-            if hasattr(self._optimizer, "_norm"):                               # optim.Adam: clip + update in two launches
-                mx = float("inf") if self._clip_grad_norm is None else float(self._clip_grad_norm)
-                self._optimizer.step(max_norm=mx, return_norm=False)             # policy only (:253-255)
-                gn = self._optimizer.norm_sq                                     # a view of the optimiser's workspace
-            else:
-                if self._clip_grad_norm is not None:
-                    torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self._clip_grad_norm)
-                gn = self.policy.grad_norm()
-                self._optimizer.step()                                           # _optimize (:606-610)
-            if distributed:
-                self._baseline_optimizer.step()
-            else:
-                critic()
-            main.wait_stream(side)
-            return gn
-
-        # The permutation is drawn once per epoch, so mini-epochs 1.. repeat mini-epoch 0's launches on the same buffers with
-        # other weights: for the small (launch-bound) batches of the reference's own configuration each minibatch's step is
-        # captured into a hipGraph in mini-epoch 1 and replayed from then on (_UpdateGraphs).
+        two_streams = dev.type == "cuda" and os.environ.get("COMMARL_CRITIC_STREAM", "1") != "0"
+        if two_streams and (getattr(self, "_side_stream", None) is None or self._side_stream.device != dev):
+            self._side_stream = torch.cuda.Stream(device=dev)
+        step = functools.partial(self._optimiser_step, distributed=distributed, two_streams=two_streams)
+        # mini-epochs 1.. repeat mini-epoch 0's launches on the same buffers with other weights: small (launch-bound) batches
+        # capture each minibatch's step into a hipGraph in mini-epoch 1 and replay it from then on (_UpdateGraphs)
         graphs = _UpdateGraphs.maybe(self, minibatches, T, distributed)
+        grad_norm = []
         try:
             for mini_epoch in range(self._optimization_mini_epochs):
                 for i, mb in enumerate(minibatches):
                     if graphs is not None and mini_epoch >= graphs.first_epoch:
-                        gn = graphs.step(i, tuple(mb) + (n_crits[i],), one_step)
+                        gn = graphs.step(i, mb, step)
                     else:
-                        gn = one_step(*mb, n_crits[i])
+                        gn = step(mb)
                         self._eager_stepped = True
                     grad_norm.append(gn.clone() if torch.is_tensor(gn) else gn)
         finally:
             if graphs is not None:                           # the optimisers leave the device-step mode whatever happened
                 graphs.close()
+        return grad_norm
+
+    def _train_once(self, runner=None, itr=None, paths=None):
+        if runner is not None:
+            itr, paths = runner.step_itr, runner.step_path
+        t_start = time.time()
+        batch = obs, avail, actions, rewards, valids, baselines, returns, dist_adjs, channels = self.process_samples(itr, paths)
+        T = rewards.shape[1]
+        from .dist import is_distributed
+        distributed = is_distributed()
+        # entropy_method 'max': no epoch-wide advantages - every loss evaluation derives its own from the current policy's
+        # entropy (_max_entropy_advantages), and the full-batch evaluations before / after the update add c * H into `rewards`
+        # in place as the reference does (its minibatches are sliced from the tensor loss_before left behind)
+        maxent = self._maximum_entropy
+        advantages = None if maxent else self._advantages(rewards, baselines, valids)
+        # The reference evaluates the two policies over the full batch eight times per epoch (old log-likelihood twice, loss
+        # before / after, KL + entropy before / after with both nets each).  Only three distinct (weights, batch) pairs are
+        # involved - last epoch's pre-update weights, this epoch's (which the old policy becomes at :204) and the post-update
+        # ones - so three forwards are run and shared, for every policy kind (no logits from a row-MLP forward: the loss runs its own)
+        full_loss = functools.partial(self._compute_loss, itr, obs, avail, actions, rewards, valids, baselines, dist_adjs, channels,
+                                      advantages, rewards_in_place=maxent)
+        with torch.no_grad():
+            _, p_old0 = self._evaluate(self._old_policy, obs, dist_adjs, channels)
+            lg_new, p_new = self._evaluate(self.policy, obs, dist_adjs, channels)
+            loss_before = float(full_loss(self._ll_from_probs(p_old0, actions), logits=lg_new))
+            kl_before, _ = self._kl_entropy(p_old0, p_new)
+            del p_old0, lg_new
+        self._old_policy.load_state_dict(self.policy.state_dict())                  # :204
+        old_ll = self._ll_from_probs(p_new, actions)                                 # the old policy now IS the policy
+
+        t_opt = time.time()
+        minibatches = self._minibatches(batch, advantages, old_ll, distributed)
+        grad_norm = self._run_steps(minibatches, T, distributed)
         torch.cuda.synchronize(obs.device)
         epoch_time = time.time() - t_opt
         self.policy.sync_weights()
 
         with torch.no_grad():
-            if shared:
-                lg_after, p_after = self.policy.evaluate_nograd(obs, dist_adjs, channels)
-                loss_after = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                      channels, advantages, old_ll, logits=lg_after, rewards_in_place=maxent))
-                kl, entropy = self._kl_entropy(p_new, p_after)
-                del lg_after, p_after, p_new
-            else:
-                loss_after = float(self._compute_loss(itr, obs, avail, actions, rewards, valids, baselines, dist_adjs,
-                                                      channels, advantages, old_ll, rewards_in_place=maxent))
-                kl, entropy = self._diagnostics(obs, actions, valids, dist_adjs, channels)
+            lg_after, p_after = self._evaluate(self.policy, obs, dist_adjs, channels)
+            loss_after = float(full_loss(old_ll, logits=lg_after))
+            kl, entropy = self._kl_entropy(p_new, p_after)
+            del lg_after, p_after, p_new
         perf = self._log_performance(itr, paths, returns, valids)
-        avg_return = perf["AverageReturn"]
         self.stats = dict(perf, LossBefore=loss_before, LossAfter=loss_after,
                           dLoss=loss_before - loss_after, KLBefore=kl_before, KL=kl, Entropy=entropy,
                           GradNorm=self._mean_grad_norm(grad_norm, obs.device), EpochTime=epoch_time,
@@ -697,7 +665,7 @@ class CentralizedMAPPO:
                           GPUMemoryMax=torch.cuda.max_memory_allocated(self._dev()) / 1024 ** 3)     # :372-383 (GiB)
         for k, v in self.stats.items():
             tabular.record(k, v)
-        return avg_return
+        return perf["AverageReturn"]
 
     def train(self, runner):
         """MABatchPolopt.train (com_marl/np/algos/ma_batch_polopt.py:72-120): sample -> train_once per epoch."""

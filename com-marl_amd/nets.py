@@ -1381,6 +1381,12 @@ class _RowMLPPolicy(_Acting, _WeightPack):
               L.ptr(step_base), int(greedy), L.ptr(actions), L.ptr(probs), device=obs.device)
         return actions, probs, None
 
+    def evaluate_nograd(self, obs_n, dist_adj=None, channels=None):
+        """One no-grad forward over a batch [..., N*d] -> (None, probs [..., N, A]): CommCategoricalMLPPolicy.evaluate_nograd's
+        contract, on act_device's launch (no logits: the PPO loss runs the autograd modules for those)."""
+        _, probs, _ = self.act_device(obs_n.reshape(-1, obs_n.shape[-1]), want_actions=False, policy_step=0)
+        return None, probs.reshape(*obs_n.shape[:-1], self._n_agents, -1)
+
     def get_actions(self, observations, avail_actions, greedy=False):
         """numpy in / numpy out (dec_categorical_mlp_policy.py:150-176, centralized_...:99-118)."""
         dev = next(self.parameters()).device

@@ -122,6 +122,7 @@ class PathBatch(Sequence):
         self._bufs = {}                       # engine buffer name -> numpy (host copies made so far)
         self._idx = None
         self._T = None
+        self._gather = None                   # gather_index()'s answer
         self._paths = {}                      # index -> the ONE _LazyPath of that path (keys a caller sets on it persist)
         self._generation = getattr(engine, "generation", None)
 
@@ -143,11 +144,35 @@ class PathBatch(Sequence):
             self._T = int((self._idx[1] + self._idx[2]).max()) if len(self._idx[0]) else 0
         return self._idx
 
+    def _check_fresh(self):
+        if self._generation != getattr(self.engine, "generation", None):
+            raise RuntimeError("this PathBatch belongs to an earlier rollout: the engine's trajectory buffers were "
+                               "overwritten by a later obtain_samples / reset (materialize() the paths you keep)")
+
+    def gather_index(self):
+        """-> (P, T, valid, t_idx, b_idx), the last three [P,T] on the device: step tau of path p sits in slot t_idx[p, tau] of env
+        b_idx[p, tau]; T is the longest path (the one host read), `valid` says tau < length.  Past a path's end the slot is
+        clamped to H - 1, the last slot of the engine's per-step buffers (those that keep the state after the last step too - obs,
+        dist_adj, channels, diameter - hold H + 1).  Built once per batch; a batch of an earlier rollout raises."""
+        self._check_fresh()
+        if self._gather is None:
+            P, T = self.length.numel(), int(self.length.max().item())
+            tau = torch.arange(T, device=self.length.device)
+            valid = tau[None, :] < self.length[:, None]
+            t_idx = (self.start[:, None] + tau[None, :]).clamp_(max=self.engine.reward64.shape[0] - 1)
+            self._gather = (P, T, valid, t_idx, self.env_idx[:, None].expand(P, T))
+        return self._gather
+
+    def padded(self, name, pad):
+        """Engine buffer `name` gathered to the padded batch [P, T, ...] on the device, `pad` outside `valid`."""
+        P, T, valid, t_idx, b_idx = self.gather_index()
+        x = getattr(self.engine, name)[t_idx, b_idx]
+        m = valid.reshape(P, T, *([1] * (x.dim() - 2)))
+        return torch.where(m, x, torch.full((), pad, dtype=x.dtype, device=x.device))
+
     def _buf(self, name):
         if name not in self._bufs:
-            if self._generation != getattr(self.engine, "generation", None):
-                raise RuntimeError("this PathBatch belongs to an earlier rollout: the engine's trajectory buffers were "
-                                   "overwritten by a later obtain_samples / reset (materialize() the paths you keep)")
+            self._check_fresh()
             self._index()
             t = getattr(self.engine, name)
             extra = 1 if name in ("obs", "dist_adj", "channels", "diameter") else 0

@@ -17,7 +17,7 @@ def main():
             return r
         setattr(obj, name, g)
     C = algos.CentralizedMAPPO
-    for n in ("process_samples", "_advantages", "_old_log_likelihood", "_diagnostics", "_log_performance", "_baseline_loss"):
+    for n in ("process_samples", "_advantages", "_evaluate", "_log_performance", "_baseline_loss"):
         wrap(C, n)
     orig_cl = C._compute_loss
     def cl(self, *a, reduce=True, **k):

@@ -23,6 +23,9 @@ reduced on the device by cm_episode_stats / cm_episode_means: nothing but K x 12
 ``eval_sweep`` does the same for K policies x C comm conditions in one rollout, on a wrapper built with ``conditions=``.
 Both take ``comm_stats=True``: how much of the offered communication was delivered and how much of the team an agent can hear
 through the net's hops (cm_comm_stats on the engine's dist_adj / channels, COMM_KEYS in every dict).
+Both take ``curves=True``: the same episodes reduced over the episodes with the STEP axis kept (cm_episode_curves /
+cm_comm_curves behind every round, cm_curve_means / cm_comm_curve_means at the end, in the same single copy) - per step the mean
+over the episodes of the zero-padded lists eval_model returns, i.e. what exp_runners/testing.py:307-324 saves as rewMat3.
 """
 import numpy as np
 import torch
@@ -196,19 +199,67 @@ class _CommStats:
         return d
 
 
-def _summary_buffers(cells, comm_stats, device):
-    """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None)."""
-    n = cells * L.SUM_COLS
-    flat = torch.empty(n + (cells * L.EPC_COLS if comm_stats else 0), dtype=torch.float64, device=device)
-    return flat, flat[:n].view(cells, L.SUM_COLS), (flat[n:].view(cells, L.EPC_COLS) if comm_stats else None)
+class _Curves:
+    """The curves=True side of eval_summary / eval_sweep: behind every round ONE cm_episode_curves launch on the engine's
+    trajectory buffers into the device table of per-step sums [cells, T, 9] - the first round overwrites it, the later ones add -
+    and, with comm_stats, ONE cm_comm_curves launch on the rows _CommStats.round has just produced into [cells, T, 4]; after the
+    last round ONE cm_curve_means (and ONE cm_comm_curve_means) launch into `out` (`comm_out`), views of the buffer the caller
+    copies to the host."""
+
+    def __init__(self, eng, batch, T, cells, n_epi, scen, out, comm_out):
+        self.eng, self.batch, self.T, self.cells, self.n_epi, self.scen = eng, batch, T, cells, n_epi, scen
+        self.out, self.comm_out = out, comm_out
+        self.sums = torch.empty(cells, T, L.EPI_COLS, dtype=torch.float64, device=batch.device)
+        self.comm_sums = None if comm_out is None else torch.empty(cells, T, L.COMM_COLS, dtype=torch.float64, device=batch.device)
+
+    def round(self, group_size, take, accumulate, comm):
+        eng, batch = self.eng, self.batch
+        L.run("cm_episode_curves", self.T, batch.B, batch.N, self.scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
+              L.ptr(eng.path_len), L.ptr(eng.dist_adj), group_size, take, int(accumulate), L.ptr(self.sums))
+        if self.comm_sums is not None:
+            L.run("cm_comm_curves", self.T, batch.B, batch.N, batch.Lh, L.ptr(eng.path_len), L.ptr(comm.stats), group_size, take,
+                  int(accumulate), L.ptr(self.comm_sums))
+
+    def means(self):
+        L.run("cm_curve_means", self.cells, self.T, self.n_epi, self.scen, self.batch.N, L.ptr(self.sums), L.ptr(self.out))
+        if self.comm_sums is not None:
+            L.run("cm_comm_curve_means", self.cells, self.T, self.n_epi, self.batch.N, self.batch.Lh, L.ptr(self.comm_sums),
+                  L.ptr(self.comm_out))
+
+    @staticmethod
+    def keys(rows, comm_rows):
+        """The host tables [cells, 9, T] (and [cells, 4, T] or None) -> per cell its `curves` dict; delivery by _CommStats.keys's
+        rule per step, for all cells at once."""
+        out = [{name: cell[i] for i, name in enumerate(['success'] + VECTORS)} for cell in rows]
+        if comm_rows is not None:
+            rd, hd = comm_rows[:, COMM_STATS.index("range_degree")], comm_rows[:, COMM_STATS.index("heard_degree")]
+            some = rd != 0
+            delivery = np.where(some, hd / np.where(some, rd, 1.0), 1.0)
+            for d, cell, dl in zip(out, comm_rows, delivery):
+                d.update({name: cell[i] for i, name in enumerate(COMM_STATS)})
+                d["delivery"] = dl
+        return out
 
 
-def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True):
+def _summary_buffers(cells, comm_stats, device, curve_steps=0):
+    """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None, and with
+    curve_steps = T > 0 its [cells, T, 9] curves view and its [cells, T, 4] comm curves view, else None)."""
+    sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm_stats else 0, cells * curve_steps * L.EPI_COLS,
+             cells * curve_steps * L.EPC_COLS if comm_stats else 0]
+    flat = torch.empty(sum(sizes), dtype=torch.float64, device=device)
+    parts = [p if p.numel() else None for p in flat.split(sizes)]
+    shapes = [(cells, L.SUM_COLS), (cells, L.EPC_COLS), (cells, curve_steps, L.EPI_COLS), (cells, curve_steps, L.EPC_COLS)]
+    return (flat,) + tuple(None if p is None else p.view(shape) for p, shape in zip(parts, shapes))
+
+
+def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True,
+           curves=False):
     """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
     refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
     [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  Per round reset, play, bump, check_status, the
     episode rows of groups of E envs into the device table [K*C, n_eval_episodes, 9] (and _CommStats.round); then the table's
-    reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer."""
+    reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer.  curves: _Curves.round behind
+    every round's rows, _Curves.means behind the reductions, their doubles in the same buffer."""
     single = not isinstance(policies, (PolicySet, list, tuple))
     C_ = 1 if conds is None else len(conds)
 
@@ -251,8 +302,9 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     chunk = conds is not None or not single
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    flat, out, comm_out = _summary_buffers(cells, comm_stats, batch.device)
+    flat, out, comm_out, curve_out, comm_curve_out = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0)
     comm = _CommStats(eng, batch, T, cells, n_epi, comm_out) if comm_stats else None
+    curve = _Curves(eng, batch, T, cells, n_epi, scen, curve_out, comm_curve_out) if curves else None
     done = 0
     while done < n_epi:
         eng.reset()
@@ -264,14 +316,25 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
               L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table))
         if comm:
             comm.round(E, take, done)
+        if curve:
+            curve.round(E, take, done > 0, comm)
         done += take
     L.run("cm_episode_means", cells, n_epi, L.ptr(table), L.ptr(out))
     if comm:
         comm.means()
+    if curve:
+        curve.means()
     host_all = flat.cpu().numpy()
-    host = host_all[:cells * L.SUM_COLS].reshape(cells, L.SUM_COLS)
-    host_comm = host_all[cells * L.SUM_COLS:].reshape(cells, L.EPC_COLS) if comm else None
+    sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm else 0, cells * T * L.EPI_COLS if curve else 0]
+    ends = np.cumsum(sizes)
+    host = host_all[:ends[0]].reshape(cells, L.SUM_COLS)
+    host_comm = host_all[ends[0]:ends[1]].reshape(cells, L.EPC_COLS) if comm else None
+    # one transposition per table: a cell's curve is then a contiguous row
+    host_curves = np.ascontiguousarray(host_all[ends[1]:ends[2]].reshape(cells, T, L.EPI_COLS).transpose(0, 2, 1)) if curve else None
+    host_comm_curves = (np.ascontiguousarray(host_all[ends[2]:].reshape(cells, T, L.EPC_COLS).transpose(0, 2, 1))
+                        if curve and comm else None)
     bound = base.bound_return
+    cell_curves = curve.keys(host_curves, host_comm_curves) if curve else None
     res = []
     for g in range(cells):
         d = dict(n_episodes=n_epi, success=float(host[g, 0]))
@@ -286,6 +349,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             d.update(comm.keys(host_comm[g]))
             if episodes:
                 d["comm_episodes"] = comm.table[g]
+        if curve:
+            d["curves"] = cell_curves[g]
         res.append(d)
     env.eval_n_epi = n_epi
     env.last_eval_average_reward = shaped([d["reward"] / bound for d in res])
@@ -293,7 +358,7 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
 
 
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
-                 episodes=False, comm_stats=False):
+                 episodes=False, comm_stats=False, curves=False):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
     eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
     the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
@@ -316,8 +381,21 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     hop), reach (mean number of team mates whose information can arrive within the net's hops), range_reach (the same without
     channel loss) and delivery = heard_degree / range_degree (1.0 when nobody is in range); with episodes=True also
     `comm_episodes`, the [n_eval_episodes, 4] device table behind the first four.  Off (the default), nothing is launched,
-    allocated or returned beyond the above and the results are bit for bit the same."""
-    return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats)
+    allocated or returned beyond the above and the results are bit for bit the same.
+    curves=True adds `curves` to every dict: numpy float64 arrays of length max_env_steps keyed success and every name of
+    VECTORS - entry t is the mean over ALL n_eval_episodes episodes of the per-step value eval_model lists for step t, an episode
+    that has ended counting as zero (the reference pads its per-step lists with zeros to max_env_steps before it saves them as
+    rewMat3, testing.py:307-324).  curves['step_cnt'][t] is therefore the share of episodes still running at step t, and another
+    curve divided by it the mean over the running episodes; a summed vector's curve adds up to the vector's summary value.  With
+    comm_stats=True also every name of COMM_KEYS, from the graphs the policies acted through at step t (delivery[t] =
+    heard_degree[t] / range_degree[t], 1.0 where nobody is in range - or no episode runs).  Behind every round ONE
+    cm_episode_curves launch (and ONE cm_comm_curves launch) adds the round's per-step sums to a device table [K, T, 9]
+    ([K, T, 4]), after the last round ONE cm_curve_means (cm_comm_curve_means) launch divides them; the doubles ride in the same
+    copy.  Integer-valued sums are exact and divided once, the reward sums have one fixed order: the same episodes give the same
+    bits.  Off (the default), nothing is launched, allocated or returned beyond the above and the results are bit for bit the
+    same."""
+    return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
+                  curves=curves)
 
 
 def sweep_layout(B, K, C, env_id_offset=0, paired=True):
@@ -333,7 +411,7 @@ def sweep_layout(B, K, C, env_id_offset=0, paired=True):
 
 
 def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
-               episodes=False, comm_stats=False):
+               episodes=False, comm_stats=False, curves=False):
     """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
     conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
     policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
@@ -347,12 +425,15 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     flag, episodes, comm_stats, the refusals and env.eval_n_epi are eval_summary's; env.last_eval_average_reward is a [K][C] list
     ([C] for a single policy).  With comm_stats=True every cell carries eval_summary's communication keys (one cm_comm_stats and
     one cm_episode_comm launch more per round, one cm_comm_means at the end, [K*C, 4] doubles more in the same copy): a robustness
-    curve can then be plotted against what was delivered (delivery, reach), not only against the knob that was turned."""
+    curve can then be plotted against what was delivered (delivery, reach), not only against the knob that was turned.
+    curves=True gives every cell eval_summary's `curves` (per round one cm_episode_curves launch with groups of E envs, with
+    comm_stats one cm_comm_curves launch; [K*C, T, 9] and [K*C, T, 4] doubles more in the same copy): when a lossy channel
+    starts to hurt, and whether delivery collapses as the team spreads out, step by step."""
     conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
     return _score("eval_sweep", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  conds=conds, paired=paired)
+                  conds=conds, paired=paired, curves=curves)
 
 
 def summary_row(summary):

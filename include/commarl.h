@@ -291,6 +291,63 @@ int cm_episode_comm(int32_t T, int32_t B, int32_t N, int32_t L,
 int cm_comm_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPC_COLS] */,
                   double *summary /* [K, CM_EPC_COLS] */, void *stream);
 
+/* Per-step evaluation curves: the rounds of cm_episode_stats / cm_episode_comm reduced over the EPISODES with the step axis kept -
+ * the mean over episodes of the per-step lists the reference's test loop pads with zeros to max_env_steps and saves as rewMat3
+ * (exp_runners/testing.py:307-324, pad_sequence(..., padding_value=0)).  Pure functions of DEVICE arrays.
+ *
+ * cm_episode_curves takes cm_episode_stats's arguments up to `take`; the env-to-group mapping (group k = b / group_size, envs
+ * with b % group_size >= take are not read), the first-episode rule and the episode length n are cm_episode_stats's.  For group k
+ * and step t it forms the SUMS over the group's `take` episodes of the per-step values below, into sums[k][t][CM_EPI_COLS]; an
+ * episode with n <= t contributes zero to every column (the reference's zero padding).  For a running episode (t < n), with
+ * d = details[t][b]:
+ *   column 0 success[t][b]
+ *          1 reward_f64[t][b]                                              (f64)
+ *          2 d[0]          3 the count 1          4 d[1]          5 d[2]          7 d[4]          8 d[3]
+ *          6 the sum of the N x N floats of dist_adj[s][b], s = t + 1 for t < n - 1 and s = n - 1 for the terminal step (n = 1:
+ *            slot 0) - the slots behind cm_episode_stats's nodeDeg; N * N when dist_adj is NULL (the constant full graph)
+ * Columns other than the reward are sums of integers (adjacency entries are 0 or 1), held exactly in a double.  accumulate = 0
+ * overwrites group k's [T, CM_EPI_COLS] block, accumulate = 1 adds to it: the rounds of an evaluation land in one table.  Exactly
+ * the blocks of the B / group_size groups are written.
+ *
+ * cm_curve_means turns `cells` such blocks into curves[cells][T][CM_EPI_COLS]: every sum divided ONCE by the exact product that
+ * makes it the mean over all n_episodes episodes of the zero-padded per-step value eval_model lists (evaluate._episode) -
+ * success, reward, step_cnt by n_episodes; capture_cnt and penalty_cnt by n_episodes (CM_CO: N * n_episodes); move_cnt, nodeDeg,
+ * variable by N * n_episodes; vars2 is 0 (CM_CO: column 8 / (N * n_episodes)).  Column order: CM_EPI_COLS's.  Column 3
+ * (step_cnt) is therefore the share of episodes still running at step t: another column divided by it is the mean over the
+ * RUNNING episodes, where the plain column is the mean over all of them with the ended ones counted as zero.
+ *
+ * cm_comm_curves does the same for the [T+1,B,CM_COMM_COLS] rows of cm_comm_stats: cm_episode_comm's arguments with
+ * (accumulate, sums) in place of the row mapping.  Step t of a running episode adds the row of slot t (the graph the policy
+ * acted through, as in cm_episode_comm) to sums[k][t][CM_COMM_COLS].  cm_comm_curve_means turns `cells` blocks into
+ * curves[cells][T][CM_EPC_COLS] with cm_episode_comm's divisors, n replaced by n_episodes: range_degree, reach and range_reach
+ * by N * n_episodes, heard_degree by N * L * n_episodes.
+ *
+ * All four: no atomics and one writer per entry.  The integer columns are exact; the reward sums add a round's envs in one fixed
+ * order (chunks of 64 envs in ascending order, a chunk's lanes through one xor butterfly) and the rounds in call order, so two
+ * runs on the same inputs write the same bits.  B = 0 or take = 0 launches nothing.  CM_ERR_ARG (text in cm_last_error) before anything is launched: what
+ * cm_episode_stats / cm_episode_comm refuse for the shared arguments, accumulate other than 0 or 1, cells, T or n_episodes
+ * below 1, or a NULL pointer other than dist_adj where there is work to do. */
+int cm_episode_curves(int32_t T, int32_t B, int32_t N, int32_t scenario,     /* CM_PP / CM_CO */
+                      const double *reward_f64,   /* [T,B]   */
+                      const int32_t *details,     /* [T,B,6] */
+                      const int32_t *success,     /* [T,B]   */
+                      const int32_t *path_len,    /* [T,B]   */
+                      const float *dist_adj,      /* [T+1,B,N,N], or NULL = constant full graph */
+                      int32_t group_size, int32_t take, int32_t accumulate,
+                      double *sums,               /* [B/group_size, T, CM_EPI_COLS] */
+                      void *stream);
+int cm_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t scenario, int32_t N,
+                   const double *sums /* [cells, T, CM_EPI_COLS] */, double *curves /* [cells, T, CM_EPI_COLS] */, void *stream);
+int cm_comm_curves(int32_t T, int32_t B, int32_t N, int32_t L,
+                   const int32_t *path_len,    /* [T,B] */
+                   const int32_t *stats,       /* [T+1,B,CM_COMM_COLS] */
+                   int32_t group_size, int32_t take, int32_t accumulate,
+                   double *sums,               /* [B/group_size, T, CM_COMM_COLS] */
+                   void *stream);
+int cm_comm_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N, int32_t L,
+                        const double *sums /* [cells, T, CM_COMM_COLS] */, double *curves /* [cells, T, CM_EPC_COLS] */,
+                        void *stream);
+
 /* Comm-DP policy weights (device pointers), reference state_dict names in comments
  * (SURVEY.md §8 a-16).  Linear weights are passed TRANSPOSED [in,out] (contiguous over the
  * output index) - the veneer keeps a transposed device copy; GCN weights are already [in,out]. */

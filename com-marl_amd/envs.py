@@ -188,6 +188,31 @@ def comm_stats(dist_adj, channels, n_hops, out=None):
     return out
 
 
+def attn_stats(attn, dist_adj, channels, n_hops, out=None):
+    """What a Comm-DP policy's attention does on every graph (cm_attn_stats, include/commarl.h): contiguous f32 CUDA tensors attn
+    [..., N, N] (row i = agent i's softmax weights, as the forward records them), dist_adj [..., N, N] and channels [..., L, N, N]
+    with the same leading shape, either mask None = all ones -> float64 [..., 6]: self, entropy, range_mass, kept_mass, eff_self,
+    eff_entropy, each summed over the graph's N rows (the last three also over the n_hops hops).  A mask entry is set when it is
+    != 0 and the diagonals count as recorded.  One launch on the current stream; `out` receives the values when given."""
+    n_hops = int(n_hops)
+    for t, tail in ((attn, 2), (dist_adj, 2), (channels, 3)):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.dim() >= tail and t.shape[-1] == t.shape[-2])
+        assert t is None or t.is_contiguous(), "cm_attn_stats reads the blocks through the raw pointer"
+    assert attn is not None, "attn_stats: attn is required"
+    lead, N = attn.shape[:-2], attn.shape[-1]
+    if dist_adj is not None:
+        assert dist_adj.shape == attn.shape and dist_adj.device == attn.device
+    if channels is not None:
+        assert channels.shape == (*lead, n_hops, N, N) and channels.device == attn.device
+    if out is None:
+        out = torch.empty(*lead, L.ATTN_COLS, dtype=torch.float64, device=attn.device)
+    assert out.dtype == torch.float64 and out.shape == (*lead, L.ATTN_COLS) and out.device == attn.device and out.is_contiguous()
+    S = out.numel() // L.ATTN_COLS
+    L.run("cm_attn_stats", S, N, n_hops, L.ptr(attn), N * N, L.ptr(dist_adj), N * N, L.ptr(channels), n_hops * N * N, L.ptr(out),
+          device=attn.device)
+    return out
+
+
 class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 

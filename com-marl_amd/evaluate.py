@@ -26,6 +26,9 @@ through the net's hops (cm_comm_stats on the engine's dist_adj / channels, COMM_
 Both take ``curves=True``: the same episodes reduced over the episodes with the STEP axis kept (cm_episode_curves /
 cm_comm_curves behind every round, cm_curve_means / cm_comm_curve_means at the end, in the same single copy) - per step the mean
 over the episodes of the zero-padded lists eval_model returns, i.e. what exp_runners/testing.py:307-324 saves as rewMat3.
+Both take ``attn_stats=True``: what the policy did with what was delivered - the self weight and the entropy of its attention rows,
+the attention mass on links in range and on links that carried something, and the same two of the weights the net really uses
+after masking and renormalising (cm_attn_stats on the engine's recorded attn / dist_adj / channels, ATTN_KEYS in every dict).
 """
 import numpy as np
 import torch
@@ -162,6 +165,18 @@ def eval_models(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200,
 SUMMARY_STATS = ['return_std', 'return_min', 'return_max']     # cm_episode_means columns behind the CM_EPI_COLS means
 COMM_STATS = ['range_degree', 'heard_degree', 'reach', 'range_reach']   # cm_episode_comm / cm_comm_means columns
 COMM_KEYS = COMM_STATS + ['delivery']                          # what comm_stats=True adds to a summary dict
+ATTN_STATS = ['self', 'entropy', 'range_mass', 'kept_mass', 'eff_self', 'eff_entropy']   # cm_episode_attn / cm_attn_means columns
+ATTN_KEYS = ['attn_' + name for name in ATTN_STATS]            # what attn_stats=True adds to a summary dict
+
+
+def _round_channels(eng, batch):
+    """-> (channels, stride in floats) of a round's graphs for cm_comm_stats / cm_attn_stats: the engine's recorded blocks, NULL
+    (ones) for a constant FC channel, the batch's constant block (the identity) with stride 0 for a constant FL channel."""
+    if eng.channels is not None:
+        return eng.channels, batch.Lh * batch.N * batch.N
+    if batch.channelType == "FC":
+        return None, 0
+    return batch.channels, 0
 
 
 class _CommStats:
@@ -179,12 +194,7 @@ class _CommStats:
     def round(self, group_size, take, row0):
         eng, batch = self.eng, self.batch
         B, N, Lh = batch.B, batch.N, batch.Lh
-        if eng.channels is not None:
-            chan, chan_stride = eng.channels, Lh * N * N
-        elif batch.channelType == "FC":
-            chan, chan_stride = None, 0
-        else:
-            chan, chan_stride = batch.channels, 0                      # FL: one constant block (the identity) for every graph
+        chan, chan_stride = _round_channels(eng, batch)
         L.run("cm_comm_stats", (self.T + 1) * B, N, Lh, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride, L.ptr(self.stats))
         L.run("cm_episode_comm", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
               L.ptr(self.table))
@@ -197,6 +207,40 @@ class _CommStats:
         d = {name: float(row[i]) for i, name in enumerate(COMM_STATS)}
         d["delivery"] = d["heard_degree"] / d["range_degree"] if d["range_degree"] != 0 else 1.0
         return d
+
+
+class _AttnStats:
+    """The attn_stats=True side of eval_summary / eval_sweep, on an engine built with store_attn=True: behind every round ONE
+    cm_attn_stats launch over the round's T x B graphs (attn[t] with dist_adj[t] / channels[t], the graph the forward of step t
+    read; constant masks by _CommStats.round's rules) and ONE cm_episode_attn launch into a device table [cells, n_epi, 6]; after
+    the last round ONE cm_attn_means launch.  curves: also ONE cm_attn_curves launch per round into the per-step sums
+    [cells, T, 6] and ONE cm_attn_curve_means launch at the end.  `out` ([cells, 6]) and `curve_out` ([cells, T, 6] or None) are
+    views of the buffer the caller copies to the host."""
+
+    def __init__(self, eng, batch, T, cells, n_epi, out, curve_out):
+        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out, self.curve_out = eng, batch, T, cells, n_epi, out, curve_out
+        f64 = dict(dtype=torch.float64, device=batch.device)
+        self.stats = torch.empty(T, batch.B, L.ATTN_COLS, **f64)
+        self.table = torch.zeros(cells, n_epi, L.EPA_COLS, **f64)
+        self.sums = None if curve_out is None else torch.empty(cells, T, L.ATTN_COLS, **f64)
+
+    def round(self, group_size, take, row0):
+        eng, batch = self.eng, self.batch
+        B, N, Lh = batch.B, batch.N, batch.Lh
+        chan, chan_stride = _round_channels(eng, batch)
+        L.run("cm_attn_stats", self.T * B, N, Lh, L.ptr(eng.attn), N * N, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride,
+              L.ptr(self.stats))
+        L.run("cm_episode_attn", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
+              L.ptr(self.table))
+        if self.sums is not None:
+            L.run("cm_attn_curves", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, int(row0 > 0),
+                  L.ptr(self.sums))
+
+    def means(self):
+        L.run("cm_attn_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
+        if self.sums is not None:
+            L.run("cm_attn_curve_means", self.cells, self.T, self.n_epi, self.batch.N, self.batch.Lh, L.ptr(self.sums),
+                  L.ptr(self.curve_out))
 
 
 class _Curves:
@@ -241,26 +285,33 @@ class _Curves:
         return out
 
 
-def _summary_buffers(cells, comm_stats, device, curve_steps=0):
+def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False):
     """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None, and with
-    curve_steps = T > 0 its [cells, T, 9] curves view and its [cells, T, 4] comm curves view, else None)."""
+    curve_steps = T > 0 its [cells, T, 9] curves view and its [cells, T, 4] comm curves view, else None).  attn_stats: two values
+    more, the buffer's [cells, 6] attention view and its [cells, T, 6] attention curves view (None without curve_steps)."""
     sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm_stats else 0, cells * curve_steps * L.EPI_COLS,
              cells * curve_steps * L.EPC_COLS if comm_stats else 0]
+    shapes = [(cells, L.SUM_COLS), (cells, L.EPC_COLS), (cells, curve_steps, L.EPI_COLS), (cells, curve_steps, L.EPC_COLS)]
+    if attn_stats:
+        sizes += [cells * L.EPA_COLS, cells * curve_steps * L.EPA_COLS]
+        shapes += [(cells, L.EPA_COLS), (cells, curve_steps, L.EPA_COLS)]
     flat = torch.empty(sum(sizes), dtype=torch.float64, device=device)
     parts = [p if p.numel() else None for p in flat.split(sizes)]
-    shapes = [(cells, L.SUM_COLS), (cells, L.EPC_COLS), (cells, curve_steps, L.EPI_COLS), (cells, curve_steps, L.EPC_COLS)]
     return (flat,) + tuple(None if p is None else p.view(shape) for p, shape in zip(parts, shapes))
 
 
 def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True,
-           curves=False):
+           curves=False, attn_stats=False):
     """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
     refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
     [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  Per round reset, play, bump, check_status, the
     episode rows of groups of E envs into the device table [K*C, n_eval_episodes, 9] (and _CommStats.round); then the table's
     reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer.  curves: _Curves.round behind
-    every round's rows, _Curves.means behind the reductions, their doubles in the same buffer."""
+    every round's rows, _Curves.means behind the reductions, their doubles in the same buffer.  attn_stats: the engine keeps
+    its attention output, _AttnStats.round / .means behind _CommStats's, their doubles at the end of the same buffer."""
     single = not isinstance(policies, (PolicySet, list, tuple))
+    if attn_stats and not all(hasattr(p, "comm") for p in ([policies] if single else policies)):
+        raise ValueError(f"{who}: attn_stats=True needs Comm-DP policies (an Obs-DP / CENT policy has no attention output)")
     C_ = 1 if conds is None else len(conds)
 
     def shaped(cells):
@@ -294,7 +345,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     env.eval_n_epi = 0
     ps.sync_weights()
     ps.reset([True] * (C_ * E))
-    eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, **({} if single else dict(groups=[C_ * E] * K)))
+    eng = RolloutEngine(batch, ps, T, store_attn=bool(attn_stats), store_probs=False,
+                        **({} if single else dict(groups=[C_ * E] * K)))
     # eval_summary of a single policy plays eval_model's rounds, which step one by one; every other call asks for the chunk
     # launch, as eval_models does.  A conditions batch declines the fused forms (two launches per step) unless the wrapper was
     # built with fused_conditions=True (GridEnvBatch.fuse_conditions): then teams of 4 play the round as one launch, a single
@@ -302,8 +354,10 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     chunk = conds is not None or not single
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    flat, out, comm_out, curve_out, comm_curve_out = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0)
+    flat, out, comm_out, curve_out, comm_curve_out, *attn_outs = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0,
+                                                                                  bool(attn_stats))
     comm = _CommStats(eng, batch, T, cells, n_epi, comm_out) if comm_stats else None
+    attn = _AttnStats(eng, batch, T, cells, n_epi, *attn_outs) if attn_stats else None
     curve = _Curves(eng, batch, T, cells, n_epi, scen, curve_out, comm_curve_out) if curves else None
     done = 0
     while done < n_epi:
@@ -316,25 +370,35 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
               L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table))
         if comm:
             comm.round(E, take, done)
+        if attn:
+            attn.round(E, take, done)
         if curve:
             curve.round(E, take, done > 0, comm)
         done += take
     L.run("cm_episode_means", cells, n_epi, L.ptr(table), L.ptr(out))
     if comm:
         comm.means()
+    if attn:
+        attn.means()
     if curve:
         curve.means()
     host_all = flat.cpu().numpy()
-    sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm else 0, cells * T * L.EPI_COLS if curve else 0]
+    sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm else 0, cells * T * L.EPI_COLS if curve else 0,
+             cells * T * L.EPC_COLS if curve and comm else 0, cells * L.EPA_COLS if attn else 0]
     ends = np.cumsum(sizes)
     host = host_all[:ends[0]].reshape(cells, L.SUM_COLS)
     host_comm = host_all[ends[0]:ends[1]].reshape(cells, L.EPC_COLS) if comm else None
     # one transposition per table: a cell's curve is then a contiguous row
     host_curves = np.ascontiguousarray(host_all[ends[1]:ends[2]].reshape(cells, T, L.EPI_COLS).transpose(0, 2, 1)) if curve else None
-    host_comm_curves = (np.ascontiguousarray(host_all[ends[2]:].reshape(cells, T, L.EPC_COLS).transpose(0, 2, 1))
+    host_comm_curves = (np.ascontiguousarray(host_all[ends[2]:ends[3]].reshape(cells, T, L.EPC_COLS).transpose(0, 2, 1))
                         if curve and comm else None)
+    host_attn = host_all[ends[3]:ends[4]].reshape(cells, L.EPA_COLS) if attn else None
     bound = base.bound_return
     cell_curves = curve.keys(host_curves, host_comm_curves) if curve else None
+    if curve and attn:
+        host_attn_curves = np.ascontiguousarray(host_all[ends[4]:].reshape(cells, T, L.EPA_COLS).transpose(0, 2, 1))
+        for d, cell in zip(cell_curves, host_attn_curves):
+            d.update({name: cell[i] for i, name in enumerate(ATTN_KEYS)})
     res = []
     for g in range(cells):
         d = dict(n_episodes=n_epi, success=float(host[g, 0]))
@@ -349,6 +413,10 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             d.update(comm.keys(host_comm[g]))
             if episodes:
                 d["comm_episodes"] = comm.table[g]
+        if attn:
+            d.update({name: float(host_attn[g, i]) for i, name in enumerate(ATTN_KEYS)})
+            if episodes:
+                d["attn_episodes"] = attn.table[g]
         if curve:
             d["curves"] = cell_curves[g]
         res.append(d)
@@ -358,7 +426,7 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
 
 
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
-                 episodes=False, comm_stats=False, curves=False):
+                 episodes=False, comm_stats=False, curves=False, attn_stats=False):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
     eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
     the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
@@ -393,9 +461,21 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     ([K, T, 4]), after the last round ONE cm_curve_means (cm_comm_curve_means) launch divides them; the doubles ride in the same
     copy.  Integer-valued sums are exact and divided once, the reward sums have one fixed order: the same episodes give the same
     bits.  Off (the default), nothing is launched, allocated or returned beyond the above and the results are bit for bit the
-    same."""
+    same.
+    attn_stats=True (Comm-DP policies; anything else raises ValueError before anything is built) adds what the policy did with
+    what was delivered.  The engine then keeps the attention matrix M every forward writes - row i is agent i's softmax over the
+    team, BEFORE any mask (the reference's attention_weights); for hop l the net uses M * dist_adj * channels[l] renormalised
+    per row.  Every dict gains ATTN_KEYS, means per agent over the graphs the policy acted through (the last three also per hop):
+    attn_self (weight on the agent itself), attn_entropy (nats, of a row of M), attn_range_mass (attention on agents in range),
+    attn_kept_mass (attention on links that carried something), attn_eff_self and attn_eff_entropy (self weight and entropy of
+    the renormalised weights the hop really uses; a row with nothing kept counts as 0); with episodes=True also `attn_episodes`,
+    the [n_eval_episodes, 6] device table behind them; with curves=True the same six names in `curves`.  Behind every round ONE
+    cm_attn_stats launch over the round's T x B graphs and ONE cm_episode_attn launch (with curves ONE cm_attn_curves more), after
+    the last round ONE cm_attn_means (cm_attn_curve_means) launch; the doubles ride in the same copy.  f64 sums in a fixed
+    order: the same episodes give the same bits.  Keeping M costs 4 T B N^2 bytes of device memory for the call.  Off (the
+    default), the engine keeps no attention and nothing is launched, allocated or returned beyond the above."""
     return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  curves=curves)
+                  curves=curves, attn_stats=attn_stats)
 
 
 def sweep_layout(B, K, C, env_id_offset=0, paired=True):
@@ -411,7 +491,7 @@ def sweep_layout(B, K, C, env_id_offset=0, paired=True):
 
 
 def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
-               episodes=False, comm_stats=False, curves=False):
+               episodes=False, comm_stats=False, curves=False, attn_stats=False):
     """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
     conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
     policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
@@ -428,12 +508,16 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     curve can then be plotted against what was delivered (delivery, reach), not only against the knob that was turned.
     curves=True gives every cell eval_summary's `curves` (per round one cm_episode_curves launch with groups of E envs, with
     comm_stats one cm_comm_curves launch; [K*C, T, 9] and [K*C, T, 4] doubles more in the same copy): when a lossy channel
-    starts to hurt, and whether delivery collapses as the team spreads out, step by step."""
+    starts to hurt, and whether delivery collapses as the team spreads out, step by step.
+    attn_stats=True gives every cell eval_summary's ATTN_KEYS (per round one cm_attn_stats and one cm_episode_attn launch with
+    groups of E envs, one cm_attn_means at the end; [K*C, 6] doubles more in the same copy, with curves [K*C, T, 6]): how much
+    attention mass a condition strands on dead links and how far the weights the hops really use concentrate - what explains the
+    curve that delivery and reach only describe."""
     conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
     return _score("eval_sweep", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  conds=conds, paired=paired, curves=curves)
+                  conds=conds, paired=paired, curves=curves, attn_stats=attn_stats)
 
 
 def summary_row(summary):

@@ -291,6 +291,62 @@ int cm_episode_comm(int32_t T, int32_t B, int32_t N, int32_t L,
 int cm_comm_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPC_COLS] */,
                   double *summary /* [K, CM_EPC_COLS] */, void *stream);
 
+/* Attention statistics: what the policy did with what the channel delivered.  The Comm-DP net records its attention matrix M
+ * (row i = agent i's softmax weights over the team, before any mask: the reference's attention_weights); at hop l it uses
+ * A_l = M * dist_adj * channels[l], renormalised per row (comm_base_net.py:101-103).  Pure functions of DEVICE arrays.
+ *
+ * cm_attn_stats turns S graphs into rows of CM_ATTN_COLS doubles.  Graph s reads the N*N floats at attn + s*attn_stride (required;
+ * attn_stride >= N*N), and dist_adj / channels as cm_comm_stats does: strides in floats, a NULL array means all ones, a stride of 0
+ * one block for every graph, any other stride at least the block size, an entry "set" when it is != 0.0f.  Unlike cm_comm_stats the
+ * DIAGONAL of both masks is used as recorded, because the net uses it.  With K_l[i][j] = (dist_adj[i][j] set) && (channels[l][i][j]
+ * set) and W_l[i] = sum_j M[i][j] K_l[i][j], each column a sum over the N rows i, the last three also over the L hops:
+ *   column 0 self        = sum_i M[i][i]
+ *          1 entropy     = sum_i -sum_j M[i][j] ln M[i][j]                 (nats; a term with M == 0 is 0)
+ *          2 range_mass  = sum_i sum_j M[i][j] (dist_adj[i][j] set)
+ *          3 kept_mass   = sum_l sum_i W_l[i]
+ *          4 eff_self    = sum_l sum_i K_l[i][i] M[i][i] / W_l[i]          (a row with W_l[i] == 0 adds 0)
+ *          5 eff_entropy = sum_l sum_i ( ln W_l[i] - (sum_j K_l[i][j] M[i][j] ln M[i][j]) / W_l[i] )      (W_l[i] == 0 adds 0)
+ * Columns 4 and 5 are the self weight and the row entropy of the renormalised A_l - defined WITHOUT the 1e-12 the net adds to the
+ * divisor.  f64 arithmetic on the f32 inputs, one log per attention value and one per row and hop, no atomics; the summation order
+ * depends on (N, L) alone - not on S, the grid or the alignment of the buffers: the same inputs give the same bits.  Exactly S
+ * rows are written; S = 0 launches nothing.  CM_ERR_ARG (text in cm_last_error) before anything is launched: S < 0, N outside
+ * 1..255, L outside 1..8, attn_stride < N*N, a stride of a non-NULL mask that is neither 0 nor at least the block size, or NULL attn
+ * or stats with S > 0.
+ *
+ * cm_episode_attn sums the rows of the slots an episode's policy acted through (0 .. n-1) into one row of CM_EPA_COLS doubles per
+ * episode: cm_episode_comm's arguments, mapping and length rule, `stats` being the [T,B,CM_ATTN_COLS] rows of cm_attn_stats.
+ * Columns 0-2 are divided by n N (means per agent), columns 3-5 by n N L (means per agent and hop), each sum divided once.
+ * cm_attn_means reduces each of K groups of E consecutive rows to their column means, as cm_comm_means does.
+ * cm_attn_curves / cm_attn_curve_means are cm_comm_curves / cm_comm_curve_means for these rows: per group and step the sum over the
+ * running episodes of slot t's row (an ended episode counts as zero; accumulate = 1 adds to the table), then every sum divided
+ * once by N * n_episodes (columns 0-2) or N * L * n_episodes (columns 3-5).  Their refusals are those of their comm twins.
+ * All sums are f64 in one fixed order (lane-strided, then an xor tree; chunks of 64 envs in ascending order). */
+#define CM_ATTN_COLS 6   /* self, entropy, range_mass, kept_mass, eff_self, eff_entropy: sums over a graph's rows (and hops) */
+#define CM_EPA_COLS 6    /* the same names: means per agent (columns 0-2), per agent and hop (columns 3-5) */
+int cm_attn_stats(int32_t S, int32_t N, int32_t L,
+                  const float *attn, int64_t attn_stride,        /* graph s: attn + s*attn_stride, N*N floats */
+                  const float *dist_adj, int64_t adj_stride,     /* graph s: dist_adj + s*adj_stride, N*N floats; NULL = ones */
+                  const float *channels, int64_t chan_stride,    /* graph s: channels + s*chan_stride, L*N*N floats; NULL = ones */
+                  double *stats,                                 /* [S, CM_ATTN_COLS] */
+                  void *stream);
+int cm_episode_attn(int32_t T, int32_t B, int32_t N, int32_t L,
+                    const int32_t *path_len,    /* [T,B] */
+                    const double *stats,        /* [T,B,CM_ATTN_COLS] */
+                    int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0,
+                    double *episodes,           /* [B/group_size * episodes_per_group, CM_EPA_COLS] */
+                    void *stream);
+int cm_attn_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPA_COLS] */,
+                  double *summary /* [K, CM_EPA_COLS] */, void *stream);
+int cm_attn_curves(int32_t T, int32_t B, int32_t N, int32_t L,
+                   const int32_t *path_len,    /* [T,B] */
+                   const double *stats,        /* [T,B,CM_ATTN_COLS] */
+                   int32_t group_size, int32_t take, int32_t accumulate,
+                   double *sums,               /* [B/group_size, T, CM_ATTN_COLS] */
+                   void *stream);
+int cm_attn_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N, int32_t L,
+                        const double *sums /* [cells, T, CM_ATTN_COLS] */, double *curves /* [cells, T, CM_EPA_COLS] */,
+                        void *stream);
+
 /* Per-step evaluation curves: the rounds of cm_episode_stats / cm_episode_comm reduced over the EPISODES with the step axis kept -
  * the mean over episodes of the per-step lists the reference's test loop pads with zeros to max_env_steps and saves as rewMat3
  * (exp_runners/testing.py:307-324, pad_sequence(..., padding_value=0)).  Pure functions of DEVICE arrays.

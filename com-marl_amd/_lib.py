@@ -18,6 +18,7 @@ ENT_ADD, ENT_SOFTPLUS, ENT_STOP_GRAD = 1, 2, 4                              # cm
 EPI_COLS, SUM_COLS = 9, 12                                                  # cm_episode_stats / cm_episode_means row widths
 COMM_COLS, EPC_COLS = 4, 4                                                  # cm_comm_stats / cm_episode_comm, cm_comm_means row widths
 ATTN_COLS, EPA_COLS = 6, 6                                                  # cm_attn_stats / cm_episode_attn, cm_attn_means row widths
+LISTEN_COLS, EPL_COLS = 6, 6                                                # cm_listen_stats / cm_episode_listen, cm_listen_means row widths
 
 
 class EnvCfg(C.Structure):
@@ -253,6 +254,15 @@ _SIGNATURES = {
     "cm_attn_curves": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_void_p, C.c_void_p]),
     "cm_attn_curve_means": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # listening statistics (csrc/cm_listen_stats.hip): cm_listen_stats, then the attention reductions with every column per agent
+    "cm_listen_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p]),
+    "cm_episode_listen": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p]),
+    "cm_listen_means": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_listen_curves": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p]),
+    "cm_listen_curve_means": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_chunk_tail": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cm_linear_act_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

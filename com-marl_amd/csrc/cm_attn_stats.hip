@@ -23,7 +23,8 @@
 // W, P and LC are template arguments, so no private array is indexed dynamically: no private segment.
 // cm_episode_attn / cm_attn_means and cm_attn_curves / cm_attn_curve_means are the reductions of cm_episode_comm / cm_comm_means
 // (csrc/cm_comm_stats.hip) and cm_comm_curves / cm_comm_curve_means (csrc/cm_episode_curves.hip) for rows of doubles: the same
-// decompositions, f64 sums in one fixed order (lane-strided, then the xor tree).
+// decompositions, f64 sums in one fixed order (lane-strided, then the xor tree).  Their host side is at::episode_rows / group_means /
+// curve_sums / curve_means (cm_internal.h), which csrc/cm_listen_stats.hip's reductions share: they take the entry point's name.
 #include "cm_internal.h"
 
 namespace cm {
@@ -530,6 +531,70 @@ static int tile_of(int groups, int T) {
     return tile;
 }
 
+// ---- the reductions' host side, shared with the cm_*listen* entry points (cm_internal.h); `who` names the entry point -----------------
+static int refuse(const char *who, const char *what) { return set_error(CM_ERR_ARG, std::string(who) + ": " + what); }
+
+int episode_rows(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
+                 int episodes_per_group, int row0, double *episodes, void *stream) {
+    if (T < 1 || B < 0) return refuse(who, "T >= 1 and B >= 0 required");
+    if (N < 1 || N > MAX_N) return refuse(who, "1 <= n_agents <= 255 required");
+    if (L < 1 || L > MAX_L) return refuse(who, "1 <= n_hops <= 8 required");
+    if (group_size < 1 || B % group_size != 0) return refuse(who, "group_size >= 1 must divide B");
+    if (take < 0 || take > group_size) return refuse(who, "0 <= take <= group_size required");
+    if (row0 < 0 || (int64_t)row0 + take > episodes_per_group)
+        return refuse(who, "rows row0 .. row0 + take - 1 must lie in 0 .. episodes_per_group - 1");
+    if (B == 0 || take == 0) return CM_OK;
+    if (!path_len || !stats || !episodes) return refuse(who, "null argument");
+    const int n_rows = (int)((int64_t)(B / group_size) * take);     // <= B
+    const int grid = (n_rows + WAVES - 1) / WAVES;
+    hipLaunchKernelGGL(episode_attn_kernel, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, T, B, N, L, path_len, stats, group_size,
+                       take, episodes_per_group, row0, n_rows, episodes);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+int group_means(const char *who, int K, int E, const double *episodes, double *summary, void *stream) {
+    if (K < 1 || E < 1) return refuse(who, "K >= 1 and E >= 1 required");
+    if (!episodes || !summary) return refuse(who, "null argument");
+    const int grid = (K + WAVES - 1) / WAVES;
+    hipLaunchKernelGGL(attn_means_kernel, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, K, E, episodes, summary);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+int curve_sums(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
+               int accumulate, double *sums, void *stream) {
+    if (T < 1 || B < 0) return refuse(who, "T >= 1 and B >= 0 required");
+    if (N < 1 || N > MAX_N) return refuse(who, "1 <= n_agents <= 255 required");
+    if (L < 1 || L > MAX_L) return refuse(who, "1 <= n_hops <= 8 required");
+    if (group_size < 1 || B % group_size != 0) return refuse(who, "group_size >= 1 must divide B");
+    if (take < 0 || take > group_size) return refuse(who, "0 <= take <= group_size required");
+    if (accumulate != 0 && accumulate != 1) return refuse(who, "accumulate must be 0 or 1");
+    if (B == 0 || take == 0) return CM_OK;
+    if (!path_len || !stats || !sums) return refuse(who, "null argument");
+    const int groups = B / group_size, tile = tile_of(groups, T), tiles = (T + tile - 1) / tile;
+    const long long n_waves = (long long)groups * tiles;
+    const long long grid = (n_waves + WAVES - 1) / WAVES;
+    if (grid > INT32_MAX) return refuse(who, "too many (group, step) pairs for one launch");
+    hipLaunchKernelGGL(attn_curves_kernel, dim3((unsigned)grid), dim3(TPB), 0, (hipStream_t)stream, T, B, path_len, stats, group_size,
+                       take, tile, tiles, n_waves, accumulate, sums);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
+int curve_means(const char *who, int cells, int T, int n_episodes, int N, int L, const double *sums, double *curves, void *stream) {
+    if (cells < 1 || T < 1 || n_episodes < 1) return refuse(who, "cells, T and n_episodes >= 1 required");
+    if (N < 1 || N > MAX_N) return refuse(who, "1 <= n_agents <= 255 required");
+    if (L < 1 || L > MAX_L) return refuse(who, "1 <= n_hops <= 8 required");
+    if (!sums || !curves) return refuse(who, "null argument");
+    const long long n = (long long)cells * T * CM_EPA_COLS;
+    const long long blocks = (n + TPB - 1) / TPB;
+    hipLaunchKernelGGL(attn_curve_means_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(TPB), 0, (hipStream_t)stream, n,
+                       n_episodes, N, L, sums, curves);
+    CM_HIP(hipGetLastError());
+    return CM_OK;
+}
+
 }  // namespace at
 }  // namespace cm
 
@@ -566,63 +631,19 @@ extern "C" int cm_attn_stats(int32_t S, int32_t N, int32_t L, const float *attn,
 extern "C" int cm_episode_attn(int32_t T, int32_t B, int32_t N, int32_t L, const int32_t *path_len, const double *stats,
                                int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0, double *episodes,
                                void *stream) {
-    if (T < 1 || B < 0) return set_error(CM_ERR_ARG, "cm_episode_attn: T >= 1 and B >= 0 required");
-    if (N < 1 || N > at::MAX_N) return set_error(CM_ERR_ARG, "cm_episode_attn: 1 <= n_agents <= 255 required");
-    if (L < 1 || L > at::MAX_L) return set_error(CM_ERR_ARG, "cm_episode_attn: 1 <= n_hops <= 8 required");
-    if (group_size < 1 || B % group_size != 0) return set_error(CM_ERR_ARG, "cm_episode_attn: group_size >= 1 must divide B");
-    if (take < 0 || take > group_size) return set_error(CM_ERR_ARG, "cm_episode_attn: 0 <= take <= group_size required");
-    if (row0 < 0 || (int64_t)row0 + take > episodes_per_group)
-        return set_error(CM_ERR_ARG, "cm_episode_attn: rows row0 .. row0 + take - 1 must lie in 0 .. episodes_per_group - 1");
-    if (B == 0 || take == 0) return CM_OK;
-    if (!path_len || !stats || !episodes) return set_error(CM_ERR_ARG, "cm_episode_attn: null argument");
-    const int n_rows = (int)((int64_t)(B / group_size) * take);     // <= B
-    const int grid = (n_rows + at::WAVES - 1) / at::WAVES;
-    hipLaunchKernelGGL(at::episode_attn_kernel, dim3(grid), dim3(at::TPB), 0, (hipStream_t)stream, T, B, N, L, path_len, stats,
-                       group_size, take, episodes_per_group, row0, n_rows, episodes);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return at::episode_rows("cm_episode_attn", T, B, N, L, path_len, stats, group_size, take, episodes_per_group, row0, episodes, stream);
 }
 
 extern "C" int cm_attn_means(int32_t K, int32_t E, const double *episodes, double *summary, void *stream) {
-    if (K < 1 || E < 1) return set_error(CM_ERR_ARG, "cm_attn_means: K >= 1 and E >= 1 required");
-    if (!episodes || !summary) return set_error(CM_ERR_ARG, "cm_attn_means: null argument");
-    const int grid = (K + at::WAVES - 1) / at::WAVES;
-    hipLaunchKernelGGL(at::attn_means_kernel, dim3(grid), dim3(at::TPB), 0, (hipStream_t)stream, K, E, episodes, summary);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return at::group_means("cm_attn_means", K, E, episodes, summary, stream);
 }
 
 extern "C" int cm_attn_curves(int32_t T, int32_t B, int32_t N, int32_t L, const int32_t *path_len, const double *stats,
                               int32_t group_size, int32_t take, int32_t accumulate, double *sums, void *stream) {
-    if (T < 1 || B < 0) return set_error(CM_ERR_ARG, "cm_attn_curves: T >= 1 and B >= 0 required");
-    if (N < 1 || N > at::MAX_N) return set_error(CM_ERR_ARG, "cm_attn_curves: 1 <= n_agents <= 255 required");
-    if (L < 1 || L > at::MAX_L) return set_error(CM_ERR_ARG, "cm_attn_curves: 1 <= n_hops <= 8 required");
-    if (group_size < 1 || B % group_size != 0) return set_error(CM_ERR_ARG, "cm_attn_curves: group_size >= 1 must divide B");
-    if (take < 0 || take > group_size) return set_error(CM_ERR_ARG, "cm_attn_curves: 0 <= take <= group_size required");
-    if (accumulate != 0 && accumulate != 1) return set_error(CM_ERR_ARG, "cm_attn_curves: accumulate must be 0 or 1");
-    if (B == 0 || take == 0) return CM_OK;
-    if (!path_len || !stats || !sums) return set_error(CM_ERR_ARG, "cm_attn_curves: null argument");
-    const int groups = B / group_size, tile = at::tile_of(groups, T), tiles = (T + tile - 1) / tile;
-    const long long n_waves = (long long)groups * tiles;
-    const long long grid = (n_waves + at::WAVES - 1) / at::WAVES;
-    if (grid > INT32_MAX) return set_error(CM_ERR_ARG, "cm_attn_curves: too many (group, step) pairs for one launch");
-    hipLaunchKernelGGL(at::attn_curves_kernel, dim3((unsigned)grid), dim3(at::TPB), 0, (hipStream_t)stream, T, B, path_len, stats,
-                       group_size, take, tile, tiles, n_waves, accumulate, sums);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return at::curve_sums("cm_attn_curves", T, B, N, L, path_len, stats, group_size, take, accumulate, sums, stream);
 }
 
 extern "C" int cm_attn_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N, int32_t L, const double *sums,
                                    double *curves, void *stream) {
-    if (cells < 1 || T < 1 || n_episodes < 1)
-        return set_error(CM_ERR_ARG, "cm_attn_curve_means: cells, T and n_episodes >= 1 required");
-    if (N < 1 || N > at::MAX_N) return set_error(CM_ERR_ARG, "cm_attn_curve_means: 1 <= n_agents <= 255 required");
-    if (L < 1 || L > at::MAX_L) return set_error(CM_ERR_ARG, "cm_attn_curve_means: 1 <= n_hops <= 8 required");
-    if (!sums || !curves) return set_error(CM_ERR_ARG, "cm_attn_curve_means: null argument");
-    const long long n = (long long)cells * T * CM_EPA_COLS;
-    const long long blocks = (n + at::TPB - 1) / at::TPB;
-    hipLaunchKernelGGL(at::attn_curve_means_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(at::TPB), 0,
-                       (hipStream_t)stream, n, n_episodes, N, L, sums, curves);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return at::curve_means("cm_attn_curve_means", cells, T, n_episodes, N, L, sums, curves, stream);
 }

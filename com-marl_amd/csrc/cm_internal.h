@@ -191,4 +191,17 @@ int agg_bwd_mfma(bool det, int S, int N, const float *attn, const float *adj, co
                  int *grid = nullptr);
 int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,
                   float *d_q, float *d_e, void *stream);
+
+// ---- cm_attn_stats.hip: the reductions of rows of six doubles, shared by cm_episode_attn / cm_attn_means / cm_attn_curves /
+// cm_attn_curve_means and their cm_*listen* twins (cm_listen_stats.hip).  `who` names the entry point in the refusals' texts.
+// Columns 0-2 are divided by n N, columns 3-5 by n N L: a caller whose six columns all take n N passes L = 1 (the product by
+// 1.0 is exact) ----
+namespace at {
+int episode_rows(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
+                 int episodes_per_group, int row0, double *episodes, void *stream);
+int group_means(const char *who, int K, int E, const double *episodes, double *summary, void *stream);
+int curve_sums(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
+               int accumulate, double *sums, void *stream);
+int curve_means(const char *who, int cells, int T, int n_episodes, int N, int L, const double *sums, double *curves, void *stream);
+}
 }

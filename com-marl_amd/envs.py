@@ -213,6 +213,25 @@ def attn_stats(attn, dist_adj, channels, n_hops, out=None):
     return out
 
 
+def listen_stats(probs, mute=None, lossless=None, out=None):
+    """Whether the messages changed the action distributions, per graph (cm_listen_stats, include/commarl.h): contiguous f32 CUDA
+    tensors probs [..., N, A] (what the policy acted on) and mute / lossless of the same shape (what it gives under the identity
+    channel / the all-ones channel), either None = identical to probs -> float64 [..., 6]: mute_kl, mute_tv, mute_flip, loss_kl,
+    loss_tv, loss_flip, each summed over the graph's N agents; a None counterfactual's three columns are exact 0.  One launch on
+    the current stream; `out` receives the values when given."""
+    assert probs is not None, "listen_stats: probs is required"
+    for t in (probs, mute, lossless):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.shape == probs.shape and t.device == probs.device)
+        assert t is None or t.is_contiguous(), "cm_listen_stats reads the blocks through the raw pointer"
+    lead, (N, A) = probs.shape[:-2], probs.shape[-2:]
+    if out is None:
+        out = torch.empty(*lead, L.LISTEN_COLS, dtype=torch.float64, device=probs.device)
+    assert out.dtype == torch.float64 and out.shape == (*lead, L.LISTEN_COLS) and out.device == probs.device and out.is_contiguous()
+    S = out.numel() // L.LISTEN_COLS
+    L.run("cm_listen_stats", S, N, A, L.ptr(probs), N * A, L.ptr(mute), N * A, L.ptr(lossless), N * A, L.ptr(out), device=probs.device)
+    return out
+
+
 class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 

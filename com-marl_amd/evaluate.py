@@ -29,6 +29,9 @@ over the episodes of the zero-padded lists eval_model returns, i.e. what exp_run
 Both take ``attn_stats=True``: what the policy did with what was delivered - the self weight and the entropy of its attention rows,
 the attention mass on links in range and on links that carried something, and the same two of the weights the net really uses
 after masking and renormalising (cm_attn_stats on the engine's recorded attn / dist_adj / channels, ATTN_KEYS in every dict).
+Both take ``listen_stats=True``: whether the messages changed what the agents did - the round replayed forward-only under a mute
+and a lossless channel (RolloutEngine.replay_probs) and the action distributions compared with the recorded ones (cm_listen_stats,
+LISTEN_KEYS in every dict).
 """
 import numpy as np
 import torch
@@ -167,6 +170,8 @@ COMM_STATS = ['range_degree', 'heard_degree', 'reach', 'range_reach']   # cm_epi
 COMM_KEYS = COMM_STATS + ['delivery']                          # what comm_stats=True adds to a summary dict
 ATTN_STATS = ['self', 'entropy', 'range_mass', 'kept_mass', 'eff_self', 'eff_entropy']   # cm_episode_attn / cm_attn_means columns
 ATTN_KEYS = ['attn_' + name for name in ATTN_STATS]            # what attn_stats=True adds to a summary dict
+LISTEN_STATS = ['kl', 'tv', 'flip']                            # per counterfactual: cm_episode_listen / cm_listen_means columns
+LISTEN_KEYS = ['listen_' + name for name in LISTEN_STATS] + ['loss_' + name for name in LISTEN_STATS]   # listen_stats=True: mute, lossless
 
 
 def _round_channels(eng, batch):
@@ -243,6 +248,48 @@ class _AttnStats:
                   L.ptr(self.curve_out))
 
 
+class _ListenStats:
+    """The listen_stats=True side of eval_summary / eval_sweep, on an engine built with store_probs=True: behind every round the
+    counterfactual replays of its T slots (RolloutEngine.replay_probs: "identity" = mute, "ones" = lossless) into two buffers
+    [T, B, N, A] of this object, ONE cm_listen_stats launch comparing the recorded probs with them over the round's T x B graphs
+    and ONE cm_episode_listen launch into a device table [cells, n_epi, 6]; after the last round ONE cm_listen_means launch.
+    curves: also ONE cm_listen_curves launch per round into the per-step sums [cells, T, 6] and ONE cm_listen_curve_means launch
+    at the end.  A wrapper with a constant FC channel skips the lossless replay, one with a constant FL channel the mute replay:
+    no buffer, no forward, the counterfactual passed as NULL (its three columns exact 0).  `out` ([cells, 6]) and `curve_out`
+    ([cells, T, 6] or None) are views of the buffer the caller copies to the host."""
+
+    def __init__(self, eng, batch, T, cells, n_epi, out, curve_out):
+        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out, self.curve_out = eng, batch, T, cells, n_epi, out, curve_out
+        self.A = eng.policy._action_dim
+        f64 = dict(dtype=torch.float64, device=batch.device)
+        self.stats = torch.empty(T, batch.B, L.LISTEN_COLS, **f64)
+        self.table = torch.zeros(cells, n_epi, L.EPL_COLS, **f64)
+        self.sums = None if curve_out is None else torch.empty(cells, T, L.LISTEN_COLS, **f64)
+        const = batch.channelType if eng.channels is None else None           # the channel every slot of every round has
+        probs = lambda skip: None if skip else torch.empty(T, batch.B, batch.N, self.A, dtype=torch.float32, device=batch.device)   # noqa: E731
+        self.mute, self.lossless = probs(const == "FL"), probs(const == "FC")
+
+    def round(self, group_size, take, row0):
+        eng, T = self.eng, self.T
+        B, N, A = self.batch.B, self.batch.N, self.A
+        if self.mute is not None:
+            eng.replay_probs(0, T, "identity", self.mute)
+        if self.lossless is not None:
+            eng.replay_probs(0, T, "ones", self.lossless)
+        L.run("cm_listen_stats", T * B, N, A, L.ptr(eng.probs), N * A, L.ptr(self.mute), N * A, L.ptr(self.lossless), N * A,
+              L.ptr(self.stats))
+        L.run("cm_episode_listen", T, B, N, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
+              L.ptr(self.table))
+        if self.sums is not None:
+            L.run("cm_listen_curves", T, B, N, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, int(row0 > 0),
+                  L.ptr(self.sums))
+
+    def means(self):
+        L.run("cm_listen_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
+        if self.sums is not None:
+            L.run("cm_listen_curve_means", self.cells, self.T, self.n_epi, self.batch.N, L.ptr(self.sums), L.ptr(self.curve_out))
+
+
 class _Curves:
     """The curves=True side of eval_summary / eval_sweep: behind every round ONE cm_episode_curves launch on the engine's
     trajectory buffers into the device table of per-step sums [cells, T, 9] - the first round overwrites it, the later ones add -
@@ -285,33 +332,41 @@ class _Curves:
         return out
 
 
-def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False):
+def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False, listen_stats=False):
     """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None, and with
     curve_steps = T > 0 its [cells, T, 9] curves view and its [cells, T, 4] comm curves view, else None).  attn_stats: two values
-    more, the buffer's [cells, 6] attention view and its [cells, T, 6] attention curves view (None without curve_steps)."""
+    more, the buffer's [cells, 6] attention view and its [cells, T, 6] attention curves view (None without curve_steps);
+    listen_stats: behind them the same two for the listening statistics, at the end of the buffer."""
     sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm_stats else 0, cells * curve_steps * L.EPI_COLS,
              cells * curve_steps * L.EPC_COLS if comm_stats else 0]
     shapes = [(cells, L.SUM_COLS), (cells, L.EPC_COLS), (cells, curve_steps, L.EPI_COLS), (cells, curve_steps, L.EPC_COLS)]
     if attn_stats:
         sizes += [cells * L.EPA_COLS, cells * curve_steps * L.EPA_COLS]
         shapes += [(cells, L.EPA_COLS), (cells, curve_steps, L.EPA_COLS)]
+    if listen_stats:
+        sizes += [cells * L.EPL_COLS, cells * curve_steps * L.EPL_COLS]
+        shapes += [(cells, L.EPL_COLS), (cells, curve_steps, L.EPL_COLS)]
     flat = torch.empty(sum(sizes), dtype=torch.float64, device=device)
     parts = [p if p.numel() else None for p in flat.split(sizes)]
     return (flat,) + tuple(None if p is None else p.view(shape) for p, shape in zip(parts, shapes))
 
 
 def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True,
-           curves=False, attn_stats=False):
+           curves=False, attn_stats=False, listen_stats=False):
     """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
     refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
     [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  Per round reset, play, bump, check_status, the
     episode rows of groups of E envs into the device table [K*C, n_eval_episodes, 9] (and _CommStats.round); then the table's
     reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer.  curves: _Curves.round behind
     every round's rows, _Curves.means behind the reductions, their doubles in the same buffer.  attn_stats: the engine keeps
-    its attention output, _AttnStats.round / .means behind _CommStats's, their doubles at the end of the same buffer."""
+    its attention output, _AttnStats.round / .means behind _CommStats's, their doubles behind the curves' in the same buffer.
+    listen_stats: the engine keeps its probabilities, _ListenStats.round / .means behind _AttnStats's, their doubles at the end."""
     single = not isinstance(policies, (PolicySet, list, tuple))
-    if attn_stats and not all(hasattr(p, "comm") for p in ([policies] if single else policies)):
+    comm_dp = all(hasattr(p, "comm") for p in ([policies] if single else policies))
+    if attn_stats and not comm_dp:
         raise ValueError(f"{who}: attn_stats=True needs Comm-DP policies (an Obs-DP / CENT policy has no attention output)")
+    if listen_stats and not comm_dp:
+        raise ValueError(f"{who}: listen_stats=True needs Comm-DP policies (an Obs-DP / CENT policy hears no messages)")
     C_ = 1 if conds is None else len(conds)
 
     def shaped(cells):
@@ -345,7 +400,7 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     env.eval_n_epi = 0
     ps.sync_weights()
     ps.reset([True] * (C_ * E))
-    eng = RolloutEngine(batch, ps, T, store_attn=bool(attn_stats), store_probs=False,
+    eng = RolloutEngine(batch, ps, T, store_attn=bool(attn_stats), store_probs=bool(listen_stats),
                         **({} if single else dict(groups=[C_ * E] * K)))
     # eval_summary of a single policy plays eval_model's rounds, which step one by one; every other call asks for the chunk
     # launch, as eval_models does.  A conditions batch declines the fused forms (two launches per step) unless the wrapper was
@@ -354,10 +409,11 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     chunk = conds is not None or not single
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    flat, out, comm_out, curve_out, comm_curve_out, *attn_outs = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0,
-                                                                                  bool(attn_stats))
+    flat, out, comm_out, curve_out, comm_curve_out, *more = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0,
+                                                                             bool(attn_stats), bool(listen_stats))
     comm = _CommStats(eng, batch, T, cells, n_epi, comm_out) if comm_stats else None
-    attn = _AttnStats(eng, batch, T, cells, n_epi, *attn_outs) if attn_stats else None
+    attn = _AttnStats(eng, batch, T, cells, n_epi, *more[:2]) if attn_stats else None
+    listen = _ListenStats(eng, batch, T, cells, n_epi, *more[-2:]) if listen_stats else None
     curve = _Curves(eng, batch, T, cells, n_epi, scen, curve_out, comm_curve_out) if curves else None
     done = 0
     while done < n_epi:
@@ -372,6 +428,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             comm.round(E, take, done)
         if attn:
             attn.round(E, take, done)
+        if listen:
+            listen.round(E, take, done)
         if curve:
             curve.round(E, take, done > 0, comm)
         done += take
@@ -380,11 +438,14 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
         comm.means()
     if attn:
         attn.means()
+    if listen:
+        listen.means()
     if curve:
         curve.means()
     host_all = flat.cpu().numpy()
     sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm else 0, cells * T * L.EPI_COLS if curve else 0,
-             cells * T * L.EPC_COLS if curve and comm else 0, cells * L.EPA_COLS if attn else 0]
+             cells * T * L.EPC_COLS if curve and comm else 0, cells * L.EPA_COLS if attn else 0,
+             cells * T * L.EPA_COLS if curve and attn else 0, cells * L.EPL_COLS if listen else 0]
     ends = np.cumsum(sizes)
     host = host_all[:ends[0]].reshape(cells, L.SUM_COLS)
     host_comm = host_all[ends[0]:ends[1]].reshape(cells, L.EPC_COLS) if comm else None
@@ -396,9 +457,14 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     bound = base.bound_return
     cell_curves = curve.keys(host_curves, host_comm_curves) if curve else None
     if curve and attn:
-        host_attn_curves = np.ascontiguousarray(host_all[ends[4]:].reshape(cells, T, L.EPA_COLS).transpose(0, 2, 1))
+        host_attn_curves = np.ascontiguousarray(host_all[ends[4]:ends[5]].reshape(cells, T, L.EPA_COLS).transpose(0, 2, 1))
         for d, cell in zip(cell_curves, host_attn_curves):
             d.update({name: cell[i] for i, name in enumerate(ATTN_KEYS)})
+    host_listen = host_all[ends[5]:ends[6]].reshape(cells, L.EPL_COLS) if listen else None
+    if curve and listen:
+        host_listen_curves = np.ascontiguousarray(host_all[ends[6]:].reshape(cells, T, L.EPL_COLS).transpose(0, 2, 1))
+        for d, cell in zip(cell_curves, host_listen_curves):
+            d.update({name: cell[i] for i, name in enumerate(LISTEN_KEYS)})
     res = []
     for g in range(cells):
         d = dict(n_episodes=n_epi, success=float(host[g, 0]))
@@ -417,6 +483,10 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             d.update({name: float(host_attn[g, i]) for i, name in enumerate(ATTN_KEYS)})
             if episodes:
                 d["attn_episodes"] = attn.table[g]
+        if listen:
+            d.update({name: float(host_listen[g, i]) for i, name in enumerate(LISTEN_KEYS)})
+            if episodes:
+                d["listen_episodes"] = listen.table[g]
         if curve:
             d["curves"] = cell_curves[g]
         res.append(d)
@@ -426,7 +496,7 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
 
 
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
-                 episodes=False, comm_stats=False, curves=False, attn_stats=False):
+                 episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
     eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
     the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
@@ -473,9 +543,25 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     cm_attn_stats launch over the round's T x B graphs and ONE cm_episode_attn launch (with curves ONE cm_attn_curves more), after
     the last round ONE cm_attn_means (cm_attn_curve_means) launch; the doubles ride in the same copy.  f64 sums in a fixed
     order: the same episodes give the same bits.  Keeping M costs 4 T B N^2 bytes of device memory for the call.  Off (the
-    default), the engine keeps no attention and nothing is launched, allocated or returned beyond the above."""
+    default), the engine keeps no attention and nothing is launched, allocated or returned beyond the above.
+    listen_stats=True (Comm-DP policies; anything else raises ValueError before anything is built) adds whether the messages
+    changed what the agents did.  The engine then keeps the probabilities p it acted on, and behind every round replays the
+    round's slots forward-only (RolloutEngine.replay_probs: the recorded observations and dist_adj; nothing is drawn, no recorded
+    buffer and no counter moves) under two counterfactual channels: mute - the identity, every agent hears only itself - and
+    lossless - all ones, everything in range is delivered.  Every dict gains LISTEN_KEYS, means per agent over the graphs the
+    policy acted through of, with q the counterfactual probabilities: listen_kl = KL(p || q_mute) in nats (q floored at FLT_MIN;
+    not clamped at 0), listen_tv = the total variation, listen_flip = the share of agents whose greedy action changes; loss_kl,
+    loss_tv, loss_flip the same against q_lossless - what the channel loss changed in the decisions; with episodes=True also
+    `listen_episodes`, the [n_eval_episodes, 6] device table behind them; with curves=True the same six names in `curves`.
+    Behind every round the replays (one forward launch per member and replay; under the identity one per block of
+    rollout.REPLAY_MASK_BYTES of mask), ONE cm_listen_stats launch over the round's T x B graphs and ONE cm_episode_listen launch
+    (with curves ONE cm_listen_curves more), after the last round ONE cm_listen_means (cm_listen_curve_means) launch; the doubles
+    ride at the end of the same copy.  A wrapper with a constant FC channel skips the lossless replay and one with a constant FL
+    channel the mute replay: exact zeros.  f64 sums in a fixed order: the same episodes give the same bits.  The probabilities
+    cost 4 T B N A bytes of device memory each (recorded, mute, lossless).  Off (the default), the engine keeps no
+    probabilities and nothing is launched, allocated or returned beyond the above."""
     return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  curves=curves, attn_stats=attn_stats)
+                  curves=curves, attn_stats=attn_stats, listen_stats=listen_stats)
 
 
 def sweep_layout(B, K, C, env_id_offset=0, paired=True):
@@ -491,7 +577,7 @@ def sweep_layout(B, K, C, env_id_offset=0, paired=True):
 
 
 def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
-               episodes=False, comm_stats=False, curves=False, attn_stats=False):
+               episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False):
     """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
     conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
     policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
@@ -512,12 +598,15 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     attn_stats=True gives every cell eval_summary's ATTN_KEYS (per round one cm_attn_stats and one cm_episode_attn launch with
     groups of E envs, one cm_attn_means at the end; [K*C, 6] doubles more in the same copy, with curves [K*C, T, 6]): how much
     attention mass a condition strands on dead links and how far the weights the hops really use concentrate - what explains the
-    curve that delivery and reach only describe."""
+    curve that delivery and reach only describe.
+    listen_stats=True gives every cell eval_summary's LISTEN_KEYS (per round the two counterfactual replays, one cm_listen_stats
+    and one cm_episode_listen launch with groups of E envs, one cm_listen_means at the end; [K*C, 6] doubles more in the same
+    copy, with curves [K*C, T, 6]): whether a condition changed any decision - a cell that loses nothing has loss_* exactly 0."""
     conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
     return _score("eval_sweep", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  conds=conds, paired=paired, curves=curves, attn_stats=attn_stats)
+                  conds=conds, paired=paired, curves=curves, attn_stats=attn_stats, listen_stats=listen_stats)
 
 
 def summary_row(summary):

@@ -24,6 +24,13 @@ from .nets import PolicySet
 
 WG_ENVS = 16                 # envs per workgroup of the wave-owned kernels: a multi-policy launch gives each workgroup one policy
 
+# replay_probs under the identity channel: bytes of the one constant mask block an engine keeps for it (cm_policy_forward reads a
+# channel block per env state, so the identity is written out for the rows of ONE launch and reused by the next) - at the
+# headline shape (N = 4, 2 hops: 128 bytes per env state) 64 slots of 4096 envs per launch; never below one env state (at most
+# 2 MB: 8 hops x 255^2).  REPLAY_ROW_ALIGN: launches start on whole workgroups of the forward kernels
+REPLAY_MASK_BYTES = 32 << 20
+REPLAY_ROW_ALIGN = 64
+
 _null = contextlib.nullcontext
 
 
@@ -103,6 +110,7 @@ class RolloutEngine:
         # copy on its own stream (all copies always hold the same value), so that the shards' chains share nothing
         self.step_bases = [torch.zeros(1, dtype=i32, device=dev) for _ in self.parts]
         self._graphs = {}
+        self._eye_rows = None                    # replay_probs' constant identity block, built on first use
         # fused: step() uses cm_rollout_step (policy forward + sample + env step in one launch) where the library has a fused
         # kernel for the shape.  fused="auto": teams of 4 only - for larger teams the fused kernel runs the env step of ONE env on
         # a 256-thread workgroup that is mostly idle (measured per step: N = 24 127 vs 95 us, N = 72 424 vs 176 us), so they take
@@ -254,6 +262,75 @@ class RolloutEngine:
         if self.channels is not None:
             o["channels"] = self.channels[t + 1][lo:hi]
         return o
+
+    # ---- forward-only replay ---------------------------------------------------------------------
+    def _identity_rows(self, rows):
+        """-> [r, Lh, N, N] identity channels (every agent hears only itself, on every hop) for r = min(rows, what
+        REPLAY_MASK_BYTES holds, at least one) env states: ONE constant block per engine, reused by every launch of every
+        replay - a [T, B, Lh, N, N] tensor is never built."""
+        env = self.env
+        cap = max(1, REPLAY_MASK_BYTES // (4 * env.Lh * env.N * env.N))
+        if cap >= REPLAY_ROW_ALIGN:
+            cap -= cap % REPLAY_ROW_ALIGN                   # whole workgroups of the forward kernels in every launch but the last
+        r = min(int(rows), cap)
+        if self._eye_rows is None or self._eye_rows.shape[0] < r:
+            self._eye_rows = torch.eye(env.N, dtype=torch.float32, device=env.device).expand(r, env.Lh, env.N, env.N).contiguous()
+        return self._eye_rows[:r]
+
+    def _replay_rows(self, pol, obs, adj, chan, channels, out):
+        """`pol`'s probabilities on the env states obs [R, N*d] / adj [R, N, N] | None under `channels` (chan [R, Lh, N, N] | None:
+        the recorded ones) into out [R, N, A]: act_device without actions, attention or a draw - one launch, or one per
+        _identity_rows block of rows under the identity."""
+        R = obs.shape[0]
+        eye = self._identity_rows(R) if channels == "identity" else None
+        step = R if eye is None else eye.shape[0]
+        for r0 in range(0, R, step):
+            r1 = min(R, r0 + step)
+            ch = eye[:r1 - r0] if eye is not None else (chan[r0:r1] if channels == "recorded" and chan is not None else None)
+            pol.act_device(obs[r0:r1], None, None if adj is None else adj[r0:r1], ch, greedy=True, want_actions=False,
+                           want_attn=False, out_probs=out[r0:r1], policy_step=0)
+
+    @torch.no_grad()
+    def replay_probs(self, t0, n, channels, out):
+        """Forward only: the action probabilities of the recorded slots t0 .. t0+n-1 - their obs[t] and dist_adj[t] as they
+        stand - under `channels` into out [n, B, N, A] (f32, contiguous, the caller's):
+            "recorded"   channels[t] as recorded (what the round's forward read: NULL where the engine keeps none),
+            "identity"   every agent hears only itself on every hop (the FL channel),
+            "ones"       everything in range is delivered (the FC channel; passed as NULL).
+        For every env they are what its policy's act_device(..., want_actions=False) returns on these inputs.  A single policy
+        takes ONE launch over the n * B rows (slots are contiguous in the buffers), a PolicySet ONE launch per member over
+        its n * (hi - lo) rows, gathered from the slots by device copies and scattered back (a member's envs are contiguous
+        within a slot only; the gathered rows of one member at a time are the replay's only temporaries).  Under the identity
+        a launch covers at most the rows of the engine's constant mask block, which REPLAY_MASK_BYTES bounds whatever n is.
+        Nothing else changes: no recorded buffer is written, nothing is drawn, and neither the sampler's Philox base nor a
+        policy's step counter moves.  The weight packs are used as they are (the round that recorded the slots synced them).
+        On the current stream, behind the round (play() has joined the shards)."""
+        env = self.env
+        B, N, d, Lh, A = env.B, env.N, env.d, env.Lh, self.policy._action_dim
+        t0, n = int(t0), int(n)
+        if channels not in ("recorded", "identity", "ones"):
+            raise ValueError(f"replay_probs: channels must be 'recorded', 'identity' or 'ones', not {channels!r}")
+        if not (n >= 1 and t0 >= 0 and t0 + n <= self.H):
+            raise ValueError(f"replay_probs: slots {t0} .. {t0 + n - 1} are not within the horizon {self.H}")
+        if not (out.dtype == torch.float32 and tuple(out.shape) == (n, B, N, A) and out.is_contiguous() and out.device == self.obs.device):
+            raise ValueError(f"replay_probs: out must be a contiguous f32 tensor [{n}, {B}, {N}, {A}] on the engine's device")
+        adj, chan = self.dist_adj, self.channels
+        if self.multi_form is None:
+            flat = lambda b, *tail: None if b is None else b[t0:t0 + n].view(n * B, *tail)    # noqa: E731
+            self._replay_rows(self.policy, flat(self.obs, N * d), flat(adj, N, N), flat(chan, Lh, N, N), channels,
+                              out.view(n * B, N, A))
+            return out
+        if channels != "recorded":
+            chan = None
+        for pol, (lo, hi) in zip(self.policy, self.groups):
+            # a member's envs are contiguous within a slot only: its rows of the n slots are gathered (device copies), go
+            # through ONE launch, and the probabilities are scattered back - 3 copies + 1 launch instead of n launches
+            rows = n * (hi - lo)
+            take = lambda b, *tail: None if b is None else b[t0:t0 + n, lo:hi].reshape(rows, *tail)   # noqa: E731
+            probs = torch.empty(rows, N, A, dtype=torch.float32, device=out.device)
+            self._replay_rows(pol, take(self.obs, N * d), take(adj, N, N), take(chan, Lh, N, N), channels, probs)
+            out[:, lo:hi] = probs.view(n, hi - lo, N, A)
+        return out
 
     def fill_diameters(self, t0, n):
         """diameter[t] of the n slots t0 .. t0+n-1 from dist_adj[t], in one launch on the current stream (the caller has

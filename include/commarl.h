@@ -347,6 +347,54 @@ int cm_attn_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N,
                         const double *sums /* [cells, T, CM_ATTN_COLS] */, double *curves /* [cells, T, CM_EPA_COLS] */,
                         void *stream);
 
+/* Listening statistics: whether the messages changed what the agents did.  For one agent row let p be the action probabilities
+ * the policy acted on and q the ones the same net gives on the same observations and range graph under a counterfactual channel
+ * - mute (the identity: every agent hears only itself) or lossless (all ones: everything in range is delivered); both f32 of
+ * length A.  In f64 on those f32 values:
+ *   kl   = sum over a with p[a] > 0 of p[a] * (ln p[a] - ln max(q[a], FLT_MIN))     (FLT_MIN = 2^-126; not clamped: f32 rows sum to
+ *                                                                                     1 only within rounding, so a hair below 0 is possible)
+ *   tv   = 0.5 * sum_a |p[a] - q[a]|
+ *   flip = 1 if argmax(p) != argmax(q) else 0                                        (the first index on ties, compared as f32)
+ * Pure functions of DEVICE arrays.
+ *
+ * cm_listen_stats turns S graphs of N agents into rows of CM_LISTEN_COLS doubles, each column the sum over the N agent rows in
+ * agent order: mute_kl, mute_tv, mute_flip, loss_kl, loss_tv, loss_flip.  Graph s reads the N*A floats at probs + s*probs_stride
+ * and, for each counterfactual that is given, at mute + s*mute_stride / lossless + s*lossless_stride (strides in floats, at least
+ * N*A).  A NULL counterfactual means "identical to probs": its three columns are written as exact 0 and nothing is read.  No
+ * atomics; the summation order depends on (N, A) alone - not on S, the grid, the strides or the alignment of the buffers: the same
+ * inputs give the same bits.  Exactly S rows are written; S = 0 launches nothing.  CM_ERR_ARG (text in cm_last_error) before
+ * anything is launched: S < 0, N outside 1..255, A outside 2..8, a stride of a non-NULL array below N*A, or NULL probs or out with
+ * S > 0.
+ *
+ * cm_episode_listen / cm_listen_means / cm_listen_curves / cm_listen_curve_means are cm_episode_attn / cm_attn_means /
+ * cm_attn_curves / cm_attn_curve_means for these rows - the same arguments without n_hops, the same mapping, length rule, refusals
+ * and fixed summation order - with ALL six columns divided by n N (N * n_episodes for the curves): there is no per-hop factor. */
+#define CM_LISTEN_COLS 6   /* mute_kl, mute_tv, mute_flip, loss_kl, loss_tv, loss_flip: sums over a graph's agent rows */
+#define CM_EPL_COLS 6      /* the same names: means per agent */
+int cm_listen_stats(int32_t S, int32_t N, int32_t A,
+                    const float *probs, int64_t probs_stride,        /* graph s: probs + s*probs_stride, N*A floats */
+                    const float *mute, int64_t mute_stride,          /* graph s: mute + s*mute_stride, N*A floats; NULL = probs */
+                    const float *lossless, int64_t lossless_stride,  /* graph s: lossless + s*lossless_stride; NULL = probs */
+                    double *out,                                     /* [S, CM_LISTEN_COLS] */
+                    void *stream);
+int cm_episode_listen(int32_t T, int32_t B, int32_t N,
+                      const int32_t *path_len,    /* [T,B] */
+                      const double *stats,        /* [T,B,CM_LISTEN_COLS] */
+                      int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0,
+                      double *episodes,           /* [B/group_size * episodes_per_group, CM_EPL_COLS] */
+                      void *stream);
+int cm_listen_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPL_COLS] */,
+                    double *summary /* [K, CM_EPL_COLS] */, void *stream);
+int cm_listen_curves(int32_t T, int32_t B, int32_t N,
+                     const int32_t *path_len,    /* [T,B] */
+                     const double *stats,        /* [T,B,CM_LISTEN_COLS] */
+                     int32_t group_size, int32_t take, int32_t accumulate,
+                     double *sums,               /* [B/group_size, T, CM_LISTEN_COLS] */
+                     void *stream);
+int cm_listen_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N,
+                          const double *sums /* [cells, T, CM_LISTEN_COLS] */, double *curves /* [cells, T, CM_EPL_COLS] */,
+                          void *stream);
+
 /* Per-step evaluation curves: the rounds of cm_episode_stats / cm_episode_comm reduced over the EPISODES with the step axis kept -
  * the mean over episodes of the per-step lists the reference's test loop pads with zeros to max_env_steps and saves as rewMat3
  * (exp_runners/testing.py:307-324, pad_sequence(..., padding_value=0)).  Pure functions of DEVICE arrays.

@@ -19,6 +19,7 @@ EPI_COLS, SUM_COLS = 9, 12                                                  # cm
 COMM_COLS, EPC_COLS = 4, 4                                                  # cm_comm_stats / cm_episode_comm, cm_comm_means row widths
 ATTN_COLS, EPA_COLS = 6, 6                                                  # cm_attn_stats / cm_episode_attn, cm_attn_means row widths
 LISTEN_COLS, EPL_COLS = 6, 6                                                # cm_listen_stats / cm_episode_listen, cm_listen_means row widths
+VALUE_COLS, EPV_COLS = 6, 6                                                 # cm_value_stats / cm_episode_value, cm_value_means row widths
 
 
 class EnvCfg(C.Structure):
@@ -263,6 +264,14 @@ _SIGNATURES = {
     "cm_listen_curves": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_void_p, C.c_void_p]),
     "cm_listen_curve_means": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # critic statistics (csrc/cm_value_stats.hip): cm_value_stats, then the attention reductions with every column per step
+    "cm_value_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                 C.c_void_p]),
+    "cm_episode_value": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    "cm_value_means": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_value_curves": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "cm_value_curve_means": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_chunk_tail": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cm_linear_act_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

@@ -232,6 +232,30 @@ def listen_stats(probs, mute=None, lossless=None, out=None):
     return out
 
 
+def value_stats(rewards, path_len, values, mute=None, lossless=None, discount=0.99, out=None):
+    """How well a critic's values explain the returns, per recorded step (cm_value_stats, include/commarl.h): contiguous CUDA
+    tensors rewards [T, B] (float64), path_len [T, B] (int32: > 0 where an episode ended) and values [T, B] (float32), and
+    mute / lossless of values' shape and type (the critic's values under the identity channel / the all-ones channel), either
+    None = identical to values -> float64 [T, B, 6]: value, ret (the return-to-go discounted by `discount` within the env's
+    first episode, no bootstrap), sq_err, ret_sq, msg_value = value - mute, loss_value = lossless - value; rows behind the first
+    episode's end are exact zeros and a None counterfactual's column is exact 0.  One launch on the current stream; `out`
+    receives the values when given."""
+    assert rewards is not None and path_len is not None and values is not None, "value_stats: rewards, path_len and values are required"
+    assert rewards.is_cuda and rewards.dim() == 2 and rewards.dtype == torch.float64
+    assert path_len.dtype == torch.int32 and path_len.shape == rewards.shape and path_len.device == rewards.device
+    for t in (values, mute, lossless):
+        assert t is None or (t.dtype == torch.float32 and t.shape == rewards.shape and t.device == rewards.device)
+    for t in (rewards, path_len, values, mute, lossless):
+        assert t is None or t.is_contiguous(), "cm_value_stats reads the arrays through the raw pointer"
+    T, B = rewards.shape
+    if out is None:
+        out = torch.empty(T, B, L.VALUE_COLS, dtype=torch.float64, device=rewards.device)
+    assert out.dtype == torch.float64 and out.shape == (T, B, L.VALUE_COLS) and out.device == rewards.device and out.is_contiguous()
+    L.run("cm_value_stats", T, B, L.ptr(rewards), L.ptr(path_len), L.ptr(values), L.ptr(mute), L.ptr(lossless), float(discount),
+          L.ptr(out), device=rewards.device)
+    return out
+
+
 class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 

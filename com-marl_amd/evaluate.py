@@ -32,6 +32,9 @@ after masking and renormalising (cm_attn_stats on the engine's recorded attn / d
 Both take ``listen_stats=True``: whether the messages changed what the agents did - the round replayed forward-only under a mute
 and a lossless channel (RolloutEngine.replay_probs) and the action distributions compared with the recorded ones (cm_listen_stats,
 LISTEN_KEYS in every dict).
+Both take ``value_stats=True, baselines=...``: how good the critic trained with each policy is - its values on the round's recorded
+slots (RolloutEngine.replay_values) against the discounted returns the episodes went on to collect, and what it believes the
+messages and the channel loss are worth (cm_value_stats, VALUE_KEYS in every dict).
 """
 import numpy as np
 import torch
@@ -172,6 +175,8 @@ ATTN_STATS = ['self', 'entropy', 'range_mass', 'kept_mass', 'eff_self', 'eff_ent
 ATTN_KEYS = ['attn_' + name for name in ATTN_STATS]            # what attn_stats=True adds to a summary dict
 LISTEN_STATS = ['kl', 'tv', 'flip']                            # per counterfactual: cm_episode_listen / cm_listen_means columns
 LISTEN_KEYS = ['listen_' + name for name in LISTEN_STATS] + ['loss_' + name for name in LISTEN_STATS]   # listen_stats=True: mute, lossless
+VALUE_STATS = ['value', 'ret', 'sq_err', 'ret_sq', 'msg_value', 'loss_value']   # cm_episode_value / cm_value_means columns
+VALUE_KEYS = ['value_mean', 'value_return', 'value_bias', 'value_rmse', 'value_ev', 'msg_value', 'loss_value']   # value_stats=True
 
 
 def _round_channels(eng, batch):
@@ -290,6 +295,102 @@ class _ListenStats:
             L.run("cm_listen_curve_means", self.cells, self.T, self.n_epi, self.batch.N, L.ptr(self.sums), L.ptr(self.curve_out))
 
 
+def _check_baselines(who, policies, value_stats, baselines):
+    """The refusals of value_stats= / baselines= (ValueErrors naming value_stats, before anything is built; `policies` a list)
+    -> the critics: one per policy, in order, or None with the switch off."""
+    if not value_stats and baselines is None:
+        return None
+    if baselines is None:
+        raise ValueError(f"{who}: value_stats=True needs baselines= (the critic trained with each policy)")
+    if not value_stats:
+        raise ValueError(f"{who}: baselines= is read by value_stats=True only")
+    critics = list(baselines) if isinstance(baselines, (list, tuple)) else [baselines]
+    if len(critics) != len(policies):
+        raise ValueError(f"{who}: value_stats=True needs one critic per policy in baselines= ({len(critics)} for {len(policies)})")
+    for k, (c, p) in enumerate(zip(critics, policies)):
+        if not callable(getattr(c, "values_device", None)):
+            raise ValueError(f"{who}: value_stats=True: baselines[{k}] has no values_device (a nets.CommBaseCritic or nets.GaussianMLPBaseline)")
+        if type(c) is not type(critics[0]):
+            raise ValueError(f"{who}: value_stats=True: the critics are of different classes ({type(critics[0]).__name__}, "
+                             f"{type(c).__name__})")
+        team = getattr(c, "_n_agents", None)                    # (a GaussianMLPBaseline knows the width of the joint observation only)
+        width = c.input_dim if team is None else team * c._dec_obs_dim
+        if (team is not None and team != p._n_agents) or width != p._n_agents * p._dec_obs_dim:
+            raise ValueError(f"{who}: value_stats=True: baselines[{k}] was built for another team size or observation width than "
+                             f"its policy ({p._n_agents} agents x {p._dec_obs_dim})")
+    return critics
+
+
+def _explained(sq_err, bias, ret, ret_sq):
+    """1 - Var[G - v] / Var[G] from the moments (arrays or floats) -> array; where Var[G] <= eps = 1e-12 max(1, E[G^2]): 1 where the
+    residual variance is <= eps too, else 0."""
+    sq_err, bias, ret, ret_sq = (np.asarray(x, np.float64) for x in (sq_err, bias, ret, ret_sq))
+    resid, var = sq_err - bias * bias, ret_sq - ret * ret
+    eps = 1e-12 * np.maximum(1.0, ret_sq)
+    flat = var <= eps
+    return np.where(flat, np.where(resid <= eps, 1.0, 0.0), 1.0 - resid / np.where(flat, 1.0, var))
+
+
+class _ValueStats:
+    """The value_stats=True side of eval_summary / eval_sweep: behind every round the critics' values of its T slots
+    (RolloutEngine.replay_values "recorded", and for Comm-DP critics "identity" = mute and "ones" = lossless, skipped under
+    _ListenStats's constant-channel rules: no buffer, no forward, the counterfactual passed as NULL) into buffers [T, B] of this
+    object, ONE cm_value_stats launch over the round's T x B steps against the engine's reward64 / path_len and ONE
+    cm_episode_value launch into a device table [cells, n_epi, 6]; after the last round ONE cm_value_means launch.  curves: also
+    ONE cm_value_curves launch per round into the per-step sums [cells, T, 6] and ONE cm_value_curve_means launch at the end.
+    `critics` is what replay_values takes: one critic, or a list with one per member.  `out` ([cells, 6]) and `curve_out`
+    ([cells, T, 6] or None) are views of the buffer the caller copies to the host."""
+
+    def __init__(self, eng, batch, T, cells, n_epi, critics, discount, out, curve_out):
+        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out, self.curve_out = eng, batch, T, cells, n_epi, out, curve_out
+        self.critics, self.discount = critics, float(discount)
+        f64 = dict(dtype=torch.float64, device=batch.device)
+        self.stats = torch.empty(T, batch.B, L.VALUE_COLS, **f64)
+        self.table = torch.zeros(cells, n_epi, L.EPV_COLS, **f64)
+        self.sums = None if curve_out is None else torch.empty(cells, T, L.VALUE_COLS, **f64)
+        graph = all(hasattr(c, "comm") for c in (critics if isinstance(critics, list) else [critics]))   # Comm-DP critics
+        const = batch.channelType if eng.channels is None else None           # the channel every slot of every round has
+        values = lambda skip: None if skip else torch.empty(T, batch.B, dtype=torch.float32, device=batch.device)   # noqa: E731
+        self.values, self.mute, self.lossless = values(False), values(not graph or const == "FL"), values(not graph or const == "FC")
+
+    def round(self, group_size, take, row0):
+        eng, T, B = self.eng, self.T, self.batch.B
+        eng.replay_values(0, T, "recorded", self.critics, self.values)
+        if self.mute is not None:
+            eng.replay_values(0, T, "identity", self.critics, self.mute)
+        if self.lossless is not None:
+            eng.replay_values(0, T, "ones", self.critics, self.lossless)
+        L.run("cm_value_stats", T, B, L.ptr(eng.reward64), L.ptr(eng.path_len), L.ptr(self.values), L.ptr(self.mute),
+              L.ptr(self.lossless), self.discount, L.ptr(self.stats))
+        L.run("cm_episode_value", T, B, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0, L.ptr(self.table))
+        if self.sums is not None:
+            L.run("cm_value_curves", T, B, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, int(row0 > 0), L.ptr(self.sums))
+
+    def means(self):
+        L.run("cm_value_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
+        if self.sums is not None:
+            L.run("cm_value_curve_means", self.cells, self.T, self.n_epi, L.ptr(self.sums), L.ptr(self.curve_out))
+
+    @staticmethod
+    def keys(row):
+        """A cm_value_means row (the six means per step) -> the VALUE_KEYS dict."""
+        mean, ret, sq_err, ret_sq, msg, loss = (float(x) for x in row)
+        bias = mean - ret
+        return dict(value_mean=mean, value_return=ret, value_bias=bias, value_rmse=float(np.sqrt(sq_err)),
+                    value_ev=float(_explained(sq_err, bias, ret, ret_sq)), msg_value=msg, loss_value=loss)
+
+    @staticmethod
+    def curve_keys(cols, step_cnt):
+        """A cell's host table [6, T] of zero-padded means and its step_cnt curve (the share of episodes still running at step
+        t) -> the VALUE_KEYS curves: value_rmse and value_ev over the episodes still running (0 and 1 where none does)."""
+        mean, ret, sq_err, ret_sq, msg, loss = cols
+        some = step_cnt > 0
+        run = lambda x: np.where(some, x / np.where(some, step_cnt, 1.0), 0.0)           # noqa: E731
+        r_mean, r_ret, r_sq, r_rsq = run(mean), run(ret), run(sq_err), run(ret_sq)
+        return dict(value_mean=mean, value_return=ret, value_bias=mean - ret, value_rmse=np.sqrt(r_sq),
+                    value_ev=np.where(some, _explained(r_sq, r_mean - r_ret, r_ret, r_rsq), 1.0), msg_value=msg, loss_value=loss)
+
+
 class _Curves:
     """The curves=True side of eval_summary / eval_sweep: behind every round ONE cm_episode_curves launch on the engine's
     trajectory buffers into the device table of per-step sums [cells, T, 9] - the first round overwrites it, the later ones add -
@@ -332,11 +433,12 @@ class _Curves:
         return out
 
 
-def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False, listen_stats=False):
+def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False, listen_stats=False, value_stats=False):
     """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None, and with
     curve_steps = T > 0 its [cells, T, 9] curves view and its [cells, T, 4] comm curves view, else None).  attn_stats: two values
     more, the buffer's [cells, 6] attention view and its [cells, T, 6] attention curves view (None without curve_steps);
-    listen_stats: behind them the same two for the listening statistics, at the end of the buffer."""
+    listen_stats: behind them the same two for the listening statistics; value_stats: behind those the same two for the critic
+    statistics, at the end of the buffer."""
     sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm_stats else 0, cells * curve_steps * L.EPI_COLS,
              cells * curve_steps * L.EPC_COLS if comm_stats else 0]
     shapes = [(cells, L.SUM_COLS), (cells, L.EPC_COLS), (cells, curve_steps, L.EPI_COLS), (cells, curve_steps, L.EPC_COLS)]
@@ -346,13 +448,16 @@ def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False,
     if listen_stats:
         sizes += [cells * L.EPL_COLS, cells * curve_steps * L.EPL_COLS]
         shapes += [(cells, L.EPL_COLS), (cells, curve_steps, L.EPL_COLS)]
+    if value_stats:
+        sizes += [cells * L.EPV_COLS, cells * curve_steps * L.EPV_COLS]
+        shapes += [(cells, L.EPV_COLS), (cells, curve_steps, L.EPV_COLS)]
     flat = torch.empty(sum(sizes), dtype=torch.float64, device=device)
     parts = [p if p.numel() else None for p in flat.split(sizes)]
     return (flat,) + tuple(None if p is None else p.view(shape) for p, shape in zip(parts, shapes))
 
 
 def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True,
-           curves=False, attn_stats=False, listen_stats=False):
+           curves=False, attn_stats=False, listen_stats=False, value_stats=False, baselines=None, discount=0.99):
     """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
     refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
     [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  Per round reset, play, bump, check_status, the
@@ -360,13 +465,18 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer.  curves: _Curves.round behind
     every round's rows, _Curves.means behind the reductions, their doubles in the same buffer.  attn_stats: the engine keeps
     its attention output, _AttnStats.round / .means behind _CommStats's, their doubles behind the curves' in the same buffer.
-    listen_stats: the engine keeps its probabilities, _ListenStats.round / .means behind _AttnStats's, their doubles at the end."""
+    listen_stats: the engine keeps its probabilities, _ListenStats.round / .means behind _AttnStats's, their doubles behind those.
+    value_stats: `baselines` checked (_check_baselines) and synced, _ValueStats.round / .means behind _ListenStats's, their doubles
+    at the end."""
     single = not isinstance(policies, (PolicySet, list, tuple))
     comm_dp = all(hasattr(p, "comm") for p in ([policies] if single else policies))
     if attn_stats and not comm_dp:
         raise ValueError(f"{who}: attn_stats=True needs Comm-DP policies (an Obs-DP / CENT policy has no attention output)")
     if listen_stats and not comm_dp:
         raise ValueError(f"{who}: listen_stats=True needs Comm-DP policies (an Obs-DP / CENT policy hears no messages)")
+    critics = _check_baselines(who, [policies] if single else list(policies), value_stats, baselines)
+    if critics is not None and not (np.isfinite(discount) and 0 <= discount <= 1):
+        raise ValueError(f"{who}: value_stats=True needs 0 <= discount <= 1, not {discount!r}")
     C_ = 1 if conds is None else len(conds)
 
     def shaped(cells):
@@ -399,6 +509,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
         batch.set_conditions(conds, *sweep_layout(B, K, C_, batch.cfg.env_id_offset, paired))
     env.eval_n_epi = 0
     ps.sync_weights()
+    for c in critics or ():
+        c.sync_weights()
     ps.reset([True] * (C_ * E))
     eng = RolloutEngine(batch, ps, T, store_attn=bool(attn_stats), store_probs=bool(listen_stats),
                         **({} if single else dict(groups=[C_ * E] * K)))
@@ -410,10 +522,12 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
     flat, out, comm_out, curve_out, comm_curve_out, *more = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0,
-                                                                             bool(attn_stats), bool(listen_stats))
+                                                                             bool(attn_stats), bool(listen_stats), critics is not None)
     comm = _CommStats(eng, batch, T, cells, n_epi, comm_out) if comm_stats else None
     attn = _AttnStats(eng, batch, T, cells, n_epi, *more[:2]) if attn_stats else None
-    listen = _ListenStats(eng, batch, T, cells, n_epi, *more[-2:]) if listen_stats else None
+    listen = _ListenStats(eng, batch, T, cells, n_epi, *more[2 * bool(attn_stats):][:2]) if listen_stats else None
+    value = (_ValueStats(eng, batch, T, cells, n_epi, critics[0] if single else critics, discount, *more[-2:])
+             if critics is not None else None)
     curve = _Curves(eng, batch, T, cells, n_epi, scen, curve_out, comm_curve_out) if curves else None
     done = 0
     while done < n_epi:
@@ -430,6 +544,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             attn.round(E, take, done)
         if listen:
             listen.round(E, take, done)
+        if value:
+            value.round(E, take, done)
         if curve:
             curve.round(E, take, done > 0, comm)
         done += take
@@ -440,12 +556,15 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
         attn.means()
     if listen:
         listen.means()
+    if value:
+        value.means()
     if curve:
         curve.means()
     host_all = flat.cpu().numpy()
     sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm else 0, cells * T * L.EPI_COLS if curve else 0,
              cells * T * L.EPC_COLS if curve and comm else 0, cells * L.EPA_COLS if attn else 0,
-             cells * T * L.EPA_COLS if curve and attn else 0, cells * L.EPL_COLS if listen else 0]
+             cells * T * L.EPA_COLS if curve and attn else 0, cells * L.EPL_COLS if listen else 0,
+             cells * T * L.EPL_COLS if curve and listen else 0, cells * L.EPV_COLS if value else 0]
     ends = np.cumsum(sizes)
     host = host_all[:ends[0]].reshape(cells, L.SUM_COLS)
     host_comm = host_all[ends[0]:ends[1]].reshape(cells, L.EPC_COLS) if comm else None
@@ -462,9 +581,14 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             d.update({name: cell[i] for i, name in enumerate(ATTN_KEYS)})
     host_listen = host_all[ends[5]:ends[6]].reshape(cells, L.EPL_COLS) if listen else None
     if curve and listen:
-        host_listen_curves = np.ascontiguousarray(host_all[ends[6]:].reshape(cells, T, L.EPL_COLS).transpose(0, 2, 1))
+        host_listen_curves = np.ascontiguousarray(host_all[ends[6]:ends[7]].reshape(cells, T, L.EPL_COLS).transpose(0, 2, 1))
         for d, cell in zip(cell_curves, host_listen_curves):
             d.update({name: cell[i] for i, name in enumerate(LISTEN_KEYS)})
+    host_value = host_all[ends[7]:ends[8]].reshape(cells, L.EPV_COLS) if value else None
+    if curve and value:
+        host_value_curves = np.ascontiguousarray(host_all[ends[8]:].reshape(cells, T, L.EPV_COLS).transpose(0, 2, 1))
+        for d, cell in zip(cell_curves, host_value_curves):
+            d.update(value.curve_keys(cell, d["step_cnt"]))
     res = []
     for g in range(cells):
         d = dict(n_episodes=n_epi, success=float(host[g, 0]))
@@ -487,6 +611,10 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
             d.update({name: float(host_listen[g, i]) for i, name in enumerate(LISTEN_KEYS)})
             if episodes:
                 d["listen_episodes"] = listen.table[g]
+        if value:
+            d.update(value.keys(host_value[g]))
+            if episodes:
+                d["value_episodes"] = value.table[g]
         if curve:
             d["curves"] = cell_curves[g]
         res.append(d)
@@ -496,7 +624,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
 
 
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
-                 episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False):
+                 episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False, value_stats=False,
+                 baselines=None, discount=0.99):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
     eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
     the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
@@ -559,9 +688,35 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     ride at the end of the same copy.  A wrapper with a constant FC channel skips the lossless replay and one with a constant FL
     channel the mute replay: exact zeros.  f64 sums in a fixed order: the same episodes give the same bits.  The probabilities
     cost 4 T B N A bytes of device memory each (recorded, mute, lossless).  Off (the default), the engine keeps no
-    probabilities and nothing is launched, allocated or returned beyond the above."""
+    probabilities and nothing is launched, allocated or returned beyond the above.
+    value_stats=True with baselines= (one critic for one policy, a list of K for K policies, critic k judging policy k's envs:
+    nets.CommBaseCritic of any aggregator and layer sizes, or nets.GaussianMLPBaseline for Obs-DP / CENT policies; all of one
+    class, built for their policy's team size and observation width - anything else, and either keyword without the other,
+    raises ValueError before anything is built) adds how good the critic trained with the policy is.  The critics are
+    sync_weights()-ed, and behind every round their values v of the round's slots are computed forward-only
+    (RolloutEngine.replay_values on the recorded observations, dist_adj and channels) and compared with G, the return-to-go of
+    the rewards discounted by `discount` within the episode (no bootstrap where max_env_steps cuts it).  Every dict gains
+    VALUE_KEYS, from means over the steps the policy acted in: value_mean = E[v], value_return = E[G], value_bias = their
+    difference, value_rmse = sqrt(E[(v - G)^2]), value_ev = 1 - Var[G - v] / Var[G] - the explained variance, 1 for a perfect
+    baseline, 0 for a constant one, negative for one worse than that (where Var[G] <= 1e-12 max(1, E[G^2]): 1 if Var[G - v] is
+    that small too, else 0) - and for Comm-DP critics msg_value = E[v - v_mute], what the critic believes the messages are worth
+    (the outcome-side twin of listen_kl), and loss_value = E[v_lossless - v], what it believes the channel loss costs, v_mute /
+    v_lossless being its values under the identity / the all-ones channel (replay_values "identity" / "ones"; a GaussianMLPBaseline
+    has no graph input: exact zeros, no forward).  E is episode-balanced like every key here: a step of episode e weighs
+    1 / (n_e E), n_e its length and E the number of episodes.  garage's ExplainedVariance pools the steps instead (each weighs
+    1 / sum_e n_e), so long episodes count for more there; with episodes=True `value_episodes`, the [n_eval_episodes, 6] device
+    table behind the keys (per episode the means over its steps of v, G, (v - G)^2, G^2, v - v_mute, v_lossless - v), times the
+    `step_cnt` column of `episodes` gives the per-episode sums to pool.  With curves=True the same seven names are in `curves`:
+    value_mean, value_return, value_bias, msg_value and loss_value zero-padded means like every curve, value_rmse and value_ev
+    over the episodes still running at step t (0 and 1 where none does).  Behind every round the replays (one forward launch
+    per critic and replay; under the identity one per block of rollout.REPLAY_MASK_BYTES of mask), ONE cm_value_stats launch
+    over the round's T x B steps and ONE cm_episode_value launch (with curves ONE cm_value_curves more), after the last round ONE
+    cm_value_means (cm_value_curve_means) launch; the doubles ride at the end of the same copy.  A wrapper with a constant FC
+    channel skips the lossless replay and one with a constant FL channel the mute replay: exact zeros.  f64 in a fixed order:
+    the same episodes give the same bits.  Off (the default), nothing is launched, allocated or returned beyond the above."""
     return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  curves=curves, attn_stats=attn_stats, listen_stats=listen_stats)
+                  curves=curves, attn_stats=attn_stats, listen_stats=listen_stats, value_stats=value_stats, baselines=baselines,
+                  discount=discount)
 
 
 def sweep_layout(B, K, C, env_id_offset=0, paired=True):
@@ -577,7 +732,8 @@ def sweep_layout(B, K, C, env_id_offset=0, paired=True):
 
 
 def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
-               episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False):
+               episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False, value_stats=False,
+               baselines=None, discount=0.99):
     """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
     conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
     policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
@@ -601,12 +757,17 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     curve that delivery and reach only describe.
     listen_stats=True gives every cell eval_summary's LISTEN_KEYS (per round the two counterfactual replays, one cm_listen_stats
     and one cm_episode_listen launch with groups of E envs, one cm_listen_means at the end; [K*C, 6] doubles more in the same
-    copy, with curves [K*C, T, 6]): whether a condition changed any decision - a cell that loses nothing has loss_* exactly 0."""
+    copy, with curves [K*C, T, 6]): whether a condition changed any decision - a cell that loses nothing has loss_* exactly 0.
+    value_stats=True, baselines= (one critic per policy) gives every cell eval_summary's VALUE_KEYS (per round the critics'
+    replays, one cm_value_stats and one cm_episode_value launch with groups of E envs, one cm_value_means at the end; [K*C, 6]
+    doubles more in the same copy, with curves [K*C, T, 6]): whether the baseline stays good at the lossy end of the curve and
+    what it believes the loss costs - a cell that loses nothing has loss_value exactly 0."""
     conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
     return _score("eval_sweep", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
-                  conds=conds, paired=paired, curves=curves, attn_stats=attn_stats, listen_stats=listen_stats)
+                  conds=conds, paired=paired, curves=curves, attn_stats=attn_stats, listen_stats=listen_stats,
+                  value_stats=value_stats, baselines=baselines, discount=discount)
 
 
 def summary_row(summary):

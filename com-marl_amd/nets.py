@@ -1542,16 +1542,18 @@ class GaussianMLPBaseline(_WeightPack, nn.Module):
     _mlp_pack = None
 
     @torch.no_grad()
-    def values_device(self, obs):
+    def values_device(self, obs, out=None):
+        """Fused no-grad forward (cm_mlp_value_forward): obs [..., input_dim] CUDA -> values [...]; `out` (f32, contiguous, one value
+        per row) receives them when given and is returned as it is."""
         dev = obs.device
         if dev.type != "cuda":
             raise L.CommarlError("baseline forward is a HIP kernel: inputs must be CUDA tensors (no CPU fallback)")
         lead = obs.shape[:-1]
         rows = obs.numel() // self.input_dim
-        values = torch.empty(rows, dtype=torch.float32, device=dev)
+        values = out if out is not None else torch.empty(rows, dtype=torch.float32, device=dev)
         w = self._mlp_struct()
         L.run("cm_mlp_value_forward", C.byref(w), rows, L.cptr(obs), L.ptr(values), device=dev)
-        return values.reshape(*lead)
+        return values.reshape(*lead) if out is None else values
 
     def forward(self, obs):
         """-> values [P,T] (:100-115).  Under no_grad this is the fused kernel."""

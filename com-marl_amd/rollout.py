@@ -332,6 +332,63 @@ class RolloutEngine:
             out[:, lo:hi] = probs.view(n, hi - lo, N, A)
         return out
 
+    def _value_rows(self, critic, obs, adj, chan, channels, out):
+        """`critic`'s values of the env states obs [R, N*d] / adj [R, N, N] | None under `channels` (chan [R, Lh, N, N] | None: the
+        recorded ones) into out [R]: values_device - one launch, or one per _identity_rows block of rows under the identity.  A
+        critic without a graph input (GaussianMLPBaseline) reads the observations alone."""
+        if not hasattr(critic, "comm"):
+            critic.values_device(obs, out=out)
+            return
+        R = obs.shape[0]
+        eye = self._identity_rows(R) if channels == "identity" else None
+        step = R if eye is None else eye.shape[0]
+        for r0 in range(0, R, step):
+            r1 = min(R, r0 + step)
+            ch = eye[:r1 - r0] if eye is not None else (chan[r0:r1] if channels == "recorded" and chan is not None else None)
+            critic.values_device(obs[r0:r1], None if adj is None else adj[r0:r1], ch, out=out[r0:r1])
+
+    @torch.no_grad()
+    def replay_values(self, t0, n, channels, critics, out):
+        """Forward only: what `critics` - one critic (nets.CommBaseCritic of any aggregator and layer sizes, or
+        nets.GaussianMLPBaseline), or a list with one per group of a PolicySet engine, critic k judging member k's envs - make of
+        the recorded slots t0 .. t0+n-1, their obs[t] and dist_adj[t] as they stand, under `channels` ("recorded", "identity" or
+        "ones": replay_probs' three), into out [n, B] (f32, contiguous, the caller's).  For every env they are what its critic's
+        values_device returns on these inputs.  A single critic takes ONE launch over the n * B rows (under the identity one per
+        block of the engine's constant mask, which REPLAY_MASK_BYTES bounds), a list ONE launch per member over its
+        n * (hi - lo) rows, gathered from the slots by device copies and scattered back.  A GaussianMLPBaseline has no graph input:
+        channels other than "recorded" are refused for it.  Nothing else changes: no recorded buffer is written and neither the
+        sampler's Philox base nor a step counter moves.  The weight packs are used as they are (the caller has run the critics'
+        sync_weights()).  On the current stream, behind the round (play() has joined the shards)."""
+        env = self.env
+        B, N, d, Lh = env.B, env.N, env.d, env.Lh
+        t0, n = int(t0), int(n)
+        if channels not in ("recorded", "identity", "ones"):
+            raise ValueError(f"replay_values: channels must be 'recorded', 'identity' or 'ones', not {channels!r}")
+        if not (n >= 1 and t0 >= 0 and t0 + n <= self.H):
+            raise ValueError(f"replay_values: slots {t0} .. {t0 + n - 1} are not within the horizon {self.H}")
+        if not (out.dtype == torch.float32 and tuple(out.shape) == (n, B) and out.is_contiguous() and out.device == self.obs.device):
+            raise ValueError(f"replay_values: out must be a contiguous f32 tensor [{n}, {B}] on the engine's device")
+        several = isinstance(critics, (list, tuple))
+        if several and (self.multi_form is None or len(critics) != len(self.groups)):
+            raise ValueError("replay_values: a list of critics needs a PolicySet engine and one critic per group")
+        if channels != "recorded" and not all(hasattr(c, "comm") for c in (critics if several else [critics])):
+            raise ValueError(f"replay_values: channels={channels!r} needs critics with a graph input (a GaussianMLPBaseline has none)")
+        adj, chan = self.dist_adj, self.channels
+        if not several:
+            flat = lambda b, *tail: None if b is None else b[t0:t0 + n].view(n * B, *tail)    # noqa: E731
+            self._value_rows(critics, flat(self.obs, N * d), flat(adj, N, N), flat(chan, Lh, N, N), channels, out.view(n * B))
+            return out
+        if channels != "recorded":
+            chan = None
+        for critic, (lo, hi) in zip(critics, self.groups):
+            # a member's envs are contiguous within a slot only: gathered, ONE launch, scattered back (as replay_probs)
+            rows = n * (hi - lo)
+            take = lambda b, *tail: None if b is None else b[t0:t0 + n, lo:hi].reshape(rows, *tail)   # noqa: E731
+            values = torch.empty(rows, dtype=torch.float32, device=out.device)
+            self._value_rows(critic, take(self.obs, N * d), take(adj, N, N), take(chan, Lh, N, N), channels, values)
+            out[:, lo:hi] = values.view(n, hi - lo)
+        return out
+
     def fill_diameters(self, t0, n):
         """diameter[t] of the n slots t0 .. t0+n-1 from dist_adj[t], in one launch on the current stream (the caller has
         joined the shards' streams: the slots are final).  Nothing without the switch."""

@@ -395,6 +395,56 @@ int cm_listen_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t 
                           const double *sums /* [cells, T, CM_LISTEN_COLS] */, double *curves /* [cells, T, CM_EPL_COLS] */,
                           void *stream);
 
+/* Critic statistics: how well the values of the critic trained with a policy explain the returns its episodes went on to collect,
+ * and what that critic believes the messages are worth.  For env b over T recorded steps let n be the length of its first episode -
+ * n = t + 1 for the first t with path_len[t][b] > 0, else T (the rule of cm_episode_stats) - and G the discounted return-to-go of
+ * its f64 rewards r:
+ *   G[n-1] = r[n-1],   G[t] = r[t] + gamma * G[t+1]     (f64, descending t, product and sum rounded separately; no bootstrap at
+ *                                                        an episode cut at T, as cm_discount_returns and the update's returns)
+ * With v = (double)values[t][b], row (t, b) for t < n holds CM_VALUE_COLS doubles:
+ *   0 value = v   1 ret = G[t]   2 sq_err = (v - G[t])^2   3 ret_sq = G[t]^2
+ *   4 msg_value = v - mute[t][b]          what the critic believes the messages are worth (mute: its value under the identity channel)
+ *   5 loss_value = lossless[t][b] - v     what it believes the channel loss costs (lossless: its value under the all-ones channel)
+ * and rows with t >= n are written as exact zeros.  Pure functions of DEVICE arrays.
+ *
+ * cm_value_stats writes exactly T*B rows.  A NULL counterfactual means "identical to values": its column is written as exact +0.0
+ * and nothing is read.  One lane per env; no atomics; the order of operations of a row depends on (T, n) alone - not on B or the
+ * grid: the same inputs give the same bits.  T = 0 or B = 0 launches nothing.  CM_ERR_ARG (text in cm_last_error) before anything
+ * is launched: T < 0 or B < 0, gamma outside [0, 1] or not finite, or NULL rewards, path_len, values or stats with T*B > 0.
+ *
+ * cm_episode_value / cm_value_means / cm_value_curves / cm_value_curve_means are cm_episode_listen / cm_listen_means /
+ * cm_listen_curves / cm_listen_curve_means for these rows - the same arguments without n_agents, the same mapping, length rule,
+ * refusals and fixed summation order - with ALL six columns divided by n (n_episodes for the curves): means per step.  From an
+ * episode's (or a cell's) means m: bias = m0 - m1, rmse = sqrt(m2), explained variance = 1 - (m2 - bias^2) / (m3 - m1^2). */
+#define CM_VALUE_COLS 6   /* value, ret, sq_err, ret_sq, msg_value, loss_value: per recorded step */
+#define CM_EPV_COLS 6     /* the same names: means per step */
+int cm_value_stats(int32_t T, int32_t B,
+                   const double *rewards,     /* [T,B] */
+                   const int32_t *path_len,   /* [T,B] */
+                   const float *values,       /* [T,B] */
+                   const float *mute,         /* [T,B]; NULL = values */
+                   const float *lossless,     /* [T,B]; NULL = values */
+                   double gamma,
+                   double *stats,             /* [T,B,CM_VALUE_COLS] */
+                   void *stream);
+int cm_episode_value(int32_t T, int32_t B,
+                     const int32_t *path_len,    /* [T,B] */
+                     const double *stats,        /* [T,B,CM_VALUE_COLS] */
+                     int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0,
+                     double *episodes,           /* [B/group_size * episodes_per_group, CM_EPV_COLS] */
+                     void *stream);
+int cm_value_means(int32_t K, int32_t E, const double *episodes /* [K*E, CM_EPV_COLS] */,
+                   double *summary /* [K, CM_EPV_COLS] */, void *stream);
+int cm_value_curves(int32_t T, int32_t B,
+                    const int32_t *path_len,    /* [T,B] */
+                    const double *stats,        /* [T,B,CM_VALUE_COLS] */
+                    int32_t group_size, int32_t take, int32_t accumulate,
+                    double *sums,               /* [B/group_size, T, CM_VALUE_COLS] */
+                    void *stream);
+int cm_value_curve_means(int32_t cells, int32_t T, int32_t n_episodes,
+                         const double *sums /* [cells, T, CM_VALUE_COLS] */, double *curves /* [cells, T, CM_EPV_COLS] */,
+                         void *stream);
+
 /* Per-step evaluation curves: the rounds of cm_episode_stats / cm_episode_comm reduced over the EPISODES with the step axis kept -
  * the mean over episodes of the per-step lists the reference's test loop pads with zeros to max_env_steps and saves as rewMat3
  * (exp_runners/testing.py:307-324, pad_sequence(..., padding_value=0)).  Pure functions of DEVICE arrays.

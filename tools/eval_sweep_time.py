@@ -17,7 +17,16 @@ one launch per round, csrc/cm_rollout_wc.hip), whose cells of policy 0 are compa
     python tools/eval_sweep_time.py kernels                 the env step alone, uniform batch then conditions batch of the same
                                                             shape, batch and (single) condition, 300 steps each: the launches a
                                                             `rocprofv3 --kernel-trace --stats` run of this command compares
-                                                            (env_kernel* against env_cond_kernel*)"""
+                                                            (env_kernel* against env_cond_kernel*)
+    python tools/eval_sweep_time.py value_stats [off]       the pp_map10 sweep on the fused wrapper with and without value_stats
+                                                            (eight CommBaseCritics as baselines): both warmed, the unchanged keys
+                                                            compared (==), then five alternating rounds of whole calls.  `off`:
+                                                            the five rounds without the switch only, passing no keyword of it - the
+                                                            leg a checkout that predates the switch can run, for alternating the two
+                                                            trees in one job
+    python tools/eval_sweep_time.py value_parts             the same round played once, then its parts on their own (device events,
+                                                            five repetitions each): the critics' recorded, mute and lossless replays
+                                                            and the cm_value_stats launch (DESIGN.md §7 "Critic statistics")"""
 import json
 import os
 import sys
@@ -124,6 +133,101 @@ def run(name):
     return same and (not fused_leg or same_f)
 
 
+def _value_setup():
+    """The pp_map10 workload's fused wrapper factory, its 8 policies and 8 critics of seeded weights."""
+    w = WORKLOADS["pp_map10"]
+    wrapper = lambda: w["cls"](True, params=w["params"], n_envs=w["envs"], device="cuda:0", seed=SEED, channel=w["channel"],   # noqa: E731
+                               conditions=w["conditions"], fused_conditions=True)
+    first = wrapper()
+    pols, critics = [], []
+    for k in range(w["K"]):
+        torch.manual_seed(k)
+        p = nets.CommCategoricalMLPPolicy(first.spec, n_agents=4, device="cuda:0")
+        p.set_rng(SEED)
+        pols.append(p)
+        critics.append(nets.CommBaseCritic(first.spec, n_agents=4, device="cuda:0"))
+    return w, wrapper, first, pols, critics
+
+
+def value_stats(off_only):
+    """eval_sweep of the pp_map10 workload on the fused wrapper, with and without value_stats, alternating (off_only: without)."""
+    w, wrapper, first, pols, critics = _value_setup()
+    B, K, C_, rounds_n = w["envs"], w["K"], len(w["conditions"]), 5
+    n_epi = B // (K * C_)
+    kw = dict(n_eval_episodes=n_epi, max_env_steps=T, eval_greedy=True, paired=True)
+    call = lambda env, flag: eval_sweep(env, pols, 0, **kw, **(dict(value_stats=True, baselines=critics) if flag else {}))   # noqa: E731
+    _, ref = sync_time(lambda: call(first, False))
+    same = None
+    if not off_only:
+        from com_marl_amd.evaluate import VALUE_KEYS
+        _, got = sync_time(lambda: call(wrapper(), True))
+        same = all(got[k][c][key] == v for k in range(K) for c in range(C_) for key, v in ref[k][c].items())
+        print(f"every key of the sweep without value_stats is unchanged with it: {same}", flush=True)
+        for c in range(C_):
+            print(f"  {w['conditions'][c]}: success {got[0][c]['success']:.3f} " + " ".join(f"{key} {got[0][c][key]:.3e}" for key in VALUE_KEYS),
+                  flush=True)
+    ms = {True: [], False: []}
+    for r in range(rounds_n):
+        for flag in ((False,) if off_only else (True, False)):
+            env = wrapper()
+            dt, _ = sync_time(lambda: call(env, flag))
+            ms[flag].append(dt * 1e3)
+            print(f"[{r}] eval_sweep {K} x {C_} cells x {n_epi} episodes, {B} envs, value_stats={flag}: {dt * 1e3:9.2f} ms", flush=True)
+    print(json.dumps({"workload": "pp_map10 fused", "envs": B, "policies": K, "conditions": C_, "steps": T, "unchanged_keys_equal": same,
+                      "with_value_stats_ms": [round(x, 3) for x in ms[True]], "without_ms": [round(x, 3) for x in ms[False]]}), flush=True)
+    return same is not False
+
+
+def value_parts():
+    """The pp_map10 round played once on the fused wrapper, then the critics' three replays and cm_value_stats, each on its own."""
+    from com_marl_amd import _lib as L
+    from com_marl_amd.evaluate import sweep_layout
+    from com_marl_amd.rollout import RolloutEngine
+    w, _, env, pols, critics = _value_setup()
+    B, K, C_, reps = w["envs"], w["K"], len(w["conditions"]), 5
+    batch = getattr(env, "env", env).batch
+    ps = nets.PolicySet(pols)
+    batch.set_conditions(w["conditions"], *sweep_layout(B, K, C_, batch.cfg.env_id_offset, True))
+    ps.sync_weights()
+    for c in critics:
+        c.sync_weights()
+    ps.reset([True] * (B // K))
+    eng = RolloutEngine(batch, ps, T, store_attn=False, store_probs=False, groups=[B // K] * K)
+    eng.reset()
+    eng.play(0, T, greedy=True, chunk=True)
+    eng.bump(T)
+    values, mute, lossless = (torch.empty(T, B, device="cuda") for _ in range(3))
+    stats = torch.empty(T, B, L.VALUE_COLS, dtype=torch.float64, device="cuda")
+    lib, st = L.lib(), L.current_stream()
+
+    def timed(job):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        job()
+        b.record()
+        torch.cuda.synchronize()
+        return round(a.elapsed_time(b) * 1e3, 1)                             # us
+
+    jobs = {
+        "round (reset + play)": lambda: (eng.reset(), eng.play(0, T, greedy=True, chunk=True)),
+        "recorded replay": lambda: eng.replay_values(0, T, "recorded", critics, values),
+        "mute replay": lambda: eng.replay_values(0, T, "identity", critics, mute),
+        "lossless replay": lambda: eng.replay_values(0, T, "ones", critics, lossless),
+        "cm_value_stats": lambda: L.check(lib.cm_value_stats(T, B, L.ptr(eng.reward64), L.ptr(eng.path_len), L.ptr(values), L.ptr(mute),
+                                                             L.ptr(lossless), 0.99, L.ptr(stats), st), "cm_value_stats"),
+        "cm_value_stats, no counterfactuals": lambda: L.check(lib.cm_value_stats(T, B, L.ptr(eng.reward64), L.ptr(eng.path_len), L.ptr(values),
+                                                                                 None, None, 0.99, L.ptr(stats), st), "cm_value_stats"),
+    }
+    res = {}
+    for name, job in jobs.items():
+        timed(job)
+        res[name] = [timed(job) for _ in range(reps)]
+        print(f"{name}: {res[name]} us", flush=True)
+    print(json.dumps({"workload": "pp_map10 fused", "envs": B, "policies": K, "steps": T, "us": res,
+                      "mean_stats_row": stats.mean((0, 1)).tolist()}), flush=True)
+
+
 def kernels():
     """300 cm_env_step launches of a uniform batch, then 300 of a conditions batch in which every env has that same condition:
     the same work per launch, env_kernel* against env_cond_kernel*."""
@@ -174,6 +278,11 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["rollout_kernels"]:
         rollout_kernels()
+        sys.exit(0)
+    if sys.argv[1:2] == ["value_stats"] and sys.argv[2:] in ([], ["off"]):
+        sys.exit(0 if value_stats(sys.argv[2:] == ["off"]) else 1)
+    if sys.argv[1:] == ["value_parts"]:
+        value_parts()
         sys.exit(0)
     names = sys.argv[1:] or list(WORKLOADS)
     ok = [run(name) for name in names]

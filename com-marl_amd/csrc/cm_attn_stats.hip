@@ -21,10 +21,8 @@
 // paths), a lane's rows in ascending order with the hops inside, then the xor tree - not by S, the grid or the load width: the
 // 16-byte and the one-float paths give the same bits.
 // W, P and LC are template arguments, so no private array is indexed dynamically: no private segment.
-// cm_episode_attn / cm_attn_means and cm_attn_curves / cm_attn_curve_means are the reductions of cm_episode_comm / cm_comm_means
-// (csrc/cm_comm_stats.hip) and cm_comm_curves / cm_comm_curve_means (csrc/cm_episode_curves.hip) for rows of doubles: the same
-// decompositions, f64 sums in one fixed order (lane-strided, then the xor tree).  Their host side is at::episode_rows / group_means /
-// curve_sums / curve_means (cm_internal.h), which csrc/cm_listen_stats.hip's reductions share: they take the entry point's name.
+// cm_episode_attn / cm_attn_means and cm_attn_curves / cm_attn_curve_means are the shared reductions of csrc/cm_stat_rows.hip on rows
+// of six doubles: columns 0-2 divided by n N, columns 3-5 (at::L_COLS) by n N L.
 #include "cm_internal.h"
 
 namespace cm {
@@ -32,7 +30,9 @@ namespace at {
 
 typedef unsigned long long u64;
 constexpr int TPB = 256, WAVES = TPB / 64, MAX_N = 255, MAX_L = 8, SMALL_N = 8, COLS = CM_ATTN_COLS;
-constexpr int SCAN = 32, MAX_TILE = 16, MIN_TILE = 4, MIN_WAVES = 1024;
+constexpr unsigned L_COLS = 0b111000u;                              // kept_mass, eff_self, eff_entropy: summed over the hops too
+static_assert(CM_ATTN_COLS == 6 && CM_EPA_COLS == CM_ATTN_COLS,
+              "cm_stat_rows.hip's <double, 6> rows; an episode row has its step rows' columns");
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -395,206 +395,6 @@ static int launch_wave(const Args &g, hipStream_t st) {
     return launch_wave_hops<W, 8>(g, st);
 }
 
-// ---- per-episode and per-cell reductions (as cm_episode_comm / cm_comm_means) ------------------------------------------------------
-__global__ __launch_bounds__(TPB) void episode_attn_kernel(int T, int B, int N, int L, const int32_t *__restrict__ path_len,
-                                                           const double *__restrict__ stats, int group_size, int take,
-                                                           int episodes_per_group, int row0, int n_rows, double *__restrict__ episodes) {
-    const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * WAVES + (threadIdx.x >> 6);          // the w-th env that is summarised
-    if (w >= n_rows) return;                                        // (wave-uniform: a ragged last workgroup)
-    const int k = w / take, j = w - k * take;
-    const size_t b = (size_t)k * group_size + j;
-
-    // ---- length: n = t + 1 for the first t with path_len[t][b] > 0, else T (as cm_episode_stats) ----
-    int first = T;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-        const int t = t0 + lane;
-        if (t < T && path_len[(size_t)t * B + b] > 0) first = t;
-        if (__ballot(first < T) != 0ull) break;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) first = min(first, __shfl_xor(first, d));
-    const int n = first < T ? first + 1 : T;
-
-    // ---- slots 0 .. n-1: the graphs the policy acted through ----
-    double c[COLS];
-#pragma unroll
-    for (int q = 0; q < COLS; ++q) c[q] = 0.0;
-    for (int t = lane; t < n; t += 64) {
-        const double *__restrict__ r = stats + ((size_t)t * B + b) * COLS;
-#pragma unroll
-        for (int q = 0; q < COLS; ++q) c[q] += r[q];
-    }
-    const double nN = (double)n * (double)N, nNL = nN * (double)L;  // exact: below 2^53
-    double out = 0.0;
-#pragma unroll
-    for (int q = 0; q < COLS; ++q) {
-        const double v = wave_sum(c[q]) / (q < 3 ? nN : nNL);
-        out = lane == q ? v : out;
-    }
-    if (lane < CM_EPA_COLS) episodes[((size_t)k * episodes_per_group + row0 + j) * CM_EPA_COLS + lane] = out;
-}
-
-__global__ __launch_bounds__(TPB) void attn_means_kernel(int K, int E, const double *__restrict__ episodes, double *__restrict__ summary) {
-    const int lane = threadIdx.x & 63;
-    const int k = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (k >= K) return;
-    const double *__restrict__ rows = episodes + (size_t)k * E * CM_EPA_COLS;
-    double s[CM_EPA_COLS];
-#pragma unroll
-    for (int c = 0; c < CM_EPA_COLS; ++c) s[c] = 0.0;
-    for (int i = lane; i < E; i += 64) {
-#pragma unroll
-        for (int c = 0; c < CM_EPA_COLS; ++c) s[c] += rows[(size_t)i * CM_EPA_COLS + c];
-    }
-    double out = 0.0;
-#pragma unroll
-    for (int c = 0; c < CM_EPA_COLS; ++c) {
-        s[c] = wave_sum(s[c]) / (double)E;
-        out = lane == c ? s[c] : out;
-    }
-    if (lane < CM_EPA_COLS) summary[(size_t)k * CM_EPA_COLS + lane] = out;
-}
-
-// ---- per-step curves (as cm_comm_curves / cm_comm_curve_means: one wave per group and tile of steps, lane l env l of a chunk) -----
-// Loads that a lane may have no use for are not branched around: such a lane reads element 0 of the array and drops the value.
-
-// does the first episode of env b (valid: the lane has one) still run at step t0?
-__device__ __forceinline__ bool running_at(const int32_t *__restrict__ path_len, int B, size_t b, int t0, bool valid) {
-    bool run = valid;
-    for (int t = 0; t < t0 && __ballot(run) != 0ull; t += SCAN) {
-        int32_t e[SCAN];
-#pragma unroll
-        for (int u = 0; u < SCAN; ++u) e[u] = path_len[(run && t + u < t0) ? (size_t)(t + u) * B + b : (size_t)0];
-#pragma unroll
-        for (int u = 0; u < SCAN; ++u) run = run & ((t + u >= t0) | (e[u] <= 0));
-    }
-    return run;
-}
-
-// the last step of the tile t0 .. t1-1 at which a lane that runs at t0 still runs, as an offset from t0 (MAX_TILE: past the tile)
-__device__ __forceinline__ int last_running(const int32_t *__restrict__ path_len, int B, size_t b, int t0, int t1, bool run) {
-    int32_t e[MAX_TILE];
-#pragma unroll
-    for (int u = 0; u < MAX_TILE; ++u) e[u] = path_len[(run && t0 + u < t1) ? (size_t)(t0 + u) * B + b : (size_t)0];
-    int last = MAX_TILE;
-#pragma unroll
-    for (int u = MAX_TILE - 1; u >= 0; --u) last = ((t0 + u < t1) & (e[u] > 0)) ? u : last;
-    return last;
-}
-
-__global__ __launch_bounds__(TPB) void attn_curves_kernel(int T, int B, const int32_t *__restrict__ path_len,
-                                                          const double *__restrict__ stats, int group_size, int take, int tile,
-                                                          int tiles, long long n_waves, int accumulate, double *__restrict__ sums) {
-    const int lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (w >= n_waves) return;                                   // (wave-uniform: a ragged last workgroup)
-    const int k = (int)(w / tiles);
-    const int t0 = (int)(w - (long long)k * tiles) * tile, t1 = min(T, t0 + tile);
-
-    for (int j0 = 0; j0 < take; j0 += 64) {                     // the group's envs, 64 at a time, in ascending order
-        const int j = j0 + lane;
-        const size_t b = (size_t)k * group_size + j;
-        const bool fresh = j0 == 0 && accumulate == 0;          // this chunk starts the table's entries
-        const bool first = running_at(path_len, B, b, t0, j < take);
-        const int stop = last_running(path_len, B, b, t0, t1, first);
-        for (int t = t0; t < t1; ++t) {
-            const bool run = first && t - t0 <= stop;
-            if (__ballot(run) == 0ull && !fresh) break;         // nothing more to add
-            // slot t: the graph the policy acted through
-            const double *__restrict__ row = stats + (run ? (size_t)t * B + b : (size_t)0) * COLS;
-            double out = 0.0;
-#pragma unroll
-            for (int q = 0; q < COLS; ++q) {
-                const double v = wave_sum(run ? row[q] : 0.0);
-                out = lane == q ? v : out;
-            }
-            if (lane < COLS) {
-                double *__restrict__ at = sums + ((size_t)k * T + t) * COLS + lane;
-                *at = (fresh ? 0.0 : *at) + out;
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(TPB) void attn_curve_means_kernel(long long n, int n_episodes, int N, int L, const double *__restrict__ sums,
-                                                               double *__restrict__ curves) {
-    const double nNE = (double)N * (double)n_episodes, nNLE = nNE * (double)L;   // exact: below 2^53
-    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB)
-        curves[i] = sums[i] / ((int)(i % CM_EPA_COLS) < 3 ? nNE : nNLE);
-}
-
-// steps per wave: MAX_TILE where that leaves MIN_WAVES waves, else halved down to MIN_TILE
-static int tile_of(int groups, int T) {
-    int tile = MAX_TILE;
-    while (tile > MIN_TILE && (long long)groups * ((T + tile - 1) / tile) < MIN_WAVES) tile >>= 1;
-    return tile;
-}
-
-// ---- the reductions' host side, shared with the cm_*listen* entry points (cm_internal.h); `who` names the entry point -----------------
-static int refuse(const char *who, const char *what) { return set_error(CM_ERR_ARG, std::string(who) + ": " + what); }
-
-int episode_rows(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
-                 int episodes_per_group, int row0, double *episodes, void *stream) {
-    if (T < 1 || B < 0) return refuse(who, "T >= 1 and B >= 0 required");
-    if (N < 1 || N > MAX_N) return refuse(who, "1 <= n_agents <= 255 required");
-    if (L < 1 || L > MAX_L) return refuse(who, "1 <= n_hops <= 8 required");
-    if (group_size < 1 || B % group_size != 0) return refuse(who, "group_size >= 1 must divide B");
-    if (take < 0 || take > group_size) return refuse(who, "0 <= take <= group_size required");
-    if (row0 < 0 || (int64_t)row0 + take > episodes_per_group)
-        return refuse(who, "rows row0 .. row0 + take - 1 must lie in 0 .. episodes_per_group - 1");
-    if (B == 0 || take == 0) return CM_OK;
-    if (!path_len || !stats || !episodes) return refuse(who, "null argument");
-    const int n_rows = (int)((int64_t)(B / group_size) * take);     // <= B
-    const int grid = (n_rows + WAVES - 1) / WAVES;
-    hipLaunchKernelGGL(episode_attn_kernel, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, T, B, N, L, path_len, stats, group_size,
-                       take, episodes_per_group, row0, n_rows, episodes);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-int group_means(const char *who, int K, int E, const double *episodes, double *summary, void *stream) {
-    if (K < 1 || E < 1) return refuse(who, "K >= 1 and E >= 1 required");
-    if (!episodes || !summary) return refuse(who, "null argument");
-    const int grid = (K + WAVES - 1) / WAVES;
-    hipLaunchKernelGGL(attn_means_kernel, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, K, E, episodes, summary);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-int curve_sums(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
-               int accumulate, double *sums, void *stream) {
-    if (T < 1 || B < 0) return refuse(who, "T >= 1 and B >= 0 required");
-    if (N < 1 || N > MAX_N) return refuse(who, "1 <= n_agents <= 255 required");
-    if (L < 1 || L > MAX_L) return refuse(who, "1 <= n_hops <= 8 required");
-    if (group_size < 1 || B % group_size != 0) return refuse(who, "group_size >= 1 must divide B");
-    if (take < 0 || take > group_size) return refuse(who, "0 <= take <= group_size required");
-    if (accumulate != 0 && accumulate != 1) return refuse(who, "accumulate must be 0 or 1");
-    if (B == 0 || take == 0) return CM_OK;
-    if (!path_len || !stats || !sums) return refuse(who, "null argument");
-    const int groups = B / group_size, tile = tile_of(groups, T), tiles = (T + tile - 1) / tile;
-    const long long n_waves = (long long)groups * tiles;
-    const long long grid = (n_waves + WAVES - 1) / WAVES;
-    if (grid > INT32_MAX) return refuse(who, "too many (group, step) pairs for one launch");
-    hipLaunchKernelGGL(attn_curves_kernel, dim3((unsigned)grid), dim3(TPB), 0, (hipStream_t)stream, T, B, path_len, stats, group_size,
-                       take, tile, tiles, n_waves, accumulate, sums);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
-int curve_means(const char *who, int cells, int T, int n_episodes, int N, int L, const double *sums, double *curves, void *stream) {
-    if (cells < 1 || T < 1 || n_episodes < 1) return refuse(who, "cells, T and n_episodes >= 1 required");
-    if (N < 1 || N > MAX_N) return refuse(who, "1 <= n_agents <= 255 required");
-    if (L < 1 || L > MAX_L) return refuse(who, "1 <= n_hops <= 8 required");
-    if (!sums || !curves) return refuse(who, "null argument");
-    const long long n = (long long)cells * T * CM_EPA_COLS;
-    const long long blocks = (n + TPB - 1) / TPB;
-    hipLaunchKernelGGL(attn_curve_means_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(TPB), 0, (hipStream_t)stream, n,
-                       n_episodes, N, L, sums, curves);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
-}
-
 }  // namespace at
 }  // namespace cm
 
@@ -631,19 +431,21 @@ extern "C" int cm_attn_stats(int32_t S, int32_t N, int32_t L, const float *attn,
 extern "C" int cm_episode_attn(int32_t T, int32_t B, int32_t N, int32_t L, const int32_t *path_len, const double *stats,
                                int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0, double *episodes,
                                void *stream) {
-    return at::episode_rows("cm_episode_attn", T, B, N, L, path_len, stats, group_size, take, episodes_per_group, row0, episodes, stream);
+    return rows::episode_rows<double, CM_ATTN_COLS>("cm_episode_attn", T, B, { N, L, at::L_COLS }, path_len, stats,
+                                   group_size, take, episodes_per_group, row0, episodes, stream);
 }
 
 extern "C" int cm_attn_means(int32_t K, int32_t E, const double *episodes, double *summary, void *stream) {
-    return at::group_means("cm_attn_means", K, E, episodes, summary, stream);
+    return rows::group_means<CM_ATTN_COLS>("cm_attn_means", K, E, episodes, summary, stream);
 }
 
 extern "C" int cm_attn_curves(int32_t T, int32_t B, int32_t N, int32_t L, const int32_t *path_len, const double *stats,
                               int32_t group_size, int32_t take, int32_t accumulate, double *sums, void *stream) {
-    return at::curve_sums("cm_attn_curves", T, B, N, L, path_len, stats, group_size, take, accumulate, sums, stream);
+    return rows::curve_sums<double, CM_ATTN_COLS>("cm_attn_curves", T, B, { N, L, at::L_COLS }, path_len, stats,
+                                   group_size, take, accumulate, sums, stream);
 }
 
 extern "C" int cm_attn_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N, int32_t L, const double *sums,
                                    double *curves, void *stream) {
-    return at::curve_means("cm_attn_curve_means", cells, T, n_episodes, N, L, sums, curves, stream);
+    return rows::curve_means<CM_ATTN_COLS>("cm_attn_curve_means", cells, T, n_episodes, { N, L, at::L_COLS }, sums, curves, stream);
 }

@@ -16,9 +16,12 @@
 //             product of hop l reads source row j from its owner with v_readlane (j is wave-uniform) and ORs it into every row that
 //             hears j.
 // W and P are template arguments, so no private array is indexed dynamically: no private segment, no flat or scratch addressing.
-// cm_episode_comm / cm_comm_means are the per-episode and per-cell reductions, laid out as cm_episode_stats / cm_episode_means are
-// (csrc/cm_episode.hip): one wave per env / per group of rows, integer sums, one fixed order.
+// cm_episode_comm / cm_comm_means are the shared reductions of csrc/cm_stat_rows.hip on rows of four int32: integer sums, every column
+// divided by n N, `delivered` (rows::COMM_L_COLS) by n N L.
 #include "cm_internal.h"
+
+static_assert(CM_COMM_COLS == 4 && CM_EPC_COLS == CM_COMM_COLS,
+              "cm_stat_rows.hip's <int32_t, 4> rows; an episode row has its step rows' columns");
 
 namespace cm {
 namespace cs {
@@ -361,69 +364,6 @@ static int launch_wave(const Args &g, hipStream_t st) {
     return CM_OK;
 }
 
-// ---- per-episode and per-cell reductions ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB) void episode_comm_kernel(int T, int B, int N, int L, const int32_t *__restrict__ path_len,
-                                                           const int32_t *__restrict__ stats, int group_size, int take,
-                                                           int episodes_per_group, int row0, int n_rows, double *__restrict__ episodes) {
-    const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * WAVES + (threadIdx.x >> 6);          // the w-th env that is summarised
-    if (w >= n_rows) return;                                        // (wave-uniform: a ragged last workgroup)
-    const int k = w / take, j = w - k * take;
-    const size_t b = (size_t)k * group_size + j;
-
-    // ---- length: n = t + 1 for the first t with path_len[t][b] > 0, else T (as cm_episode_stats) ----
-    int first = T;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-        const int t = t0 + lane;
-        if (t < T && path_len[(size_t)t * B + b] > 0) first = t;
-        if (__ballot(first < T) != 0ull) break;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) first = min(first, __shfl_xor(first, d));
-    const int n = first < T ? first + 1 : T;
-
-    // ---- slots 0 .. n-1: the graphs the policy acted through ----
-    long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    for (int t = lane; t < n; t += 64) {
-        const int32_t *__restrict__ r = stats + ((size_t)t * B + b) * CM_COMM_COLS;
-        c0 += r[0];
-        c1 += r[1];
-        c2 += r[2];
-        c3 += r[3];
-    }
-    c0 = wave_sum(c0);
-    c1 = wave_sum(c1);
-    c2 = wave_sum(c2);
-    c3 = wave_sum(c3);
-    const double nN = (double)n * (double)N;                        // exact: both below 2^31
-    double out = (double)c0 / nN;
-    out = lane == 1 ? (double)c1 / (nN * (double)L) : out;
-    out = lane == 2 ? (double)c2 / nN : out;
-    out = lane == 3 ? (double)c3 / nN : out;
-    if (lane < CM_EPC_COLS) episodes[((size_t)k * episodes_per_group + row0 + j) * CM_EPC_COLS + lane] = out;
-}
-
-__global__ __launch_bounds__(TPB) void comm_means_kernel(int K, int E, const double *__restrict__ episodes, double *__restrict__ summary) {
-    const int lane = threadIdx.x & 63;
-    const int k = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (k >= K) return;
-    const double *__restrict__ rows = episodes + (size_t)k * E * CM_EPC_COLS;
-    double s[CM_EPC_COLS];
-#pragma unroll
-    for (int c = 0; c < CM_EPC_COLS; ++c) s[c] = 0.0;
-    for (int i = lane; i < E; i += 64) {
-#pragma unroll
-        for (int c = 0; c < CM_EPC_COLS; ++c) s[c] += rows[(size_t)i * CM_EPC_COLS + c];
-    }
-    double out = 0.0;
-#pragma unroll
-    for (int c = 0; c < CM_EPC_COLS; ++c) {
-        s[c] = wave_sum(s[c]) / (double)E;
-        out = lane == c ? s[c] : out;
-    }
-    if (lane < CM_EPC_COLS) summary[(size_t)k * CM_EPC_COLS + lane] = out;
-}
-
 }  // namespace cs
 }  // namespace cm
 
@@ -459,28 +399,10 @@ extern "C" int cm_comm_stats(int32_t S, int32_t N, int32_t L, const float *dist_
 extern "C" int cm_episode_comm(int32_t T, int32_t B, int32_t N, int32_t L, const int32_t *path_len, const int32_t *stats,
                                int32_t group_size, int32_t take, int32_t episodes_per_group, int32_t row0, double *episodes,
                                void *stream) {
-    if (T < 1 || B < 0) return set_error(CM_ERR_ARG, "cm_episode_comm: T >= 1 and B >= 0 required");
-    if (N < 1 || N > cs::MAX_N) return set_error(CM_ERR_ARG, "cm_episode_comm: 1 <= n_agents <= 255 required");
-    if (L < 1 || L > cs::MAX_L) return set_error(CM_ERR_ARG, "cm_episode_comm: 1 <= n_hops <= 8 required");
-    if (group_size < 1 || B % group_size != 0) return set_error(CM_ERR_ARG, "cm_episode_comm: group_size >= 1 must divide B");
-    if (take < 0 || take > group_size) return set_error(CM_ERR_ARG, "cm_episode_comm: 0 <= take <= group_size required");
-    if (row0 < 0 || (int64_t)row0 + take > episodes_per_group)
-        return set_error(CM_ERR_ARG, "cm_episode_comm: rows row0 .. row0 + take - 1 must lie in 0 .. episodes_per_group - 1");
-    if (B == 0 || take == 0) return CM_OK;
-    if (!path_len || !stats || !episodes) return set_error(CM_ERR_ARG, "cm_episode_comm: null argument");
-    const int n_rows = (int)((int64_t)(B / group_size) * take);     // <= B
-    const int grid = (n_rows + cs::WAVES - 1) / cs::WAVES;
-    hipLaunchKernelGGL(cs::episode_comm_kernel, dim3(grid), dim3(cs::TPB), 0, (hipStream_t)stream, T, B, N, L, path_len, stats,
-                       group_size, take, episodes_per_group, row0, n_rows, episodes);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return rows::episode_rows<int32_t, CM_COMM_COLS>("cm_episode_comm", T, B, { N, L, rows::COMM_L_COLS }, path_len, stats, group_size, take,
+                                                     episodes_per_group, row0, episodes, stream);
 }
 
 extern "C" int cm_comm_means(int32_t K, int32_t E, const double *episodes, double *summary, void *stream) {
-    if (K < 1 || E < 1) return set_error(CM_ERR_ARG, "cm_comm_means: K >= 1 and E >= 1 required");
-    if (!episodes || !summary) return set_error(CM_ERR_ARG, "cm_comm_means: null argument");
-    const int grid = (K + cs::WAVES - 1) / cs::WAVES;
-    hipLaunchKernelGGL(cs::comm_means_kernel, dim3(grid), dim3(cs::TPB), 0, (hipStream_t)stream, K, E, episodes, summary);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return rows::group_means<CM_COMM_COLS>("cm_comm_means", K, E, episodes, summary, stream);
 }

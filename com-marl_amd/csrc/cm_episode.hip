@@ -16,22 +16,16 @@
 // next to which the adjacency walk (coalesced) is the traffic that counts.
 // Output columns are chosen by lane through selects, no private array is indexed dynamically: no private segment, no flat or
 // scratch addressing.
-#include "cm_internal.h"
+#include "cm_episode_dev.h"
 
 #include <math.h>
 
 namespace cm {
 namespace epi {
 
+using namespace ep;
 typedef unsigned long long u64;
 constexpr int TPB = 256, WAVES = TPB / 64, MAX_N = 255, UNROLL = 4;
-
-template <typename V>
-__device__ __forceinline__ V wave_sum(V v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 template <int VEC>
 __device__ __forceinline__ float load_sum(const float *p) {
@@ -56,16 +50,7 @@ __global__ __launch_bounds__(TPB) void episode_stats_kernel(int T, int B, int N,
     const int k = w / take, j = w - k * take;
     const size_t b = (size_t)k * group_size + j;
 
-    // ---- length: n = t + 1 for the first t with path_len[t][b] > 0, else T ----
-    int first = T;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-        const int t = t0 + lane;
-        if (t < T && path_len[(size_t)t * B + b] > 0) first = t;
-        if (__ballot(first < T) != 0ull) break;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) first = min(first, __shfl_xor(first, d));
-    const int n = first < T ? first + 1 : T;
+    const int n = episode_len(path_len, T, B, b, lane);         // t + 1 for the first t with path_len[t][b] > 0, else T
 
     // ---- columns ----
     double r = 0.0;

@@ -2,6 +2,7 @@
 // cm_episode_stats / cm_episode_comm reduced over EPISODES with the step axis kept (gfx950): what exp_runners/testing.py:307-324
 // pads with zeros to max_env_steps and saves as rewMat3, averaged over the episodes.  The curves kernels write per-step SUMS over a
 // group's episodes (an episode that has ended contributes zero: the zero padding); the means kernels divide every sum once.
+// cm_comm_curves / cm_comm_curve_means are the shared reductions of csrc/cm_stat_rows.hip on cm_comm_stats' rows of four int32.
 // One wave owns one group and one tile of consecutive steps; a 256-thread workgroup holds four independent waves - no LDS, no
 // barrier, no atomic, one writer per table entry.  A wave's work on its tile t0 .. t0 + tile - 1, for every chunk of 64 envs of the
 // group (lane l owns env l of the chunk):
@@ -23,19 +24,19 @@
 // The tile length is chosen on the host from the number of groups and steps (more waves for few groups, fewer scans of path_len
 // for many); it changes no sum's order.  Output columns are chosen by lane through selects, no private array is indexed
 // dynamically: no private segment, no flat or scratch addressing.
-#include "cm_internal.h"
+#include "cm_episode_dev.h"
 
 namespace cm {
 namespace crv {
 
+using namespace ep;
 typedef unsigned long long u64;
-constexpr int TPB = 256, WAVES = TPB / 64, MAX_N = 255, MAX_L = 8, UNROLL = 4, SCAN = 32;
-constexpr int MAX_TILE = 16, MIN_TILE = 4, MIN_WAVES = 1024;
+constexpr int TPB = 256, WAVES = TPB / 64, MAX_N = 255, UNROLL = 4;
 
-// Eight (four) columns per lane -> every lane holds the wave's total of ONE column, column lane >> 3 (lane >> 4): a butterfly
-// that halves the columns a lane carries at each of its first stages - a lane keeps the half its lane bit names, sends the
-// other half to its partner and adds what it receives - and carries one column through the rest.  10 (7) exchanges instead of
-// 48 (24); the order of every sum is fixed.  All indices are compile-time: the arrays live in registers.
+// Eight columns per lane -> every lane holds the wave's total of ONE column, column lane >> 3: a butterfly that halves the columns
+// a lane carries at each of its first stages - a lane keeps the half its lane bit names, sends the other half to its partner and
+// adds what it receives - and carries one column through the rest.  10 exchanges instead of 48; the order of every sum is fixed.
+// All indices are compile-time: the arrays live in registers.
 __device__ __forceinline__ double wave_sum8(const double (&v)[8], int lane) {
     const bool h5 = (lane & 32) != 0, h4 = (lane & 16) != 0, h3 = (lane & 8) != 0;
     double a[4], b[2];
@@ -49,17 +50,6 @@ __device__ __forceinline__ double wave_sum8(const double (&v)[8], int lane) {
     return s;
 }
 
-__device__ __forceinline__ double wave_sum4(const double (&v)[4], int lane) {
-    const bool h5 = (lane & 32) != 0, h4 = (lane & 16) != 0;
-    double a[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) a[i] = (h5 ? v[2 + i] : v[i]) + __shfl_xor(h5 ? v[i] : v[2 + i], 32);
-    double s = (h4 ? a[1] : a[0]) + __shfl_xor(h4 ? a[0] : a[1], 16);
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-    return s;
-}
-
 template <int VEC>
 __device__ __forceinline__ float load_sum(const float *p) {
     if constexpr (VEC == 4) {
@@ -68,34 +58,6 @@ __device__ __forceinline__ float load_sum(const float *p) {
     } else {
         return *p;
     }
-}
-
-// Loads that a lane may have no use for are not branched around (a branch per load makes every load wait for the one before):
-// such a lane reads element 0 of the array instead - in bounds, one cache line for all of them - and drops the value.
-
-// does the first episode of env b (valid: the lane has one) still run at step t0?
-__device__ __forceinline__ bool running_at(const int32_t *__restrict__ path_len, int B, size_t b, int t0, bool valid) {
-    bool run = valid;
-    for (int t = 0; t < t0 && __ballot(run) != 0ull; t += SCAN) {
-        int32_t e[SCAN];
-#pragma unroll
-        for (int u = 0; u < SCAN; ++u) e[u] = path_len[(run && t + u < t0) ? (size_t)(t + u) * B + b : (size_t)0];
-#pragma unroll
-        for (int u = 0; u < SCAN; ++u) run = run & ((t + u >= t0) | (e[u] <= 0));
-    }
-    return run;
-}
-
-// The last step of the tile t0 .. t1-1 at which a lane that runs at t0 still runs, as an offset from t0: that of its first
-// path_len > 0, or MAX_TILE when there is none.  One load per row, all in flight.
-__device__ __forceinline__ int last_running(const int32_t *__restrict__ path_len, int B, size_t b, int t0, int t1, bool run) {
-    int32_t e[MAX_TILE];
-#pragma unroll
-    for (int u = 0; u < MAX_TILE; ++u) e[u] = path_len[(run && t0 + u < t1) ? (size_t)(t0 + u) * B + b : (size_t)0];
-    int last = MAX_TILE;
-#pragma unroll
-    for (int u = MAX_TILE - 1; u >= 0; --u) last = ((t0 + u < t1) & (e[u] > 0)) ? u : last;
-    return last;
 }
 
 // The 0 / 1 floats of the N x N blocks of the envs named in `mask` (bit e: the e-th env of the run), summed: `base` is the first
@@ -181,38 +143,6 @@ __global__ __launch_bounds__(TPB) void episode_curves_kernel(int T, int B, int N
     }
 }
 
-__global__ __launch_bounds__(TPB) void comm_curves_kernel(int T, int B, const int32_t *__restrict__ path_len,
-                                                          const int32_t *__restrict__ stats, int group_size, int take, int tile,
-                                                          int tiles, long long n_waves, int accumulate, double *__restrict__ sums) {
-    const int lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (w >= n_waves) return;                                   // (wave-uniform: a ragged last workgroup)
-    const int k = (int)(w / tiles);
-    const int t0 = (int)(w - (long long)k * tiles) * tile, t1 = min(T, t0 + tile);
-
-    for (int j0 = 0; j0 < take; j0 += 64) {
-        const int j = j0 + lane;
-        const size_t b = (size_t)k * group_size + j;
-        const bool fresh = j0 == 0 && accumulate == 0;
-        const bool first = running_at(path_len, B, b, t0, j < take);
-        const int stop = last_running(path_len, B, b, t0, t1, first);
-        for (int t = t0; t < t1; ++t) {
-            const bool run = first && t - t0 <= stop;
-            if (__ballot(run) == 0ull && !fresh) break;
-            // slot t: the graph the policy acted through
-            const int32_t *__restrict__ row = stats + (run ? (size_t)t * B + b : (size_t)0) * CM_COMM_COLS;
-            double v[4] = { (double)row[0], (double)row[1], (double)row[2], (double)row[3] };
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = run ? v[c] : 0.0;
-            const double out = wave_sum4(v, lane);              // column lane >> 4
-            if ((lane & 15) == 0) {
-                double *__restrict__ at = sums + ((size_t)k * T + t) * CM_COMM_COLS + (lane >> 4);
-                *at = (fresh ? 0.0 : *at) + out;
-            }
-        }
-    }
-}
-
 // every entry of a sums table divided once by its column's exact product; one thread per entry
 __global__ __launch_bounds__(TPB) void curve_means_kernel(long long n, int n_episodes, int scenario, int N, const double *__restrict__ sums,
                                                           double *__restrict__ curves) {
@@ -224,20 +154,6 @@ __global__ __launch_bounds__(TPB) void curve_means_kernel(long long n, int n_epi
         const double v = sums[i] / (whole ? nE : nNE);
         curves[i] = (pp && c == 8) ? 0.0 : v;
     }
-}
-
-__global__ __launch_bounds__(TPB) void comm_curve_means_kernel(long long n, int n_episodes, int N, int L, const double *__restrict__ sums,
-                                                               double *__restrict__ curves) {
-    const double nNE = (double)N * (double)n_episodes, nNLE = nNE * (double)L;   // exact: below 2^53
-    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB)
-        curves[i] = sums[i] / ((int)(i % CM_EPC_COLS) == 1 ? nNLE : nNE);
-}
-
-// steps per wave: MAX_TILE where that leaves MIN_WAVES waves, else halved down to MIN_TILE
-static int tile_of(int groups, int T) {
-    int tile = MAX_TILE;
-    while (tile > MIN_TILE && (long long)groups * ((T + tile - 1) / tile) < MIN_WAVES) tile >>= 1;
-    return tile;
 }
 
 static unsigned means_grid(long long n) {
@@ -293,34 +209,11 @@ extern "C" int cm_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int3
 
 extern "C" int cm_comm_curves(int32_t T, int32_t B, int32_t N, int32_t L, const int32_t *path_len, const int32_t *stats,
                               int32_t group_size, int32_t take, int32_t accumulate, double *sums, void *stream) {
-    if (T < 1 || B < 0) return set_error(CM_ERR_ARG, "cm_comm_curves: T >= 1 and B >= 0 required");
-    if (N < 1 || N > crv::MAX_N) return set_error(CM_ERR_ARG, "cm_comm_curves: 1 <= n_agents <= 255 required");
-    if (L < 1 || L > crv::MAX_L) return set_error(CM_ERR_ARG, "cm_comm_curves: 1 <= n_hops <= 8 required");
-    if (group_size < 1 || B % group_size != 0) return set_error(CM_ERR_ARG, "cm_comm_curves: group_size >= 1 must divide B");
-    if (take < 0 || take > group_size) return set_error(CM_ERR_ARG, "cm_comm_curves: 0 <= take <= group_size required");
-    if (accumulate != 0 && accumulate != 1) return set_error(CM_ERR_ARG, "cm_comm_curves: accumulate must be 0 or 1");
-    if (B == 0 || take == 0) return CM_OK;
-    if (!path_len || !stats || !sums) return set_error(CM_ERR_ARG, "cm_comm_curves: null argument");
-    const int groups = B / group_size, tile = crv::tile_of(groups, T), tiles = (T + tile - 1) / tile;
-    const long long n_waves = (long long)groups * tiles;
-    const long long grid = (n_waves + crv::WAVES - 1) / crv::WAVES;
-    if (grid > INT32_MAX) return set_error(CM_ERR_ARG, "cm_comm_curves: too many (group, step) pairs for one launch");
-    hipLaunchKernelGGL(crv::comm_curves_kernel, dim3((unsigned)grid), dim3(crv::TPB), 0, (hipStream_t)stream, T, B, path_len, stats,
-                       group_size, take, tile, tiles, n_waves, accumulate, sums);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return rows::curve_sums<int32_t, CM_COMM_COLS>("cm_comm_curves", T, B, { N, L, rows::COMM_L_COLS }, path_len, stats, group_size, take,
+                                                   accumulate, sums, stream);
 }
 
 extern "C" int cm_comm_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N, int32_t L, const double *sums,
                                    double *curves, void *stream) {
-    if (cells < 1 || T < 1 || n_episodes < 1)
-        return set_error(CM_ERR_ARG, "cm_comm_curve_means: cells, T and n_episodes >= 1 required");
-    if (N < 1 || N > crv::MAX_N) return set_error(CM_ERR_ARG, "cm_comm_curve_means: 1 <= n_agents <= 255 required");
-    if (L < 1 || L > crv::MAX_L) return set_error(CM_ERR_ARG, "cm_comm_curve_means: 1 <= n_hops <= 8 required");
-    if (!sums || !curves) return set_error(CM_ERR_ARG, "cm_comm_curve_means: null argument");
-    const long long n = (long long)cells * T * CM_EPC_COLS;
-    hipLaunchKernelGGL(crv::comm_curve_means_kernel, dim3(crv::means_grid(n)), dim3(crv::TPB), 0, (hipStream_t)stream, n, n_episodes,
-                       N, L, sums, curves);
-    CM_HIP(hipGetLastError());
-    return CM_OK;
+    return rows::curve_means<CM_COMM_COLS>("cm_comm_curve_means", cells, T, n_episodes, { N, L, rows::COMM_L_COLS }, sums, curves, stream);
 }

@@ -192,16 +192,26 @@ int agg_bwd_mfma(bool det, int S, int N, const float *attn, const float *adj, co
 int attn_bwd_mfma(int S, int N, const float *q, const float *e, const float *m, const float *d_m, const float *add0, const float *add1,
                   float *d_q, float *d_e, void *stream);
 
-// ---- cm_attn_stats.hip: the reductions of rows of six doubles, shared by cm_episode_attn / cm_attn_means / cm_attn_curves /
-// cm_attn_curve_means and their cm_*listen* twins (cm_listen_stats.hip).  `who` names the entry point in the refusals' texts.
-// Columns 0-2 are divided by n N, columns 3-5 by n N L: a caller whose six columns all take n N passes L = 1 (the product by
-// 1.0 is exact) ----
-namespace at {
-int episode_rows(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
+// ---- cm_stat_rows.hip: the four reductions of a statistics family's per-step rows, behind cm_episode_<family>, cm_<family>_means,
+// cm_<family>_curves and cm_<family>_curve_means of comm, attn, listen and value.  Instantiated for the two row kinds there are:
+// <int32_t, CM_COMM_COLS> and <double, 6>.  `who` names the entry point in the refusals' texts ----
+namespace rows {
+// what a family's columns are divided by, next to the number of steps or episodes: N (the agents; 1 for one value per step), and
+// for the columns set in l_cols also L (the hops)
+struct Div {
+    int N, L = 1;
+    unsigned l_cols = 0u;
+};
+constexpr unsigned COMM_L_COLS = 0b0010u;   // cm_comm_stats' `delivered` is counted per hop
+template <typename V, int COLS>
+int episode_rows(const char *who, int T, int B, Div d, const int32_t *path_len, const V *stats, int group_size, int take,
                  int episodes_per_group, int row0, double *episodes, void *stream);
+template <int COLS>
 int group_means(const char *who, int K, int E, const double *episodes, double *summary, void *stream);
-int curve_sums(const char *who, int T, int B, int N, int L, const int32_t *path_len, const double *stats, int group_size, int take,
-               int accumulate, double *sums, void *stream);
-int curve_means(const char *who, int cells, int T, int n_episodes, int N, int L, const double *sums, double *curves, void *stream);
+template <typename V, int COLS>
+int curve_sums(const char *who, int T, int B, Div d, const int32_t *path_len, const V *stats, int group_size, int take, int accumulate,
+               double *sums, void *stream);
+template <int COLS>
+int curve_means(const char *who, int cells, int T, int n_episodes, Div d, const double *sums, double *curves, void *stream);
 }
 }

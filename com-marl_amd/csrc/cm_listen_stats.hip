@@ -18,9 +18,11 @@
 // the same bits.  The order depends on (N, A) alone - a row's terms in ascending a, a lane's rows in ascending order, then the xor
 // tree - not on S, the grid or the load width.  A and P are template arguments: no private array is indexed dynamically, no
 // private segment.
-// The four reductions are those of the attention rows (cm_attn_stats.hip: at::episode_rows, ...) with every column divided by n N:
-// they are launched with L = 1.
+// The four reductions are the shared ones of csrc/cm_stat_rows.hip on rows of six doubles, every column divided by n N.
 #include "cm_internal.h"
+
+static_assert(CM_LISTEN_COLS == 6 && CM_EPL_COLS == CM_LISTEN_COLS,
+              "cm_stat_rows.hip's <double, 6> rows; an episode row has its step rows' columns");
 
 #include <cfloat>
 
@@ -202,22 +204,24 @@ extern "C" int cm_listen_stats(int32_t S, int32_t N, int32_t A, const float *pro
     }
 }
 
-// every column is a mean per agent: the attention rows' reductions with L = 1 (n N L = n N, exactly)
+// every column is a mean per agent: divided by n N (rows::Div{ N }), none also by L
 extern "C" int cm_episode_listen(int32_t T, int32_t B, int32_t N, const int32_t *path_len, const double *stats, int32_t group_size,
                                  int32_t take, int32_t episodes_per_group, int32_t row0, double *episodes, void *stream) {
-    return at::episode_rows("cm_episode_listen", T, B, N, 1, path_len, stats, group_size, take, episodes_per_group, row0, episodes, stream);
+    return rows::episode_rows<double, CM_LISTEN_COLS>("cm_episode_listen", T, B, { N }, path_len, stats,
+                                   group_size, take, episodes_per_group, row0, episodes, stream);
 }
 
 extern "C" int cm_listen_means(int32_t K, int32_t E, const double *episodes, double *summary, void *stream) {
-    return at::group_means("cm_listen_means", K, E, episodes, summary, stream);
+    return rows::group_means<CM_LISTEN_COLS>("cm_listen_means", K, E, episodes, summary, stream);
 }
 
 extern "C" int cm_listen_curves(int32_t T, int32_t B, int32_t N, const int32_t *path_len, const double *stats, int32_t group_size,
                                 int32_t take, int32_t accumulate, double *sums, void *stream) {
-    return at::curve_sums("cm_listen_curves", T, B, N, 1, path_len, stats, group_size, take, accumulate, sums, stream);
+    return rows::curve_sums<double, CM_LISTEN_COLS>("cm_listen_curves", T, B, { N }, path_len, stats,
+                                   group_size, take, accumulate, sums, stream);
 }
 
 extern "C" int cm_listen_curve_means(int32_t cells, int32_t T, int32_t n_episodes, int32_t N, const double *sums, double *curves,
                                      void *stream) {
-    return at::curve_means("cm_listen_curve_means", cells, T, n_episodes, N, 1, sums, curves, stream);
+    return rows::curve_means<CM_LISTEN_COLS>("cm_listen_curve_means", cells, T, n_episodes, { N }, sums, curves, stream);
 }

@@ -13,9 +13,12 @@
 // shuffles; the batches are unrolled with constant indices, so no private array is indexed dynamically: no private segment.  A
 // row depends on its env's column of the inputs alone, its order of operations on (T, n) alone - not on B or the grid: the same
 // inputs give the same bits.  The NULL counterfactuals are template arguments: their column is the constant +0.0, nothing is read.
-// The four reductions are those of the attention rows (cm_attn_stats.hip: at::episode_rows, ...) with every column divided by n
-// (n_episodes for the curves): they are launched with N = 1, L = 1.
+// The four reductions are the shared ones of csrc/cm_stat_rows.hip on rows of six doubles, every column divided by n (n_episodes
+// for the curves): rows::Div{ 1 }, no column also by N or L.
 #include "cm_internal.h"
+
+static_assert(CM_VALUE_COLS == 6 && CM_EPV_COLS == CM_VALUE_COLS,
+              "cm_stat_rows.hip's <double, 6> rows; an episode row has its step rows' columns");
 
 #include <cmath>
 
@@ -116,21 +119,23 @@ extern "C" int cm_value_stats(int32_t T, int32_t B, const double *rewards, const
     return CM_OK;
 }
 
-// every column is a mean per step: the attention rows' reductions with N = 1, L = 1 (n N L = n, exactly)
+// every column is a mean per step: divided by n alone (rows::Div{ 1 })
 extern "C" int cm_episode_value(int32_t T, int32_t B, const int32_t *path_len, const double *stats, int32_t group_size, int32_t take,
                                 int32_t episodes_per_group, int32_t row0, double *episodes, void *stream) {
-    return at::episode_rows("cm_episode_value", T, B, 1, 1, path_len, stats, group_size, take, episodes_per_group, row0, episodes, stream);
+    return rows::episode_rows<double, CM_VALUE_COLS>("cm_episode_value", T, B, { 1 }, path_len, stats,
+                                   group_size, take, episodes_per_group, row0, episodes, stream);
 }
 
 extern "C" int cm_value_means(int32_t K, int32_t E, const double *episodes, double *summary, void *stream) {
-    return at::group_means("cm_value_means", K, E, episodes, summary, stream);
+    return rows::group_means<CM_VALUE_COLS>("cm_value_means", K, E, episodes, summary, stream);
 }
 
 extern "C" int cm_value_curves(int32_t T, int32_t B, const int32_t *path_len, const double *stats, int32_t group_size, int32_t take,
                                int32_t accumulate, double *sums, void *stream) {
-    return at::curve_sums("cm_value_curves", T, B, 1, 1, path_len, stats, group_size, take, accumulate, sums, stream);
+    return rows::curve_sums<double, CM_VALUE_COLS>("cm_value_curves", T, B, { 1 }, path_len, stats,
+                                   group_size, take, accumulate, sums, stream);
 }
 
 extern "C" int cm_value_curve_means(int32_t cells, int32_t T, int32_t n_episodes, const double *sums, double *curves, void *stream) {
-    return at::curve_means("cm_value_curve_means", cells, T, n_episodes, 1, 1, sums, curves, stream);
+    return rows::curve_means<CM_VALUE_COLS>("cm_value_curve_means", cells, T, n_episodes, { 1 }, sums, curves, stream);
 }

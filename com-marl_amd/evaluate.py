@@ -21,21 +21,27 @@ Differences a maintainer should know (documented, not silent):
 ``eval_summary`` plays the same rounds and returns only each policy's score (the CSV row of exp_runners/testing.py:329-335),
 reduced on the device by cm_episode_stats / cm_episode_means: nothing but K x 12 doubles is copied to the host.
 ``eval_sweep`` does the same for K policies x C comm conditions in one rollout, on a wrapper built with ``conditions=``.
-Both take ``comm_stats=True``: how much of the offered communication was delivered and how much of the team an agent can hear
-through the net's hops (cm_comm_stats on the engine's dist_adj / channels, COMM_KEYS in every dict).
-Both take ``curves=True``: the same episodes reduced over the episodes with the STEP axis kept (cm_episode_curves /
-cm_comm_curves behind every round, cm_curve_means / cm_comm_curve_means at the end, in the same single copy) - per step the mean
-over the episodes of the zero-padded lists eval_model returns, i.e. what exp_runners/testing.py:307-324 saves as rewMat3.
-Both take ``attn_stats=True``: what the policy did with what was delivered - the self weight and the entropy of its attention rows,
-the attention mass on links in range and on links that carried something, and the same two of the weights the net really uses
-after masking and renormalising (cm_attn_stats on the engine's recorded attn / dist_adj / channels, ATTN_KEYS in every dict).
-Both take ``listen_stats=True``: whether the messages changed what the agents did - the round replayed forward-only under a mute
-and a lossless channel (RolloutEngine.replay_probs) and the action distributions compared with the recorded ones (cm_listen_stats,
-LISTEN_KEYS in every dict).
-Both take ``value_stats=True, baselines=...``: how good the critic trained with each policy is - its values on the round's recorded
-slots (RolloutEngine.replay_values) against the discounted returns the episodes went on to collect, and what it believes the
-messages and the channel loss are worth (cm_value_stats, VALUE_KEYS in every dict).
+Both take five switches.  Each adds its keys to every dict, its doubles ride in the same single copy, and one that is off
+launches, allocates and returns nothing:
+  ``curves=True``        the same episodes reduced over the episodes with the STEP axis kept - per step the mean over the episodes
+                         of the zero-padded lists eval_model returns, i.e. what exp_runners/testing.py:307-324 saves as rewMat3;
+  ``comm_stats=True``    COMM_KEYS: how much of the offered communication was delivered and how much of the team an agent can hear
+                         through the net's hops (cm_comm_stats on the engine's dist_adj / channels);
+  ``attn_stats=True``    ATTN_KEYS: what the policy did with what was delivered - the self weight and the entropy of its attention
+                         rows, the attention mass on links in range and on links that carried something, and the same two of the
+                         weights the net really uses after masking and renormalising (cm_attn_stats on the engine's recorded attn);
+  ``listen_stats=True``  LISTEN_KEYS: whether the messages changed what the agents did - the round replayed forward-only under a
+                         mute and a lossless channel (RolloutEngine.replay_probs), compared with the recorded probabilities
+                         (cm_listen_stats);
+  ``value_stats=True, baselines=...``  VALUE_KEYS: how good the critic trained with each policy is - its values on the round's slots
+                         (RolloutEngine.replay_values) against the discounted returns the episodes went on to collect, and what it
+                         believes the messages and the channel loss are worth (cm_value_stats).
+The four statistics families are one _Side each, told apart by a _Family description (FAMILIES); _layout describes the one buffer.
 """
+import collections
+import itertools
+import math
+
 import numpy as np
 import torch
 
@@ -46,15 +52,20 @@ from .rollout import RolloutEngine
 VECTORS = ['reward', 'capture_cnt', 'step_cnt', 'move_cnt', 'penalty_cnt', 'nodeDeg', 'variable', 'vars2']   # testing.py:209
 
 
-def _first_episodes(eng, base, T, greedy, chunk=False):
-    """reset + T steps; returns host arrays for every env's first episode.  chunk: the T steps as chunk launches where the
-    engine has them (one launch for every member of a PolicySet on the wave-owned kernel); bit-identical to stepping them one
-    by one."""
+def _play_round(eng, batch, T, greedy, chunk):
+    """One round: reset + T steps, every env's first episode on the engine's trajectory buffers.  chunk: the T steps as chunk
+    launches where the engine has them (one launch for every member of a PolicySet on the wave-owned kernel); bit-identical to
+    stepping them one by one."""
     eng.reset()
     eng.play(0, T, greedy=greedy, chunk=chunk)
     eng.bump(T)
-    base.batch.check_status()
-    pl = eng.path_len[:T]                                                  # [T,B]
+    batch.check_status()
+
+
+def _first_episodes(eng, base, T, greedy, chunk=False):
+    """_play_round; returns host arrays for every env's first episode."""
+    _play_round(eng, base.batch, T, greedy, chunk)
+    pl = eng.path_len[:T]                                                 # [T,B]
     ended = pl > 0
     # first t at which each env finished (T-1 when the loop limit cut it, eval_pp.py:73)
     first = torch.where(ended.any(0), ended.to(torch.int32).argmax(0), torch.full_like(pl[0], T - 1)).long()
@@ -189,110 +200,117 @@ def _round_channels(eng, batch):
     return batch.channels, 0
 
 
-class _CommStats:
-    """The comm_stats=True side of eval_summary / eval_sweep: behind every round ONE cm_comm_stats launch on the engine's
-    dist_adj / channels (all T + 1 slots of all B envs) and ONE cm_episode_comm launch into a device table [cells, n_epi, 4];
-    after the last round ONE cm_comm_means launch into `self.out`, a view of the tail of the buffer the caller copies to the host.
-    A constant fully connected adjacency and a constant FC channel are passed as NULL (ones), a constant FL channel as the
-    batch's constant block with stride 0."""
+def _counterfactuals(eng, batch, graph=True):
+    """-> (mute, lossless): which counterfactual replays a round needs - under the identity (every agent hears only itself) and under
+    the all-ones channel (everything in range is delivered).  A constant FL channel IS the mute one and a constant FC channel the
+    lossless one: that replay is skipped - no buffer, no forward, the counterfactual passed as NULL (its columns exact 0).  graph:
+    the nets read the channel at all (a critic without a graph input needs neither)."""
+    const = batch.channelType if eng.channels is None else None               # the channel every slot of every round has
+    return graph and const != "FL", graph and const != "FC"
 
-    def __init__(self, eng, batch, T, cells, n_epi, out):
-        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out = eng, batch, T, cells, n_epi, out
-        self.stats = torch.empty(T + 1, batch.B, L.COMM_COLS, dtype=torch.int32, device=batch.device)
-        self.table = torch.zeros(cells, n_epi, L.EPC_COLS, dtype=torch.float64, device=batch.device)
 
-    def round(self, group_size, take, row0):
-        eng, batch = self.eng, self.batch
-        B, N, Lh = batch.B, batch.N, batch.Lh
+# ---- what produces a family's per-step rows: called once per call with the engine, the batch, T and the side's `stats` (it may
+# allocate its own buffers then), -> the round's launches.  (Nothing here refers back to the _Side: no reference cycle keeps the
+# device buffers waiting for the garbage collector.) ----
+def _comm_rows(eng, batch, T, stats):
+    """cm_comm_stats on the engine's dist_adj / channels, all T + 1 slots of all B envs.  A constant fully connected adjacency and a
+    constant FC channel are passed as NULL (ones), a constant FL channel as the batch's constant block with stride 0."""
+    B, N, Lh = batch.B, batch.N, batch.Lh
+
+    def fill():
         chan, chan_stride = _round_channels(eng, batch)
-        L.run("cm_comm_stats", (self.T + 1) * B, N, Lh, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride, L.ptr(self.stats))
-        L.run("cm_episode_comm", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
-              L.ptr(self.table))
-
-    def means(self):
-        L.run("cm_comm_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
-
-    @staticmethod
-    def keys(row):
-        d = {name: float(row[i]) for i, name in enumerate(COMM_STATS)}
-        d["delivery"] = d["heard_degree"] / d["range_degree"] if d["range_degree"] != 0 else 1.0
-        return d
+        L.run("cm_comm_stats", (T + 1) * B, N, Lh, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride, L.ptr(stats))
+    return fill
 
 
-class _AttnStats:
-    """The attn_stats=True side of eval_summary / eval_sweep, on an engine built with store_attn=True: behind every round ONE
-    cm_attn_stats launch over the round's T x B graphs (attn[t] with dist_adj[t] / channels[t], the graph the forward of step t
-    read; constant masks by _CommStats.round's rules) and ONE cm_episode_attn launch into a device table [cells, n_epi, 6]; after
-    the last round ONE cm_attn_means launch.  curves: also ONE cm_attn_curves launch per round into the per-step sums
-    [cells, T, 6] and ONE cm_attn_curve_means launch at the end.  `out` ([cells, 6]) and `curve_out` ([cells, T, 6] or None) are
-    views of the buffer the caller copies to the host."""
+def _attn_rows(eng, batch, T, stats):
+    """cm_attn_stats over the round's T x B graphs, on an engine built with store_attn=True: attn[t] with dist_adj[t] / channels[t],
+    the graph the forward of step t read; constant masks by _comm_rows' rules."""
+    B, N, Lh = batch.B, batch.N, batch.Lh
 
-    def __init__(self, eng, batch, T, cells, n_epi, out, curve_out):
-        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out, self.curve_out = eng, batch, T, cells, n_epi, out, curve_out
+    def fill():
+        chan, chan_stride = _round_channels(eng, batch)
+        L.run("cm_attn_stats", T * B, N, Lh, L.ptr(eng.attn), N * N, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride, L.ptr(stats))
+    return fill
+
+
+def _listen_rows(eng, batch, T, stats):
+    """The counterfactual replays of the round's T slots (RolloutEngine.replay_probs: "identity" = mute, "ones" = lossless; skipped
+    by _counterfactuals' rule) into two buffers [T, B, N, A], then cm_listen_stats comparing the recorded probs - the engine is built
+    with store_probs=True - with them over the round's T x B graphs."""
+    B, N, A = batch.B, batch.N, eng.policy._action_dim
+    mute, lossless = (torch.empty(T, B, N, A, dtype=torch.float32, device=batch.device) if wanted else None
+                      for wanted in _counterfactuals(eng, batch))
+
+    def fill():
+        if mute is not None:
+            eng.replay_probs(0, T, "identity", mute)
+        if lossless is not None:
+            eng.replay_probs(0, T, "ones", lossless)
+        L.run("cm_listen_stats", T * B, N, A, L.ptr(eng.probs), N * A, L.ptr(mute), N * A, L.ptr(lossless), N * A, L.ptr(stats))
+    return fill
+
+
+def _value_rows(eng, batch, T, stats, critics, discount):
+    """The critics' values of the round's T slots (RolloutEngine.replay_values "recorded", and for Comm-DP critics "identity" = mute
+    and "ones" = lossless, skipped by _counterfactuals' rule) into buffers [T, B], then cm_value_stats over the round's T x B steps
+    against the engine's reward64 / path_len.  `critics` is what replay_values takes: one critic, or a list with one per member."""
+    graph = all(hasattr(c, "comm") for c in (critics if isinstance(critics, list) else [critics]))   # Comm-DP critics
+    values, mute, lossless = (torch.empty(T, batch.B, dtype=torch.float32, device=batch.device) if wanted else None
+                              for wanted in (True,) + _counterfactuals(eng, batch, graph))
+
+    def fill():
+        eng.replay_values(0, T, "recorded", critics, values)
+        if mute is not None:
+            eng.replay_values(0, T, "identity", critics, mute)
+        if lossless is not None:
+            eng.replay_values(0, T, "ones", critics, lossless)
+        L.run("cm_value_stats", T, batch.B, L.ptr(eng.reward64), L.ptr(eng.path_len), L.ptr(values), L.ptr(mute), L.ptr(lossless),
+              float(discount), L.ptr(stats))
+    return fill
+
+
+class _Side:
+    """One statistics family (a _Family of FAMILIES) of an eval_summary / eval_sweep call: its device state - `stats`, the round's
+    per-step rows; `table` [cells, n_epi, cols], the episode rows; with curves `sums` [cells, T, cols], the per-step sums - and its
+    launches.  Behind every round the family's rows (_Family.rows: ONE stats launch, for listen and value behind their replays) and
+    ONE cm_episode_<name> launch into the table, with curves ONE cm_<name>_curves launch more; after the last round ONE
+    cm_<name>_means launch and with curves ONE cm_<name>_curve_means launch, into `out` ([cells, cols]) and `curve_out`
+    ([cells, T, cols] or None), views of the buffer the caller copies to the host.
+    The comm family (curves_last) predates the curves: its two curve launches come behind _Curves', not with its own round and
+    means, and the launch order is part of the contract - so the caller runs round_curves / curve_means for it behind _Curves."""
+
+    def __init__(self, fam, eng, batch, T, cells, n_epi, out, curve_out, **given):
+        self.fam, self.eng, self.batch, self.T = fam, eng, batch, T
+        self.cells, self.n_epi, self.out, self.curve_out = cells, n_epi, out, curve_out
         f64 = dict(dtype=torch.float64, device=batch.device)
-        self.stats = torch.empty(T, batch.B, L.ATTN_COLS, **f64)
-        self.table = torch.zeros(cells, n_epi, L.EPA_COLS, **f64)
-        self.sums = None if curve_out is None else torch.empty(cells, T, L.ATTN_COLS, **f64)
+        self.stats = torch.empty(T + fam.more_slots, batch.B, fam.cols, dtype=fam.dtype, device=batch.device)
+        self.table = torch.zeros(cells, n_epi, fam.cols, **f64)
+        self.sums = None if curve_out is None else torch.empty(cells, T, fam.cols, **f64)
+        self.sizes = fam.sizes(batch)                           # the reductions' trailing size arguments
+        self.fill = fam.rows(eng, batch, T, self.stats, **given)
 
     def round(self, group_size, take, row0):
-        eng, batch = self.eng, self.batch
-        B, N, Lh = batch.B, batch.N, batch.Lh
-        chan, chan_stride = _round_channels(eng, batch)
-        L.run("cm_attn_stats", self.T * B, N, Lh, L.ptr(eng.attn), N * N, L.ptr(eng.dist_adj), N * N, L.ptr(chan), chan_stride,
-              L.ptr(self.stats))
-        L.run("cm_episode_attn", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
-              L.ptr(self.table))
-        if self.sums is not None:
-            L.run("cm_attn_curves", self.T, B, N, Lh, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, int(row0 > 0),
-                  L.ptr(self.sums))
+        self.fill()
+        L.run(f"cm_episode_{self.fam.name}", self.T, self.batch.B, *self.sizes, L.ptr(self.eng.path_len), L.ptr(self.stats),
+              group_size, take, self.n_epi, row0, L.ptr(self.table))
+        if not self.fam.curves_last:
+            self.round_curves(group_size, take, row0)
+
+    def round_curves(self, group_size, take, row0):
+        if self.sums is not None:                               # the first round overwrites the sums, the later ones add
+            L.run(f"cm_{self.fam.name}_curves", self.T, self.batch.B, *self.sizes, L.ptr(self.eng.path_len), L.ptr(self.stats),
+                  group_size, take, int(row0 > 0), L.ptr(self.sums))
 
     def means(self):
-        L.run("cm_attn_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
+        L.run(f"cm_{self.fam.name}_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
+        if not self.fam.curves_last:
+            self.curve_means()
+
+    def curve_means(self):
         if self.sums is not None:
-            L.run("cm_attn_curve_means", self.cells, self.T, self.n_epi, self.batch.N, self.batch.Lh, L.ptr(self.sums),
+            L.run(f"cm_{self.fam.name}_curve_means", self.cells, self.T, self.n_epi, *self.sizes, L.ptr(self.sums),
                   L.ptr(self.curve_out))
-
-
-class _ListenStats:
-    """The listen_stats=True side of eval_summary / eval_sweep, on an engine built with store_probs=True: behind every round the
-    counterfactual replays of its T slots (RolloutEngine.replay_probs: "identity" = mute, "ones" = lossless) into two buffers
-    [T, B, N, A] of this object, ONE cm_listen_stats launch comparing the recorded probs with them over the round's T x B graphs
-    and ONE cm_episode_listen launch into a device table [cells, n_epi, 6]; after the last round ONE cm_listen_means launch.
-    curves: also ONE cm_listen_curves launch per round into the per-step sums [cells, T, 6] and ONE cm_listen_curve_means launch
-    at the end.  A wrapper with a constant FC channel skips the lossless replay, one with a constant FL channel the mute replay:
-    no buffer, no forward, the counterfactual passed as NULL (its three columns exact 0).  `out` ([cells, 6]) and `curve_out`
-    ([cells, T, 6] or None) are views of the buffer the caller copies to the host."""
-
-    def __init__(self, eng, batch, T, cells, n_epi, out, curve_out):
-        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out, self.curve_out = eng, batch, T, cells, n_epi, out, curve_out
-        self.A = eng.policy._action_dim
-        f64 = dict(dtype=torch.float64, device=batch.device)
-        self.stats = torch.empty(T, batch.B, L.LISTEN_COLS, **f64)
-        self.table = torch.zeros(cells, n_epi, L.EPL_COLS, **f64)
-        self.sums = None if curve_out is None else torch.empty(cells, T, L.LISTEN_COLS, **f64)
-        const = batch.channelType if eng.channels is None else None           # the channel every slot of every round has
-        probs = lambda skip: None if skip else torch.empty(T, batch.B, batch.N, self.A, dtype=torch.float32, device=batch.device)   # noqa: E731
-        self.mute, self.lossless = probs(const == "FL"), probs(const == "FC")
-
-    def round(self, group_size, take, row0):
-        eng, T = self.eng, self.T
-        B, N, A = self.batch.B, self.batch.N, self.A
-        if self.mute is not None:
-            eng.replay_probs(0, T, "identity", self.mute)
-        if self.lossless is not None:
-            eng.replay_probs(0, T, "ones", self.lossless)
-        L.run("cm_listen_stats", T * B, N, A, L.ptr(eng.probs), N * A, L.ptr(self.mute), N * A, L.ptr(self.lossless), N * A,
-              L.ptr(self.stats))
-        L.run("cm_episode_listen", T, B, N, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0,
-              L.ptr(self.table))
-        if self.sums is not None:
-            L.run("cm_listen_curves", T, B, N, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, int(row0 > 0),
-                  L.ptr(self.sums))
-
-    def means(self):
-        L.run("cm_listen_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
-        if self.sums is not None:
-            L.run("cm_listen_curve_means", self.cells, self.T, self.n_epi, self.batch.N, L.ptr(self.sums), L.ptr(self.curve_out))
 
 
 def _check_baselines(who, policies, value_stats, baselines):
@@ -331,143 +349,118 @@ def _explained(sq_err, bias, ret, ret_sq):
     return np.where(flat, np.where(resid <= eps, 1.0, 0.0), 1.0 - resid / np.where(flat, 1.0, var))
 
 
-class _ValueStats:
-    """The value_stats=True side of eval_summary / eval_sweep: behind every round the critics' values of its T slots
-    (RolloutEngine.replay_values "recorded", and for Comm-DP critics "identity" = mute and "ones" = lossless, skipped under
-    _ListenStats's constant-channel rules: no buffer, no forward, the counterfactual passed as NULL) into buffers [T, B] of this
-    object, ONE cm_value_stats launch over the round's T x B steps against the engine's reward64 / path_len and ONE
-    cm_episode_value launch into a device table [cells, n_epi, 6]; after the last round ONE cm_value_means launch.  curves: also
-    ONE cm_value_curves launch per round into the per-step sums [cells, T, 6] and ONE cm_value_curve_means launch at the end.
-    `critics` is what replay_values takes: one critic, or a list with one per member.  `out` ([cells, 6]) and `curve_out`
-    ([cells, T, 6] or None) are views of the buffer the caller copies to the host."""
+def _value_keys(cols):
+    """The six cm_value_means columns (the means per step: floats, or arrays over the cells) -> the VALUE_KEYS dict."""
+    mean, ret, sq_err, ret_sq, msg, loss = cols
+    bias = mean - ret
+    return dict(value_mean=mean, value_return=ret, value_bias=bias, value_rmse=np.sqrt(sq_err),
+                value_ev=_explained(sq_err, bias, ret, ret_sq)[()], msg_value=msg, loss_value=loss)
 
-    def __init__(self, eng, batch, T, cells, n_epi, critics, discount, out, curve_out):
-        self.eng, self.batch, self.T, self.cells, self.n_epi, self.out, self.curve_out = eng, batch, T, cells, n_epi, out, curve_out
-        self.critics, self.discount = critics, float(discount)
-        f64 = dict(dtype=torch.float64, device=batch.device)
-        self.stats = torch.empty(T, batch.B, L.VALUE_COLS, **f64)
-        self.table = torch.zeros(cells, n_epi, L.EPV_COLS, **f64)
-        self.sums = None if curve_out is None else torch.empty(cells, T, L.VALUE_COLS, **f64)
-        graph = all(hasattr(c, "comm") for c in (critics if isinstance(critics, list) else [critics]))   # Comm-DP critics
-        const = batch.channelType if eng.channels is None else None           # the channel every slot of every round has
-        values = lambda skip: None if skip else torch.empty(T, batch.B, dtype=torch.float32, device=batch.device)   # noqa: E731
-        self.values, self.mute, self.lossless = values(False), values(not graph or const == "FL"), values(not graph or const == "FC")
 
-    def round(self, group_size, take, row0):
-        eng, T, B = self.eng, self.T, self.batch.B
-        eng.replay_values(0, T, "recorded", self.critics, self.values)
-        if self.mute is not None:
-            eng.replay_values(0, T, "identity", self.critics, self.mute)
-        if self.lossless is not None:
-            eng.replay_values(0, T, "ones", self.critics, self.lossless)
-        L.run("cm_value_stats", T, B, L.ptr(eng.reward64), L.ptr(eng.path_len), L.ptr(self.values), L.ptr(self.mute),
-              L.ptr(self.lossless), self.discount, L.ptr(self.stats))
-        L.run("cm_episode_value", T, B, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, self.n_epi, row0, L.ptr(self.table))
-        if self.sums is not None:
-            L.run("cm_value_curves", T, B, L.ptr(eng.path_len), L.ptr(self.stats), group_size, take, int(row0 > 0), L.ptr(self.sums))
+def _value_curve_keys(cols, step_cnt):
+    """The six columns of zero-padded means over the steps ([6, T] of a cell, or [6, cells, T]) and the step_cnt curves (the share
+    of episodes still running at step t) -> the VALUE_KEYS curves: value_rmse and value_ev over the episodes still running (0 and 1
+    where none does)."""
+    mean, ret, sq_err, ret_sq, msg, loss = cols
+    some = step_cnt > 0
+    run = lambda x: np.where(some, x / np.where(some, step_cnt, 1.0), 0.0)           # noqa: E731
+    r_mean, r_ret, r_sq, r_rsq = run(mean), run(ret), run(sq_err), run(ret_sq)
+    return dict(value_mean=mean, value_return=ret, value_bias=mean - ret, value_rmse=np.sqrt(r_sq),
+                value_ev=np.where(some, _explained(r_sq, r_mean - r_ret, r_ret, r_rsq), 1.0), msg_value=msg, loss_value=loss)
 
-    def means(self):
-        L.run("cm_value_means", self.cells, self.n_epi, L.ptr(self.table), L.ptr(self.out))
-        if self.sums is not None:
-            L.run("cm_value_curve_means", self.cells, self.T, self.n_epi, L.ptr(self.sums), L.ptr(self.curve_out))
 
-    @staticmethod
-    def keys(row):
-        """A cm_value_means row (the six means per step) -> the VALUE_KEYS dict."""
-        mean, ret, sq_err, ret_sq, msg, loss = (float(x) for x in row)
-        bias = mean - ret
-        return dict(value_mean=mean, value_return=ret, value_bias=bias, value_rmse=float(np.sqrt(sq_err)),
-                    value_ev=float(_explained(sq_err, bias, ret, ret_sq)), msg_value=msg, loss_value=loss)
+def _comm_keys(cols):
+    """The four cm_comm_means columns (floats, or arrays over the cells, or over cells and steps) -> the COMM_KEYS dict: delivery =
+    heard_degree / range_degree, 1.0 where nobody is in range."""
+    d = dict(zip(COMM_STATS, cols))
+    some = d["range_degree"] != 0
+    d["delivery"] = np.where(some, d["heard_degree"] / np.where(some, d["range_degree"], 1.0), 1.0)
+    return d
 
-    @staticmethod
-    def curve_keys(cols, step_cnt):
-        """A cell's host table [6, T] of zero-padded means and its step_cnt curve (the share of episodes still running at step
-        t) -> the VALUE_KEYS curves: value_rmse and value_ev over the episodes still running (0 and 1 where none does)."""
-        mean, ret, sq_err, ret_sq, msg, loss = cols
-        some = step_cnt > 0
-        run = lambda x: np.where(some, x / np.where(some, step_cnt, 1.0), 0.0)           # noqa: E731
-        r_mean, r_ret, r_sq, r_rsq = run(mean), run(ret), run(sq_err), run(ret_sq)
-        return dict(value_mean=mean, value_return=ret, value_bias=mean - ret, value_rmse=np.sqrt(r_sq),
-                    value_ev=np.where(some, _explained(r_sq, r_mean - r_ret, r_ret, r_rsq), 1.0), msg_value=msg, loss_value=loss)
+
+def _named(names):
+    """-> keys(cols) of a family whose keys are its columns."""
+    return lambda cols: dict(zip(names, cols))
+
+
+# What tells the statistics families apart.  name: the stem of the four reductions cm_episode_<name>, cm_<name>_means,
+# cm_<name>_curves, cm_<name>_curve_means and of the buffer's sections; cols / dtype / more_slots: a step row of `stats`
+# [T + more_slots, B, cols] (an episode row has the same columns); sizes(batch): the reductions' trailing size arguments; rows(eng,
+# ...): what produces a round's stats (above); keys(cols): the host side, elementwise on the columns of the family's means
+# ([cols, cells]) -> what the dicts gain, and on those of its curves ([cols, cells, T]) -> what their `curves` gain - the latter
+# through curve_keys(cols, step_cnt) where the curves need the share of running episodes; curves_last: the curve launches and
+# sections come behind the episode curves', not with the family's own (_Side).
+_Family = collections.namedtuple("_Family", "name cols dtype more_slots sizes rows keys curve_keys curves_last",
+                                 defaults=(None, False))
+FAMILIES = dict(
+    comm_stats=_Family("comm", L.COMM_COLS, torch.int32, 1, lambda batch: (batch.N, batch.Lh), _comm_rows, _comm_keys,
+                       curves_last=True),
+    attn_stats=_Family("attn", L.ATTN_COLS, torch.float64, 0, lambda batch: (batch.N, batch.Lh), _attn_rows,
+                       _named(ATTN_KEYS)),
+    listen_stats=_Family("listen", L.LISTEN_COLS, torch.float64, 0, lambda batch: (batch.N,), _listen_rows,
+                         _named(LISTEN_KEYS)),
+    value_stats=_Family("value", L.VALUE_COLS, torch.float64, 0, lambda batch: (), _value_rows, _value_keys,
+                        _value_curve_keys))
 
 
 class _Curves:
     """The curves=True side of eval_summary / eval_sweep: behind every round ONE cm_episode_curves launch on the engine's
-    trajectory buffers into the device table of per-step sums [cells, T, 9] - the first round overwrites it, the later ones add -
-    and, with comm_stats, ONE cm_comm_curves launch on the rows _CommStats.round has just produced into [cells, T, 4]; after the
-    last round ONE cm_curve_means (and ONE cm_comm_curve_means) launch into `out` (`comm_out`), views of the buffer the caller
-    copies to the host."""
+    trajectory buffers into the device table of per-step sums [cells, T, 9] - the first round overwrites it, the later ones add;
+    after the last round ONE cm_curve_means launch into `out`, a view of the buffer the caller copies to the host."""
 
-    def __init__(self, eng, batch, T, cells, n_epi, scen, out, comm_out):
-        self.eng, self.batch, self.T, self.cells, self.n_epi, self.scen = eng, batch, T, cells, n_epi, scen
-        self.out, self.comm_out = out, comm_out
+    def __init__(self, eng, batch, T, cells, n_epi, scen, out):
+        self.eng, self.batch, self.T, self.cells, self.n_epi, self.scen, self.out = eng, batch, T, cells, n_epi, scen, out
         self.sums = torch.empty(cells, T, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-        self.comm_sums = None if comm_out is None else torch.empty(cells, T, L.COMM_COLS, dtype=torch.float64, device=batch.device)
 
-    def round(self, group_size, take, accumulate, comm):
+    def round(self, group_size, take, row0):
         eng, batch = self.eng, self.batch
         L.run("cm_episode_curves", self.T, batch.B, batch.N, self.scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success),
-              L.ptr(eng.path_len), L.ptr(eng.dist_adj), group_size, take, int(accumulate), L.ptr(self.sums))
-        if self.comm_sums is not None:
-            L.run("cm_comm_curves", self.T, batch.B, batch.N, batch.Lh, L.ptr(eng.path_len), L.ptr(comm.stats), group_size, take,
-                  int(accumulate), L.ptr(self.comm_sums))
+              L.ptr(eng.path_len), L.ptr(eng.dist_adj), group_size, take, int(row0 > 0), L.ptr(self.sums))
 
     def means(self):
         L.run("cm_curve_means", self.cells, self.T, self.n_epi, self.scen, self.batch.N, L.ptr(self.sums), L.ptr(self.out))
-        if self.comm_sums is not None:
-            L.run("cm_comm_curve_means", self.cells, self.T, self.n_epi, self.batch.N, self.batch.Lh, L.ptr(self.comm_sums),
-                  L.ptr(self.comm_out))
 
     @staticmethod
-    def keys(rows, comm_rows):
-        """The host tables [cells, 9, T] (and [cells, 4, T] or None) -> per cell its `curves` dict; delivery by _CommStats.keys's
-        rule per step, for all cells at once."""
-        out = [{name: cell[i] for i, name in enumerate(['success'] + VECTORS)} for cell in rows]
-        if comm_rows is not None:
-            rd, hd = comm_rows[:, COMM_STATS.index("range_degree")], comm_rows[:, COMM_STATS.index("heard_degree")]
-            some = rd != 0
-            delivery = np.where(some, hd / np.where(some, rd, 1.0), 1.0)
-            for d, cell, dl in zip(out, comm_rows, delivery):
-                d.update({name: cell[i] for i, name in enumerate(COMM_STATS)})
-                d["delivery"] = dl
-        return out
+    def keys(rows):
+        """The host table [cells, 9, T] -> per cell its `curves` dict."""
+        return [dict(zip(['success'] + VECTORS, cell)) for cell in rows]
 
 
-def _summary_buffers(cells, comm_stats, device, curve_steps=0, attn_stats=False, listen_stats=False, value_stats=False):
-    """-> (the one buffer that is copied to the host, its [cells, 12] summary view, its [cells, 4] comm view or None, and with
-    curve_steps = T > 0 its [cells, T, 9] curves view and its [cells, T, 4] comm curves view, else None).  attn_stats: two values
-    more, the buffer's [cells, 6] attention view and its [cells, T, 6] attention curves view (None without curve_steps);
-    listen_stats: behind them the same two for the listening statistics; value_stats: behind those the same two for the critic
-    statistics, at the end of the buffer."""
-    sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm_stats else 0, cells * curve_steps * L.EPI_COLS,
-             cells * curve_steps * L.EPC_COLS if comm_stats else 0]
-    shapes = [(cells, L.SUM_COLS), (cells, L.EPC_COLS), (cells, curve_steps, L.EPI_COLS), (cells, curve_steps, L.EPC_COLS)]
-    if attn_stats:
-        sizes += [cells * L.EPA_COLS, cells * curve_steps * L.EPA_COLS]
-        shapes += [(cells, L.EPA_COLS), (cells, curve_steps, L.EPA_COLS)]
-    if listen_stats:
-        sizes += [cells * L.EPL_COLS, cells * curve_steps * L.EPL_COLS]
-        shapes += [(cells, L.EPL_COLS), (cells, curve_steps, L.EPL_COLS)]
-    if value_stats:
-        sizes += [cells * L.EPV_COLS, cells * curve_steps * L.EPV_COLS]
-        shapes += [(cells, L.EPV_COLS), (cells, curve_steps, L.EPV_COLS)]
-    flat = torch.empty(sum(sizes), dtype=torch.float64, device=device)
-    parts = [p if p.numel() else None for p in flat.split(sizes)]
-    return (flat,) + tuple(None if p is None else p.view(shape) for p, shape in zip(parts, shapes))
+def _layout(cells, T, fams, curves):
+    """The one buffer that is copied to the host, as both sides read it: the ordered (name, shape) of its sections of doubles for
+    the active families `fams` (in FAMILIES' order).  The summary [cells, 12]; a curves_last family's means [cells, cols]; with
+    curves the episode curves [cells, T, 9] and that family's "<name>_curves" [cells, T, cols]; then per other family "<name>"
+    and with curves "<name>_curves"."""
+    first, rest = [f for f in fams if f.curves_last], [f for f in fams if not f.curves_last]
+    sections = [("summary", (cells, L.SUM_COLS))] + [(f.name, (cells, f.cols)) for f in first]
+    if curves:
+        sections += [("curves", (cells, T, L.EPI_COLS))] + [(f.name + "_curves", (cells, T, f.cols)) for f in first]
+    for f in rest:
+        sections += [(f.name, (cells, f.cols))] + ([(f.name + "_curves", (cells, T, f.cols))] if curves else [])
+    return sections
+
+
+def _cut(flat, layout):
+    """-> {name: its section of `flat`, shaped}: views of the device buffer (a torch tensor) or of its host copy (a numpy array)."""
+    ends = itertools.accumulate(math.prod(shape) for _, shape in layout)
+    return {name: flat[end - math.prod(shape):end].reshape(shape) for (name, shape), end in zip(layout, ends)}
+
+
+def _host_tables(host_all, layout):
+    """_cut of the host copy, with one transposition per curve table: [cells, cols, T], a cell's curve is then a contiguous row."""
+    return {name: np.ascontiguousarray(part.transpose(0, 2, 1)) if part.ndim == 3 else part
+            for name, part in _cut(host_all, layout).items()}
 
 
 def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True,
            curves=False, attn_stats=False, listen_stats=False, value_stats=False, baselines=None, discount=0.99):
     """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
     refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
-    [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  Per round reset, play, bump, check_status, the
-    episode rows of groups of E envs into the device table [K*C, n_eval_episodes, 9] (and _CommStats.round); then the table's
-    reduction (and _CommStats.means), and the one copy to the host of _summary_buffers' buffer.  curves: _Curves.round behind
-    every round's rows, _Curves.means behind the reductions, their doubles in the same buffer.  attn_stats: the engine keeps
-    its attention output, _AttnStats.round / .means behind _CommStats's, their doubles behind the curves' in the same buffer.
-    listen_stats: the engine keeps its probabilities, _ListenStats.round / .means behind _AttnStats's, their doubles behind those.
-    value_stats: `baselines` checked (_check_baselines) and synced, _ValueStats.round / .means behind _ListenStats's, their doubles
-    at the end."""
+    [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  The refusals; the engine (it keeps its attention
+    output for attn_stats and its probabilities for listen_stats; `baselines` checked by _check_baselines and synced); the active
+    _Sides in FAMILIES' order, their views cut from the one buffer by _layout.  Per round _play_round, the episode rows of groups of
+    E envs into the device table [K*C, n_eval_episodes, 9], every side's round, _Curves.round and the curves_last sides' curve sums;
+    then the means in the same order, the one copy to the host, and the dicts from the sides' keys."""
     single = not isinstance(policies, (PolicySet, list, tuple))
     comm_dp = all(hasattr(p, "comm") for p in ([policies] if single else policies))
     if attn_stats and not comm_dp:
@@ -521,100 +514,60 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     chunk = conds is not None or not single
     scen = L.CM_PP if batch.scenario == "pp" else L.CM_CO
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
-    flat, out, comm_out, curve_out, comm_curve_out, *more = _summary_buffers(cells, comm_stats, batch.device, T if curves else 0,
-                                                                             bool(attn_stats), bool(listen_stats), critics is not None)
-    comm = _CommStats(eng, batch, T, cells, n_epi, comm_out) if comm_stats else None
-    attn = _AttnStats(eng, batch, T, cells, n_epi, *more[:2]) if attn_stats else None
-    listen = _ListenStats(eng, batch, T, cells, n_epi, *more[2 * bool(attn_stats):][:2]) if listen_stats else None
-    value = (_ValueStats(eng, batch, T, cells, n_epi, critics[0] if single else critics, discount, *more[-2:])
-             if critics is not None else None)
-    curve = _Curves(eng, batch, T, cells, n_epi, scen, curve_out, comm_curve_out) if curves else None
+    on = dict(comm_stats=comm_stats, attn_stats=attn_stats, listen_stats=listen_stats, value_stats=critics is not None)
+    given = dict(value_stats=dict(critics=critics and (critics[0] if single else critics), discount=discount))
+    layout = _layout(cells, T, [fam for switch, fam in FAMILIES.items() if on[switch]], bool(curves))
+    flat = torch.empty(sum(math.prod(shape) for _, shape in layout), dtype=torch.float64, device=batch.device)
+    views = _cut(flat, layout)
+    sides = [_Side(fam, eng, batch, T, cells, n_epi, views[fam.name], views.get(fam.name + "_curves"), **given.get(switch, {}))
+             for switch, fam in FAMILIES.items() if on[switch]]
+    last = [side for side in sides if side.fam.curves_last]
+    curve = _Curves(eng, batch, T, cells, n_epi, scen, views["curves"]) if curves else None
     done = 0
     while done < n_epi:
-        eng.reset()
-        eng.play(0, T, greedy=bool(eval_greedy), chunk=chunk)
-        eng.bump(T)
-        batch.check_status()
+        _play_round(eng, batch, T, bool(eval_greedy), chunk)
         take = min(E, n_epi - done)
         L.run("cm_episode_stats", T, B, N, scen, L.ptr(eng.reward64), L.ptr(eng.details), L.ptr(eng.success), L.ptr(eng.path_len),
               L.ptr(eng.dist_adj), E, take, n_epi, done, L.ptr(table))
-        if comm:
-            comm.round(E, take, done)
-        if attn:
-            attn.round(E, take, done)
-        if listen:
-            listen.round(E, take, done)
-        if value:
-            value.round(E, take, done)
+        for side in sides:
+            side.round(E, take, done)
         if curve:
-            curve.round(E, take, done > 0, comm)
+            curve.round(E, take, done)
+        for side in last:
+            side.round_curves(E, take, done)
         done += take
-    L.run("cm_episode_means", cells, n_epi, L.ptr(table), L.ptr(out))
-    if comm:
-        comm.means()
-    if attn:
-        attn.means()
-    if listen:
-        listen.means()
-    if value:
-        value.means()
+    L.run("cm_episode_means", cells, n_epi, L.ptr(table), L.ptr(views["summary"]))
+    for side in sides:
+        side.means()
     if curve:
         curve.means()
-    host_all = flat.cpu().numpy()
-    sizes = [cells * L.SUM_COLS, cells * L.EPC_COLS if comm else 0, cells * T * L.EPI_COLS if curve else 0,
-             cells * T * L.EPC_COLS if curve and comm else 0, cells * L.EPA_COLS if attn else 0,
-             cells * T * L.EPA_COLS if curve and attn else 0, cells * L.EPL_COLS if listen else 0,
-             cells * T * L.EPL_COLS if curve and listen else 0, cells * L.EPV_COLS if value else 0]
-    ends = np.cumsum(sizes)
-    host = host_all[:ends[0]].reshape(cells, L.SUM_COLS)
-    host_comm = host_all[ends[0]:ends[1]].reshape(cells, L.EPC_COLS) if comm else None
-    # one transposition per table: a cell's curve is then a contiguous row
-    host_curves = np.ascontiguousarray(host_all[ends[1]:ends[2]].reshape(cells, T, L.EPI_COLS).transpose(0, 2, 1)) if curve else None
-    host_comm_curves = (np.ascontiguousarray(host_all[ends[2]:ends[3]].reshape(cells, T, L.EPC_COLS).transpose(0, 2, 1))
-                        if curve and comm else None)
-    host_attn = host_all[ends[3]:ends[4]].reshape(cells, L.EPA_COLS) if attn else None
+    for side in last:
+        side.curve_means()
+    host = _host_tables(flat.cpu().numpy(), layout)
     bound = base.bound_return
-    cell_curves = curve.keys(host_curves, host_comm_curves) if curve else None
-    if curve and attn:
-        host_attn_curves = np.ascontiguousarray(host_all[ends[4]:ends[5]].reshape(cells, T, L.EPA_COLS).transpose(0, 2, 1))
-        for d, cell in zip(cell_curves, host_attn_curves):
-            d.update({name: cell[i] for i, name in enumerate(ATTN_KEYS)})
-    host_listen = host_all[ends[5]:ends[6]].reshape(cells, L.EPL_COLS) if listen else None
-    if curve and listen:
-        host_listen_curves = np.ascontiguousarray(host_all[ends[6]:ends[7]].reshape(cells, T, L.EPL_COLS).transpose(0, 2, 1))
-        for d, cell in zip(cell_curves, host_listen_curves):
-            d.update({name: cell[i] for i, name in enumerate(LISTEN_KEYS)})
-    host_value = host_all[ends[7]:ends[8]].reshape(cells, L.EPV_COLS) if value else None
-    if curve and value:
-        host_value_curves = np.ascontiguousarray(host_all[ends[8]:].reshape(cells, T, L.EPV_COLS).transpose(0, 2, 1))
-        for d, cell in zip(cell_curves, host_value_curves):
-            d.update(value.curve_keys(cell, d["step_cnt"]))
+    by_cols = lambda name: np.moveaxis(host[name], 1, 0)                   # noqa: E731  [cols, cells] or [cols, cells, T]
+    side_keys = [side.fam.keys(by_cols(side.fam.name)) for side in sides]    # per side: name -> [cells]
+    cell_curves = curve.keys(host["curves"]) if curve else None
+    for fam in (side.fam for side in sides if curve):
+        cols = by_cols(fam.name + "_curves")
+        step_cnt = by_cols("curves")[1 + VECTORS.index("step_cnt")]                                  # [cells, T]
+        more = fam.keys(cols) if fam.curve_keys is None else fam.curve_keys(cols, step_cnt)
+        for g, d in enumerate(cell_curves):
+            d.update({name: v[g] for name, v in more.items()})
     res = []
-    for g in range(cells):
-        d = dict(n_episodes=n_epi, success=float(host[g, 0]))
-        d.update({vec: float(host[g, 1 + i]) for i, vec in enumerate(VECTORS)})
-        d.update({name: float(host[g, L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
+    for g, row in enumerate(host["summary"]):
+        d = dict(n_episodes=n_epi, success=float(row[0]))
+        d.update({vec: float(row[1 + i]) for i, vec in enumerate(VECTORS)})
+        d.update({name: float(row[L.EPI_COLS + i]) for i, name in enumerate(SUMMARY_STATS)})
         d["bound_return"] = bound
         if conds is not None:
             d["condition"] = conds[g % C_]
         if episodes:
             d["episodes"] = table[g]
-        if comm:
-            d.update(comm.keys(host_comm[g]))
+        for side, keys in zip(sides, side_keys):
+            d.update({name: float(v[g]) for name, v in keys.items()})
             if episodes:
-                d["comm_episodes"] = comm.table[g]
-        if attn:
-            d.update({name: float(host_attn[g, i]) for i, name in enumerate(ATTN_KEYS)})
-            if episodes:
-                d["attn_episodes"] = attn.table[g]
-        if listen:
-            d.update({name: float(host_listen[g, i]) for i, name in enumerate(LISTEN_KEYS)})
-            if episodes:
-                d["listen_episodes"] = listen.table[g]
-        if value:
-            d.update(value.keys(host_value[g]))
-            if episodes:
-                d["value_episodes"] = value.table[g]
+                d[side.fam.name + "_episodes"] = side.table[g]
         if curve:
             d["curves"] = cell_curves[g]
         res.append(d)
@@ -641,14 +594,19 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     it once per episode, so there is no _co entry here.  render / inspect_steps are not parameters (UI is out of scope).
     flag[0] set returns None per policy, as eval_models returns its empty tuples.  Afterwards env.eval_n_epi and
     env.last_eval_average_reward (a list of K for several policies) are what eval_models / eval_model leave.
+    The five switches below have this in common.  A statistics family <f> (comm, attn, listen, value) takes, behind every round,
+    ONE cm_<f>_stats launch over the round's recorded slots (for listen and value behind their forward-only replays) and ONE
+    cm_episode_<f> launch into a device table [K, n_eval_episodes, cols] (with curves ONE cm_<f>_curves more, into per-step
+    sums [K, T, cols]); after the last round ONE cm_<f>_means launch (with curves ONE cm_<f>_curve_means more).  Their doubles
+    ride in the same single device-to-host copy as the summary.  Sums are integers or f64 in one fixed order and every value is
+    divided once: the same episodes give the same bits.  With episodes=True a family also returns `<f>_episodes`, its
+    [n_eval_episodes, cols] slice of the table as a device tensor, and with curves=True its keys also in `curves`.  Off (the
+    default), a switch launches, allocates and returns nothing, and everything else is bit for bit the same.
     comm_stats=True adds the communication statistics of the graphs the policy acted through (slots 0 .. n-1 of each episode;
-    include/commarl.h, cm_comm_stats): behind every round ONE cm_comm_stats launch on the engine's dist_adj / channels and ONE
-    cm_episode_comm launch, after the last round ONE cm_comm_means launch whose [K, 4] doubles ride in the same device-to-host
-    copy as the summary.  Every dict gains range_degree (mean number of agents in range), heard_degree (mean number heard per
-    hop), reach (mean number of team mates whose information can arrive within the net's hops), range_reach (the same without
-    channel loss) and delivery = heard_degree / range_degree (1.0 when nobody is in range); with episodes=True also
-    `comm_episodes`, the [n_eval_episodes, 4] device table behind the first four.  Off (the default), nothing is launched,
-    allocated or returned beyond the above and the results are bit for bit the same.
+    include/commarl.h, cm_comm_stats, on the engine's dist_adj / channels).  Every dict gains range_degree (mean number of agents
+    in range), heard_degree (mean number heard per hop), reach (mean number of team mates whose information can arrive within the
+    net's hops), range_reach (the same without channel loss) and delivery = heard_degree / range_degree (1.0 when nobody is in
+    range); `comm_episodes` holds the first four.
     curves=True adds `curves` to every dict: numpy float64 arrays of length max_env_steps keyed success and every name of
     VECTORS - entry t is the mean over ALL n_eval_episodes episodes of the per-step value eval_model lists for step t, an episode
     that has ended counting as zero (the reference pads its per-step lists with zeros to max_env_steps before it saves them as
@@ -656,23 +614,17 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     curve divided by it the mean over the running episodes; a summed vector's curve adds up to the vector's summary value.  With
     comm_stats=True also every name of COMM_KEYS, from the graphs the policies acted through at step t (delivery[t] =
     heard_degree[t] / range_degree[t], 1.0 where nobody is in range - or no episode runs).  Behind every round ONE
-    cm_episode_curves launch (and ONE cm_comm_curves launch) adds the round's per-step sums to a device table [K, T, 9]
-    ([K, T, 4]), after the last round ONE cm_curve_means (cm_comm_curve_means) launch divides them; the doubles ride in the same
-    copy.  Integer-valued sums are exact and divided once, the reward sums have one fixed order: the same episodes give the same
-    bits.  Off (the default), nothing is launched, allocated or returned beyond the above and the results are bit for bit the
-    same.
+    cm_episode_curves launch adds the round's per-step sums to a device table [K, T, 9], after the last round ONE cm_curve_means
+    launch divides them (the comm family's two curve launches come behind these).  Integer-valued sums are exact, the reward
+    sums have one fixed order.
     attn_stats=True (Comm-DP policies; anything else raises ValueError before anything is built) adds what the policy did with
     what was delivered.  The engine then keeps the attention matrix M every forward writes - row i is agent i's softmax over the
     team, BEFORE any mask (the reference's attention_weights); for hop l the net uses M * dist_adj * channels[l] renormalised
     per row.  Every dict gains ATTN_KEYS, means per agent over the graphs the policy acted through (the last three also per hop):
     attn_self (weight on the agent itself), attn_entropy (nats, of a row of M), attn_range_mass (attention on agents in range),
     attn_kept_mass (attention on links that carried something), attn_eff_self and attn_eff_entropy (self weight and entropy of
-    the renormalised weights the hop really uses; a row with nothing kept counts as 0); with episodes=True also `attn_episodes`,
-    the [n_eval_episodes, 6] device table behind them; with curves=True the same six names in `curves`.  Behind every round ONE
-    cm_attn_stats launch over the round's T x B graphs and ONE cm_episode_attn launch (with curves ONE cm_attn_curves more), after
-    the last round ONE cm_attn_means (cm_attn_curve_means) launch; the doubles ride in the same copy.  f64 sums in a fixed
-    order: the same episodes give the same bits.  Keeping M costs 4 T B N^2 bytes of device memory for the call.  Off (the
-    default), the engine keeps no attention and nothing is launched, allocated or returned beyond the above.
+    the renormalised weights the hop really uses; a row with nothing kept counts as 0); `attn_episodes` holds the same six.
+    Keeping M costs 4 T B N^2 bytes of device memory for the call; off, the engine keeps no attention.
     listen_stats=True (Comm-DP policies; anything else raises ValueError before anything is built) adds whether the messages
     changed what the agents did.  The engine then keeps the probabilities p it acted on, and behind every round replays the
     round's slots forward-only (RolloutEngine.replay_probs: the recorded observations and dist_adj; nothing is drawn, no recorded
@@ -680,15 +632,10 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     lossless - all ones, everything in range is delivered.  Every dict gains LISTEN_KEYS, means per agent over the graphs the
     policy acted through of, with q the counterfactual probabilities: listen_kl = KL(p || q_mute) in nats (q floored at FLT_MIN;
     not clamped at 0), listen_tv = the total variation, listen_flip = the share of agents whose greedy action changes; loss_kl,
-    loss_tv, loss_flip the same against q_lossless - what the channel loss changed in the decisions; with episodes=True also
-    `listen_episodes`, the [n_eval_episodes, 6] device table behind them; with curves=True the same six names in `curves`.
-    Behind every round the replays (one forward launch per member and replay; under the identity one per block of
-    rollout.REPLAY_MASK_BYTES of mask), ONE cm_listen_stats launch over the round's T x B graphs and ONE cm_episode_listen launch
-    (with curves ONE cm_listen_curves more), after the last round ONE cm_listen_means (cm_listen_curve_means) launch; the doubles
-    ride at the end of the same copy.  A wrapper with a constant FC channel skips the lossless replay and one with a constant FL
-    channel the mute replay: exact zeros.  f64 sums in a fixed order: the same episodes give the same bits.  The probabilities
-    cost 4 T B N A bytes of device memory each (recorded, mute, lossless).  Off (the default), the engine keeps no
-    probabilities and nothing is launched, allocated or returned beyond the above.
+    loss_tv, loss_flip the same against q_lossless - what the channel loss changed in the decisions; `listen_episodes` holds the same
+    six.  A replay is one forward launch per member, under the identity one per block of rollout.REPLAY_MASK_BYTES of mask.  A
+    wrapper with a constant FC channel skips the lossless replay and one with a constant FL channel the mute replay: exact zeros.
+    The probabilities cost 4 T B N A bytes of device memory each (recorded, mute, lossless); off, the engine keeps none.
     value_stats=True with baselines= (one critic for one policy, a list of K for K policies, critic k judging policy k's envs:
     nets.CommBaseCritic of any aggregator and layer sizes, or nets.GaussianMLPBaseline for Obs-DP / CENT policies; all of one
     class, built for their policy's team size and observation width - anything else, and either keyword without the other,
@@ -708,12 +655,9 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     table behind the keys (per episode the means over its steps of v, G, (v - G)^2, G^2, v - v_mute, v_lossless - v), times the
     `step_cnt` column of `episodes` gives the per-episode sums to pool.  With curves=True the same seven names are in `curves`:
     value_mean, value_return, value_bias, msg_value and loss_value zero-padded means like every curve, value_rmse and value_ev
-    over the episodes still running at step t (0 and 1 where none does).  Behind every round the replays (one forward launch
-    per critic and replay; under the identity one per block of rollout.REPLAY_MASK_BYTES of mask), ONE cm_value_stats launch
-    over the round's T x B steps and ONE cm_episode_value launch (with curves ONE cm_value_curves more), after the last round ONE
-    cm_value_means (cm_value_curve_means) launch; the doubles ride at the end of the same copy.  A wrapper with a constant FC
-    channel skips the lossless replay and one with a constant FL channel the mute replay: exact zeros.  f64 in a fixed order:
-    the same episodes give the same bits.  Off (the default), nothing is launched, allocated or returned beyond the above."""
+    over the episodes still running at step t (0 and 1 where none does).  A replay is one forward launch per critic, under
+    the identity one per block of rollout.REPLAY_MASK_BYTES of mask; the constant-channel rule of listen_stats skips the same
+    replays here: exact zeros."""
     return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
                   curves=curves, attn_stats=attn_stats, listen_stats=listen_stats, value_stats=value_stats, baselines=baselines,
                   discount=discount)
@@ -745,23 +689,19 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     channel kind whose params carry condition c, with E envs - at env's env_id_offset when paired (under greedy evaluation the
     points of a curve then differ only through the condition), at the cell's first env otherwise.
     flag, episodes, comm_stats, the refusals and env.eval_n_epi are eval_summary's; env.last_eval_average_reward is a [K][C] list
-    ([C] for a single policy).  With comm_stats=True every cell carries eval_summary's communication keys (one cm_comm_stats and
-    one cm_episode_comm launch more per round, one cm_comm_means at the end, [K*C, 4] doubles more in the same copy): a robustness
-    curve can then be plotted against what was delivered (delivery, reach), not only against the knob that was turned.
-    curves=True gives every cell eval_summary's `curves` (per round one cm_episode_curves launch with groups of E envs, with
-    comm_stats one cm_comm_curves launch; [K*C, T, 9] and [K*C, T, 4] doubles more in the same copy): when a lossy channel
-    starts to hurt, and whether delivery collapses as the team spreads out, step by step.
-    attn_stats=True gives every cell eval_summary's ATTN_KEYS (per round one cm_attn_stats and one cm_episode_attn launch with
-    groups of E envs, one cm_attn_means at the end; [K*C, 6] doubles more in the same copy, with curves [K*C, T, 6]): how much
-    attention mass a condition strands on dead links and how far the weights the hops really use concentrate - what explains the
-    curve that delivery and reach only describe.
-    listen_stats=True gives every cell eval_summary's LISTEN_KEYS (per round the two counterfactual replays, one cm_listen_stats
-    and one cm_episode_listen launch with groups of E envs, one cm_listen_means at the end; [K*C, 6] doubles more in the same
-    copy, with curves [K*C, T, 6]): whether a condition changed any decision - a cell that loses nothing has loss_* exactly 0.
-    value_stats=True, baselines= (one critic per policy) gives every cell eval_summary's VALUE_KEYS (per round the critics'
-    replays, one cm_value_stats and one cm_episode_value launch with groups of E envs, one cm_value_means at the end; [K*C, 6]
-    doubles more in the same copy, with curves [K*C, T, 6]): whether the baseline stays good at the lossy end of the curve and
-    what it believes the loss costs - a cell that loses nothing has loss_value exactly 0."""
+    ([C] for a single policy).  The five switches are eval_summary's, with its launches per round and at the end (the reductions
+    with groups of E envs) and K*C cells in place of K policies in every table; their doubles ride in the same copy.
+    comm_stats=True: every cell carries eval_summary's communication keys - a robustness curve can then be plotted against what
+    was delivered (delivery, reach), not only against the knob that was turned.
+    curves=True: every cell carries eval_summary's `curves` - when a lossy channel starts to hurt, and whether delivery collapses
+    as the team spreads out, step by step.
+    attn_stats=True: every cell carries eval_summary's ATTN_KEYS - how much attention mass a condition strands on dead links and
+    how far the weights the hops really use concentrate: what explains the curve that delivery and reach only describe.
+    listen_stats=True: every cell carries eval_summary's LISTEN_KEYS - whether a condition changed any decision; a cell that
+    loses nothing has loss_* exactly 0.
+    value_stats=True, baselines= (one critic per policy): every cell carries eval_summary's VALUE_KEYS - whether the baseline
+    stays good at the lossy end of the curve and what it believes the loss costs; a cell that loses nothing has loss_value
+    exactly 0."""
     conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")

@@ -277,18 +277,48 @@ class RolloutEngine:
             self._eye_rows = torch.eye(env.N, dtype=torch.float32, device=env.device).expand(r, env.Lh, env.N, env.N).contiguous()
         return self._eye_rows[:r]
 
-    def _replay_rows(self, pol, obs, adj, chan, channels, out):
-        """`pol`'s probabilities on the env states obs [R, N*d] / adj [R, N, N] | None under `channels` (chan [R, Lh, N, N] | None:
-        the recorded ones) into out [R, N, A]: act_device without actions, attention or a draw - one launch, or one per
-        _identity_rows block of rows under the identity."""
-        R = obs.shape[0]
-        eye = self._identity_rows(R) if channels == "identity" else None
-        step = R if eye is None else eye.shape[0]
-        for r0 in range(0, R, step):
-            r1 = min(R, r0 + step)
-            ch = eye[:r1 - r0] if eye is not None else (chan[r0:r1] if channels == "recorded" and chan is not None else None)
-            pol.act_device(obs[r0:r1], None, None if adj is None else adj[r0:r1], ch, greedy=True, want_actions=False,
-                           want_attn=False, out_probs=out[r0:r1], policy_step=0)
+    def _replay(self, who, t0, n, channels, actors, several, launch, out, tail, check=None):
+        """The route of replay_probs / replay_values (`who`, for the refusals' texts): `actors` - one policy / critic, or with
+        `several` one per group - on the recorded slots t0 .. t0+n-1 under `channels`, into out [n, B, *tail].  launch(actor, obs
+        [R, N*d], adj [R, N, N] | None, ch [R, Lh, N, N] | None, out [R, *tail]) is the forward-only launch on R env states.  One
+        actor takes the n * B rows as they lie (slots are contiguous in the buffers); of several each takes its n * (hi - lo) rows,
+        gathered from the slots by device copies and scattered back (a member's envs are contiguous within a slot only; the
+        gathered rows of one member at a time are the replay's only temporaries).  Either way ONE launch per actor, or one per
+        _identity_rows block of rows under the identity.  check(): the caller's own refusals, behind the common ones."""
+        env = self.env
+        B, N, d, Lh = env.B, env.N, env.d, env.Lh
+        t0, n = int(t0), int(n)
+        if channels not in ("recorded", "identity", "ones"):
+            raise ValueError(f"{who}: channels must be 'recorded', 'identity' or 'ones', not {channels!r}")
+        if not (n >= 1 and t0 >= 0 and t0 + n <= self.H):
+            raise ValueError(f"{who}: slots {t0} .. {t0 + n - 1} are not within the horizon {self.H}")
+        if not (out.dtype == torch.float32 and tuple(out.shape) == (n, B) + tail and out.is_contiguous() and out.device == self.obs.device):
+            raise ValueError(f"{who}: out must be a contiguous f32 tensor [{', '.join(map(str, (n, B) + tail))}] on the engine's device")
+        if check is not None:
+            check()
+        adj, chan = self.dist_adj, self.channels if channels == "recorded" else None     # (NULL where the engine keeps none)
+
+        def rows(actor, obs, adj, chan, out):
+            R = obs.shape[0]
+            eye = self._identity_rows(R) if channels == "identity" else None
+            step = R if eye is None else eye.shape[0]
+            for r0 in range(0, R, step):
+                r1 = min(R, r0 + step)
+                ch = eye[:r1 - r0] if eye is not None else (None if chan is None else chan[r0:r1])
+                launch(actor, obs[r0:r1], None if adj is None else adj[r0:r1], ch, out[r0:r1])
+
+        if not several:
+            flat = lambda b, *shape: None if b is None else b[t0:t0 + n].view(n * B, *shape)    # noqa: E731
+            rows(actors, flat(self.obs, N * d), flat(adj, N, N), flat(chan, Lh, N, N), out.view(n * B, *tail))
+            return out
+        for actor, (lo, hi) in zip(actors, self.groups):
+            # 3 copies + 1 launch instead of n launches
+            R = n * (hi - lo)
+            take = lambda b, *shape: None if b is None else b[t0:t0 + n, lo:hi].reshape(R, *shape)   # noqa: E731
+            mine = torch.empty(R, *tail, dtype=torch.float32, device=out.device)
+            rows(actor, take(self.obs, N * d), take(adj, N, N), take(chan, Lh, N, N), mine)
+            out[:, lo:hi] = mine.view(n, hi - lo, *tail)
+        return out
 
     @torch.no_grad()
     def replay_probs(self, t0, n, channels, out):
@@ -305,47 +335,11 @@ class RolloutEngine:
         Nothing else changes: no recorded buffer is written, nothing is drawn, and neither the sampler's Philox base nor a
         policy's step counter moves.  The weight packs are used as they are (the round that recorded the slots synced them).
         On the current stream, behind the round (play() has joined the shards)."""
-        env = self.env
-        B, N, d, Lh, A = env.B, env.N, env.d, env.Lh, self.policy._action_dim
-        t0, n = int(t0), int(n)
-        if channels not in ("recorded", "identity", "ones"):
-            raise ValueError(f"replay_probs: channels must be 'recorded', 'identity' or 'ones', not {channels!r}")
-        if not (n >= 1 and t0 >= 0 and t0 + n <= self.H):
-            raise ValueError(f"replay_probs: slots {t0} .. {t0 + n - 1} are not within the horizon {self.H}")
-        if not (out.dtype == torch.float32 and tuple(out.shape) == (n, B, N, A) and out.is_contiguous() and out.device == self.obs.device):
-            raise ValueError(f"replay_probs: out must be a contiguous f32 tensor [{n}, {B}, {N}, {A}] on the engine's device")
-        adj, chan = self.dist_adj, self.channels
-        if self.multi_form is None:
-            flat = lambda b, *tail: None if b is None else b[t0:t0 + n].view(n * B, *tail)    # noqa: E731
-            self._replay_rows(self.policy, flat(self.obs, N * d), flat(adj, N, N), flat(chan, Lh, N, N), channels,
-                              out.view(n * B, N, A))
-            return out
-        if channels != "recorded":
-            chan = None
-        for pol, (lo, hi) in zip(self.policy, self.groups):
-            # a member's envs are contiguous within a slot only: its rows of the n slots are gathered (device copies), go
-            # through ONE launch, and the probabilities are scattered back - 3 copies + 1 launch instead of n launches
-            rows = n * (hi - lo)
-            take = lambda b, *tail: None if b is None else b[t0:t0 + n, lo:hi].reshape(rows, *tail)   # noqa: E731
-            probs = torch.empty(rows, N, A, dtype=torch.float32, device=out.device)
-            self._replay_rows(pol, take(self.obs, N * d), take(adj, N, N), take(chan, Lh, N, N), channels, probs)
-            out[:, lo:hi] = probs.view(n, hi - lo, N, A)
-        return out
+        def launch(pol, obs, adj, ch, probs):                   # act_device without actions, attention or a draw
+            pol.act_device(obs, None, adj, ch, greedy=True, want_actions=False, want_attn=False, out_probs=probs, policy_step=0)
 
-    def _value_rows(self, critic, obs, adj, chan, channels, out):
-        """`critic`'s values of the env states obs [R, N*d] / adj [R, N, N] | None under `channels` (chan [R, Lh, N, N] | None: the
-        recorded ones) into out [R]: values_device - one launch, or one per _identity_rows block of rows under the identity.  A
-        critic without a graph input (GaussianMLPBaseline) reads the observations alone."""
-        if not hasattr(critic, "comm"):
-            critic.values_device(obs, out=out)
-            return
-        R = obs.shape[0]
-        eye = self._identity_rows(R) if channels == "identity" else None
-        step = R if eye is None else eye.shape[0]
-        for r0 in range(0, R, step):
-            r1 = min(R, r0 + step)
-            ch = eye[:r1 - r0] if eye is not None else (chan[r0:r1] if channels == "recorded" and chan is not None else None)
-            critic.values_device(obs[r0:r1], None if adj is None else adj[r0:r1], ch, out=out[r0:r1])
+        return self._replay("replay_probs", t0, n, channels, self.policy, self.multi_form is not None, launch, out,
+                            (self.env.N, self.policy._action_dim))
 
     @torch.no_grad()
     def replay_values(self, t0, n, channels, critics, out):
@@ -359,35 +353,21 @@ class RolloutEngine:
         channels other than "recorded" are refused for it.  Nothing else changes: no recorded buffer is written and neither the
         sampler's Philox base nor a step counter moves.  The weight packs are used as they are (the caller has run the critics'
         sync_weights()).  On the current stream, behind the round (play() has joined the shards)."""
-        env = self.env
-        B, N, d, Lh = env.B, env.N, env.d, env.Lh
-        t0, n = int(t0), int(n)
-        if channels not in ("recorded", "identity", "ones"):
-            raise ValueError(f"replay_values: channels must be 'recorded', 'identity' or 'ones', not {channels!r}")
-        if not (n >= 1 and t0 >= 0 and t0 + n <= self.H):
-            raise ValueError(f"replay_values: slots {t0} .. {t0 + n - 1} are not within the horizon {self.H}")
-        if not (out.dtype == torch.float32 and tuple(out.shape) == (n, B) and out.is_contiguous() and out.device == self.obs.device):
-            raise ValueError(f"replay_values: out must be a contiguous f32 tensor [{n}, {B}] on the engine's device")
         several = isinstance(critics, (list, tuple))
-        if several and (self.multi_form is None or len(critics) != len(self.groups)):
-            raise ValueError("replay_values: a list of critics needs a PolicySet engine and one critic per group")
-        if channels != "recorded" and not all(hasattr(c, "comm") for c in (critics if several else [critics])):
-            raise ValueError(f"replay_values: channels={channels!r} needs critics with a graph input (a GaussianMLPBaseline has none)")
-        adj, chan = self.dist_adj, self.channels
-        if not several:
-            flat = lambda b, *tail: None if b is None else b[t0:t0 + n].view(n * B, *tail)    # noqa: E731
-            self._value_rows(critics, flat(self.obs, N * d), flat(adj, N, N), flat(chan, Lh, N, N), channels, out.view(n * B))
-            return out
-        if channels != "recorded":
-            chan = None
-        for critic, (lo, hi) in zip(critics, self.groups):
-            # a member's envs are contiguous within a slot only: gathered, ONE launch, scattered back (as replay_probs)
-            rows = n * (hi - lo)
-            take = lambda b, *tail: None if b is None else b[t0:t0 + n, lo:hi].reshape(rows, *tail)   # noqa: E731
-            values = torch.empty(rows, dtype=torch.float32, device=out.device)
-            self._value_rows(critic, take(self.obs, N * d), take(adj, N, N), take(chan, Lh, N, N), channels, values)
-            out[:, lo:hi] = values.view(n, hi - lo)
-        return out
+
+        def check():
+            if several and (self.multi_form is None or len(critics) != len(self.groups)):
+                raise ValueError("replay_values: a list of critics needs a PolicySet engine and one critic per group")
+            if channels != "recorded" and not all(hasattr(c, "comm") for c in (critics if several else [critics])):
+                raise ValueError(f"replay_values: channels={channels!r} needs critics with a graph input (a GaussianMLPBaseline has none)")
+
+        def launch(critic, obs, adj, ch, values):
+            if hasattr(critic, "comm"):
+                critic.values_device(obs, adj, ch, out=values)
+            else:                                               # (a GaussianMLPBaseline reads the observations alone)
+                critic.values_device(obs, out=values)
+
+        return self._replay("replay_values", t0, n, channels, critics, several, launch, out, (), check)
 
     def fill_diameters(self, t0, n):
         """diameter[t] of the n slots t0 .. t0+n-1 from dist_adj[t], in one launch on the current stream (the caller has

@@ -68,10 +68,10 @@ def test_argument_errors_answer_without_a_gpu():
 def test_kernels_have_no_private_segment_no_spill_no_flat_or_scratch_addressing_no_atomic_and_no_barrier():
     ks = isa.kernels(isa.listing("cm_episode_curves"))
     names = [k.name for k in ks]
-    # the curves kernel with 16-byte and 4-byte adjacency positions, the comm curves kernel and the two means kernels
-    assert len(ks) == 5, names
-    assert sum("episode_curves_kernel" in n for n in names) == 2 and sum("comm_curves_kernel" in n for n in names) == 1
-    assert sum("curve_means_kernel" in n for n in names) == 2
+    # the curves kernel with 16-byte and 4-byte adjacency positions and its means kernel (the comm family's two are shared
+    # reductions of cm_stat_rows: tests/test_stat_rows_isa.py)
+    assert len(ks) == 3, names
+    assert sum("episode_curves_kernel" in n for n in names) == 2 and sum("curve_means_kernel" in n for n in names) == 1
     for k in ks:
         assert k.private_segment_fixed_size == 0, k.name
         assert k.vgpr_spill_count == 0, k.name

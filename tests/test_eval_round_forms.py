@@ -107,13 +107,72 @@ def test_eval_sweep_of_a_single_policy_asks_for_the_chunk(spy):
 def test_eval_summary_without_comm_stats_allocates_none(spy, monkeypatch):
     from com_marl_amd import evaluate
 
-    class Refusing:
-        def __init__(self, *a, **kw):
-            raise AssertionError("comm_stats=False built a _CommStats")
+    from tests.test_value_stats import _critics
 
-    monkeypatch.setattr(evaluate, "_CommStats", Refusing)
+    class Refusing:
+        def __init__(self, fam, *a, **kw):
+            raise AssertionError(f"built a _Side for {fam.name}")
+
+    monkeypatch.setattr(evaluate, "_Side", Refusing)
     env = _wrapper()
-    out = evaluate.eval_summary(env, _policies(env, 2), 0, n_eval_episodes=24, max_env_steps=T, comm_stats=False)
-    assert all(not set(evaluate.COMM_KEYS) & set(o) for o in out)
-    with pytest.raises(AssertionError, match="built a _CommStats"):                           # the replacement bites
-        evaluate.eval_summary(_wrapper(), _policies(env, 2), 0, n_eval_episodes=24, max_env_steps=T, comm_stats=True)
+    pols = _policies(env, 2)
+    out = evaluate.eval_summary(env, pols, 0, n_eval_episodes=24, max_env_steps=T, comm_stats=False, attn_stats=False,
+                                listen_stats=False, value_stats=False)
+    keys = set(evaluate.COMM_KEYS + evaluate.ATTN_KEYS + evaluate.LISTEN_KEYS + evaluate.VALUE_KEYS)
+    assert all(not keys & set(o) for o in out)
+    for switch, fam in evaluate.FAMILIES.items():                                             # the replacement bites, for each switch
+        kw = dict(baselines=_critics(env, 2)) if switch == "value_stats" else {}
+        with pytest.raises(AssertionError, match=f"built a _Side for {fam.name}"):
+            evaluate.eval_summary(_wrapper(), pols, 0, n_eval_episodes=24, max_env_steps=T, **{switch: True}, **kw)
+
+
+def test_all_switches_at_once_equal_each_switch_alone():
+    """eval_sweep of 2 policies x 2 conditions x 8 envs, 12 episodes: two rounds, the second ragged (take = 4 < 8 at row0 = 8).  With
+    all five switches on, every key, episode table and curve of every cell is bit for bit what a call with that family alone
+    returns - without and with curves - and the keys of a call with every switch off are the same in all of them: no section of
+    the one buffer, no side's place in the order and no round's accumulate depends on which other switches are on."""
+    import numpy as np
+    import torch
+    from com_marl_amd import evaluate
+    from tests.test_value_stats import _critics
+
+    def same(a, b, what):
+        if isinstance(a, torch.Tensor):
+            assert torch.equal(a, b), what
+        elif isinstance(a, np.ndarray):
+            np.testing.assert_array_equal(a, b, err_msg=str(what))
+        else:
+            assert a == b, what
+
+    env = _wrapper(channel="IID", conditions=CONDS)
+    pols, critics = _policies(env, 2), _critics(env, 2)
+
+    def sweep(**kw):
+        if kw.get("value_stats"):
+            kw["baselines"] = critics
+        return evaluate.eval_sweep(_wrapper(channel="IID", conditions=CONDS), pols, 0, n_eval_episodes=12, max_env_steps=T,
+                                   episodes=True, **kw)
+
+    families = {"comm_stats": evaluate.COMM_KEYS, "attn_stats": evaluate.ATTN_KEYS, "listen_stats": evaluate.LISTEN_KEYS,
+                "value_stats": evaluate.VALUE_KEYS}
+    every = sweep(curves=True, **{switch: True for switch in families})
+    none = sweep()
+    calls = [((), False, none), ((), True, sweep(curves=True))]
+    for switch in families:
+        calls += [((switch,), False, sweep(**{switch: True})), ((switch,), True, sweep(curves=True, **{switch: True}))]
+    for on, curves, got in calls:
+        for k in range(2):
+            for c in range(2):
+                cell, full, what = got[k][c], every[k][c], (on, curves, k, c)
+                names = [name for switch in on for name in families[switch]]
+                tables = [switch[:-len("stats")] + "episodes" for switch in on]
+                assert set(cell) == set(none[k][c]) | set(names) | set(tables) | ({"curves"} if curves else set()), what
+                for key, v in cell.items():
+                    if key != "curves":
+                        same(v, full[key], what + (key,))
+                if curves:
+                    assert set(cell["curves"]) == set(["success"] + evaluate.VECTORS + names), what
+                    for key, v in cell["curves"].items():
+                        same(v, full["curves"][key], what + ("curves", key))
+    assert set(every[0][0]) == set(none[0][0]) | {"curves", "comm_episodes", "attn_episodes", "listen_episodes", "value_episodes"} | {
+        name for names in families.values() for name in names}

@@ -160,8 +160,9 @@ def test_curve_keys_are_taken_over_the_episodes_still_running():
     assert got["msg_value"].tolist() == [0.5, 0.5, 0.0] and got["loss_value"].tolist() == [0.25, 0.5, 0.0]
     assert got["value_rmse"].tolist() == [2.0, 0.0, 0.0]                 # sqrt(4), sqrt(0 / 0.5), nothing runs
     assert got["value_ev"].tolist() == [0.0, 1.0, 1.0]                   # constant returns: 0 with an error left, 1 without; 1 where none runs
-    from com_marl_amd.evaluate import VALUE_KEYS, _ValueStats
-    mine = _ValueStats.curve_keys(np.ascontiguousarray(curves.T), np.array([1.0, 0.5, 0.0]))
+    from com_marl_amd.evaluate import FAMILIES, VALUE_KEYS
+    value = FAMILIES["value_stats"]
+    mine = value.curve_keys(np.ascontiguousarray(curves.T), np.array([1.0, 0.5, 0.0]))
     assert list(mine) == VALUE_KEYS == R.KEYS
     for k in R.KEYS:
         np.testing.assert_array_equal(mine[k], got[k], err_msg=k)
@@ -169,7 +170,7 @@ def test_curve_keys_are_taken_over_the_episodes_still_running():
     for _ in range(20):
         v, g = rng.standard_normal(7), rng.standard_normal(7)
         row = [v.mean(), g.mean(), ((v - g) ** 2).mean(), (g * g).mean(), 0.25, -0.5]
-        a, b = _ValueStats.keys(row), R.keys(row)
+        a, b = value.keys(row), R.keys(row)
         assert a == b and list(a) == R.KEYS
         assert a["value_ev"] == pytest.approx(1 - np.var(g - v) / np.var(g), rel=1e-9)
 
@@ -187,15 +188,15 @@ def test_symbols_are_declared_bound_and_exported():
 
 def test_the_keywords_and_their_defaults():
     from com_marl_amd import envs, evaluate, nets, rollout
-    for fn in (evaluate.eval_summary, evaluate.eval_sweep, evaluate._score, evaluate._summary_buffers):
+    for fn in (evaluate.eval_summary, evaluate.eval_sweep, evaluate._score):
         par = inspect.signature(fn).parameters
-        assert list(par)[-3:] == ["value_stats", "baselines", "discount"] or fn is evaluate._summary_buffers
+        assert list(par)[-3:] == ["value_stats", "baselines", "discount"]
         assert par["value_stats"].default is False
     for fn in (evaluate.eval_summary, evaluate.eval_sweep, evaluate._score):
         par = inspect.signature(fn).parameters
         assert par["baselines"].default is None and par["discount"].default == 0.99
         assert list(par).index("listen_stats") == len(par) - 4          # appended behind the existing keywords
-    assert list(inspect.signature(evaluate._summary_buffers).parameters)[-2:] == ["listen_stats", "value_stats"]
+    assert list(evaluate.FAMILIES)[-2:] == ["listen_stats", "value_stats"]      # the buffer's layout: the families in this order
     assert list(inspect.signature(envs.value_stats).parameters) == ["rewards", "path_len", "values", "mute", "lossless", "discount", "out"]
     assert inspect.signature(envs.value_stats).parameters["discount"].default == 0.99
     assert list(inspect.signature(rollout.RolloutEngine.replay_values).parameters) == ["self", "t0", "n", "channels", "critics", "out"]
@@ -253,28 +254,36 @@ def test_refusals_name_value_stats_before_anything_is_built():
 
 
 def test_summary_buffers_put_the_value_views_last_and_leave_the_others_where_they_were():
+    """Restated on evaluate._layout, for every combination of the four family switches and curves: every active section at the
+    byte offset the buffer's order gives it - summary, comm, curves, comm curves, attn, attn curves, listen, listen curves, value,
+    value curves - no section for what is off, and the host slices on the same bytes as the device views."""
+    import itertools
+    import torch
     from com_marl_amd import _lib as L
-    from com_marl_amd.evaluate import _summary_buffers
+    from com_marl_amd.evaluate import FAMILIES, _cut, _layout
     cells, T = 3, 5
-    for comm in (False, True):
-        for attn in (False, True):
-            for listen in (False, True):
-                for steps in (0, T):
-                    base = _summary_buffers(cells, comm, "cpu", steps, attn, listen)
-                    got = _summary_buffers(cells, comm, "cpu", steps, attn, listen, value_stats=True)
-                    assert len(got) == len(base) + 2
-                    for a, b in zip(base[1:], got[1:]):
-                        assert (a is None) == (b is None)
-                        if a is not None:
-                            assert a.shape == b.shape and a.data_ptr() - base[0].data_ptr() == b.data_ptr() - got[0].data_ptr()
-                    out, curve_out = got[-2:]
-                    assert tuple(out.shape) == (cells, L.EPV_COLS) and out.data_ptr() - got[0].data_ptr() == 8 * base[0].numel()
-                    if steps:
-                        assert tuple(curve_out.shape) == (cells, T, L.EPV_COLS)
-                        assert curve_out.data_ptr() == out.data_ptr() + 8 * out.numel()
-                        assert got[0].numel() == base[0].numel() + cells * (1 + T) * L.EPV_COLS
-                    else:
-                        assert curve_out is None and got[0].numel() == base[0].numel() + cells * L.EPV_COLS
+    for comm, attn, listen, value, curves in itertools.product((False, True), repeat=5):
+        on = dict(comm_stats=comm, attn_stats=attn, listen_stats=listen, value_stats=value)
+        layout = _layout(cells, T, [fam for switch, fam in FAMILIES.items() if on[switch]], curves)
+        # the order written down: (name, shape, present)
+        want = [("summary", (cells, L.SUM_COLS), True), ("comm", (cells, L.EPC_COLS), comm),
+                ("curves", (cells, T, L.EPI_COLS), curves), ("comm_curves", (cells, T, L.EPC_COLS), comm and curves),
+                ("attn", (cells, L.EPA_COLS), attn), ("attn_curves", (cells, T, L.EPA_COLS), attn and curves),
+                ("listen", (cells, L.EPL_COLS), listen), ("listen_curves", (cells, T, L.EPL_COLS), listen and curves),
+                ("value", (cells, L.EPV_COLS), value), ("value_curves", (cells, T, L.EPV_COLS), value and curves)]
+        total = sum(int(np.prod(shape)) for _, shape, present in want if present)
+        flat = torch.empty(total, dtype=torch.float64, device="cpu")
+        device, host = _cut(flat, layout), _cut(flat.numpy(), layout)
+        assert list(device) == list(host) == [name for name, _, present in want if present]     # nothing for what is off
+        offset = 0
+        for name, shape, present in want:
+            if not present:
+                continue
+            assert tuple(device[name].shape) == host[name].shape == shape, name
+            assert device[name].data_ptr() - flat.data_ptr() == 8 * offset, name
+            assert host[name].ctypes.data == device[name].data_ptr() and host[name].flags["C_CONTIGUOUS"], name
+            offset += int(np.prod(shape))
+        assert offset == total
 
 
 def test_argument_errors_answer_without_a_gpu():

@@ -20,6 +20,8 @@ COMM_COLS, EPC_COLS = 4, 4                                                  # cm
 ATTN_COLS, EPA_COLS = 6, 6                                                  # cm_attn_stats / cm_episode_attn, cm_attn_means row widths
 LISTEN_COLS, EPL_COLS = 6, 6                                                # cm_listen_stats / cm_episode_listen, cm_listen_means row widths
 VALUE_COLS, EPV_COLS = 6, 6                                                 # cm_value_stats / cm_episode_value, cm_value_means row widths
+BOOT_OUT, BOOT_MAX_R = 4, 4096                                              # cm_boot_quantiles: lo, hi, se, p_gt per key; resamples per call
+BOOT_COLUMNS, BOOT_COMM, BOOT_VALUE = 0, 1, 2                               # cm_boot_quantiles' kinds -> 4 / 6 / 9, 5, 7 keys
 
 
 class EnvCfg(C.Structure):
@@ -272,6 +274,10 @@ _SIGNATURES = {
     "cm_value_means": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cm_value_curves": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "cm_value_curve_means": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # bootstrap intervals and paired contrasts of the episode tables (csrc/cm_boot.hip)
+    "cm_boot_means": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cm_boot_quantiles": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p]),
     "cm_chunk_tail": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cm_linear_act_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

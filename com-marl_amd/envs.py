@@ -256,6 +256,95 @@ def value_stats(rewards, path_len, values, mute=None, lossless=None, discount=0.
     return out
 
 
+BOOT_KINDS = {"columns": L.BOOT_COLUMNS, "comm": L.BOOT_COMM, "value": L.BOOT_VALUE}   # bootstrap's kind= -> cm_boot_quantiles' kind
+
+
+def boot_keys(kind, cols):
+    """How many keys cm_boot_quantiles forms from rows of `cols` columns: the columns themselves (4, 6 or 9), the comm family's 5
+    (its 4 columns and delivery), the value family's 7 (VALUE_KEYS from its 6 columns).  ValueError for any other pair."""
+    if kind not in BOOT_KINDS or cols not in {"columns": (4, 6, 9), "comm": (4,), "value": (6,)}[kind]:
+        raise ValueError(f"bootstrap: kind={kind!r} does not take rows of {cols} columns (columns: 4, 6 or 9; comm: 4; value: 6)")
+    return {"columns": cols, "comm": 5, "value": 7}[kind]
+
+
+def boot_ranks(level, n_boot, who="bootstrap", name="level"):
+    """The order statistics of a two-sided interval at `level` from n_boot resamples -> (lo_rank, hi_rank) with
+    lo_rank = min(floor((1 - level) / 2 * n_boot), (n_boot - 1) // 2) and hi_rank = n_boot - 1 - lo_rank.  ValueError (naming
+    `name` / n_boot) unless 0 < level < 1 and 2 <= n_boot <= 4096."""
+    if isinstance(level, bool) or not isinstance(level, (int, float)) or not 0 < level < 1:      # (a NaN fails the comparison too)
+        raise ValueError(f"{who}: {name}= must be a confidence level with 0 < {name} < 1, not {level!r}")
+    if isinstance(n_boot, bool) or not isinstance(n_boot, (int, np.integer)) or not 2 <= n_boot <= L.BOOT_MAX_R:
+        raise ValueError(f"{who}: n_boot= must be an integer in 2..{L.BOOT_MAX_R}, not {n_boot!r}")
+    lo = min(math.floor((1 - level) / 2 * n_boot), (int(n_boot) - 1) // 2)
+    return lo, int(n_boot) - 1 - lo
+
+
+def boot_seed_words(seed, who="bootstrap", name="seed"):
+    """A bootstrap seed 0 .. 2^64 - 1 -> (lo, hi), the two Philox key words; ValueError naming `name` for anything else."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"{who}: {name}= must be an integer in 0..2^64-1, not {seed!r}")
+    return int(seed) & 0xFFFFFFFF, int(seed) >> 32
+
+
+def boot_means(table, n_boot, seed=0, out=None):
+    """The resampled means of every cell of a contiguous float64 CUDA tensor table [cells, n, cols] (cols 4, 6 or 9; row e of a cell
+    one episode) -> float64 [cells, n_boot, cols] (cm_boot_means, include/commarl.h): resample r draws n rows with replacement from
+    the Philox stream of (seed, r) - the same rows for every cell, column and table.  One launch on the current stream."""
+    assert table.is_cuda and table.dtype == torch.float64 and table.dim() == 3
+    assert table.is_contiguous(), "cm_boot_means reads the table through the raw pointer"
+    cells, n, cols = table.shape
+    lo, hi = boot_seed_words(seed)
+    if out is None:
+        out = torch.empty(cells, int(n_boot), cols, dtype=torch.float64, device=table.device)
+    assert out.dtype == torch.float64 and out.shape == (cells, int(n_boot), cols) and out.device == table.device and out.is_contiguous()
+    L.run("cm_boot_means", cells, n, cols, L.ptr(table), int(n_boot), lo, hi, L.ptr(out), device=table.device)
+    return out
+
+
+def boot_quantiles(means, lo_rank, hi_rank, kind="columns", ref_cell=None, out=None):
+    """boot_means' tensor [cells, n_boot, cols] -> float64 [cells, keys, 4] (cm_boot_quantiles): per cell and key (boot_keys) the
+    order statistics lo_rank and hi_rank of the key's resampled values, their standard deviation (ddof 1) and the share above
+    zero (ties half) - with ref_cell (an int32 CUDA tensor [cells], entries in 0 .. cells-1) of the values minus those of cell
+    ref_cell[g] in the same resample.  One launch on the current stream."""
+    assert means.is_cuda and means.dtype == torch.float64 and means.dim() == 3
+    assert means.is_contiguous(), "cm_boot_quantiles reads the means through the raw pointer"
+    cells, R, cols = means.shape
+    keys = boot_keys(kind, cols)
+    if ref_cell is not None:
+        assert ref_cell.dtype == torch.int32 and ref_cell.shape == (cells,) and ref_cell.device == means.device and ref_cell.is_contiguous()
+    if out is None:
+        out = torch.empty(cells, keys, L.BOOT_OUT, dtype=torch.float64, device=means.device)
+    assert out.dtype == torch.float64 and out.shape == (cells, keys, L.BOOT_OUT) and out.device == means.device and out.is_contiguous()
+    L.run("cm_boot_quantiles", BOOT_KINDS[kind], cells, R, cols, L.ptr(means), L.ptr(ref_cell), int(lo_rank), int(hi_rank), L.ptr(out),
+          device=means.device)
+    return out
+
+
+def bootstrap(table, level, n_boot=2000, seed=0, kind="columns", ref_cell=None):
+    """Bootstrap intervals of the means of per-episode tables of your own (cm_boot_means + cm_boot_quantiles, include/commarl.h):
+    table a contiguous float64 CUDA tensor [cells, n, cols], row e of a cell one episode -> float64 [cells, keys, 4] on the
+    device: per cell and key the interval (lo, hi) at confidence `level` - order statistics of n_boot resampled means, not
+    interpolated (boot_ranks) - the bootstrap standard error se, and p_gt, the share of resamples above zero (ties half).
+    kind: "columns" - the keys are the 4, 6 or 9 columns; "comm" - evaluate.COMM_KEYS from the 4 comm columns; "value" -
+    evaluate.VALUE_KEYS from the 6 value columns, each key formed per resample from the resampled means as the host forms it from
+    the means.  Resample r picks the same rows in every cell (and in every call with the same `seed` and n): with ref_cell (a
+    sequence of `cells` ints in 0 .. cells-1) everything is of the PAIRED difference of cell g and cell ref_cell[g] - meaningful
+    only when row e of both cells is the same scenario (evaluate.sweep_layout(paired=True)); a cell referred to itself holds exact
+    zeros and p_gt 0.5.  ValueError for a level outside (0, 1), n_boot outside 2..4096, a seed outside 0..2^64-1, a kind that does
+    not take the table's columns or a ref_cell entry out of range.  Two launches on the current stream."""
+    lo_rank, hi_rank = boot_ranks(level, n_boot)
+    boot_seed_words(seed)
+    assert table.dim() == 3
+    boot_keys(kind, table.shape[2])
+    ref = None
+    if ref_cell is not None:
+        ref_host = np.asarray(ref_cell.cpu() if isinstance(ref_cell, torch.Tensor) else ref_cell, dtype=np.int64)
+        if ref_host.shape != (table.shape[0],) or ref_host.min() < 0 or ref_host.max() >= table.shape[0]:
+            raise ValueError(f"bootstrap: ref_cell= must hold one cell index in 0..{table.shape[0] - 1} per cell")
+        ref = torch.as_tensor(ref_host, dtype=torch.int32).to(table.device)
+    return boot_quantiles(boot_means(table, n_boot, seed), lo_rank, hi_rank, kind, ref)
+
+
 class GridEnvBatch:
     """B envs stepped by one kernel launch.  All tensors are torch CUDA tensors."""
 

@@ -37,6 +37,9 @@ launches, allocates and returns nothing:
                          (RolloutEngine.replay_values) against the discounted returns the episodes went on to collect, and what it
                          believes the messages and the channel loss are worth (cm_value_stats).
 The four statistics families are one _Side each, told apart by a _Family description (FAMILIES); _layout describes the one buffer.
+``ci=level`` adds bootstrap intervals and standard errors of every mean above, resampled over the episodes on the device tables
+(cm_boot_means / cm_boot_quantiles; one index stream for every cell, column and table), and eval_sweep's ``contrast=`` the paired
+difference of every cell against a reference condition or policy; off (the default) they launch, allocate and return nothing.
 """
 import collections
 import itertools
@@ -46,6 +49,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import envs as _envs
 from .nets import PolicySet
 from .rollout import RolloutEngine
 
@@ -389,18 +393,19 @@ def _named(names):
 # ...): what produces a round's stats (above); keys(cols): the host side, elementwise on the columns of the family's means
 # ([cols, cells]) -> what the dicts gain, and on those of its curves ([cols, cells, T]) -> what their `curves` gain - the latter
 # through curve_keys(cols, step_cnt) where the curves need the share of running episodes; curves_last: the curve launches and
-# sections come behind the episode curves', not with the family's own (_Side).
-_Family = collections.namedtuple("_Family", "name cols dtype more_slots sizes rows keys curve_keys curves_last",
-                                 defaults=(None, False))
+# sections come behind the episode curves', not with the family's own (_Side); kind: how cm_boot_quantiles forms the family's keys
+# from a row of resampled means (envs.BOOT_KINDS) - the device twin of keys(cols), in the same order.
+_Family = collections.namedtuple("_Family", "name cols dtype more_slots sizes rows keys curve_keys curves_last kind",
+                                 defaults=(None, False, "columns"))
 FAMILIES = dict(
     comm_stats=_Family("comm", L.COMM_COLS, torch.int32, 1, lambda batch: (batch.N, batch.Lh), _comm_rows, _comm_keys,
-                       curves_last=True),
+                       curves_last=True, kind="comm"),
     attn_stats=_Family("attn", L.ATTN_COLS, torch.float64, 0, lambda batch: (batch.N, batch.Lh), _attn_rows,
                        _named(ATTN_KEYS)),
     listen_stats=_Family("listen", L.LISTEN_COLS, torch.float64, 0, lambda batch: (batch.N,), _listen_rows,
                          _named(LISTEN_KEYS)),
     value_stats=_Family("value", L.VALUE_COLS, torch.float64, 0, lambda batch: (), _value_rows, _value_keys,
-                        _value_curve_keys))
+                        _value_curve_keys, kind="value"))
 
 
 class _Curves:
@@ -426,17 +431,21 @@ class _Curves:
         return [dict(zip(['success'] + VECTORS, cell)) for cell in rows]
 
 
-def _layout(cells, T, fams, curves):
+def _layout(cells, T, fams, curves, boot=()):
     """The one buffer that is copied to the host, as both sides read it: the ordered (name, shape) of its sections of doubles for
     the active families `fams` (in FAMILIES' order).  The summary [cells, 12]; a curves_last family's means [cells, cols]; with
     curves the episode curves [cells, T, 9] and that family's "<name>_curves" [cells, T, cols]; then per other family "<name>"
-    and with curves "<name>_curves"."""
+    and with curves "<name>_curves".  boot: behind all of these, per name of `boot` ("boot" with ci=, then "contrast" with
+    contrast=) the cm_boot_quantiles blocks "summary_<name>" [cells, 9, 4] and per family "<family>_<name>" [cells, keys, 4]."""
     first, rest = [f for f in fams if f.curves_last], [f for f in fams if not f.curves_last]
     sections = [("summary", (cells, L.SUM_COLS))] + [(f.name, (cells, f.cols)) for f in first]
     if curves:
         sections += [("curves", (cells, T, L.EPI_COLS))] + [(f.name + "_curves", (cells, T, f.cols)) for f in first]
     for f in rest:
         sections += [(f.name, (cells, f.cols))] + ([(f.name + "_curves", (cells, T, f.cols))] if curves else [])
+    for b in boot:
+        sections += [(f"summary_{b}", (cells, L.EPI_COLS, L.BOOT_OUT))]
+        sections += [(f"{f.name}_{b}", (cells, _envs.boot_keys(f.kind, f.cols), L.BOOT_OUT)) for f in fams]
     return sections
 
 
@@ -448,19 +457,57 @@ def _cut(flat, layout):
 
 def _host_tables(host_all, layout):
     """_cut of the host copy, with one transposition per curve table: [cells, cols, T], a cell's curve is then a contiguous row."""
-    return {name: np.ascontiguousarray(part.transpose(0, 2, 1)) if part.ndim == 3 else part
+    return {name: np.ascontiguousarray(part.transpose(0, 2, 1)) if name.endswith("curves") else part
             for name, part in _cut(host_all, layout).items()}
 
 
+def _check_boot(who, ci, n_boot, boot_seed, contrast, sweep, paired):
+    """The refusals of ci= / n_boot= / boot_seed= / contrast= that need no cell count (ValueErrors naming the keyword, before
+    anything is built) -> None with ci off, else the interval's (lo_rank, hi_rank) (envs.boot_ranks).  Off, the other three must
+    be at their defaults: a resample count or seed nobody reads is refused, not ignored."""
+    if contrast is not None and not sweep:
+        raise ValueError(f"{who}: contrast= is eval_sweep's (the policies of eval_summary play unpaired envs: no paired difference)")
+    if ci is None:
+        for name, given, default in (("n_boot", n_boot, 2000), ("boot_seed", boot_seed, 0), ("contrast", contrast, None)):
+            if given != default:
+                raise ValueError(f"{who}: {name}= is read with ci= only (ci=None: no intervals)")
+        return None
+    ranks = _envs.boot_ranks(ci, n_boot, who, "ci")
+    _envs.boot_seed_words(boot_seed, who, "boot_seed")
+    if contrast is not None:
+        if not paired:
+            raise ValueError(f"{who}: contrast= needs paired=True (row e of two cells must be the same scenario)")
+        if not isinstance(contrast, dict) or len(contrast) != 1 or next(iter(contrast)) not in ("condition", "policy"):
+            raise ValueError(f"{who}: contrast= takes dict(condition=c0) or dict(policy=k0), not {contrast!r}")
+    return ranks
+
+
+def _contrast_cells(who, contrast, K, C_):
+    """contrast= of eval_sweep over K policies x C_ conditions -> per cell g = k*C_ + c the cell it is compared with: (k, c0) for
+    dict(condition=c0), (k0, c) for dict(policy=k0); None without.  ValueError naming contrast for an index out of range."""
+    if contrast is None:
+        return None
+    (axis, at), = contrast.items()
+    size = C_ if axis == "condition" else K
+    if isinstance(at, bool) or not isinstance(at, (int, np.integer)) or not 0 <= at < size:
+        raise ValueError(f"{who}: contrast=dict({axis}={at!r}): the index must lie in 0..{size - 1}")
+    at = int(at)
+    return [(g // C_) * C_ + at if axis == "condition" else at * C_ + g % C_ for g in range(K * C_)]
+
+
 def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats, conds=None, paired=True,
-           curves=False, attn_stats=False, listen_stats=False, value_stats=False, baselines=None, discount=0.99):
+           curves=False, attn_stats=False, ci=None, n_boot=2000, boot_seed=0, contrast=None, listen_stats=False,
+           value_stats=False, baselines=None, discount=0.99):
     """eval_summary (conds None: one cell per policy) and eval_sweep (one cell per policy and condition) - `who` for the
     refusals' texts.  The B envs are K policies x C conditions x E envs, cell g = k*C + c owning the contiguous envs
     [g*E, (g+1)*E), policy k the C*E envs of its cells: the engine's groups.  The refusals; the engine (it keeps its attention
     output for attn_stats and its probabilities for listen_stats; `baselines` checked by _check_baselines and synced); the active
     _Sides in FAMILIES' order, their views cut from the one buffer by _layout.  Per round _play_round, the episode rows of groups of
     E envs into the device table [K*C, n_eval_episodes, 9], every side's round, _Curves.round and the curves_last sides' curve sums;
-    then the means in the same order, the one copy to the host, and the dicts from the sides' keys."""
+    then the means in the same order, the one copy to the host, and the dicts from the sides' keys.  With ci= behind the means, per
+    table (the summary's, then every side's) ONE cm_boot_means launch into a scratch [cells, n_boot, cols] and ONE cm_boot_quantiles
+    launch - with contrast= one more, against the cells of _contrast_cells - into sections of the same buffer."""
+    ranks = _check_boot(who, ci, n_boot, boot_seed, contrast, conds is not None, paired)
     single = not isinstance(policies, (PolicySet, list, tuple))
     comm_dp = all(hasattr(p, "comm") for p in ([policies] if single else policies))
     if attn_stats and not comm_dp:
@@ -471,6 +518,7 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     if critics is not None and not (np.isfinite(discount) and 0 <= discount <= 1):
         raise ValueError(f"{who}: value_stats=True needs 0 <= discount <= 1, not {discount!r}")
     C_ = 1 if conds is None else len(conds)
+    ref_of = _contrast_cells(who, contrast, 1 if single else len(policies), C_)
 
     def shaped(cells):
         """K*C values in cell order -> the caller's [K] (eval_summary) or [K][C] (eval_sweep); a single policy: its entry."""
@@ -516,7 +564,8 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
     table = torch.zeros(cells, n_epi, L.EPI_COLS, dtype=torch.float64, device=batch.device)
     on = dict(comm_stats=comm_stats, attn_stats=attn_stats, listen_stats=listen_stats, value_stats=critics is not None)
     given = dict(value_stats=dict(critics=critics and (critics[0] if single else critics), discount=discount))
-    layout = _layout(cells, T, [fam for switch, fam in FAMILIES.items() if on[switch]], bool(curves))
+    boot = () if ranks is None else ("boot",) if ref_of is None else ("boot", "contrast")
+    layout = _layout(cells, T, [fam for switch, fam in FAMILIES.items() if on[switch]], bool(curves), boot)
     flat = torch.empty(sum(math.prod(shape) for _, shape in layout), dtype=torch.float64, device=batch.device)
     views = _cut(flat, layout)
     sides = [_Side(fam, eng, batch, T, cells, n_epi, views[fam.name], views.get(fam.name + "_curves"), **given.get(switch, {}))
@@ -543,6 +592,13 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
         curve.means()
     for side in last:
         side.curve_means()
+    if boot:                                                    # every table resampled by the same index stream (boot_seed)
+        ref_dev = None if ref_of is None else torch.tensor(ref_of, dtype=torch.int32, device=batch.device)
+        for name, rows, kind in [("summary", table, "columns")] + [(side.fam.name, side.table, side.fam.kind) for side in sides]:
+            resampled = _envs.boot_means(rows, n_boot, boot_seed)               # [cells, n_boot, cols]: freed with the call
+            _envs.boot_quantiles(resampled, *ranks, kind, out=views[name + "_boot"])
+            if ref_dev is not None:
+                _envs.boot_quantiles(resampled, *ranks, kind, ref_dev, out=views[name + "_contrast"])
     host = _host_tables(flat.cpu().numpy(), layout)
     bound = base.bound_return
     by_cols = lambda name: np.moveaxis(host[name], 1, 0)                   # noqa: E731  [cols, cells] or [cols, cells, T]
@@ -571,14 +627,27 @@ def _score(who, env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag
         if curve:
             d["curves"] = cell_curves[g]
         res.append(d)
+    # the bootstrap blocks, [cells, keys, 4] each: the summary's keys are its nine means, a side's its keys in their order
+    named = [(["success"] + VECTORS, "summary")] + [(list(keys), side.fam.name) for side, keys in zip(sides, side_keys)]
+    blocks = {b: [host[f"{tab}_{b}"].tolist() for _, tab in named] for b in boot}      # (floats at once, not one numpy scalar a time)
+    for g, d in enumerate(res if boot else ()):
+        rows = [(name, block[g][i]) for (names, _), block in zip(named, blocks["boot"]) for i, name in enumerate(names)]
+        d["ci"] = {name: (lo, hi) for name, (lo, hi, _, _) in rows}
+        d["se"] = {name: se for name, (_, _, se, _) in rows}
+        if ref_of is not None:                                  # diff: of the point estimates already here
+            to = res[ref_of[g]]
+            d["contrast"] = {name: dict(diff=d[name] - to[name], lo=row[0], hi=row[1], se=row[2], p_gt=row[3])
+                             for (names, _), block in zip(named, blocks["contrast"]) for i, name in enumerate(names)
+                             for row in (block[g][i],)}
+            d["contrast_ref"] = (ref_of[g] // C_, ref_of[g] % C_)
     env.eval_n_epi = n_epi
     env.last_eval_average_reward = shaped([d["reward"] / bound for d in res])
     return shaped(res)
 
 
 def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, seed=1, flag=None,
-                 episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False, value_stats=False,
-                 baselines=None, discount=0.99):
+                 episodes=False, comm_stats=False, curves=False, attn_stats=False, ci=None, n_boot=2000, boot_seed=0,
+                 contrast=None, listen_stats=False, value_stats=False, baselines=None, discount=0.99):
     """The score of one policy, a list of policies or a nets.PolicySet: the episodes eval_models plays (one policy: the ones
     eval_model plays), reduced on the device instead of copied to the host.  Behind every round ONE cm_episode_stats launch on
     the engine's trajectory buffers writes the round's episode rows into a device table [K, n_eval_episodes, 9] (success, then
@@ -657,10 +726,23 @@ def eval_summary(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200
     value_mean, value_return, value_bias, msg_value and loss_value zero-padded means like every curve, value_rmse and value_ev
     over the episodes still running at step t (0 and 1 where none does).  A replay is one forward launch per critic, under
     the identity one per block of rollout.REPLAY_MASK_BYTES of mask; the constant-channel rule of listen_stats skips the same
-    replays here: exact zeros."""
+    replays here: exact zeros.
+    ci=level (0 < level < 1; None, the default, launches, allocates and returns nothing) says how far to trust every mean above:
+    a percentile bootstrap over the episodes, on the device tables.  Resample r draws n_eval_episodes episode rows with
+    replacement - the same rows in every table and every cell (the Philox stream of boot_seed, include/commarl.h cm_boot_means) -
+    and every key is formed from the resampled column means exactly as the point estimate is formed from the means, so delivery,
+    value_bias, value_rmse and value_ev are resampled jointly, not column by column.  Every dict gains `ci`: name -> (lo, hi), the
+    order statistics lo_rank = min(floor((1 - level) / 2 * n_boot), (n_boot - 1) // 2) and n_boot - 1 - lo_rank of the n_boot
+    values (not interpolated), and `se`: name -> the bootstrap standard error (their standard deviation, ddof 1) - for success,
+    every name of VECTORS and every key of every active family; not for return_std / return_min / return_max, bound_return or
+    curves.  After the last round, per table (the summary's and each active family's) ONE cm_boot_means launch into a device
+    scratch of n_boot * cols doubles per cell, freed with the call, and ONE cm_boot_quantiles launch; the [K, keys, 4] blocks ride
+    in the same single copy to the host.  n_boot in 2..4096, boot_seed in 0..2^64-1; either given without ci, and ci outside
+    (0, 1), raises ValueError before anything is built.  contrast= is eval_sweep's and raises ValueError here: the policies of
+    this call play different envs, there is no paired difference between them."""
     return _score("eval_summary", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
                   curves=curves, attn_stats=attn_stats, listen_stats=listen_stats, value_stats=value_stats, baselines=baselines,
-                  discount=discount)
+                  discount=discount, ci=ci, n_boot=n_boot, boot_seed=boot_seed, contrast=contrast)
 
 
 def sweep_layout(B, K, C, env_id_offset=0, paired=True):
@@ -676,8 +758,8 @@ def sweep_layout(B, K, C, env_id_offset=0, paired=True):
 
 
 def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, eval_greedy=True, paired=True, flag=None,
-               episodes=False, comm_stats=False, curves=False, attn_stats=False, listen_stats=False, value_stats=False,
-               baselines=None, discount=0.99):
+               episodes=False, comm_stats=False, curves=False, attn_stats=False, ci=None, n_boot=2000, boot_seed=0,
+               contrast=None, listen_stats=False, value_stats=False, baselines=None, discount=0.99):
     """eval_summary over a grid of checkpoints x comm conditions in ONE rollout: `env` is a wrapper built with a list of C
     conditions (envs.GridEnvBatch(conditions=...): the points of a --teRcom / --tepl / --Pgb / --Pbg curve), `policies` one
     policy, a list or a nets.PolicySet (K policies).  The call lays the B = K*C*E envs out itself (sweep_layout; B % (K*C) != 0
@@ -701,13 +783,26 @@ def eval_sweep(env, policies, itr=None, n_eval_episodes=100, max_env_steps=200, 
     loses nothing has loss_* exactly 0.
     value_stats=True, baselines= (one critic per policy): every cell carries eval_summary's VALUE_KEYS - whether the baseline
     stays good at the lossy end of the curve and what it believes the loss costs; a cell that loses nothing has loss_value
-    exactly 0."""
+    exactly 0.
+    ci=level, n_boot=, boot_seed=: every cell carries eval_summary's `ci` and `se` - the error bars of the curve.  All cells are
+    resampled by the same index stream.
+    contrast=dict(condition=c0) or dict(policy=k0) (needs ci and paired=True): cell (k, c) is compared with cell (k, c0), or with
+    (k0, c).  Paired, row e of every cell is the same scenario - the same Philox env id, every round reset at the same rng_step -
+    so the difference of two cells is resampled over the SAME episodes in both, which removes the scenario-to-scenario variance
+    from it: "is checkpoint 7 better than checkpoint 5 at pl = 0.3" and "does delivery differ between these two ranges" are what
+    it answers.  Every dict gains `contrast`: name -> dict(diff=, lo=, hi=, se=, p_gt=) over the names of `ci` - diff the
+    difference of the two point estimates, (lo, hi) and se the interval and standard error of the resampled difference, p_gt the
+    share of resamples in which this cell's value is above the other's (ties half; near 0 or 1: the sign of diff is settled) - and
+    `contrast_ref` = (k, c) of the cell compared with.  A cell compared with itself holds exact zeros and p_gt = 0.5.  It costs
+    ONE more cm_boot_quantiles launch per table.  contrast without ci, with paired=False, with both or neither key or an index
+    out of range raises ValueError before anything is built."""
     conds = getattr(env, "env", env).batch.conditions
     if conds is None:
         raise ValueError("eval_sweep: the wrapper was built without conditions= (eval_summary scores a uniform wrapper)")
     return _score("eval_sweep", env, policies, n_eval_episodes, max_env_steps, eval_greedy, flag, episodes, comm_stats,
                   conds=conds, paired=paired, curves=curves, attn_stats=attn_stats, listen_stats=listen_stats,
-                  value_stats=value_stats, baselines=baselines, discount=discount)
+                  value_stats=value_stats, baselines=baselines, discount=discount, ci=ci, n_boot=n_boot, boot_seed=boot_seed,
+                  contrast=contrast)
 
 
 def summary_row(summary):

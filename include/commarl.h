@@ -445,6 +445,59 @@ int cm_value_curve_means(int32_t cells, int32_t T, int32_t n_episodes,
                          const double *sums /* [cells, T, CM_VALUE_COLS] */, double *curves /* [cells, T, CM_EPV_COLS] */,
                          void *stream);
 
+/* Bootstrap intervals and paired contrasts of the evaluation scores: the episode tables the reductions above fill - table
+ * [cells, n, cols] doubles, row e of a cell one episode - resampled over the EPISODES on the device.  Pure functions of DEVICE
+ * arrays.
+ *
+ * cm_boot_means forms R resampled means of every cell.  Resample r draws n rows with replacement,
+ *   idx_j = ((uint64_t)w_j * n) >> 32,  j = 0 .. n-1,
+ *   w_j   = component j & 3 of philox4x32_10(counter = (r, j >> 2, SITE_BOOT = 10, 0), key = (seed_lo, seed_hi))
+ * (csrc/cm_rng.h), and means[g][r][c] = (sum_j table[g][idx_j][c]) / n: the sum f64, sequential in ascending j, divided ONCE.  The
+ * index stream depends on (seed, r, j) alone - NOT on the cell, the column or the table: resample r of every cell, every column and
+ * every table of a call with one seed picks the same episodes.  That is what makes a key derived from several columns a joint
+ * resample and the difference of two cells a PAIRED one.  The multiply-high mapping prefers some rows by at most n / 2^32 in
+ * probability.  One lane per resample, one workgroup per cell and block of 256 resamples; the cell's table is staged in LDS when
+ * n * cols * 8 <= 32768 bytes (the staging budget; the environment variable COMMARL_BOOT_STAGE_BYTES, read at every call, lowers
+ * it - a debugging switch) and read from global memory above it, the same sums in the same order either way: the same bits.  No
+ * atomics, one writer per output, the same inputs give the same bits.  cols must be 4, 6 or 9 (the row widths there are).
+ * CM_ERR_ARG (text in cm_last_error) before anything is launched: cells < 1, n < 1, another cols, R outside 2..CM_BOOT_MAX_R, a
+ * NULL table or means.
+ *
+ * cm_boot_quantiles turns those means into CM_BOOT_OUT doubles per cell and KEY.  `kind` says how a key comes from the cols
+ * columns m of a row of means, operation by operation what evaluate.py's host functions do on the point estimates:
+ *   CM_BOOT_COLUMNS  cols keys: key k = m[k]                                              (cols 4, 6 or 9)
+ *   CM_BOOT_COMM     5 keys: m[0 .. 3], then delivery = m[0] != 0 ? m[1] / m[0] : 1.0     (cols 4: range_degree, heard_degree, ...)
+ *   CM_BOOT_VALUE    7 keys: m[0], m[1], bias = m[0] - m[1], rmse = sqrt(m[2]),           (cols 6: value, ret, sq_err, ret_sq,
+ *                    ev, m[4], m[5], where with resid = m[2] - bias * bias, var = m[3] - m[1] * m[1] and                msg, loss)
+ *                    eps = 1e-12 * max(1.0, m[3]):  ev = var <= eps ? (resid <= eps ? 1.0 : 0.0) : 1.0 - resid / var
+ * every product, sum, quotient and root a separately rounded f64 operation.  One workgroup per (cell g, key k) forms
+ *   v_r = key_k(means[g][r][:])                                      ref_cell == NULL
+ *   v_r = key_k(means[g][r][:]) - key_k(means[ref_cell[g]][r][:])    else: the contrast of cell g against cell ref_cell[g]
+ * for r = 0 .. R-1, sorts them ascending in LDS (a bitonic network, padded with +inf to a power of two) and writes out[g][k][:]:
+ *   0 lo   = sorted[lo_rank]           1 hi = sorted[hi_rank]        order statistics, not interpolated
+ *   2 se   = sqrt(sum_r (v_r - mean)^2 / (R - 1)), mean = (sum_r v_r) / R: two passes, each sum in one fixed order
+ *   3 p_gt = (#{v_r > 0} + 0.5 * #{v_r == 0}) / R: integer counts, divided once
+ * A cell whose ref_cell is itself holds exact zeros and p_gt = 0.5.  ref_cell[g] must lie in 0 .. cells-1: the CALLER checks that
+ * (the table lives on the device); an entry outside is read as g itself, never out of bounds.  No atomics, one writer per output,
+ * the same inputs give the same bits.  CM_ERR_ARG (text in cm_last_error) before anything is launched: another kind, a cols the
+ * kind does not take, cells < 1, R outside 2..CM_BOOT_MAX_R, not 0 <= lo_rank <= hi_rank < R, a NULL means or out. */
+#define CM_BOOT_OUT 4        /* lo, hi, se, p_gt */
+#define CM_BOOT_MAX_R 4096   /* resamples per call: the sort's LDS tile */
+#define CM_BOOT_COLUMNS 0
+#define CM_BOOT_COMM 1
+#define CM_BOOT_VALUE 2
+int cm_boot_means(int32_t cells, int32_t n, int32_t cols,
+                  const double *table,        /* [cells, n, cols] */
+                  int32_t R, uint32_t seed_lo, uint32_t seed_hi,
+                  double *means,              /* [cells, R, cols] */
+                  void *stream);
+int cm_boot_quantiles(int32_t kind, int32_t cells, int32_t R, int32_t cols,
+                      const double *means,    /* [cells, R, cols] */
+                      const int32_t *ref_cell,/* [cells] or NULL */
+                      int32_t lo_rank, int32_t hi_rank,
+                      double *out,            /* [cells, keys, CM_BOOT_OUT] */
+                      void *stream);
+
 /* Per-step evaluation curves: the rounds of cm_episode_stats / cm_episode_comm reduced over the EPISODES with the step axis kept -
  * the mean over episodes of the per-step lists the reference's test loop pads with zeros to max_env_steps and saves as rewMat3
  * (exp_runners/testing.py:307-324, pad_sequence(..., padding_value=0)).  Pure functions of DEVICE arrays.

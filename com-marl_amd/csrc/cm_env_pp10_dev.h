@@ -190,10 +190,13 @@ __device__ __forceinline__ void draw_stage(const EnvDev &p, uint32_t rng_step, i
 // `out`: the launch's bases, `off`: this step's element offsets into them.  `last`: the launch's last step - the only one whose
 // state write-back anything reads (no load of the launch reads the state arrays: the next launch and the host see what the last
 // step left), so the others keep the state in registers only.
+// `ahead`: called once, every lane of the wave active, behind the emission's last scalar load and in front of its stores - what the
+// caller wants requested from LDS for the next step (a scalar load's lgkmcnt(0) behind it would drain the request at once).
 // Reference lines as in env_body / pp_small_step.
+template <class AHEAD>
 __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const Emit em, int act_off, const cm_step_out &out,
                                      const StepOff &off, bool last, int grp, int b_raw, bool grp_live, int lds_base, bool all_valid,
-                                     int obs_copy, int draw) {
+                                     int obs_copy, int draw, AHEAD ahead) {
     Grp<16> g;
     const int tx = thread_x();
     g.sub = (tx & (WAVE - 1)) / 16; g.sl = tx % 16;
@@ -366,8 +369,9 @@ __device__ __forceinline__ void step(const EnvDev &p, State &st, Pre &pre, const
         const int sc = pre.step_count_in + 1;
         pre.t_step = p.lut_step[sc <= p.max_steps ? sc : p.max_steps];
     }
+    if (sl == 0 && commit) *at32(o.success, off.success + ub) = succ;
+    ahead();
     if (!commit) return;
-    if (sl == 0) *at32(o.success, off.success + ub) = succ;
     const uint32_t ob = off.obs + ub * (N * D) + (uint32_t)sl;
     float *oc = reinterpret_cast<float *>(smem + obs_copy);
 #pragma unroll

@@ -95,6 +95,10 @@ template <int KB> struct Act { v8h hi[KB], lo[KB]; };
 
 #define CM_MFW(A, B, ACC) ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, ACC, 0, 0, 0)
 
+// A 16-byte LDS read from a 32-bit LDS address kept in a register
+typedef __attribute__((address_space(3))) const v4f *LdsV4;
+__device__ __forceinline__ LdsV4 lds_v4(uint32_t addr) { return (LdsV4)(uintptr_t)addr; }
+
 // One layer's A fragments in registers.  fetch() is issued one layer AHEAD of run(): with one wave per SIMD nothing else
 // hides the LDS latency (a read issued next to its MFMA cost ~60 exposed cycles per (tile, k block): 86 of them per step).
 template <int KB, int CT>
@@ -117,26 +121,83 @@ struct Frags {
         // k block); the barrier keeps the whole batch of reads where it was written: ahead of the layer that runs meanwhile
         __builtin_amdgcn_sched_barrier(0);
     }
+    // The LEAN tile's form: `addr` is this lane's LDS byte address of its chunk of the image's first fragment (LaneAddr, computed once
+    // per launch), `slot` the layer's offset in uint4 - a slot below 64 KB costs no address arithmetic at all (the offset field).
+    // A batch that reaches past 64 KB takes ONE add for its base (opaque, or the compiler folds it back into every read's own add).
+    __device__ __forceinline__ void fetch_at(uint32_t addr, int slot) {
+        uint32_t rel = 16u * (uint32_t)slot;
+        if (16 * (slot + CT * KB * 2 * FRAG) > 65536) { addr += rel; rel = 0u; asm("" : "+v"(addr)); }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int q = 0; q < KB; ++q) {
+                h[ct][q] = __builtin_bit_cast(v8h, *lds_v4(addr + rel + 16u * (uint32_t)(((ct * KB + q) * 2 + 0) * FRAG)));
+                l[ct][q] = __builtin_bit_cast(v8h, *lds_v4(addr + rel + 16u * (uint32_t)(((ct * KB + q) * 2 + 1) * FRAG)));
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // A use of the batch's LAST read that the wait insertion sees: LDS answers in order, so the one wait it takes covers the whole
+    // batch and whatever was read in front of it (the layer's biases).  Without it every MFMA waits for just its own fragments, and
+    // once more than 15 younger reads are outstanding (lgkmcnt is a 4-bit counter) such a wait cannot be expressed any more: the
+    // compiler clamps it, and the wave drains a look-ahead batch it issued a moment ago.  No instruction of its own.
+    __device__ __forceinline__ void landed() {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : "+v"(l[CT - 1][KB - 1]));
+        __builtin_amdgcn_sched_barrier(0);
+    }
 };
 
 // A layer's accumulator start values (bias, features 16 ct + 4 g + r) in registers.  LDS answers in order: read next to its first MFMA,
-// a bias float4 queues behind the whole look-ahead batch of the NEXT layer's fragments; fetch() goes in front of that batch, and
-// the barrier keeps it there.  fetch<C0>() reads tiles C0 .. CT - 1 only.  ON false: nothing is read here, the layer reads its biases
-// where it always did.
+// a bias float4 queues behind the whole look-ahead batch of the NEXT layer's fragments.  Read in front of that batch it still waits for
+// most of it once more than 14 younger reads are outstanding at its consumer (lgkmcnt is a 4-bit counter: the wait is clamped to
+// lgkmcnt(14)), so the biases travel with their OWN layer's batch and one landed() covers both.  fetch_at<C0>() reads tiles
+// C0 .. CT - 1 only.  ON false: nothing is read here, the layer reads its biases where it always did.
 template <int CT, bool ON>
 struct BiasR {
     v4f b[ON ? CT : 1];
+    // as Frags::fetch_at: `addr` is the LDS byte address of this lane's four floats of the bias block's first tile, `off` in floats
     template <int C0 = 0>
-    __device__ __forceinline__ void fetch(const float *bias, int g) {
-        if constexpr (ON) {
+    __device__ __forceinline__ void fetch_at(uint32_t addr, int off) {
 #pragma unroll
-            for (int ct = C0; ct < CT; ++ct) { const float4 v = *reinterpret_cast<const float4 *>(bias + 16 * ct + 4 * g); b[ct] = (v4f){ v.x, v.y, v.z, v.w }; }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int ct = C0; ct < CT; ++ct) b[ct] = *lds_v4(addr + 4u * (uint32_t)(off + 16 * ct));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // as Frags::landed(), where the biases are the last thing read in front of their layer
+    __device__ __forceinline__ void landed() {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : "+v"(b[CT - 1]));
+        __builtin_amdgcn_sched_barrier(0);
     }
     __device__ __forceinline__ const v4f *regs() const { return ON ? b : nullptr; }
 };
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
+// The first encoder layer's biases and fragments, requested by the CALLER of the lean tile one step ahead (cm_rollout_w_body.h): at
+// the top of a step nothing runs that could cover their 24 reads.  ON false: empty, the tile reads its own.
+template <bool ON>
+struct E1Ahead {
+    struct None {};
+    std::conditional_t<ON, BiasR<8, true>, None> r;
+    std::conditional_t<ON, Frags<1, 8>, None> f;
+    // this lane's two read addresses in the image (fragment chunk, bias float4), for every read of the tile: computed once per launch
+    // and opaque from there on, so that neither the request in the env phase nor the tile rebuilds them every step
+    uint32_t fa, ba;
+    template <int LHOPS>
+    __device__ __forceinline__ void init(const unsigned char *lds, int lane) {
+        if constexpr (ON) {
+            typedef __attribute__((address_space(3))) const unsigned char *LdsB;
+            fa = (uint32_t)(uintptr_t)(LdsB)(lds + 16 * lane);
+            ba = (uint32_t)(uintptr_t)(LdsB)(lds + (size_t)pack_w(LHOPS).bias * 16 + 16 * (lane >> 4));
+            asm volatile("" : "+v"(fa), "+v"(ba));
+        }
+    }
+    template <int LHOPS>
+    __device__ __forceinline__ void fetch() {
+        if constexpr (ON) {
+            r.fetch_at(ba, bias_map(LHOPS).e1);
+            f.fetch_at(fa, pack_w(LHOPS).enc1);
+        }
+    }
+};
 
 // ---- epilogue arithmetic, written STAGE-WISE over small arrays: with one wave per SIMD a dependent instruction costs ~1.7x
 // an independent one (and a transcendental twice a plain one), so every stage below is N independent instructions ----------
@@ -207,15 +268,16 @@ __device__ __forceinline__ void split_stage(const float (&y)[N], h16 (&h)[N], h1
 // backward pass reads back) - features 16 ct + 4 g .. + 3 of row c are one 16-byte store.
 // PB0: the accumulators of tiles ct >= PB0 start from pb[ct] (BiasR, read ahead) instead of a read of `bias` here.  mid(): called once in front of the
 // MFMAs of the middle tile pair (what the caller wants requested while this layer's second half runs).
-template <int KB, int CT, bool TANH, bool BIAS, int SPLIT = SPLIT_DEFAULT, int PB0 = CT, class MID = NoHook>
+template <int KB, int CT, bool TANH, bool BIAS, int SPLIT = SPLIT_DEFAULT, int PB0 = CT, class MID = NoHook, class LATE = NoHook>
 __device__ __forceinline__ void dense_act(const Frags<KB, CT> &f, const float *bias, const Act<KB> &x, Act<CT / 2> &y, v4f *keep, int lane,
-                                          float *sv = nullptr, const v4f *pb = nullptr, MID mid = MID{}) {
+                                          float *sv = nullptr, const v4f *pb = nullptr, MID mid = MID{}, LATE late = LATE{}) {
     const int g = lane >> 4;
     const v4f zero = (v4f){ 0.f, 0.f, 0.f, 0.f };
     v4f acc[CT];
 #pragma unroll
     for (int p = 0; p <= CT / 2; ++p) {
         if constexpr (!std::is_same<MID, NoHook>::value) { if (p == CT / 4) mid(); }
+        if constexpr (!std::is_same<LATE, NoHook>::value) { if (p == CT / 2 - 1) late(); }
         if (p < CT / 2) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -361,17 +423,20 @@ __device__ __forceinline__ T *at32(T *base, uint32_t elem) { return reinterpret_
 //   * h3 / h4 come from the resident AGPRs (ResidentW<true>) instead of two more fragment batches from LDS;
 //   * the look-ahead batches of e2 and of the attention layer are requested at the MIDDLE of the layer that runs meanwhile (e1, e2)
 //     instead of in front of it: the first half's fragments are dead by then, and half a layer still covers the reads;
-//   * every layer's biases are read in front of the fragment batch that would otherwise queue ahead of them: e1 / e2 tiles of the
-//     second half in front of the batch at the layer's middle (the first half's reads have only the layer's own fragments ahead),
-//     the hop biases and b1 in front of the hop's batch, b2 / b3 / b4 (no batch left to hide behind) at the middle of x1;
+//   * every layer's biases are read with that layer's OWN fragment batch and one wait the compiler can see (landed()) covers the batch
+//     where its first consumer is, so that no wait of the step is a clamped lgkmcnt(14) that drains the batch issued a moment before:
+//     the hop biases in front of their hop's f_g, b1 in front of f_x1, e2's behind f_e2 at e1's last tile pair (in front of it they do
+//     not fit in the registers), b2 / b3 / b4 (no batch left to hide behind) at the middle of x1;
+//   * the first layer's fragments and biases are not read here at all: the caller requested them one step ahead (E1Ahead `e1a`), and
+//     every read of the tile goes through the two lane addresses `e1a` carries (no address arithmetic per step);
 //   * the sampler's Philox word is not computed here: the caller's draw stage has left it in LDS (`draw_off`: byte offset of the
 //     16 action entries of this wave and step, 16 bytes apart, row c's word first), read behind the 128 -> 64 layer.
 template <int LHOPS, bool OBS_LDS = false, bool TRAIN = false, int HEADK = 0, bool STEP32 = false, bool LEAN = false>
 __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const ResidentW<LEAN> &res, const unsigned char *lds, int blk,
-                                              int32_t *act_lds, int obs_row = 0, const StepOff so = StepOff{}, int draw_off = 0) {
+                                              int32_t *act_lds, int obs_row = 0, const StepOff so = StepOff{}, int draw_off = 0, E1Ahead<LEAN> *e1a = nullptr) {
     static_assert(!STEP32 || (!TRAIN && HEADK == 0), "step offsets: the acting forward of the rollout");
     static_assert(!LEAN || (!TRAIN && HEADK == 0), "the lean tile: the acting forward of the rollout");
-    constexpr int E1H = LEAN ? 4 : 8, E2H = LEAN ? 2 : 4;       // first e1 / e2 tile whose bias is read ahead (at the layer's middle)
+    constexpr int E1H = LEAN ? 0 : 8, E2H = LEAN ? 0 : 4;       // first e1 / e2 tile whose bias is read ahead (0: all, with the layer's own batch)
     constexpr int PB_H2 = LEAN ? 0 : 4, PB_H3 = LEAN ? 0 : 2;    // h2 / h3: every tile's bias read ahead (0), or none (the tile count)
     static_assert(HEADK == 0 || TRAIN, "the critic head exists as training forward only");
     static_assert(LHOPS >= 1 && LHOPS <= 2, "wave-owned forward: one or two hops");
@@ -412,26 +477,32 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     if constexpr (!LEAN) draw_step = a.policy_step + (a.step_base ? *a.step_base : 0u);
 
     // ---- encoder (every layer's fragments are fetched while the layer before it runs) ----
-    Frags<1, 8> f_e1; f_e1.template fetch<LEAN>(WL + pk.enc1, lane);
-    BiasR<8, LEAN> r_e1;
+    Frags<1, 8> f_e1;
+    if constexpr (!LEAN) f_e1.template fetch<LEAN>(WL + pk.enc1, lane);
     Frags<4, 4> f_e2;
+    BiasR<4, LEAN> r_e2;
     if constexpr (!LEAN) f_e2.template fetch<LEAN>(WL + pk.enc2, lane);
     auto sv_row = [&](float *base, int width) -> float * { return (TRAIN && base && rv) ? base + grow * (size_t)width : nullptr; };
     Act<4> a1;
+    if constexpr (LEAN) e1a->f.landed();
     if constexpr (LEAN)
-        dense_act<1, 8, true, true, SPLIT_DEFAULT, E1H>(f_e1, BL + bm.e1, xo, a1, nullptr, lane, nullptr, r_e1.regs(),
-                                                        [&] { r_e1.template fetch<E1H>(BL + bm.e1, g); f_e2.template fetch<LEAN>(WL + pk.enc2, lane); });
+        dense_act<1, 8, true, true, SPLIT_DEFAULT, E1H>(e1a->f, BL + bm.e1, xo, a1, nullptr, lane, nullptr, e1a->r.regs(),
+                                                        [&] { f_e2.fetch_at(e1a->fa, pk.enc2); }, [&] { r_e2.fetch_at(e1a->ba, bm.e2); });
+    if constexpr (LEAN) r_e2.landed();
     else dense_act<1, 8, true, true>(f_e1, BL + bm.e1, xo, a1, nullptr, lane, sv_row(a.sv_a1, EH));
-    BiasR<4, LEAN> r_e2;
     Frags<2, 4> f_at;
     if constexpr (!LEAN) f_at.template fetch<LEAN>(WL + pk.attn, lane);
     v4f E[4];
     Act<2> xe;
     if constexpr (LEAN)
         dense_act<4, 4, true, true, SPLIT_DEFAULT, E2H>(f_e2, BL + bm.e2, a1, xe, E, lane, nullptr, r_e2.regs(),
-                                                        [&] { r_e2.template fetch<E2H>(BL + bm.e2, g); f_at.template fetch<LEAN>(WL + pk.attn, lane); });
+                                                        [&] { f_at.fetch_at(e1a->fa, pk.attn); });
     else dense_act<4, 4, true, true>(f_e2, BL + bm.e2, a1, xe, E, lane, sv_row(a.sv_e, EMB));
-    Frags<2, 4> f_g; f_g.template fetch<LEAN>(WL + pk.gcn, lane);
+    if constexpr (LEAN) f_at.landed();
+    BiasR<4, LEAN> r_g[LHOPS];
+    Frags<2, 4> f_g;
+    if constexpr (LEAN) { r_g[0].fetch_at(e1a->ba, bm.g); f_g.fetch_at(e1a->fa, pk.gcn); }
+    else f_g.template fetch<LEAN>(WL + pk.gcn, lane);
     CM_WPROBE(3);
 
     // ---- attention: Q = E.Wa^T, scores^T = E.Q^T, softmax row in the diagonal lanes ----
@@ -439,6 +510,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     {
         Act<2> xq;
         dense_act<2, 4, false, false>(f_at, nullptr, xe, xq, nullptr, lane, sv_row(a.sv_q, EMB));
+        if constexpr (LEAN) f_g.landed();                        // hop 0's batch, here: H.Wg_0 does not wait for the softmax and may run under it
         v4f hh = (v4f){ 0.f, 0.f, 0.f, 0.f };
 #pragma unroll
         for (int q = 0; q < 2; ++q) { CM_MFW(xe.hi[q], xq.lo[q], hh); CM_MFW(xe.lo[q], xq.hi[q], hh); CM_MFW(xe.hi[q], xq.hi[q], hh); }
@@ -469,6 +541,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
 #pragma unroll
     for (int l = 0; l < LHOPS; ++l) {
         v4f hw[4];                                             // H.Wg_l: rows 4 g + r, feature 16 ct + c
+        if constexpr (LEAN) { if (l > 0) f_g.landed(); }
         dense_f32<2, 4, true, false>(f_g, nullptr, xh, hw, lane);
         if constexpr (TRAIN) {
             // H.Wg_l in the non-transposed form: this lane holds rows 4 g + r of the tile (env g of the wave), feature 16 ct + c.
@@ -481,11 +554,12 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
                     for (int r = 0; r < 4; ++r) dst[(size_t)r * EMB + 16 * ct] = hw[ct][r] * (1.0f / TANH_PRESCALE);
             }
         }
-        BiasR<4, LEAN> r_g; r_g.fetch(BL + bm.g + l * EMB, g);
-        if (l + 1 < LHOPS) f_g.template fetch<LEAN>(WL + pk.gcn + (l + 1) * frag_u4(EMB, EMB), lane);
-        else {
-            r_b1.fetch(BL + bm.b1, g);
-            f_x1.template fetch<LEAN>(WL + pk.x1, lane);
+        if constexpr (LEAN) {
+            if (l + 1 < LHOPS) { r_g[l + 1].fetch_at(e1a->ba, bm.g + (l + 1) * EMB); f_g.fetch_at(e1a->fa, pk.gcn + (l + 1) * frag_u4(EMB, EMB)); }
+            else { r_b1.fetch_at(e1a->ba, bm.b1); f_x1.fetch_at(e1a->fa, pk.x1); }
+        } else {
+            if (l + 1 < LHOPS) f_g.template fetch<LEAN>(WL + pk.gcn + (l + 1) * frag_u4(EMB, EMB), lane);
+            else f_x1.template fetch<LEAN>(WL + pk.x1, lane);
         }
         float cf[4], den = 0.0f;
 #pragma unroll
@@ -522,7 +596,7 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
             v4f b0;
-            if constexpr (LEAN) b0 = r_g.b[ct];
+            if constexpr (LEAN) b0 = r_g[l].b[ct];
             else { const float4 b = *reinterpret_cast<const float4 *>(BL + bm.g + l * EMB + 16 * ct + 4 * g); b0 = (v4f){ b.x, b.y, b.z, b.w }; }
             acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], bl, b0, 0, 0, 0);
             acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(al[ct], bh, acc[ct], 0, 0, 0);
@@ -569,8 +643,9 @@ __device__ __forceinline__ void policy_tile_w(const FwdArgs &a, int n_act, const
     // ---- head: 64 -> 128 -> 64 (resident fragments) -> 32 -> logits ----
     Act<4> x1;
     if constexpr (LEAN) {
+        f_x1.landed();
         dense_act<2, 8, true, true, SPLIT_DEFAULT, 0>(f_x1, BL + bm.b1, xh, x1, nullptr, lane, nullptr, r_b1.regs(),
-                                                      [&] { r_b2.fetch(BL + bm.b2, g); r_b3.fetch(BL + bm.b3, g); r_b4.fetch(BL + bm.b4, g); });
+                                                      [&] { r_b2.fetch_at(e1a->ba, bm.b2); r_b3.fetch_at(e1a->ba, bm.b3); r_b4.fetch_at(e1a->ba, bm.b4); });
     } else dense_act<2, 8, true, true>(f_x1, BL + bm.b1, xh, x1, nullptr, lane, sv_row(a.sv_x1, H1));
     Frags<2, 2> f_h3_lds;
     Frags<1, 2> f_h4_lds;

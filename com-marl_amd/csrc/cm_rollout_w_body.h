@@ -15,7 +15,9 @@
 // buffer is a 32-bit element offset from the launch's base (no per-step pointer rebuild, no null test at a store), and the
 // state arrays are written by the launch's last step only.  The step's common Philox draws (the sampler's action word, the preys'
 // first four trial words) are computed for two steps at once on every even step of the loop (pp10::draw_stage) and handed over
-// through a per-wave LDS buffer in the image's h3 / h4 slots, which these builds do not stage.
+// through a per-wave LDS buffer in the image's h3 / h4 slots, which these builds do not stage.  The first encoder layer's fragments and
+// biases of step t + 1 are requested in the env phase of step t (mw::E1Ahead; step 0's behind the staging barrier, the last step's are
+// discarded): at the top of a step nothing runs that could cover their 24 LDS reads.
 // constexpr bool COND (true in cm_rollout_wc.hip only; the non-carried, tape-less builds: a handle with a condition table has adj_const off): the including
 // kernel also provides  const EnvCondDev *cond  - the handle's device table (cm_env_set_conditions).  A 16-lane env group loads its
 // env's record ONCE, ahead of the step loop (the table cannot change under a running launch), and its env phase runs on a
@@ -55,6 +57,8 @@
     __syncthreads();                                                     // the only workgroup barrier of the launch
     if (probe) { g_w_probe[3] = __builtin_amdgcn_s_memtime() - t_in; g_w_probe[0] = g_w_probe[1] = g_w_probe[2] = g_w_probe[4] = 0; }
     const int envs = FULLWG ? mw::WG_ENVS : min(mw::WG_ENVS, a.S - (int)blockIdx.x * mw::WG_ENVS);
+    mw::E1Ahead<SHAPE == 1> e1a;                                         // SHAPE 1: step t + 1's first-layer reads, requested in step t
+    if constexpr (SHAPE == 1) { e1a.template init<LHOPS>(lds_w, thread_x() & 63); e1a.template fetch<LHOPS>(); }
     EnvPre pre{};
     pp10::State st{};                                                    // SHAPE 1: the env in registers (cm_env_pp10_dev.h)
     pp10::Pre pp{};
@@ -93,7 +97,9 @@
         asm volatile("" ::: "memory");                                   // keep each step's loads inside the step
         const int tx = thread_x(), grp = tx / LPE;
         const bool live = FULLWG || grp < envs;
-        const bool env_wave = FULLWG || (tx & ~63) / LPE < envs;        // a wave with an env of its own
+        bool env_wave = FULLWG || (tx & ~63) / LPE < envs;              // a wave with an env of its own
+        // SHAPE 1: as a scalar, so that the env phase and the idle wave's request below are two branches and not two masked passes
+        if constexpr (SHAPE == 1 && !FULLWG) env_wave = __builtin_amdgcn_readfirstlane(tx >> 6) * (64 / LPE) < envs;
         const int b_raw = blockIdx.x * mw::WG_ENVS + (live ? grp : 0);
         mf::FwdArgs at = a;
         at.policy_step = a.policy_step + (uint32_t)t;
@@ -118,7 +124,7 @@
         if constexpr (PRE && !CARRY) pre = env_prefetch<CM_PP, LPE>(p, b_raw, live);   // env state requested in front of the policy forward
         if constexpr (SHAPE == 1)
             mw::policy_tile_w<LHOPS, true, false, 0, true, true>(at, n_act, res, lds_w, blockIdx.x, act, obs_row,
-                                                           mw::StepOff{ ut * (uint32_t)c.actions, ut * (uint32_t)c.probs, ut * (uint32_t)c.attn }, draw);
+                                                           mw::StepOff{ ut * (uint32_t)c.actions, ut * (uint32_t)c.probs, ut * (uint32_t)c.attn }, draw, &e1a);
         else mw::policy_tile_w<LHOPS, CARRY>(at, n_act, res, lds_w, blockIdx.x, act, obs_row);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's action words are in LDS
         const unsigned long long t1 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -135,7 +141,7 @@
         if (ot.success) ot.success += (size_t)t * c.success;
         if (ot.path_len) ot.path_len += (size_t)t * c.path_len;
         }
-        if (env_wave) {
+        if (SHAPE == 1 && !FULLWG ? __builtin_expect(env_wave, true) : env_wave) {
             const int32_t *my_act = act + (live ? grp : 0) * 4;
             if constexpr (COND) {                                        // the non-carried forms below, on the env's own comm scalars
                 const EnvDev q = apply_cond(p, cv);
@@ -147,7 +153,8 @@
             } else if constexpr (CARRY && SHAPE == 1) {
                 const pp10::StepOff so{ ut * (uint32_t)c.obs, ut * (uint32_t)c.reward, ut * (uint32_t)c.reward_f64, ut * (uint32_t)c.done,
                                         ut * (uint32_t)c.details, ut * (uint32_t)c.prey_alive, ut * (uint32_t)c.success, ut * (uint32_t)c.path_len };
-                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, so, t == c.n_steps - 1, grp, b_raw, live, ENV_BASE, FULLWG, obs_env, draw + mw::DRAW_WAVE_BYTES / 4);
+                pp10::step(p, st, pp, em, ACT_OFF + (live ? grp : 0) * 16, ot, so, t == c.n_steps - 1, grp, b_raw, live, ENV_BASE, FULLWG, obs_env, draw + mw::DRAW_WAVE_BYTES / 4,
+                           [&] { e1a.template fetch<LHOPS>(); });
             } else if constexpr (CARRY) {
                 const bool bad = env_stage<CM_PP, LPE>(p, pre, my_act, grp, ENV_BASE);
                 EnvCarry carry{ pre.step_count_in, pre.succ, 0 };
@@ -159,7 +166,7 @@
                 env_body<CM_PP, LPE>(p, nullptr, my_act, tape, ot, 0, grp, b_raw, live, ENV_BASE, nullptr, true, pre.rng_step, pre.step_count_in,
                                      pre.succ, pre.t_row, pre.t_col, pre.t_step0, pre.t_step, pre.t_rew, bad, FULLWG);
             } else env_body<CM_PP, LPE>(p, nullptr, my_act, tape, ot, 0, grp, b_raw, live, ENV_BASE);
-        }
+        } else e1a.template fetch<LHOPS>();                               // SHAPE 1, a wave without an env: no step that requests them
         // step t + 1 reads what this WAVE wrote (observation, masks, env state): its stores are performed before its next loads;
         // the CU's vector L1 is write-through and shared, so workgroup scope needs no cache maintenance (as rollout_chunk_kernel)
         const unsigned long long tf = probe ? __builtin_amdgcn_s_memtime() : 0ull;

@@ -888,6 +888,7 @@ def main():
 
     fx = {}
     if args.only and args.only.startswith(('ppo_step', 'variants_', 'ppo_math', 'adam', 'adj_ties_grid32', 'faults_direct', 'env_pp_map10_cond', 'net_options_', 'env_pp_map40', 'env_co_map40',
+                                                       'env_pp_map30_cap4_hunt', 'env_co_map20_full',
                                                        'net_grads_')):
         return late(save, args)
     # config 1/2: PP map10 sen1 den.04 cap2 (full 200-step horizon, chasing so captures happen)
@@ -960,6 +961,12 @@ def late(save, args, ns=None):
     save('env_pp_map40_cap4', lambda: record_env(ns, 'pp', pp_params(40, 2, 0.08, 4, max_env_steps=9), B=2, T=12, seed=41,
                                                  p_random=0.3))
     save('env_co_map40', lambda: record_env(ns, 'co', co_params(40, 2, 0.06, max_env_steps=8), B=2, T=11, seed=42, p_random=1.0))
+    # where a purposeful team plays (tests/purposeful_teams.py): a map-30 hunt of few preys that ends by success and starts over,
+    # and Coverage maps 20 and 40 swept to full coverage (final reward, done) with the episode after it begun
+    save('env_pp_map30_cap4_hunt', lambda: record_env(ns, 'pp', dict(pp_params(30, 2, 0.08, 4, max_env_steps=80), n_preys=8), B=2,
+                                                      T=70, seed=43, p_random=0.15))
+    save('env_co_map20_full', lambda: record_env(ns, 'co', co_params(20, 2, 0.06), B=1, T=75, seed=44, p_random=0.15))
+    save('env_co_map40_full', lambda: record_env(ns, 'co', co_params(40, 2, 0.06), B=1, T=40, seed=45, p_random=0.15))
     save('ppo_math', lambda: record_ppo_math(ns))
     save('adam', lambda: record_adam(ns))
     save('ppo_step', lambda: record_ppo_step())

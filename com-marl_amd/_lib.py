@@ -22,6 +22,9 @@ LISTEN_COLS, EPL_COLS = 6, 6                                                # cm
 VALUE_COLS, EPV_COLS = 6, 6                                                 # cm_value_stats / cm_episode_value, cm_value_means row widths
 BOOT_OUT, BOOT_MAX_R = 4, 4096                                              # cm_boot_quantiles: lo, hi, se, p_gt per key; resamples per call
 BOOT_COLUMNS, BOOT_COMM, BOOT_VALUE = 0, 1, 2                               # cm_boot_quantiles' kinds -> 4 / 6 / 9, 5, 7 keys
+# cm_ppo_update_stats' row: CM_UPD_COLS columns, in the order of their CM_UPD_* indices
+UPD_COLUMNS = ("n_valid", "approx_kl", "kl", "clip_frac", "ratio_min", "ratio_max", "entropy", "stopped")
+UPD_COLS = len(UPD_COLUMNS)
 
 
 class EnvCfg(C.Structure):
@@ -336,6 +339,14 @@ _SIGNATURES = {
     "cm_gauss_nll_forward_det_ws_bytes": (C.c_size_t, [C.c_int64]),
     "cm_gauss_nll_forward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    # per-step PPO update statistics and the device-side KL early stop (csrc/cm_ppo_stats.hip; the gated Adam is in cm_ppo.hip)
+    "cm_ppo_update_stats_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cm_ppo_update_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_float, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "cm_multi_adam_step_gated": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p]),
 }
 EXPORTED = tuple(_SIGNATURES)
 

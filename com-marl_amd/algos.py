@@ -127,7 +127,8 @@ class _UpdateGraphs:
         grp = lambda o: tuple((g["lr"], tuple(g["betas"]), g["eps"]) for g in o.param_groups)   # noqa: E731
         self.hyper = (T, grp(algo._optimizer), grp(algo._baseline_optimizer), algo._lr_clip_range, algo._policy_ent_coeff,
                       algo._entropy_method, algo._use_softplus_entropy, algo._stop_entropy_gradient, algo._positive_adv,
-                      algo._clip_grad_norm, os.environ.get("COMMARL_CRITIC_STREAM", "1"), deterministic())
+                      algo._clip_grad_norm, os.environ.get("COMMARL_CRITIC_STREAM", "1"), deterministic(),
+                      algo._update_stats, algo._target_kl)   # (the stop threshold is an argument of the captured statistics launch)
         return self
 
     def __init__(self, algo, owner):
@@ -153,7 +154,8 @@ class _UpdateGraphs:
         if self.broken:
             return fn(inputs)
         if not self.armed:                                   # the moments exist, the step counts are known
-            self.algo._optimizer.begin_device_steps(self.n_steps)
+            if self.algo._target_kl is None:                 # (under target_kl the policy's optimiser is armed for the whole
+                self.algo._optimizer.begin_device_steps(self.n_steps)   # train_once, behind the gate: _run_steps arms and books it)
             self.algo._baseline_optimizer.begin_device_steps(self.n_steps)
             self.armed = True
         if self.cur[i] is None:
@@ -214,18 +216,30 @@ class _UpdateGraphs:
     def close(self):
         """Book the epoch's replayed steps into the optimisers' host state (idempotent); the graphs stay for later epochs."""
         if self.armed:
-            self.algo._optimizer.end_device_steps(self.done)
+            if self.algo._target_kl is None:
+                self.algo._optimizer.end_device_steps(self.done)
             self.algo._baseline_optimizer.end_device_steps(self.done)
             self.armed, self.done = False, 0
         self.cur = [None] * len(self.cur)
 
 
 class CentralizedMAPPO:
+    _update_stats, _target_kl, update_rows = False, None, None      # (an algo pickled before these switches existed: off)
+
     def __init__(self, env_spec, policy, baseline, optimizer=None, baseline_optimizer=None,
                  optimization_n_minibatches=1, optimization_mini_epochs=1, policy_lr=3e-4, lr_clip_range=2e-1,
                  max_path_length=500, num_train_per_epoch=1, discount=0.99, gae_lambda=1, center_adv=True,
                  positive_adv=False, policy_ent_coeff=0.0, use_softplus_entropy=False, stop_entropy_gradient=False,
-                 entropy_method='no_entropy', clip_grad_norm=None, device='cpu'):
+                 entropy_method='no_entropy', clip_grad_norm=None, device='cpu', update_stats=None, target_kl=None):
+        """update_stats / target_kl (both opt-in, not in the reference): per-step statistics of the policy update (`update_rows`,
+        and the PolicySteps / ApproxKL / ClipFraction stats) and the KL early stop on top of them.  With target_kl set, the
+        first optimiser step of an epoch in front of which the approximate KL (k3, mean of (r - 1) - log r over the minibatch's
+        valid steps) exceeds kl_stop = 1.5 * target_kl - the factor Spinning Up and Stable-Baselines3 use - is not applied to the
+        policy, and none after it; the critic keeps taking every scheduled step.  The decision is taken and obeyed on the
+        device (cm_ppo_update_stats, cm_multi_adam_step_gated).  target_kl implies update_stats.  None falls back to
+        COMMARL_UPDATE_STATS (1 = on) / COMMARL_TARGET_KL (a float), so the reference's unmodified runners can switch it on."""
+        self._update_stats, self._target_kl = self._resolve_update_stats(update_stats, target_kl)
+        self.update_rows = None
         self.device = device
         self.env_spec, self.policy, self.baseline = env_spec, policy, baseline
         self.discount, self.max_path_length, self.n_samples = discount, max_path_length, num_train_per_epoch
@@ -263,7 +277,24 @@ class CentralizedMAPPO:
         st.pop("_bucket", None)
         st.pop("_eager_stepped", None)                   # per process: the first optimiser steps of a process run eagerly
         st.pop("_update_graphs", None)                   # hipGraphs of optimiser steps (rebuilt on demand)
+        st.pop("_upd_state", None)                       # device tables of the update statistics (re-made on first use)
         return st
+
+    @staticmethod
+    def _resolve_update_stats(update_stats, target_kl):
+        """-> (update_stats: bool, target_kl: float or None) from the ctor's arguments and their environment fall-backs."""
+        if update_stats is None:
+            update_stats = os.environ.get("COMMARL_UPDATE_STATS", "") == "1"
+        if target_kl is None and os.environ.get("COMMARL_TARGET_KL", "") != "":
+            target_kl = os.environ["COMMARL_TARGET_KL"]
+        if target_kl is not None:
+            try:
+                target_kl = float(target_kl)
+            except (TypeError, ValueError):
+                raise ValueError(f"target_kl must be a finite float > 0, got {target_kl!r}") from None
+            if not (np.isfinite(target_kl) and target_kl > 0):
+                raise ValueError(f"target_kl must be a finite float > 0, got {target_kl!r}")
+        return bool(update_stats) or target_kl is not None, target_kl
 
     @staticmethod
     def _check_entropy_configuration(entropy_method, center_adv, stop_entropy_gradient, policy_ent_coeff):
@@ -404,11 +435,12 @@ class CentralizedMAPPO:
         return float(kl), float(h.mean())
 
     def _compute_loss(self, itr, obs, avail_actions, actions, rewards, valids, baselines, dist_adjs, channels,
-                      advantages=None, old_ll=None, reduce=True, logits=None, rewards_in_place=False):
+                      advantages=None, old_ll=None, reduce=True, logits=None, rewards_in_place=False, logits_out=None):
         """:390-438.  Returns -(mean over valid steps of clipped surrogate + c * entropy); with
         reduce=False returns (sum, count) for the count-weighted multi-GPU reduction.
         entropy_method 'max' ignores `advantages`: they come from this call's entropy (_max_entropy_advantages), and
-        rewards_in_place says whether r + c * H is written back into `rewards` (the full-batch calls of train_once)."""
+        rewards_in_place says whether r + c * H is written back into `rewards` (the full-batch calls of train_once).
+        logits_out: a list that receives the detached logits the fused loss ran on (the update statistics judge the same ones)."""
         maxent = self._maximum_entropy
         if advantages is None and not maxent:
             advantages = self._advantages(rewards, baselines, valids)
@@ -417,6 +449,8 @@ class CentralizedMAPPO:
         if _fused_loss_ok(self.policy, obs, avail_actions, actions, valids):
             if logits is None:
                 logits = self.policy._logits(obs, dist_adjs, channels)               # [P,T,N,A]
+            if logits_out is not None:
+                logits_out.append(logits.detach())
             if maxent:
                 advantages = self._max_entropy_advantages(logits, rewards, baselines, rewards_in_place)
             total, count = _SurrogateFn.apply(logits, actions, old_ll, advantages, valids, self._lr_clip_range,
@@ -566,8 +600,11 @@ class CentralizedMAPPO:
         # step).  The distributed step keeps the critic first: its gradients must be there when the bucket is reduced.
         if distributed:
             self._critic_step(mb, side, distributed)
+        lg = [] if self._update_stats else None
         loss_sum, n_valid = self._compute_loss(None, mb.obs, None, mb.actions, mb.rewards, mb.valids, mb.baselines, mb.dist_adjs,
-                                               mb.channels, mb.advantages, mb.old_ll, reduce=False)
+                                               mb.channels, mb.advantages, mb.old_ll, reduce=False, logits_out=lg)
+        if self._update_stats:                                               # this step's row (and the gate), on the policy's stream
+            self._launch_update_stats(lg[0], mb)
         if distributed:
             loss_sum.backward()
             main.wait_stream(side)
@@ -589,9 +626,78 @@ class CentralizedMAPPO:
         main.wait_stream(side)
         return gn
 
+    # ------------------------------------------------------------------------------------------
+    # update statistics and the KL early stop (update_stats / target_kl; csrc/cm_ppo_stats.hip)
+    # ------------------------------------------------------------------------------------------
+    def _check_update_stats(self, minibatches, distributed):
+        """What the statistics and the stop need, each refusal with its reason -> the number of scheduled optimiser steps."""
+        from .optim import Adam as FusedAdam
+        what = "target_kl" if self._target_kl is not None else "update_stats"
+        mb = minibatches[0]
+        if self._target_kl is not None and distributed:
+            raise NotImplementedError("target_kl in a distributed update: the ranks would have to agree on the gate "
+                                      "(update_stats alone is allowed, with rank-local rows)")
+        if not _fused_loss_ok(self.policy, mb.obs, None, mb.actions, mb.valids):
+            raise L.CommarlError(f"{what} needs the fused PPO loss (a CUDA batch, a policy with _logits and at most 8 actions, "
+                                 "COMMARL_FUSED_LOSS not 0): the statistics are taken from the logits that loss runs on")
+        if not isinstance(self._optimizer, FusedAdam):
+            raise L.CommarlError(f"{what} needs com_marl_amd.optim.Adam as the policy's optimiser (its device-side step), "
+                                 f"not {type(self._optimizer).__name__}")
+        n = self._optimization_mini_epochs * len(minibatches)
+        if n > FusedAdam.DEV_STEP_CAPACITY:
+            raise L.CommarlError(f"{what}: {self._optimization_mini_epochs} mini-epochs x {len(minibatches)} minibatches = {n} optimiser "
+                                 f"steps per epoch, the row table holds optim.Adam.DEV_STEP_CAPACITY = {FusedAdam.DEV_STEP_CAPACITY}")
+        return n
+
+    def _upd(self, dev):
+        """The device side of the statistics: row table, row cursor, gate and workspace, allocated once per device (a step
+        captured in one epoch replays in later ones on the same addresses)."""
+        from .optim import Adam as FusedAdam
+        st = getattr(self, "_upd_state", None)
+        if st is None or st["rows"].device != dev:
+            ws_bytes = int(L.lib().cm_ppo_update_stats_ws_bytes(1 << 16, 1))       # the largest grid's
+            st = self._upd_state = dict(
+                rows=torch.zeros(FusedAdam.DEV_STEP_CAPACITY, L.UPD_COLS, dtype=torch.float64, device=dev),
+                cursor=torch.zeros(1, dtype=torch.int32, device=dev), gate=torch.zeros(1, dtype=torch.int32, device=dev),
+                ws=torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev), ws_bytes=ws_bytes)
+        return st
+
+    def _launch_update_stats(self, logits, mb):
+        """cm_ppo_update_stats on the step's logits: the row of the step about to be taken and, under target_kl, the gate the
+        policy's Adam obeys.  Two small launches on the current (the policy's) stream, part of a captured step."""
+        P, T, N, A = logits.shape
+        st = self._upd(logits.device)
+        gated = self._target_kl is not None
+        L.run("cm_ppo_update_stats", P, T, N, A, L.cptr(logits), L.cptr(mb.actions), L.cptr(mb.old_ll), L.ptr(mb.valids),
+              float(self._lr_clip_range), 1.5 * self._target_kl if gated else 0.0, L.ptr(st["rows"]), st["rows"].shape[0],
+              L.ptr(st["cursor"]), L.ptr(st["gate"]) if gated else None, L.ptr(st["ws"]), st["ws_bytes"], device=logits.device)
+
+    def _collect_update_rows(self, n_scheduled, n_minibatches):
+        """After the epoch's synchronise: the row table to the host (one copy) -> update_rows and the number of applied policy
+        steps, which under target_kl is booked into the policy optimiser's host state here."""
+        st = self._upd_state
+        rows = st["rows"][:n_scheduled].cpu().numpy()
+        n_rows = min(int(st["cursor"].item()), n_scheduled)              # (fewer than scheduled only if the steps were cut short)
+        rows = rows[:n_rows]
+        applied = int((rows[:, L.UPD_COLUMNS.index("stopped")] == 0).sum())
+        if self._target_kl is not None:
+            self._optimizer.end_device_steps(applied)
+        out = {name: rows[:, c].copy() for c, name in enumerate(L.UPD_COLUMNS)}
+        k = np.arange(n_rows)
+        out["mini_epoch"], out["minibatch"] = k // n_minibatches, k % n_minibatches
+        self.update_rows = out
+        return applied
+
     def _run_steps(self, minibatches, T, distributed):
         """optimization_mini_epochs passes over the minibatches (:209-268) -> the gradient norm of every step, in order."""
         dev = minibatches[0].obs.device
+        if self._update_stats:
+            n_scheduled = self._check_update_stats(minibatches, distributed)
+            st = self._upd(dev)
+            st["cursor"].zero_()                              # outside any graph: every epoch's rows start at 0, its gate open
+            st["gate"].zero_()
+            if self._target_kl is not None:
+                self._optimizer.begin_gated_steps(n_scheduled, st["gate"])
         # The critic has its own trunk (a-17): its forward / backward (/ optimiser step) share nothing with the policy's
         # but the minibatch, so they run on a second HIP stream and fill the gaps of the policy's launch chain.
         two_streams = dev.type == "cuda" and os.environ.get("COMMARL_CRITIC_STREAM", "1") != "0"
@@ -611,6 +717,11 @@ class CentralizedMAPPO:
                         gn = step(mb)
                         self._eager_stepped = True
                     grad_norm.append(gn.clone() if torch.is_tensor(gn) else gn)
+        except BaseException:
+            if self._target_kl is not None:                  # the gated optimiser too: what was applied is booked, then the error
+                torch.cuda.synchronize(dev)
+                self._collect_update_rows(n_scheduled, len(minibatches))
+            raise
         finally:
             if graphs is not None:                           # the optimisers leave the device-step mode whatever happened
                 graphs.close()
@@ -649,6 +760,14 @@ class CentralizedMAPPO:
         grad_norm = self._run_steps(minibatches, T, distributed)
         torch.cuda.synchronize(obs.device)
         epoch_time = time.time() - t_opt
+        upd_stats = {}
+        if self._update_stats:
+            applied = self._collect_update_rows(len(grad_norm), len(minibatches))
+            rows = self.update_rows
+            upd_stats = dict(PolicySteps=applied, ApproxKL=float(rows["approx_kl"].max()) if len(grad_norm) else 0.0,
+                             ClipFraction=float(rows["clip_frac"][rows["stopped"] == 0].mean()) if applied else 0.0)
+            if self._target_kl is not None:                  # GradNorm: over the applied steps (the stop is sticky: the first ones)
+                grad_norm = grad_norm[:applied]
         self.policy.sync_weights()
 
         with torch.no_grad():
@@ -662,7 +781,8 @@ class CentralizedMAPPO:
                           GradNorm=self._mean_grad_norm(grad_norm, obs.device), EpochTime=epoch_time,
                           TrainOnceTime=time.time() - t_start, MaxPathLength=T,
                           EnvSteps=int(valids.sum().item()),
-                          GPUMemoryMax=torch.cuda.max_memory_allocated(self._dev()) / 1024 ** 3)     # :372-383 (GiB)
+                          GPUMemoryMax=torch.cuda.max_memory_allocated(self._dev()) / 1024 ** 3,     # :372-383 (GiB)
+                          **upd_stats)
         for k, v in self.stats.items():
             tabular.record(k, v)
         return perf["AverageReturn"]

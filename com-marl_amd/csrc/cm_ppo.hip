@@ -612,9 +612,14 @@ __global__ __launch_bounds__(256) void multi_norm_kernel(TensorTable t, float *w
 
 // bc_tab / cursor (cm_multi_adam_step_dev): the two bias-correction factors come from a device table indexed by a device step
 // counter, so that a captured hipGraph of the optimiser step can be replayed for successive steps
+// GATED (cm_multi_adam_step_gated) adds one trailing argument, the device gate word the launch before this one wrote: with
+// *gate != 0 the step is not taken - norm_ws[0] still receives |g|^2, and the parameters, the moments and the gradients (not
+// clipped) stay as they are.  The ungated instantiation has no such argument: its argument block and code are what they were.
+template <bool GATED = false, class... Gate>
 __global__ __launch_bounds__(256) void multi_adam_kernel(TensorTable t, float *norm_ws, float max_norm, float lr,
                                                         float b1, float b2, float eps, float bc1, float sqrt_bc2,
-                                                        const float *__restrict__ bc_tab, const int32_t *__restrict__ cursor, int tab_steps) {
+                                                        const float *__restrict__ bc_tab, const int32_t *__restrict__ cursor, int tab_steps,
+                                                        Gate... gate) {
     if (bc_tab) {
         int c = *cursor;
         c = c < 0 ? 0 : (c >= tab_steps ? tab_steps - 1 : c);
@@ -627,6 +632,10 @@ __global__ __launch_bounds__(256) void multi_adam_kernel(TensorTable t, float *n
         const float c = max_norm / (sqrtf(nsq) + 1e-6f);
         coef = c < 1.0f ? c : 1.0f;
         if (blockIdx.x == 0 && threadIdx.x == 0) norm_ws[0] = nsq;
+    }
+    if constexpr (GATED) {
+        const int32_t *const g[] = { gate... };
+        if (*g[0] != 0) return;
     }
     const bool norm_sq = norm_ws != nullptr;
     const float step_size = lr / bc1;
@@ -876,7 +885,7 @@ extern "C" int cm_multi_copy_t(int32_t n, const float *const *src, float *const 
 
 static int multi_adam(int32_t n, float *const *params, float *const *grads, float *const *exp_avg, float *const *exp_avg_sq, const int64_t *sizes,
                       float *norm_ws, float max_norm, float lr, float beta1, float beta2, float eps, int32_t step, const float *bc_tab,
-                      const int32_t *cursor, int32_t tab_steps, void *stream) {
+                      const int32_t *cursor, int32_t tab_steps, void *stream, const int32_t *gate = nullptr) {
     if (n < 0 || n > 40) return set_error(CM_ERR_ARG, "cm_multi_adam_step: at most 40 tensors per call");
     if (n == 0) return CM_OK;
     if (!params || !grads || !exp_avg || !exp_avg_sq || !sizes) return set_error(CM_ERR_ARG, "cm_multi_adam_step: bad argument");
@@ -887,9 +896,13 @@ static int multi_adam(int32_t n, float *const *params, float *const *grads, floa
     const hipStream_t st = (hipStream_t)stream;
     if (norm_ws) hipLaunchKernelGGL(multi_norm_kernel, dim3(NORM_BLOCKS), dim3(256), 0, st, t, norm_ws);
     const int hs = bc_tab ? 1 : step;
-    hipLaunchKernelGGL(multi_adam_kernel, dim3(64), dim3(256), 0, st, t, norm_ws, max_norm, lr, beta1, beta2, eps,
-                       (float)(1.0 - pow((double)beta1, (double)hs)), (float)sqrt(1.0 - pow((double)beta2, (double)hs)), bc_tab, cursor,
-                       (int)tab_steps);
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)hs)), sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, (double)hs));
+    if (gate)
+        hipLaunchKernelGGL((multi_adam_kernel<true, const int32_t *>), dim3(64), dim3(256), 0, st, t, norm_ws, max_norm, lr, beta1, beta2, eps,
+                           bc1, sqrt_bc2, bc_tab, cursor, (int)tab_steps, gate);
+    else
+        hipLaunchKernelGGL((multi_adam_kernel<false>), dim3(64), dim3(256), 0, st, t, norm_ws, max_norm, lr, beta1, beta2, eps, bc1, sqrt_bc2,
+                           bc_tab, cursor, (int)tab_steps);
     CM_HIP(hipGetLastError());
     return CM_OK;
 }
@@ -913,6 +926,16 @@ extern "C" int cm_multi_adam_step_dev(int32_t n, float *const *params, float *co
                                       const float *bc_table, const int32_t *cursor, int32_t table_steps, void *stream) {
     return multi_adam(n, params, grads, exp_avg, exp_avg_sq, sizes, norm_ws, max_norm, lr, beta1, beta2, eps, 0, bc_table, cursor, table_steps,
                       stream);
+}
+
+// cm_multi_adam_step_dev behind a device gate (the KL early stop of the PPO update, cm_ppo_stats.hip): *gate == 0 takes the step
+// bit for bit, *gate != 0 leaves parameters, moments and gradients alone and still reports |g|^2
+extern "C" int cm_multi_adam_step_gated(int32_t n, float *const *params, float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                                        const int64_t *sizes, float *norm_ws, float max_norm, float lr, float beta1, float beta2, float eps,
+                                        const float *bc_table, const int32_t *cursor, int32_t table_steps, const int32_t *gate, void *stream) {
+    if (!gate) return set_error(CM_ERR_ARG, "cm_multi_adam_step_gated: null gate");
+    return multi_adam(n, params, grads, exp_avg, exp_avg_sq, sizes, norm_ws, max_norm, lr, beta1, beta2, eps, 0, bc_table, cursor, table_steps,
+                      stream, gate);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

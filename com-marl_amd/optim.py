@@ -49,6 +49,41 @@ class Adam(torch.optim.Optimizer):
         buf[1].zero_()
         self._dev_steps = dict(table=buf[0], cursor=buf[1], n=n_steps, params=ps)
 
+    def begin_gated_steps(self, n_steps, gate):
+        """begin_device_steps() behind a device gate (`gate`: one int32 on the parameters' device, written by
+        cm_ppo_update_stats): until end_device_steps(), every step() is cm_multi_adam_step_gated - eager and captured ones alike -
+        and does nothing once the gate is set.  Armed for a whole train_once, so a never-stepped optimiser is accepted: the
+        parameters without state get zero moments, and the first step number is 1.  How many of the `n_steps` were applied is
+        only known on the device; the caller reads it after its synchronise and books it with end_device_steps(n_applied).
+        The bias-correction cursor keeps advancing through stopped steps, which read it and do nothing."""
+        assert len(self.param_groups) == 1, "device steps: one parameter group"
+        assert 1 <= n_steps <= self.DEV_STEP_CAPACITY, "device steps: at most DEV_STEP_CAPACITY steps per begin_gated_steps()"
+        group = self.param_groups[0]
+        ps = [p for p in group["params"] if p.grad is not None or self.state[p]]
+        if not ps:                                            # never stepped, no gradient yet: every trainable parameter
+            ps = [p for p in group["params"] if p.requires_grad]
+        dev = ps[0].device
+        assert gate.dtype == torch.int32 and gate.device == dev and gate.numel() == 1
+        with torch.no_grad():
+            for p in ps:
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        steps = {int(self.state[p]["step"]) for p in ps}
+        assert len(steps) == 1, "device steps: parameters that have stepped together"
+        b1, b2 = group["betas"]
+        host = torch.zeros(self.DEV_STEP_CAPACITY, 2, dtype=torch.float32)
+        L.lib().cm_adam_bias_corrections(float(b1), float(b2), steps.pop() + 1, n_steps, host.data_ptr())
+        buf = getattr(self, "_dev_step_buf", None)
+        if buf is None or buf[0].device != dev:
+            buf = self._dev_step_buf = (torch.zeros(self.DEV_STEP_CAPACITY, 2, dtype=torch.float32, device=dev),
+                                        torch.zeros(1, dtype=torch.int32, device=dev))
+        buf[0].copy_(host)
+        buf[1].zero_()
+        self._dev_steps = dict(table=buf[0], cursor=buf[1], n=n_steps, params=ps, gate=gate)
+
     def end_device_steps(self, n_done):
         """Book the `n_done` replayed steps into the host-side state (and the parameters' version counters)."""
         ds, self._dev_steps = self._dev_steps, None
@@ -106,7 +141,11 @@ class Adam(torch.optim.Optimizer):
             args = (n, arr(ps), arr(grads), arr([self.state[p]["exp_avg"] for p in ps]),
                     arr([self.state[p]["exp_avg_sq"] for p in ps]), sizes, norm_ptr,
                     float(max_norm if max_norm is not None else 0.0), float(group["lr"]), float(b1), float(b2), float(group["eps"]))
-            if ds is not None:
+            if ds is not None and ds.get("gate") is not None:                       # begin_gated_steps
+                L.run("cm_multi_adam_step_gated", *args, ds["table"].data_ptr(), ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY,
+                      ds["gate"].data_ptr(), device=dev)
+                ds["cursor"].add_(1)
+            elif ds is not None:
                 L.run("cm_multi_adam_step_dev", *args, ds["table"].data_ptr(), ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY,
                       device=dev)
                 ds["cursor"].add_(1)

@@ -1009,6 +1009,12 @@ void cm_adam_bias_corrections(float beta1, float beta2, int32_t first_step, int3
 int cm_multi_adam_step_dev(int32_t n, float *const *params, float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                            const int64_t *sizes, float *norm_ws, float max_norm, float lr, float beta1, float beta2, float eps,
                            const float *bc_table, const int32_t *cursor, int32_t table_steps, void *stream);
+/* cm_multi_adam_step_dev behind a DEVICE gate word (required; the KL early stop of cm_ppo_update_stats below writes it in the
+ * launch before).  *gate == 0: cm_multi_adam_step_dev's step, bit for bit.  *gate != 0: the step is not taken - norm_ws[0] still
+ * receives the pre-clip |g|^2, and parameters, moments and gradients (not clipped, not written back) stay untouched. */
+int cm_multi_adam_step_gated(int32_t n, float *const *params, float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                             const int64_t *sizes, float *norm_ws, float max_norm, float lr, float beta1, float beta2, float eps,
+                             const float *bc_table, const int32_t *cursor, int32_t table_steps, const int32_t *gate, void *stream);
 
 /* The critic's loss (comm_base_critic.py:59-89: -Normal(values, std.mean()).log_prob(returns).mean(); values = the per-agent
  * outputs summed over the team, :110-112; std = exp(clamp(log_std, min)) of gaussian_mlp_module.py:62-188) in one launch, its
@@ -1101,6 +1107,40 @@ int cm_ppo_surrogate_det(int32_t P, int32_t T, int32_t N, int32_t A, const float
 size_t cm_gauss_nll_forward_det_ws_bytes(int64_t S);
 int cm_gauss_nll_forward_det(int64_t S, int32_t N, const float *per_agent, const float *returns, const float *log_std, float min_log_std,
                              int32_t has_min, float *out, void *ws, size_t ws_bytes, void *stream);
+
+/* ---- Per-step PPO update statistics and the device-side KL early stop (csrc/cm_ppo_stats.hip, DESIGN.md "Update statistics") ----
+ * One row of CM_UPD_COLS doubles per call, from cm_ppo_surrogate's inputs (padded [P,T] batch, logits [P*T,N,A], 1 <= A <= 8,
+ * step (p,t) valid iff t < lens[p]).  Per valid step new_ll and H = mean_i H_i are cm_ppo_surrogate's Categorical arithmetic
+ * (the same device function), lr = new_ll - old_ll is taken in f32 as the loss takes it, r = expf(lr) is the ratio the loss
+ * clamps; the sums are f64:
+ *   CM_UPD_N_VALID    number of valid steps
+ *   CM_UPD_APPROX_KL  mean of expm1(lr) - lr        (the k3 estimator of KL(old || new), >= 0)
+ *   CM_UPD_KL         mean of -lr                   (k1)
+ *   CM_UPD_CLIP_FRAC  share of valid steps with |r - 1| > clip (f32 compare)
+ *   CM_UPD_RATIO_MIN / CM_UPD_RATIO_MAX  range of r over the valid steps
+ *   CM_UPD_ENTROPY    mean of H (no softplus)
+ *   CM_UPD_STOPPED    1.0 if the optimiser step this row precedes is not to be applied, else 0.0
+ * rows [max_rows][CM_UPD_COLS], row_cursor [1] (int32), gate [1] (int32, nullable): DEVICE memory.  The call writes
+ * rows[clamp(*row_cursor, 0, max_rows - 1)], then *row_cursor += 1.  With was = gate ? *gate : 0,
+ *   stop = was || (kl_stop > 0 && n_valid > 0 && approx_kl > kl_stop)
+ * (kl_stop <= 0 or NaN never stops; no valid step gives a row of zeros and never stops) and *gate = stop when gate != NULL: the
+ * gate is sticky until the host clears it.  cm_multi_adam_step_gated reads it.  ws: at least cm_ppo_update_stats_ws_bytes(P, T)
+ * bytes of DEVICE memory, contents ignored (per-workgroup f64 partials, added in a fixed order by a second launch: no float
+ * atomics, the row is bit-reproducible, so there is no deterministic twin).  Bad arguments, a NULL or too-small workspace
+ * return CM_ERR_ARG before anything is launched. */
+#define CM_UPD_COLS 8
+#define CM_UPD_N_VALID 0
+#define CM_UPD_APPROX_KL 1
+#define CM_UPD_KL 2
+#define CM_UPD_CLIP_FRAC 3
+#define CM_UPD_RATIO_MIN 4
+#define CM_UPD_RATIO_MAX 5
+#define CM_UPD_ENTROPY 6
+#define CM_UPD_STOPPED 7
+size_t cm_ppo_update_stats_ws_bytes(int32_t P, int32_t T);
+int cm_ppo_update_stats(int32_t P, int32_t T, int32_t N, int32_t A, const float *logits, const int32_t *actions,
+                        const float *old_ll, const int32_t *lens, float clip, double kl_stop, double *rows, int32_t max_rows,
+                        int32_t *row_cursor, int32_t *gate, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ from torch.distributions import Categorical
 
 from . import _lib as L
 from . import deterministic
+from .optim import Adam as FusedAdam
 from .sampler import CentralizedMAOnPolicyVectorizedSampler, PathBatch, tabular
 
 
@@ -64,6 +65,12 @@ def _fused_loss_ok(policy, obs, avail_actions, actions, valids):
             and actions.dtype == torch.int32 and valids.dtype == torch.int32 and os.environ.get("COMMARL_FUSED_LOSS", "1") != "0")
 
 
+def _is_fused_adam(opt):
+    """com_marl_amd.optim.Adam, or an optimiser of any class that offers the same: the clip folded into step(max_norm=...) and
+    the device-step mode the update graphs and the KL stop are built on.  torch.optim.Adam is not one."""
+    return hasattr(opt, "begin_device_steps")
+
+
 @contextlib.contextmanager
 def _torch_deterministic():
     """Deterministic update mode: the framework / library operations of the update (the input-gradient GEMMs of nets._LinearFn and
@@ -96,7 +103,10 @@ class _UpdateGraphs:
     number of envs and path length) copies its tensors into the captured step's input buffers and replays - no capture at
     all (a capture costs as much host time as ~5 replayed steps).  For small batches the step is launch-bound (~3 ms of
     host work per eager step at the reference's 30 000 agent-steps per epoch); large batches keep the eager path
-    (COMMARL_UPDATE_GRAPH=1 forces the graphs, =0 disables them; the default threshold is in agent rows per minibatch)."""
+    (COMMARL_UPDATE_GRAPH=1 forces the graphs, =0 disables them; the default threshold is in agent rows per minibatch).
+    Bookkeeping: at its first replayed or captured step it puts into the device-step mode those of the two optimisers that are
+    not in it yet (under target_kl _run_steps has armed the policy's, behind the gate), and close() books the replayed steps
+    into exactly those; _run_steps closes it, whatever happened."""
     MAX_ROWS = 1 << 18
     MAX_CACHED = 12
 
@@ -106,7 +116,7 @@ class _UpdateGraphs:
         E = algo._optimization_mini_epochs
         obs = minibatches[0].obs
         if (mode == "0" or distributed or not obs.is_cuda or E < 3
-                or not all(hasattr(o, "begin_device_steps") for o in (algo._optimizer, algo._baseline_optimizer))
+                or not all(_is_fused_adam(o) for o in (algo._optimizer, algo._baseline_optimizer))
                 or E * len(minibatches) > algo._optimizer.DEV_STEP_CAPACITY
                 or not _fused_loss_ok(algo.policy, obs, None, minibatches[0].actions, minibatches[0].valids)   # (the framework's Categorical
                 or not all(getattr(n, "_graph_capturable_update", False) for n in (algo.policy, algo.baseline))):   # validates on the host)
@@ -136,12 +146,12 @@ class _UpdateGraphs:
         self.cache = collections.OrderedDict()               # (minibatch index, shapes) -> [graph, output, input tensors]
         self.pool, self.stream = None, None
         self.cur, self.done, self.n_steps, self.first_epoch = [], 0, 0, 1
-        self.armed, self.broken, self.hyper = False, False, None
+        self.armed, self.broken, self.hyper = None, False, None   # armed: the optimisers this epoch's steps put into device-step mode
         self.captured = self.reused = 0                       # (counters: captures taken / earlier epochs' graphs taken over)
 
     def _begin(self, n_mb, n_steps, first_epoch):
         self.cur, self.done, self.n_steps, self.first_epoch = [None] * n_mb, 0, n_steps, first_epoch
-        self.armed, self.broken = False, False
+        self.armed, self.broken = None, False
 
     def _key(self, i, inputs):
         return (i, self.hyper) + tuple(None if t is None else (tuple(t.shape), t.dtype) for t in inputs)
@@ -153,11 +163,10 @@ class _UpdateGraphs:
         switches the rest of the epoch back to eager steps."""
         if self.broken:
             return fn(inputs)
-        if not self.armed:                                   # the moments exist, the step counts are known
-            if self.algo._target_kl is None:                 # (under target_kl the policy's optimiser is armed for the whole
-                self.algo._optimizer.begin_device_steps(self.n_steps)   # train_once, behind the gate: _run_steps arms and books it)
-            self.algo._baseline_optimizer.begin_device_steps(self.n_steps)
-            self.armed = True
+        if self.armed is None:                               # the moments exist, the step counts are known
+            self.armed = [o for o in (self.algo._optimizer, self.algo._baseline_optimizer) if o._dev_steps is None]
+            for o in self.armed:
+                o.begin_device_steps(self.n_steps)
         if self.cur[i] is None:
             key = self._key(i, inputs)
             ent = self.cache.get(key)
@@ -214,13 +223,93 @@ class _UpdateGraphs:
         return g, out
 
     def close(self):
-        """Book the epoch's replayed steps into the optimisers' host state (idempotent); the graphs stay for later epochs."""
-        if self.armed:
-            if self.algo._target_kl is None:
-                self.algo._optimizer.end_device_steps(self.done)
-            self.algo._baseline_optimizer.end_device_steps(self.done)
-            self.armed, self.done = False, 0
+        """Book the epoch's replayed steps into the host state of the optimisers armed here (idempotent); the graphs stay for
+        later epochs."""
+        for o in self.armed or ():
+            o.end_device_steps(self.done)
+        self.armed, self.done = None, 0
         self.cur = [None] * len(self.cur)
+
+
+class _UpdateStats:
+    """The per-step update statistics and the KL early stop (update_stats / target_kl; csrc/cm_ppo_stats.hip), all of it that
+    is not PPO: the switches, the refusals, the launch, the row collection and the summary stats.  An instance is the device
+    side - row table, row cursor, gate and workspace, allocated once per device (a step captured in one epoch replays in later
+    ones on the same addresses) - and lives as algo._upd_state: made by the first arm(), so there is none while both switches
+    are off, and left out of the algo's pickle."""
+
+    @staticmethod
+    def resolve(update_stats, target_kl):
+        """-> (update_stats: bool, target_kl: float or None) from the ctor's arguments and their environment fall-backs."""
+        if update_stats is None:
+            update_stats = os.environ.get("COMMARL_UPDATE_STATS", "") == "1"
+        if target_kl is None and os.environ.get("COMMARL_TARGET_KL", "") != "":
+            target_kl = os.environ["COMMARL_TARGET_KL"]
+        if target_kl is not None:
+            try:
+                target_kl = float(target_kl)
+            except (TypeError, ValueError):
+                raise ValueError(f"target_kl must be a finite float > 0, got {target_kl!r}") from None
+            if not (np.isfinite(target_kl) and target_kl > 0):
+                raise ValueError(f"target_kl must be a finite float > 0, got {target_kl!r}")
+        return bool(update_stats) or target_kl is not None, target_kl
+
+    @classmethod
+    def arm(cls, algo, minibatches, distributed):
+        """What the statistics and the stop need, each refusal with its reason; then the device side for this epoch's
+        `n_steps` scheduled optimiser steps, its row cursor at 0 and its gate open (outside any graph)."""
+        what = "target_kl" if algo._target_kl is not None else "update_stats"
+        mb = minibatches[0]
+        if algo._target_kl is not None and distributed:
+            raise NotImplementedError("target_kl in a distributed update: the ranks would have to agree on the gate "
+                                      "(update_stats alone is allowed, with rank-local rows)")
+        if not _fused_loss_ok(algo.policy, mb.obs, None, mb.actions, mb.valids):
+            raise L.CommarlError(f"{what} needs the fused PPO loss (a CUDA batch, a policy with _logits and at most 8 actions, "
+                                 "COMMARL_FUSED_LOSS not 0): the statistics are taken from the logits that loss runs on")
+        if not _is_fused_adam(algo._optimizer):
+            raise L.CommarlError(f"{what} needs com_marl_amd.optim.Adam as the policy's optimiser (its device-side step), "
+                                 f"not {type(algo._optimizer).__name__}")
+        n = algo._optimization_mini_epochs * len(minibatches)
+        if n > FusedAdam.DEV_STEP_CAPACITY:
+            raise L.CommarlError(f"{what}: {algo._optimization_mini_epochs} mini-epochs x {len(minibatches)} minibatches = {n} optimiser "
+                                 f"steps per epoch, the row table holds optim.Adam.DEV_STEP_CAPACITY = {FusedAdam.DEV_STEP_CAPACITY}")
+        self = getattr(algo, "_upd_state", None)
+        if self is None or self.rows.device != mb.obs.device:
+            self = algo._upd_state = cls(mb.obs.device)
+        self.n_steps, self.n_minibatches = n, len(minibatches)
+        self.cursor.zero_()
+        self.gate.zero_()
+        return self
+
+    def __init__(self, dev):
+        self.ws_bytes = int(L.lib().cm_ppo_update_stats_ws_bytes(1 << 16, 1))       # the largest grid's
+        self.rows = torch.zeros(FusedAdam.DEV_STEP_CAPACITY, L.UPD_COLS, dtype=torch.float64, device=dev)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.gate = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(self.ws_bytes // 8, dtype=torch.float64, device=dev)
+
+    def launch(self, algo, logits, mb):
+        """cm_ppo_update_stats on the step's logits: the row of the step about to be taken and, under target_kl, the gate the
+        policy's Adam obeys.  Two small launches on the current (the policy's) stream, part of a captured step."""
+        P, T, N, A = logits.shape
+        gated = algo._target_kl is not None
+        L.run("cm_ppo_update_stats", P, T, N, A, L.cptr(logits), L.cptr(mb.actions), L.cptr(mb.old_ll), L.ptr(mb.valids),
+              float(algo._lr_clip_range), 1.5 * algo._target_kl if gated else 0.0, L.ptr(self.rows), self.rows.shape[0],
+              L.ptr(self.cursor), L.ptr(self.gate) if gated else None, L.ptr(self.ws), self.ws_bytes, device=logits.device)
+
+    def collect(self):
+        """After the epoch's synchronise: the row table to the host (one copy) -> (update_rows, the number of applied policy
+        steps, the PolicySteps / ApproxKL / ClipFraction stats)."""
+        rows = self.rows[:self.n_steps].cpu().numpy()
+        n_rows = min(int(self.cursor.item()), self.n_steps)              # (fewer than scheduled only if the steps were cut short)
+        rows = rows[:n_rows]
+        out = {name: rows[:, c].copy() for c, name in enumerate(L.UPD_COLUMNS)}
+        k = np.arange(n_rows)
+        out["mini_epoch"], out["minibatch"] = k // self.n_minibatches, k % self.n_minibatches
+        went = out["stopped"] == 0
+        applied = int(went.sum())
+        return out, applied, dict(PolicySteps=applied, ApproxKL=float(out["approx_kl"].max()) if n_rows else 0.0,
+                                  ClipFraction=float(out["clip_frac"][went].mean()) if applied else 0.0)
 
 
 class CentralizedMAPPO:
@@ -238,7 +327,7 @@ class CentralizedMAPPO:
         policy, and none after it; the critic keeps taking every scheduled step.  The decision is taken and obeyed on the
         device (cm_ppo_update_stats, cm_multi_adam_step_gated).  target_kl implies update_stats.  None falls back to
         COMMARL_UPDATE_STATS (1 = on) / COMMARL_TARGET_KL (a float), so the reference's unmodified runners can switch it on."""
-        self._update_stats, self._target_kl = self._resolve_update_stats(update_stats, target_kl)
+        self._update_stats, self._target_kl = _UpdateStats.resolve(update_stats, target_kl)
         self.update_rows = None
         self.device = device
         self.env_spec, self.policy, self.baseline = env_spec, policy, baseline
@@ -255,7 +344,6 @@ class CentralizedMAPPO:
         # default: the multi-tensor Adam of optim.py (two launches per step, clip folded in); it and torch.optim.Adam are
         # the same update as the vendored torch-1.9 Adam (my_optimizer/_functional.py:72-98): pinned by tests against the
         # reference's optimiser.
-        from .optim import Adam as FusedAdam
         on_gpu = next(policy.parameters()).is_cuda
         opt = optimizer or (FusedAdam if on_gpu else torch.optim.Adam)
         bopt = baseline_optimizer or (FusedAdam if on_gpu else torch.optim.Adam)
@@ -279,22 +367,6 @@ class CentralizedMAPPO:
         st.pop("_update_graphs", None)                   # hipGraphs of optimiser steps (rebuilt on demand)
         st.pop("_upd_state", None)                       # device tables of the update statistics (re-made on first use)
         return st
-
-    @staticmethod
-    def _resolve_update_stats(update_stats, target_kl):
-        """-> (update_stats: bool, target_kl: float or None) from the ctor's arguments and their environment fall-backs."""
-        if update_stats is None:
-            update_stats = os.environ.get("COMMARL_UPDATE_STATS", "") == "1"
-        if target_kl is None and os.environ.get("COMMARL_TARGET_KL", "") != "":
-            target_kl = os.environ["COMMARL_TARGET_KL"]
-        if target_kl is not None:
-            try:
-                target_kl = float(target_kl)
-            except (TypeError, ValueError):
-                raise ValueError(f"target_kl must be a finite float > 0, got {target_kl!r}") from None
-            if not (np.isfinite(target_kl) and target_kl > 0):
-                raise ValueError(f"target_kl must be a finite float > 0, got {target_kl!r}")
-        return bool(update_stats) or target_kl is not None, target_kl
 
     @staticmethod
     def _check_entropy_configuration(entropy_method, center_adv, stop_entropy_gradient, policy_ent_coeff):
@@ -604,14 +676,14 @@ class CentralizedMAPPO:
         loss_sum, n_valid = self._compute_loss(None, mb.obs, None, mb.actions, mb.rewards, mb.valids, mb.baselines, mb.dist_adjs,
                                                mb.channels, mb.advantages, mb.old_ll, reduce=False, logits_out=lg)
         if self._update_stats:                                               # this step's row (and the gate), on the policy's stream
-            self._launch_update_stats(lg[0], mb)
+            self._upd_state.launch(self, lg[0], mb)
         if distributed:
             loss_sum.backward()
             main.wait_stream(side)
             self._allreduce_grads(n_valid, mb.n_crit)
         else:
             (loss_sum / n_valid).backward()
-        if hasattr(self._optimizer, "_norm"):                               # optim.Adam: clip + update in two launches
+        if _is_fused_adam(self._optimizer):                                  # optim.Adam: clip + update in two launches
             self._optimizer.step(max_norm=self._max_norm(), return_norm=False)   # policy only (:253-255)
             gn = self._optimizer.norm_sq                                     # a view of the optimiser's workspace
         else:
@@ -626,78 +698,15 @@ class CentralizedMAPPO:
         main.wait_stream(side)
         return gn
 
-    # ------------------------------------------------------------------------------------------
-    # update statistics and the KL early stop (update_stats / target_kl; csrc/cm_ppo_stats.hip)
-    # ------------------------------------------------------------------------------------------
-    def _check_update_stats(self, minibatches, distributed):
-        """What the statistics and the stop need, each refusal with its reason -> the number of scheduled optimiser steps."""
-        from .optim import Adam as FusedAdam
-        what = "target_kl" if self._target_kl is not None else "update_stats"
-        mb = minibatches[0]
-        if self._target_kl is not None and distributed:
-            raise NotImplementedError("target_kl in a distributed update: the ranks would have to agree on the gate "
-                                      "(update_stats alone is allowed, with rank-local rows)")
-        if not _fused_loss_ok(self.policy, mb.obs, None, mb.actions, mb.valids):
-            raise L.CommarlError(f"{what} needs the fused PPO loss (a CUDA batch, a policy with _logits and at most 8 actions, "
-                                 "COMMARL_FUSED_LOSS not 0): the statistics are taken from the logits that loss runs on")
-        if not isinstance(self._optimizer, FusedAdam):
-            raise L.CommarlError(f"{what} needs com_marl_amd.optim.Adam as the policy's optimiser (its device-side step), "
-                                 f"not {type(self._optimizer).__name__}")
-        n = self._optimization_mini_epochs * len(minibatches)
-        if n > FusedAdam.DEV_STEP_CAPACITY:
-            raise L.CommarlError(f"{what}: {self._optimization_mini_epochs} mini-epochs x {len(minibatches)} minibatches = {n} optimiser "
-                                 f"steps per epoch, the row table holds optim.Adam.DEV_STEP_CAPACITY = {FusedAdam.DEV_STEP_CAPACITY}")
-        return n
-
-    def _upd(self, dev):
-        """The device side of the statistics: row table, row cursor, gate and workspace, allocated once per device (a step
-        captured in one epoch replays in later ones on the same addresses)."""
-        from .optim import Adam as FusedAdam
-        st = getattr(self, "_upd_state", None)
-        if st is None or st["rows"].device != dev:
-            ws_bytes = int(L.lib().cm_ppo_update_stats_ws_bytes(1 << 16, 1))       # the largest grid's
-            st = self._upd_state = dict(
-                rows=torch.zeros(FusedAdam.DEV_STEP_CAPACITY, L.UPD_COLS, dtype=torch.float64, device=dev),
-                cursor=torch.zeros(1, dtype=torch.int32, device=dev), gate=torch.zeros(1, dtype=torch.int32, device=dev),
-                ws=torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev), ws_bytes=ws_bytes)
-        return st
-
-    def _launch_update_stats(self, logits, mb):
-        """cm_ppo_update_stats on the step's logits: the row of the step about to be taken and, under target_kl, the gate the
-        policy's Adam obeys.  Two small launches on the current (the policy's) stream, part of a captured step."""
-        P, T, N, A = logits.shape
-        st = self._upd(logits.device)
-        gated = self._target_kl is not None
-        L.run("cm_ppo_update_stats", P, T, N, A, L.cptr(logits), L.cptr(mb.actions), L.cptr(mb.old_ll), L.ptr(mb.valids),
-              float(self._lr_clip_range), 1.5 * self._target_kl if gated else 0.0, L.ptr(st["rows"]), st["rows"].shape[0],
-              L.ptr(st["cursor"]), L.ptr(st["gate"]) if gated else None, L.ptr(st["ws"]), st["ws_bytes"], device=logits.device)
-
-    def _collect_update_rows(self, n_scheduled, n_minibatches):
-        """After the epoch's synchronise: the row table to the host (one copy) -> update_rows and the number of applied policy
-        steps, which under target_kl is booked into the policy optimiser's host state here."""
-        st = self._upd_state
-        rows = st["rows"][:n_scheduled].cpu().numpy()
-        n_rows = min(int(st["cursor"].item()), n_scheduled)              # (fewer than scheduled only if the steps were cut short)
-        rows = rows[:n_rows]
-        applied = int((rows[:, L.UPD_COLUMNS.index("stopped")] == 0).sum())
-        if self._target_kl is not None:
-            self._optimizer.end_device_steps(applied)
-        out = {name: rows[:, c].copy() for c, name in enumerate(L.UPD_COLUMNS)}
-        k = np.arange(n_rows)
-        out["mini_epoch"], out["minibatch"] = k // n_minibatches, k % n_minibatches
-        self.update_rows = out
-        return applied
-
     def _run_steps(self, minibatches, T, distributed):
-        """optimization_mini_epochs passes over the minibatches (:209-268) -> the gradient norm of every step, in order."""
+        """optimization_mini_epochs passes over the minibatches (:209-268), up to and including the epoch's synchronise -> (the
+        gradient norm of every applied policy step, in order; the update statistics' stats, {} when they are off).
+        The one owner of the optimisers' device-step mode: whoever arms one - this function the policy's, behind the gate, under
+        target_kl; _UpdateGraphs at its first replayed step those not armed yet - does so inside the try, and the finally takes
+        both out of it with the applied steps booked."""
         dev = minibatches[0].obs.device
-        if self._update_stats:
-            n_scheduled = self._check_update_stats(minibatches, distributed)
-            st = self._upd(dev)
-            st["cursor"].zero_()                              # outside any graph: every epoch's rows start at 0, its gate open
-            st["gate"].zero_()
-            if self._target_kl is not None:
-                self._optimizer.begin_gated_steps(n_scheduled, st["gate"])
+        gated = self._target_kl is not None
+        stats = _UpdateStats.arm(self, minibatches, distributed) if self._update_stats else None   # (refuses before any step)
         # The critic has its own trunk (a-17): its forward / backward (/ optimiser step) share nothing with the policy's
         # but the minibatch, so they run on a second HIP stream and fill the gaps of the policy's launch chain.
         two_streams = dev.type == "cuda" and os.environ.get("COMMARL_CRITIC_STREAM", "1") != "0"
@@ -706,9 +715,11 @@ class CentralizedMAPPO:
         step = functools.partial(self._optimiser_step, distributed=distributed, two_streams=two_streams)
         # mini-epochs 1.. repeat mini-epoch 0's launches on the same buffers with other weights: small (launch-bound) batches
         # capture each minibatch's step into a hipGraph in mini-epoch 1 and replay it from then on (_UpdateGraphs)
-        graphs = _UpdateGraphs.maybe(self, minibatches, T, distributed)
-        grad_norm = []
+        graphs, grad_norm, upd_stats = None, [], {}
         try:
+            if gated:                                        # for the whole train_once: the host learns how many steps were
+                self._optimizer.begin_device_steps(stats.n_steps, gate=stats.gate)   # applied only after the synchronise
+            graphs = _UpdateGraphs.maybe(self, minibatches, T, distributed)
             for mini_epoch in range(self._optimization_mini_epochs):
                 for i, mb in enumerate(minibatches):
                     if graphs is not None and mini_epoch >= graphs.first_epoch:
@@ -717,15 +728,16 @@ class CentralizedMAPPO:
                         gn = step(mb)
                         self._eager_stepped = True
                     grad_norm.append(gn.clone() if torch.is_tensor(gn) else gn)
-        except BaseException:
-            if self._target_kl is not None:                  # the gated optimiser too: what was applied is booked, then the error
-                torch.cuda.synchronize(dev)
-                self._collect_update_rows(n_scheduled, len(minibatches))
-            raise
         finally:
-            if graphs is not None:                           # the optimisers leave the device-step mode whatever happened
+            if graphs is not None:                           # the count of replayed steps, into the optimisers the graphs armed
                 graphs.close()
-        return grad_norm
+            torch.cuda.synchronize(dev)
+            if stats is not None:                            # the rows, and from them the steps the gate let through
+                self.update_rows, applied, upd_stats = stats.collect()
+                if gated:
+                    self._optimizer.end_device_steps(applied)
+        # GradNorm: over the applied steps (the stop is sticky: the first ones)
+        return (grad_norm[:applied] if gated else grad_norm), upd_stats
 
     def _train_once(self, runner=None, itr=None, paths=None):
         if runner is not None:
@@ -757,17 +769,8 @@ class CentralizedMAPPO:
 
         t_opt = time.time()
         minibatches = self._minibatches(batch, advantages, old_ll, distributed)
-        grad_norm = self._run_steps(minibatches, T, distributed)
-        torch.cuda.synchronize(obs.device)
+        grad_norm, upd_stats = self._run_steps(minibatches, T, distributed)   # (ends with the epoch's synchronise)
         epoch_time = time.time() - t_opt
-        upd_stats = {}
-        if self._update_stats:
-            applied = self._collect_update_rows(len(grad_norm), len(minibatches))
-            rows = self.update_rows
-            upd_stats = dict(PolicySteps=applied, ApproxKL=float(rows["approx_kl"].max()) if len(grad_norm) else 0.0,
-                             ClipFraction=float(rows["clip_frac"][rows["stopped"] == 0].mean()) if applied else 0.0)
-            if self._target_kl is not None:                  # GradNorm: over the applied steps (the stop is sticky: the first ones)
-                grad_norm = grad_norm[:applied]
         self.policy.sync_weights()
 
         with torch.no_grad():

@@ -5,12 +5,25 @@ Same update rule, defaults and state layout as the reference's vendored torch-1.
 (com_marl/torch/algos/my_optimizer/adam.py:56-120, _functional.py:72-98; state keys ``step`` / ``exp_avg`` /
 ``exp_avg_sq``), so ``state_dict()`` interchanges with ``torch.optim.Adam``.  ``step(max_norm=...)`` folds
 ``torch.nn.utils.clip_grad_norm_`` (centralized_ma_ppo.py:253-255) into the same launches and returns the pre-clip norm
-as a DEVICE tensor - nothing in an optimiser step waits for the host."""
+as a DEVICE tensor - nothing in an optimiser step waits for the host.
+
+One device-step mode (begin_device_steps .. end_device_steps): the step number lives on the device, so ONE captured hipGraph
+of a step replays for successive steps, and behind a `gate` word the steps stop applying once the device says so."""
 import ctypes as C
 
 import torch
 
 from . import _lib as L
+
+
+def _zero_state(state, ps):
+    """step 0 and zero moments for the parameters of `ps` that have no state yet."""
+    for p in ps:
+        st = state[p]
+        if not st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
 
 class Adam(torch.optim.Optimizer):
@@ -27,50 +40,25 @@ class Adam(torch.optim.Optimizer):
     # ------------------------------------------------------------------------------------------
     DEV_STEP_CAPACITY = 256      # optimiser steps one begin_device_steps() can cover (the reference schedule takes 30 per epoch)
 
-    def begin_device_steps(self, n_steps):
+    def begin_device_steps(self, n_steps, gate=None):
         """From now until end_device_steps(), step() reads the bias corrections of step `step + 1 + cursor` from a device table
         and advances the device cursor itself (both captured with the step); the host-side ``state[p]['step']`` stands still.
         Table and cursor are allocated once per optimiser and refilled in place: a hipGraph captured in one epoch can be
-        replayed in a later one."""
-        ps = [p for g in self.param_groups for p in g["params"] if p.grad is not None or self.state[p]]
-        steps = {int(self.state[p]["step"]) for p in ps if self.state[p]}
-        assert len(steps) == 1 and len(self.param_groups) == 1, "device steps: one parameter group that has stepped together"
-        assert 1 <= n_steps <= self.DEV_STEP_CAPACITY, "device steps: at most DEV_STEP_CAPACITY steps per begin_device_steps()"
-        first = steps.pop() + 1
-        b1, b2 = self.param_groups[0]["betas"]
-        host = torch.zeros(self.DEV_STEP_CAPACITY, 2, dtype=torch.float32)
-        L.lib().cm_adam_bias_corrections(float(b1), float(b2), first, n_steps, host.data_ptr())
-        dev = ps[0].device
-        buf = getattr(self, "_dev_step_buf", None)
-        if buf is None or buf[0].device != dev:
-            buf = self._dev_step_buf = (torch.zeros(self.DEV_STEP_CAPACITY, 2, dtype=torch.float32, device=dev),
-                                        torch.zeros(1, dtype=torch.int32, device=dev))
-        buf[0].copy_(host)
-        buf[1].zero_()
-        self._dev_steps = dict(table=buf[0], cursor=buf[1], n=n_steps, params=ps)
-
-    def begin_gated_steps(self, n_steps, gate):
-        """begin_device_steps() behind a device gate (`gate`: one int32 on the parameters' device, written by
-        cm_ppo_update_stats): until end_device_steps(), every step() is cm_multi_adam_step_gated - eager and captured ones alike -
-        and does nothing once the gate is set.  Armed for a whole train_once, so a never-stepped optimiser is accepted: the
-        parameters without state get zero moments, and the first step number is 1.  How many of the `n_steps` were applied is
-        only known on the device; the caller reads it after its synchronise and books it with end_device_steps(n_applied).
-        The bias-correction cursor keeps advancing through stopped steps, which read it and do nothing."""
+        replayed in a later one.  A never-stepped optimiser is accepted: the parameters without state get zero moments, and the
+        first step number is 1.
+        gate (one int32 on the parameters' device, written by cm_ppo_update_stats): every step() is then
+        cm_multi_adam_step_gated - eager and captured ones alike - and does nothing once the gate is set.  How many of the
+        `n_steps` were applied is only known on the device; the caller reads it after its synchronise and books it with
+        end_device_steps(n_applied).  The cursor keeps advancing through stopped steps, which read it and do nothing."""
         assert len(self.param_groups) == 1, "device steps: one parameter group"
-        assert 1 <= n_steps <= self.DEV_STEP_CAPACITY, "device steps: at most DEV_STEP_CAPACITY steps per begin_gated_steps()"
+        assert 1 <= n_steps <= self.DEV_STEP_CAPACITY, "device steps: at most DEV_STEP_CAPACITY steps per begin_device_steps()"
         group = self.param_groups[0]
         ps = [p for p in group["params"] if p.grad is not None or self.state[p]]
         if not ps:                                            # never stepped, no gradient yet: every trainable parameter
             ps = [p for p in group["params"] if p.requires_grad]
         dev = ps[0].device
-        assert gate.dtype == torch.int32 and gate.device == dev and gate.numel() == 1
-        with torch.no_grad():
-            for p in ps:
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        assert gate is None or (gate.dtype == torch.int32 and gate.device == dev and gate.numel() == 1)
+        _zero_state(self.state, ps)
         steps = {int(self.state[p]["step"]) for p in ps}
         assert len(steps) == 1, "device steps: parameters that have stepped together"
         b1, b2 = group["betas"]
@@ -102,6 +90,7 @@ class Adam(torch.optim.Optimizer):
         step)."""
         assert closure is None
         out = None
+        ds = self._dev_steps
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -110,18 +99,12 @@ class Adam(torch.optim.Optimizer):
             if dev.type != "cuda":
                 raise L.CommarlError("com_marl_amd.optim.Adam updates CUDA parameters (there is no CPU path)")
             b1, b2 = group["betas"]
-            for p in ps:
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if self._dev_steps is None:
-                    st["step"] = int(st["step"]) + 1
+            _zero_state(self.state, ps)
+            if ds is None:
+                for p in ps:
+                    self.state[p]["step"] = int(self.state[p]["step"]) + 1
             steps = {int(self.state[p]["step"]) for p in ps}
             assert len(steps) == 1, "parameters of one group step together"
-            step = steps.pop()
-            ds = self._dev_steps
             grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
             for p, g in zip(ps, grads):
                 if g is not p.grad:
@@ -137,20 +120,17 @@ class Adam(torch.optim.Optimizer):
                 out = self._norm[0]
             if n > 40:
                 raise L.CommarlError("cm_multi_adam_step takes at most 40 tensors per parameter group")
-            # what both entry points take before their step number (host value, or the device table and its cursor)
+            # what every entry point takes before its step number
             args = (n, arr(ps), arr(grads), arr([self.state[p]["exp_avg"] for p in ps]),
                     arr([self.state[p]["exp_avg_sq"] for p in ps]), sizes, norm_ptr,
                     float(max_norm if max_norm is not None else 0.0), float(group["lr"]), float(b1), float(b2), float(group["eps"]))
-            if ds is not None and ds.get("gate") is not None:                       # begin_gated_steps
-                L.run("cm_multi_adam_step_gated", *args, ds["table"].data_ptr(), ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY,
-                      ds["gate"].data_ptr(), device=dev)
+            if ds is None:                                                          # the host's step number
+                L.run("cm_multi_adam_step", *args, steps.pop(), device=dev)
+            else:                                                                   # the device table and its cursor[, the gate]
+                gated = ds["gate"] is not None
+                L.run("cm_multi_adam_step_gated" if gated else "cm_multi_adam_step_dev", *args, ds["table"].data_ptr(),
+                      ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY, *((ds["gate"].data_ptr(),) if gated else ()), device=dev)
                 ds["cursor"].add_(1)
-            elif ds is not None:
-                L.run("cm_multi_adam_step_dev", *args, ds["table"].data_ptr(), ds["cursor"].data_ptr(), self.DEV_STEP_CAPACITY,
-                      device=dev)
-                ds["cursor"].add_(1)
-            else:
-                L.run("cm_multi_adam_step", *args, step, device=dev)
             # the kernel wrote through raw pointers: tell torch (and the nets' weight-pack cache, which keys on the version
             # counters) that the parameters changed
             for p in ps:

@@ -111,6 +111,54 @@ def test_switches_and_their_environment_fallbacks(monkeypatch):
     assert b._update_stats is True and b._target_kl == a._target_kl
 
 
+def test_adam_device_step_session_bookkeeping():
+    """optim.Adam's device-step session on CPU parameters (arming and booking are host work: no launch, and
+    cm_adam_bias_corrections is host code): a never-stepped optimiser behind a gate, an ungated session after it, the refusals."""
+    import torch
+    from com_marl_amd.optim import Adam
+    cap = Adam.DEV_STEP_CAPACITY
+    ps = [torch.nn.Parameter(torch.randn(3, 2)), torch.nn.Parameter(torch.randn(5))]
+    opt = Adam(ps, lr=1e-3, betas=(0.9, 0.999))
+    for bad in (0, cap + 1):
+        with pytest.raises(AssertionError):
+            opt.begin_device_steps(bad)
+    with pytest.raises(AssertionError):
+        opt.begin_device_steps(5, gate=torch.zeros(1, dtype=torch.int64))
+    assert opt._dev_steps is None and not any(opt.state[p] for p in ps)             # a refusal arms nothing
+
+    def table(first, n):
+        """Rows first .. first + n - 1 in float64, rounded once to float32 (the betas cross the C ABI as floats)."""
+        b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
+        want = np.zeros((cap, 2), np.float32)
+        for i in range(n):
+            want[i] = 1.0 - b1 ** (first + i), math.sqrt(1.0 - b2 ** (first + i))
+        return want
+
+    # never stepped, behind a gate: zero moments, the first step number is 1
+    versions = [p._version for p in ps]
+    opt.begin_device_steps(5, gate=torch.zeros(1, dtype=torch.int32))
+    ds = opt._dev_steps
+    for p in ps:
+        st = opt.state[p]
+        assert st["step"] == 0 and st["exp_avg"].shape == p.shape and st["exp_avg_sq"].shape == p.shape
+        assert not st["exp_avg"].any() and not st["exp_avg_sq"].any()
+    assert ds["table"].dtype == torch.float32 and ds["table"].numpy().tobytes() == table(1, 5).tobytes()
+    assert int(ds["cursor"].item()) == 0
+    opt.end_device_steps(3)
+    assert opt._dev_steps is None
+    assert [int(opt.state[p]["step"]) for p in ps] == [3, 3]
+    assert all(p._version > v for p, v in zip(ps, versions))
+
+    # ungated, after a session: the table starts at step 4, in the same table and cursor tensors
+    opt.begin_device_steps(2)
+    ds2 = opt._dev_steps
+    assert ds2.get("gate") is None
+    assert ds2["table"].data_ptr() == ds["table"].data_ptr() and ds2["cursor"].data_ptr() == ds["cursor"].data_ptr()
+    assert ds2["table"].numpy().tobytes() == table(4, 2).tobytes() and int(ds2["cursor"].item()) == 0
+    opt.end_device_steps(2)
+    assert opt._dev_steps is None and [int(opt.state[p]["step"]) for p in ps] == [5, 5]
+
+
 def test_kernels_of_the_unit_use_no_scratch_and_spill_nothing():
     from tests import isa
     ks = isa.kernels(isa.listing("cm_ppo_stats"))

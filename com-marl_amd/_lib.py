@@ -339,7 +339,7 @@ _SIGNATURES = {
     "cm_gauss_nll_forward_det_ws_bytes": (C.c_size_t, [C.c_int64]),
     "cm_gauss_nll_forward_det": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
-    # per-step PPO update statistics and the device-side KL early stop (csrc/cm_ppo_stats.hip; the gated Adam is in cm_ppo.hip)
+    # per-step PPO update statistics and the device-side KL early stop (csrc/cm_ppo_stats.hip; the gated Adam is in cm_optim.hip)
     "cm_ppo_update_stats_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cm_ppo_update_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_float, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -1,9 +1,9 @@
 // cm_graph_any.hip - the graph ops of the PPO update for ANY embedding width E in 1..128 (gfx950):
 //   cm_attention_forward_any / _backward_any     M = softmax_j(q_i . e_j) and its gradients
 //   cm_masked_agg_forward_any / _backward_any    out = tanh(A.(HW) + b), A = M*R*C row-renormalised, and its gradients
-// cm_attention_* / cm_masked_agg_* (cm_ppo.hip, cm_ppo_mfma.hip) are built for E = 64: their lane map o = tid % E needs
+// cm_attention_* / cm_masked_agg_* (cm_graph_ops.hip, cm_graph_ops_mfma.hip) are built for E = 64: their lane map o = tid % E needs
 // E | 256.  Here E is a run-time argument: the N x E products are dealt to the threads as (group of RC rows, column) work
-// items, so any width runs; the arithmetic per element is that of the E = 64 first-generation kernels of cm_ppo.hip (tanh'
+// items, so any width runs; the arithmetic per element is that of the E = 64 first-generation kernels of cm_graph_ops.hip (tanh'
 // as one fma, the +1e-12 row sum, softmax with the max subtracted, the same order of every sum).
 // A 256-thread workgroup owns EPB whole envs per round of a grid-stride loop.  LDS planes (floats, integer offsets into one
 // array, every base a multiple of 4): N x N planes with row stride NP = N | 1, N x E planes with row stride SE = pad4(E) + 4.
@@ -28,7 +28,7 @@ struct Plan { int EPB, NP, SE, matN, matE, rv; size_t agg_fwd, agg_bwd, attn_fwd
 __host__ inline int r4(int x) { return (x + 3) & ~3; }
 __host__ inline Plan plan(int N, int E) {
     Plan p;
-    p.EPB = (N % RC == 0) ? (48 / N > 0 ? 48 / N : 1) : 1;  // agg_epb of cm_ppo.hip: a group of RC rows never straddles envs
+    p.EPB = (N % RC == 0) ? (48 / N > 0 ? 48 / N : 1) : 1;  // agg_epb of cm_graph_ops.hip: a group of RC rows never straddles envs
     const int rows = p.EPB * N;
     p.NP = N | 1;
     p.SE = r4(E) + 4;

@@ -1,9 +1,10 @@
-// cm_ppo_mfma.hip - backward of the masked aggregation and of the attention softmax for teams of 8 .. 128 agents (the
+// cm_graph_ops_mfma.hip - backward of the masked aggregation and of the attention softmax for teams of 8 .. 128 agents (the
 // PPO update's N x N operators; reference: comm_base_net.py:99-105 + graph_conv_module.py:63-70, attention_module.py:38-47
-// and their autograd).  Per env these are two skinny GEMM pairs,
+// and their autograd).  No C entry point of its own: cm::agg_bwd_mfma and cm::attn_bwd_mfma (cm_internal.h) are what
+// cm_masked_agg_backward* and cm_attention_backward (cm_graph_ops.hip) call.  Per env these are two skinny GEMM pairs,
 //     aggregation:  d_hw = A^T . dP   [N,N]^T [N,64]       dA = dP . hw^T   [N,64] [64,N]
 //     attention  :  d_q  = dS . e     [N,N]   [N,64]       d_e = dS^T . q   [N,N]^T [N,64]
-// which the first-generation kernels (cm_ppo.hip, kept for N < 8) ran as scalar loops over LDS: 53 ms per launch at
+// which the first-generation kernels (cm_graph_ops.hip, kept for N < 8) ran as scalar loops over LDS: 53 ms per launch at
 // N = 72 (4.9 M agent rows), 55 % of that config's update.  Here a workgroup owns one env at a time, the N x N matrix and
 // the two [N,64] tiles sit in LDS once, and all four products run on v_mfma_f32_16x16x4_f32; the softmax / renormalisation
 // gradients are finished in the accumulator registers (16-lane row reductions), so the N x N gradient goes straight to HBM.

@@ -185,7 +185,7 @@ int linear_bwd_stream(bool det, long R, int K, int O, const float *x, const floa
 int encoder_bwd_chain(bool det, long R, int d, const float *obs, const float *a1, const float *e, const float *w2, const float *dy,
                       const float *dy2, float *dw2, float *db2, float *dw1, float *db1, void *stream, int *grid = nullptr);
 size_t lin2_slab_row(int d);
-// cm_ppo_mfma.hip: teams of 8 .. 128 on the matrix cores (slab row: d_bias, 64 floats)
+// cm_graph_ops_mfma.hip: teams of 8 .. 128 on the matrix cores (slab row: d_bias, 64 floats)
 int agg_bwd_mfma(bool det, int S, int N, const float *attn, const float *adj, const float *chan, long ch_stride, const float *hw,
                  const float *out, const float *out_minus, const float *d_out, float *d_attn, float *d_hw, float *d_bias, void *stream,
                  int *grid = nullptr);

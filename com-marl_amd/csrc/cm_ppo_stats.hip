@@ -3,7 +3,7 @@
 //                           minibatch's logits and old log-likelihoods, and the decision whether the step about to be taken is applied
 // The optimiser steps of a minibatch replay from hipGraphs with their step counter on the device (algos._UpdateGraphs), so a
 // `target_kl` stop cannot be a host-side `if`: this unit takes the decision on the device (a sticky gate word) and
-// cm_multi_adam_step_gated (cm_ppo.hip) obeys it.
+// cm_multi_adam_step_gated (cm_optim.hip) obeys it.
 //
 // Two launches, the shape of gauss_nll_fwd_kernel<DET> + gauss_nll_finish_kernel: a grid-stride kernel of at most UPD_MAX_BLOCKS
 // workgroups writes per-workgroup f64 partials and the ratio's min / max into the workspace; a one-workgroup finish kernel adds

@@ -5,7 +5,7 @@ reference, two execution paths:
     (``cm_policy_forward`` / ``cm_critic_forward``, csrc/cm_policy.hip);
   * PPO update (autograd): dense per-agent GEMMs on PyTorch-ROCm (rocBLAS / MFMA), the
     adjacency-masked aggregation as the custom HIP op ``masked_aggregate``
-    (``cm_masked_agg_forward/backward``, csrc/cm_ppo.hip).
+    (``cm_masked_agg_forward/backward``, csrc/cm_graph_ops.hip).
 
 Reference: com_marl/torch/modules/comm_base_net.py, attention_module.py, graph_conv_module.py,
 mlp_encoder_module.py, categorical_mlp_module.py, gaussian_mlp_module.py,

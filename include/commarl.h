@@ -988,7 +988,7 @@ int cm_encoder_backward(int64_t R, int32_t d, const float *obs, const float *a1,
  * one framework copy per tensor).  n <= 40. */
 int cm_multi_copy_t(int32_t n, const float *const *src, float *const *dst, const int32_t *rows, const int32_t *cols,
                     const int32_t *transpose, void *stream);
-/* Multi-tensor Adam step with optional gradient-norm clip, two launches for a whole net (csrc/cm_ppo.hip): the vendored
+/* Multi-tensor Adam step with optional gradient-norm clip, two launches for a whole net (csrc/cm_optim.hip): the vendored
  * torch-1.9 Adam of the reference (com_marl/torch/algos/my_optimizer/_functional.py:72-98, no weight decay / amsgrad) preceded
  * - when norm_ws != NULL - by torch.nn.utils.clip_grad_norm_(params, max_norm) (centralized_ma_ppo.py:253-255), the clipped
  * gradient written back.  params / grads / exp_avg / exp_avg_sq: HOST arrays of n <= 40 DEVICE pointers, sizes[k] elements

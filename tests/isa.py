@@ -5,7 +5,8 @@ Needs hipcc, no GPU.
     python -m tests.isa diff <other-tree>
 
 compiles every unit of the Makefile's SRC in this tree and in <other-tree> (each with its own Makefile's command) and reports
-per kernel symbol whether the instruction streams are the same; the exit status is non-zero if any differ or are missing."""
+per kernel symbol whether the instruction streams and the resource footprints (registers, LDS, scratch, spills) are the same,
+also for a symbol the other tree has in another unit ("moved from"); the exit status is non-zero if any differ or are missing."""
 import functools
 from concurrent.futures import ThreadPoolExecutor
 import os
@@ -22,6 +23,8 @@ MFMA = re.compile(r"^v_mfma_")
 # what issues on the vector ALU: v_* without the matrix pipe; the AGPR copies are VALU instructions as well
 VALU = re.compile(r"^v_(?!mfma_)")
 FLAT_OR_SCRATCH = re.compile(r"^(flat_(load|store|atomic)|scratch_)")
+FOOTPRINT_KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count",
+                  "sgpr_spill_count")
 
 
 def csrc(root=ROOT):
@@ -77,6 +80,14 @@ class Kernel:
     @property
     def vgpr_spill_count(self):
         return self._meta_int("vgpr_spill_count")
+
+    @property
+    def footprint(self):
+        """What decides occupancy: register, LDS, scratch and spill counts.  (kernels() splits the listing at `.agpr_count:`,
+        so that one value is what the block opens with.)"""
+        fp = {key: self._meta_int(key) for key in FOOTPRINT_KEYS}
+        fp["agpr_count"] = int(re.match(r"\s*(\d+)", self.meta).group(1))
+        return fp
 
     def count(self, prefix):
         return sum(1 for ln in self.lines if ln.startswith(prefix))
@@ -167,25 +178,37 @@ def _streams(unit, root):
     # unit's block labels (.LBB<ordinal>_<block>: the order in which the host code first names the instantiations)
     def norm(ln):
         return re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"__hip_cuid_\w+", "__hip_cuid", ln))
-    return {k.name: [norm(ln) for ln in k.lines] for k in kernels(asm)}
+    return {k.name: ([norm(ln) for ln in k.lines], k.footprint) for k in kernels(asm)}
 
 
 def diff(other):
-    """Per kernel symbol of every unit of either tree: identical / differs / only here / only there.  Returns the number that
-    are not identical."""
+    """Per kernel symbol of every unit of either tree: identical / differs / only here / only there, where identical covers the
+    instruction stream and the resource footprint.  A symbol the other tree has in a different unit is compared all the same
+    and reported as moved.  Returns the number that are not identical."""
     here, there = units(ROOT), units(other)
     with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:           # the compiles, side by side; _listing keeps them
         list(pool.map(lambda job: _listing(*job), [(u, ROOT) for u in here] + [(u, other) for u in there]))
-    bad = total = 0
-    for unit in here + [u for u in there if u not in here]:
-        a = _streams(unit, ROOT) if unit in here else {}
-        b = _streams(unit, other) if unit in there else {}
-        for name in sorted(set(a) | set(b)):
-            verdict = "only here" if name not in b else "only there" if name not in a else "identical" if a[name] == b[name] else "differs"
-            total += 1
-            bad += verdict != "identical"
-            print(f"{unit}: {verdict:10s} {name}" + (f" ({len(a[name])} instruction lines)" if verdict == "identical" else ""))
-    print(f"{total} kernels in {len(set(here) | set(there))} units, {bad} not identical")
+    a = {(u, name): k for u in here for name, k in _streams(u, ROOT).items()}
+    b = {(u, name): k for u in there for name, k in _streams(u, other).items()}
+    elsewhere = {}                                # symbol -> the other tree's units that hold it and have no such symbol here
+    for u, name in sorted(b):
+        if (u, name) not in a:
+            elsewhere.setdefault(name, []).append(u)
+    bad = 0
+    for u, name in sorted(a):
+        src = u if (u, name) in b else elsewhere[name].pop(0) if elsewhere.get(name) else None
+        if src is None:
+            verdict = "only here"
+        else:
+            verdict = "identical" if a[u, name] == b[src, name] else "differs"
+            verdict += f" (moved from {src})" if src != u else ""
+        bad += not verdict.startswith("identical")
+        print(f"{u}: {verdict:10s} {name}" + (f" ({len(a[u, name][0])} instruction lines)" if verdict.startswith("identical") else ""))
+    gone = [(u, name) for name, us in sorted(elsewhere.items()) for u in us]
+    for u, name in gone:
+        print(f"{u}: {'only there':10s} {name}")
+    bad += len(gone)
+    print(f"{len(a) + len(gone)} kernels in {len(set(here) | set(there))} units, {bad} not identical")
     return bad
 
 

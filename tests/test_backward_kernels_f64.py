@@ -42,21 +42,22 @@ TAU = 1e-5
 DEV = "cuda:0"
 F64 = torch.float64
 
-# Which kernel a shape reaches (N: team size, S: envs).  Dispatchers: cm_ppo.hip cm_masked_agg_backward_r (:1067-1095),
-# cm_attention_backward (:1224-1246); matrix-core choice cm_ppo_mfma.hip agg_bwd_m / attn_bwd_mfma (:374-404)
-# with NT = ceil(N / 16) and MAXNT = 2 (NT <= 2), 5 (NT <= 5), 8.
+# Which kernel a shape reaches (N: team size, S: envs).  Dispatchers: cm_graph_ops.hip masked_agg_backward (behind
+# cm_masked_agg_backward_r / _det) and cm_attention_backward; matrix-core choice cm_graph_ops_mfma.hip agg_bwd_m (behind
+# agg_bwd_mfma) / attn_bwd_mfma with NT = ceil(N / 16) and MAXNT = 2 (NT <= 2), 5 (NT <= 5), 8.
 SHAPES = [
     # N, S, branch
-    (4, 1, "quad kernels agg_bwd4 / attn_bwd4 (cm_ppo.hip:1073,1231), one env"),
+    (4, 1, "quad kernels agg_bwd4 / attn_bwd4 (the N == 4 branches of masked_agg_backward, cm_attention_backward), one env"),
     (4, 15, "quad kernels, one ragged 16-env chunk"),
-    (4, 8192, "quad kernels, 512 chunks: last grid of <= 64 workgroups looping (cm_ppo.hip:1076)"),
-    (4, 8193, "quad kernels, 513 chunks: grid 513 (cm_ppo.hip:1076), ragged tail; the fused path's 32 bias replicas (nets.py:474)"),
-    (4, 40001, "quad kernels: agg_bwd4 grid capped at 2048 and looping (cm_ppo.hip:1076-1077), ragged tail"),
-    (4, 70001, "quad kernels: attn_bwd4 grid capped at 4096 and looping (cm_ppo.hip:1232), ragged tail"),
-    (3, 15, "first-generation agg_bwd_kernel / attn_bwd_kernel (N < 8: cm_ppo_mfma.hip:377,396 return 1)"),
+    (4, 8192, "quad kernels, 512 chunks: last grid of <= 64 workgroups looping (masked_agg_backward's grid choice)"),
+    (4, 8193, "quad kernels, 513 chunks: grid 513 (masked_agg_backward's grid choice), ragged tail; the fused path's 32 bias "
+              "replicas (nets._FusedNetFn.backward)"),
+    (4, 40001, "quad kernels: agg_bwd4 grid capped at 2048 and looping (masked_agg_backward's grid choice), ragged tail"),
+    (4, 70001, "quad kernels: attn_bwd4 grid capped at 4096 and looping (cm_attention_backward), ragged tail"),
+    (3, 15, "first-generation agg_bwd_kernel / attn_bwd_kernel (N < 8: agg_bwd_mfma, attn_bwd_mfma return 1)"),
     (5, 1001, "first-generation kernels"),
     (6, 257, "first-generation kernels"),
-    (8, 37, "matrix-core MAXNT 2 (NT 1), smallest N it takes (cm_ppo_mfma.hip:377)"),
+    (8, 37, "matrix-core MAXNT 2 (NT 1), smallest N it takes (agg_bwd_mfma's N < 8 refusal)"),
     (32, 37, "matrix-core MAXNT 2 at its upper boundary (NT 2)"),
     (33, 15, "matrix-core MAXNT 5 at its lower boundary (NT 3)"),
     (80, 9, "matrix-core MAXNT 5 at its upper boundary (NT 5), largest fused team"),
@@ -197,7 +198,7 @@ def _agg_call(S, N, attn, adj, chan_all, hop, hw, out, minus, d_out, reps, det, 
 
 # (with_adj, channels (L, l) | None, out_minus, bias_replicas, bias, edge)
 AGG_VARIANTS = [
-    (True, (2, 1), True, 32, True, "none"),          # the fused path's last hop of 2 (nets.py:471-488)
+    (True, (2, 1), True, 32, True, "none"),          # the fused path's last hop of 2 (nets._FusedNetFn.backward's hop loop)
     (True, (3, 0), False, 1, True, "masked_row"),
     (False, (4, 2), False, 1, True, "saturated"),
     (True, None, True, 32, False, "peaked"),
@@ -208,7 +209,7 @@ AGG_VARIANTS = [
 def _agg_case(N, S, variant, det, seed):
     with_adj, chv, use_minus, reps, has_bias, edge = variant
     if det:
-        reps = 1                                                    # the _det twin has one bias row (nets.py:479)
+        reps = 1                                                    # the _det twin has one bias row (nets._FusedNetFn.backward)
     g = torch.Generator().manual_seed(seed)
     Lh, hop = chv if chv is not None else (1, 0)
     adj, ch = _masks(g, S, N, Lh, edge == "masked_row")

@@ -1,4 +1,4 @@
-"""The PPO update's loss, scan and optimiser kernels (the lower half of com-marl_amd/csrc/cm_ppo.hip), each called through
+"""The PPO update's loss, scan and optimiser kernels (com-marl_amd/csrc/cm_ppo.hip and cm_optim.hip), each called through
 the C ABI with the arguments the update passes (algos.py _SurrogateFn / _advantages / process_samples, nets.py _GaussNLLFn /
 _flat_copy, optim.py Adam.step), against a float64 reference of the same operation (torch float64 on the GPU or numpy float64
 on the host: it shares no code with the kernels):
@@ -19,22 +19,26 @@ each row against its own max|ref64|, floored at 1e-3 of the tensor's (tests/test
 prints, per judged quantity, its worst STRICT ratio (that metric), its worst APPLIED one, and the strict ratio of plain float32
 torch (numpy for the scans) evaluating the same formula.
 
-Which branch or grid boundary each shape reaches (cm_ppo.hip):
-  surrogate  256 steps per workgroup, one wave per 64 (:664, :1254): S = 1 (one lane), 255 (ragged last wave), 256 (full
-             workgroup), 257 (second workgroup of one lane), 3 x 200 and 13 x 300 ragged (s -> (path, t) of :669 across
-             workgroups; 16 block sums into the f64 atomic of :770 / the slab of :769).  A = 1: every probability on the upper
-             clamp (:696, :742); logits of +-40: probabilities under the lower clamp; all-equal logits: the largest entropy,
-             under CM_ENT_SOFTPLUS (:711); r at, inside and outside 1 +- clip with both signs of adv and adv = 0 (:716-718).
-  gauss nll  forward grid capped at 256 workgroups (:1308): S = 65536 one pass, 65537 and 262145 loop (:941); backward capped
-             at 1024 (:1333): 262145 loops (:1012); S = 1, 255, 257: lanes past S.  log_std above / at / below min_log_std and
-             has_min = 0 (:932, :1019); g NULL (:1010); d_log_std NULL (:1018).
-  returns, gae  64 paths per workgroup (:1217, :1226): P = 63, 64, 65, 130 around the boundary (p >= P of :548, :563); T = 1, 2,
-             200; lens NULL (:549, :575); paths of length 1 and 2 (variance 0; :582).
-  adam       64 x 256 threads (:888-890): tensors of 16383 / 16384 / 16385 elements take one pass, one pass, two passes with a
-             one-element tail; 50 000 takes four with a ragged tail (:605, :635); clip active / inactive / norm_ws NULL (:624);
-             _dev: cursor -1, 0, 1, n - 1, n against a table of n rows (:618-622).
-  copy_t     64 x 256 threads (:872): 200 x 131 in each mode takes two passes (:854, :856); [1, C], [R, 1], 128 x 128, 21 x 128,
-             128 x 21; n = 40 fills the table (:846).
+Which branch or grid boundary each shape reaches (surrogate, gauss nll, returns, gae: cm_ppo.hip; adam, copy_t: cm_optim.hip):
+  surrogate  256 steps per workgroup, one wave per 64 (ppo_surrogate_kernel, sized by ppo_surrogate): S = 1 (one lane), 255
+             (ragged last wave), 256 (full workgroup), 257 (second workgroup of one lane), 3 x 200 and 13 x 300 ragged (the
+             kernel's s -> (path, t) across workgroups; 16 block sums into its f64 atomic / the slab of its DET form).  A = 1:
+             every probability on the upper clamp (both passes); logits of +-40: probabilities under the lower clamp; all-equal
+             logits: the largest entropy, under CM_ENT_SOFTPLUS; r at, inside and outside 1 +- clip with both signs of adv and
+             adv = 0 (the kernel's torch.min tie split and clamp window).
+  gauss nll  forward grid capped at 256 workgroups (gauss_nll_forward): S = 65536 one pass, 65537 and 262145 loop
+             (gauss_nll_fwd_kernel); backward capped at 1024 (cm_gauss_nll_backward): 262145 loops (gauss_nll_bwd_kernel);
+             S = 1, 255, 257: lanes past S.  log_std above / at / below min_log_std and has_min = 0 (gauss_sigma, the backward
+             kernel's d_log_std); g NULL; d_log_std NULL.
+  returns, gae  64 paths per workgroup (cm_discount_returns, cm_gae): P = 63, 64, 65, 130 around the boundary (p >= P of
+             returns_kernel, gae_kernel); T = 1, 2, 200; lens NULL; paths of length 1 and 2 (variance 0 in gae_kernel's
+             normalisation).
+  adam       64 x 256 threads (multi_adam): tensors of 16383 / 16384 / 16385 elements take one pass, one pass, two passes with a
+             one-element tail; 50 000 takes four with a ragged tail (the grid-stride loops of multi_norm_kernel and
+             multi_adam_kernel); clip active / inactive / norm_ws NULL; _dev: cursor -1, 0, 1, n - 1, n against a table of n rows
+             (multi_adam_kernel clamps the cursor).
+  copy_t     64 x 256 threads (cm_multi_copy_t): 200 x 131 in each mode takes two passes (both loops of multi_copy_t_kernel);
+             [1, C], [R, 1], 128 x 128, 21 x 128, 128 x 21; n = 40 fills the table (CopyTable).
 
 Where the APPLIED metric is wider than the STRICT one, and why.  Figures: measured on the MI355X, worst over the cases named;
 "float32" is plain float32 torch (numpy for the scans) evaluating the same formula from the same inputs.
@@ -648,7 +652,7 @@ BIG = 3                                                                      # i
 
 
 def _adam_ref(ps, gs, ms, vs, lr, step, max_norm, dtype=F64):
-    """The header formula (cm_ppo.hip:589-592) in `dtype` -> |g|^2, clipped gradients, exp_avg, exp_avg_sq, steps p_old - p_new."""
+    """The formula of the Adam header comment of cm_optim.hip in `dtype` -> |g|^2, clipped gradients, exp_avg, exp_avg_sq, steps p_old - p_new."""
     gsq = sum((g.to(dtype) ** 2).sum() for g in gs)
     coef = 1.0
     if max_norm is not None:

@@ -617,5 +617,5 @@ class RolloutEngine:
 
     def invalidate_graphs(self):
         """Call after the policy weights were re-packed at a new address (never needed when
-        parameters are updated in place: the pack buffer is rewritten, see nets._packed)."""
+        parameters are updated in place: the pack buffer is rewritten, see nets.pack._WeightPack._packed)."""
         self._graphs.clear()

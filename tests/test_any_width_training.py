@@ -71,8 +71,14 @@ def test_width_64_never_asks_for_a_route(torch_cuda, monkeypatch, spy):
 
     def boom(*a):
         raise AssertionError("graph_op_route consulted for E = 64")
-    monkeypatch.setattr(nets, "graph_op_route", boom)
+    # AttentionModule and masked_aggregate resolve the name in their own module (nets.graph): a patch on the façade reaches neither
+    from com_marl_amd.nets import graph
+    assert nets.AttentionModule.__module__ == nets.masked_aggregate.__module__ == graph.__name__
+    monkeypatch.setattr(graph, "graph_op_route", boom)
     S, N = 3, 4
+    with pytest.raises(AssertionError, match="graph_op_route consulted"):    # the patch is live: a width other than 64 does ask
+        nets.AttentionModule(32, "dot").to(DEV)(torch.tanh(torch.randn(S, N, 32, device=DEV)))
+    assert spy.calls == []
     e = torch.tanh(torch.randn(S, N, 64, device=DEV))
     m = nets.AttentionModule(64, "dot").to(DEV)(e)
     out = nets.masked_aggregate(m, None, None, 0, e, None)

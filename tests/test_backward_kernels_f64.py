@@ -1,5 +1,5 @@
 """The three backward entry points of the fused training path, called through the C ABI with every argument that path
-passes (com-marl_amd/nets.py _FusedNetFn.backward), against a float64 reference of the same operation built from
+passes (com-marl_amd/nets/comm.py _FusedNetFn.backward), against a float64 reference of the same operation built from
 tests/f64_commnet.py (torch float64 on the GPU: it shares no code with the kernels):
 
   cm_masked_agg_backward_r / _det  channels of hop l of L (pointer offset + stride), out_minus NULL or set, bias_replicas 1 or 32

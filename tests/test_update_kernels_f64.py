@@ -1,5 +1,5 @@
 """The PPO update's loss, scan and optimiser kernels (com-marl_amd/csrc/cm_ppo.hip and cm_optim.hip), each called through
-the C ABI with the arguments the update passes (algos.py _SurrogateFn / _advantages / process_samples, nets.py _GaussNLLFn /
+the C ABI with the arguments the update passes (algos.py _SurrogateFn / _advantages / process_samples, nets/layers.py _GaussNLLFn /
 _flat_copy, optim.py Adam.step), against a float64 reference of the same operation (torch float64 on the GPU or numpy float64
 on the host: it shares no code with the kernels):
 

@@ -45,12 +45,14 @@ __device__ __forceinline__ float relu_bwd(float dy, float y) { return y > 0.0f ?
 // Widths that are a power-of-two number of float4s (16 / 32 / 64 / 128: every hidden width of the nets) take the vector
 // path: ALL of a thread's loads (<= 8 float4 per operand) are issued before the first LDS write, so a chunk exposes ONE
 // HBM round trip (the row-loop staging of cm_linear_wgrad exposed one per 16-row slice: ~11 us per chunk).  Other widths
-// (the observation, the 5 logits, the critic's scalar) are small and go four loads at a time.
+// (the observation, the 5 logits, the critic's scalar) are small and go four loads at a time - as does any width whose
+// src / src2 / yv is not 16-byte aligned (the ABI asks for 4 bytes; one wave-uniform test of the kernel arguments).
 template <int ACT>
 __device__ __forceinline__ void stage(float *dst, int stride, const float *__restrict__ src, const float *__restrict__ yv, int W,
                                       long r0, int rows, int tid, const float *__restrict__ src2 = nullptr) {
     const int w4 = W >> 2;
-    if ((W & 3) == 0 && (w4 & (w4 - 1)) == 0 && w4 >= 4 && w4 <= 32) {
+    const bool al16 = !(((uintptr_t)src | (uintptr_t)src2 | (uintptr_t)(ACT ? yv : nullptr)) & 15);
+    if (al16 && (W & 3) == 0 && (w4 & (w4 - 1)) == 0 && w4 >= 4 && w4 <= 32) {
         const int x = tid & (w4 - 1), rstep = TPB / w4, rb = tid / w4, ni = ROWS / rstep;      // ni = w4 / 4 <= 8
         constexpr bool DZ = ACT != 0;
         float4 q[8], y[DZ ? 8 : 1];

@@ -23,10 +23,11 @@ constexpr int TPB = 256;
 typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int WG_ROWS = 64;
 
-// coalesced [WG_ROWS x W] global -> LDS copy (float4 when the row is a power-of-two number of float4s)
+// coalesced [WG_ROWS x W] global -> LDS copy (float4 when the row is a power-of-two number of float4s and src is 16-byte
+// aligned; the ABI asks for 4 bytes)
 __device__ __forceinline__ void stage_rows(float *dst, int stride, const float *__restrict__ src, int W, long r0, int rows, int tid) {
     const int w4 = W >> 2;
-    if ((W & 3) == 0 && (w4 & (w4 - 1)) == 0 && w4 <= TPB) {
+    if (!((uintptr_t)src & 15) && (W & 3) == 0 && (w4 & (w4 - 1)) == 0 && w4 <= TPB) {
         const int x = tid & (w4 - 1), rstep = TPB / w4;
         for (int r = tid / w4; r < WG_ROWS; r += rstep) {
             const float4 v = r < rows ? reinterpret_cast<const float4 *>(src + (r0 + r) * W)[x] : make_float4(0.f, 0.f, 0.f, 0.f);

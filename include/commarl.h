@@ -949,7 +949,8 @@ int cm_attention_backward_any(int32_t S, int32_t N, int32_t E, const float *q, c
 /* Weight gradient of a per-agent dense layer over R rows: c[p][q] += sum_r a[r][p] * b[r][q] (c [P,Q] must be
  * zeroed by the caller; accumulated with float atomics), colsum_a[p] += sum_r a[r][p] (or NULL).
  * nn.Linear backward: a = dY [R,out], b = X [R,in] -> c = dW [out,in], colsum_a = db.
- * GraphConvolutionModule (H.W, graph_conv_module.py:63): a = H [R,in], b = dZ [R,out] -> c = dW [in,out]. */
+ * GraphConvolutionModule (H.W, graph_conv_module.py:63): a = H [R,in], b = dZ [R,out] -> c = dW [in,out].
+ * Alignment: every pointer 4-byte aligned (any float *); 16-byte aligned a / b only select the faster (float4) loads. */
 int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, const float *b, float *c, float *colsum_a,
                     void *stream);
 
@@ -962,7 +963,9 @@ int cm_linear_wgrad(int64_t R, int32_t P, int32_t Q, const float *a, const float
  *              is a second gradient flowing into the same output (saves the caller's accumulation pass);
  *              dx[r][k] = sum_o dz[r][o] w(k,o)   (dx may be NULL: first layer);
  *              dw += dz^T.x in w's own layout and db += colsum(dz) (db may be NULL), float atomics:
- *              the caller zeroes dw / db. */
+ *              the caller zeroes dw / db.
+ * Alignment: every pointer 4-byte aligned (any float *).  16-byte aligned x / dy / dy2 / y / dx only select the faster
+ * path (float4 staging; the streaming kernels of csrc/cm_linear_bwd.hip): the results are the same to rounding. */
 int cm_linear_act_forward(int64_t R, int32_t in_dim, int32_t out_dim, const float *x, const float *w, int32_t w_layout,
                           const float *bias, int32_t act, float *y, void *stream);
 int cm_linear_act_backward(int64_t R, int32_t in_dim, int32_t out_dim, const float *x, const float *w, int32_t w_layout,

@@ -25,6 +25,10 @@ BOOT_COLUMNS, BOOT_COMM, BOOT_VALUE = 0, 1, 2                               # cm
 # cm_ppo_update_stats' row: CM_UPD_COLS columns, in the order of their CM_UPD_* indices
 UPD_COLUMNS = ("n_valid", "approx_kl", "kl", "clip_frac", "ratio_min", "ratio_max", "entropy", "stopped")
 UPD_COLS = len(UPD_COLUMNS)
+# cm_segment_episodes' table: CM_SEG_COLS columns, in the order of their CM_SEG_* indices (details_0..4: CM_SEG_DETAILS + k)
+SEG_COLUMNS = ("count", "ret_sum", "ret_sumsq", "ret_min", "ret_max", "disc_sum", "len_sum", "success") + tuple(
+    f"details_{k}" for k in range(5))
+SEG_COLS = len(SEG_COLUMNS)
 
 
 class EnvCfg(C.Structure):
@@ -347,6 +351,14 @@ _SIGNATURES = {
     "cm_multi_adam_step_gated": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_void_p]),
+    # fixed-length rollout segments (csrc/cm_segments.hip): bootstrapped targets, batch-wide normalisation, episode bookkeeping
+    "cm_segment_targets": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cm_adv_normalize_ws_bytes": (C.c_size_t, []),
+    "cm_adv_normalize": (C.c_int, [C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cm_segment_episodes_ws_bytes": (C.c_size_t, [C.c_int32]),
+    "cm_segment_episodes": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 EXPORTED = tuple(_SIGNATURES)
 

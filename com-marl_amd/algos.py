@@ -29,7 +29,7 @@ from torch.distributions import Categorical
 from . import _lib as L
 from . import deterministic
 from .optim import Adam as FusedAdam
-from .sampler import CentralizedMAOnPolicyVectorizedSampler, PathBatch, tabular
+from .sampler import CentralizedMAOnPolicyVectorizedSampler, PathBatch, SegmentBatch, tabular
 
 
 class _SurrogateFn(torch.autograd.Function):
@@ -312,22 +312,58 @@ class _UpdateStats:
                                   ClipFraction=float(out["clip_frac"][went].mean()) if applied else 0.0)
 
 
+def _resolve_segment_steps(segment_steps):
+    """-> segment_steps: None (off) or an int >= 1, from the ctor's argument and its environment fall-back."""
+    if segment_steps is None:
+        segment_steps = os.environ.get("COMMARL_SEGMENT_STEPS", "") or None
+        if segment_steps is None:
+            return None
+    bad = ValueError(f"segment_steps must be an integer >= 1, got {segment_steps!r}")
+    if isinstance(segment_steps, bool) or not isinstance(segment_steps, (int, np.integer, str)):
+        raise bad                                            # (a float is refused even when it is whole: 8.0 is a typo for 8)
+    try:
+        n = int(segment_steps)
+    except ValueError:
+        raise bad from None
+    if n < 1:
+        raise bad
+    return n
+
+
 class CentralizedMAPPO:
     _update_stats, _target_kl, update_rows = False, None, None      # (an algo pickled before these switches existed: off)
+    _segment_steps = None
 
     def __init__(self, env_spec, policy, baseline, optimizer=None, baseline_optimizer=None,
                  optimization_n_minibatches=1, optimization_mini_epochs=1, policy_lr=3e-4, lr_clip_range=2e-1,
                  max_path_length=500, num_train_per_epoch=1, discount=0.99, gae_lambda=1, center_adv=True,
                  positive_adv=False, policy_ent_coeff=0.0, use_softplus_entropy=False, stop_entropy_gradient=False,
-                 entropy_method='no_entropy', clip_grad_norm=None, device='cpu', update_stats=None, target_kl=None):
+                 entropy_method='no_entropy', clip_grad_norm=None, device='cpu', update_stats=None, target_kl=None,
+                 segment_steps=None):
         """update_stats / target_kl (both opt-in, not in the reference): per-step statistics of the policy update (`update_rows`,
         and the PolicySteps / ApproxKL / ClipFraction stats) and the KL early stop on top of them.  With target_kl set, the
         first optimiser step of an epoch in front of which the approximate KL (k3, mean of (r - 1) - log r over the minibatch's
         valid steps) exceeds kl_stop = 1.5 * target_kl - the factor Spinning Up and Stable-Baselines3 use - is not applied to the
         policy, and none after it; the critic keeps taking every scheduled step.  The decision is taken and obeyed on the
         device (cm_ppo_update_stats, cm_multi_adam_step_gated).  target_kl implies update_stats.  None falls back to
-        COMMARL_UPDATE_STATS (1 = on) / COMMARL_TARGET_KL (a float), so the reference's unmodified runners can switch it on."""
+        COMMARL_UPDATE_STATS (1 = on) / COMMARL_TARGET_KL (a float), so the reference's unmodified runners can switch it on.
+
+        segment_steps (opt-in, not in the reference; None falls back to COMMARL_SEGMENT_STEPS): an integer n >= 1 trains on
+        fixed-length rollout segments instead of whole episodes.  The sampler's obtain_samples then answers with
+        obtain_segments(itr, n): every env runs n more steps per epoch, without a reset in between, and train_once takes the
+        SegmentBatch with P = n_envs, T = n, valids = n.  Episode ends inside a segment cut the return and GAE scans, the
+        cut at the segment's end is bootstrapped from the critic's value of the state behind it (cm_segment_targets); the time
+        limit is a terminal state like any other end, as in the reference.  center_adv then means ONE normalisation over the
+        whole batch per epoch (cm_adv_normalize; biased variance, eps 1e-8) - the reference's per-path normalisation has no
+        meaning for fragments of episodes.  The progress columns come from the episodes that ended in the segment (NaN means and
+        NumTrajs 0 when none did).  positive_adv, update_stats, target_kl, the deterministic mode and the entropy methods
+        'no_entropy' and 'regularized' work as on whole paths; entropy_method='max' (its per-minibatch cm_entropy_gae has no
+        done-aware form) and a distributed update (the batch-wide moments would have to be reduced over the ranks) are refused
+        with NotImplementedError."""
         self._update_stats, self._target_kl = _UpdateStats.resolve(update_stats, target_kl)
+        self._segment_steps = _resolve_segment_steps(segment_steps)
+        if self._segment_steps is not None and entropy_method == 'max':
+            raise NotImplementedError(self._SEGMENTS_MAXENT)
         self.update_rows = None
         self.device = device
         self.env_spec, self.policy, self.baseline = env_spec, policy, baseline
@@ -358,6 +394,9 @@ class CentralizedMAPPO:
         self.episode_reward_mean = collections.deque(maxlen=100)
         self.stats = {}
 
+    _SEGMENTS_MAXENT = ("rollout segments with entropy_method='max': its per-minibatch cm_entropy_gae recomputes the advantages "
+                        "from the padded rows and has no done-aware form")
+
     def __getstate__(self):
         """Snapshots pickle the algo (snapshotter.py:102-104); a HIP stream is not picklable and is re-made on first use."""
         st = dict(self.__dict__)
@@ -366,6 +405,7 @@ class CentralizedMAPPO:
         st.pop("_eager_stepped", None)                   # per process: the first optimiser steps of a process run eagerly
         st.pop("_update_graphs", None)                   # hipGraphs of optimiser steps (rebuilt on demand)
         st.pop("_upd_state", None)                       # device tables of the update statistics (re-made on first use)
+        st.pop("_norm_ws", None)                         # cm_adv_normalize's workspace
         return st
 
     @staticmethod
@@ -391,6 +431,8 @@ class CentralizedMAPPO:
         baselines [P,T], returns [P,T], dist_adjs [P,T,N,N]|None, channels [P,T,L,N,N]|None), all on device.
         Zero padding for obs/actions/rewards/returns, ONE padding for the masks (App. A-5)."""
         dev = self._dev()
+        if isinstance(paths, SegmentBatch):
+            return self._process_segments(paths)
         if isinstance(paths, PathBatch):
             e = paths.engine
             P, T = paths.gather_index()[:2]
@@ -425,6 +467,42 @@ class CentralizedMAPPO:
         with torch.no_grad():                                                       # :653-657
             baselines = self._baseline_forward(obs, dist_adjs, channels)
         return obs, None, actions, rewards, valids, baselines, returns, dist_adjs, channels
+
+    def _process_segments(self, seg):
+        """process_samples of a SegmentBatch: P = n_envs rows of T = n_steps steps, all valid.  The [P,T,...] tensors are
+        transposed copies of the engine's time-major slots (the minibatches gather rows of them); rewards and dones are not
+        copied for the targets: cm_segment_targets reads them where they are.  The raw advantages stay on the batch
+        (seg.advantages) for _segment_advantages."""
+        seg._check_fresh()
+        e, n, P = seg.engine, seg.n_steps, seg.B
+        rows = lambda b: None if b is None else b[:n].transpose(0, 1).contiguous()      # noqa: E731  ([n,B,...] -> [B,n,...])
+        obs, actions = rows(e.obs).reshape(P, n, -1), rows(e.actions)
+        dist_adjs, channels = rows(e.dist_adj), rows(e.channels)
+        rewards = e.reward64[:n].to(torch.float32).t().contiguous()
+        valids = torch.full((P,), n, dtype=torch.int32, device=obs.device)
+        self.temp_max_path_length = n
+        with torch.no_grad():
+            baselines = self._baseline_forward(obs, dist_adjs, channels).contiguous()
+            b_obs, b_adj, b_ch = seg.bootstrap()
+            step = lambda x: None if x is None else x.unsqueeze(1)                       # noqa: E731  (a batch of one-step rows)
+            v_last = self._baseline_forward(step(b_obs), step(b_adj), step(b_ch)).reshape(P).contiguous()
+        adv, returns = torch.empty_like(baselines), torch.empty_like(baselines)
+        L.run("cm_segment_targets", P, n, L.ptr(e.reward64), L.ptr(e.done), 1, P, L.ptr(baselines), L.ptr(v_last),
+              float(self.discount), float(self._gae_lambda), L.ptr(adv), L.ptr(returns), device=obs.device)
+        seg.advantages, seg.v_last = adv, v_last
+        return obs, None, actions, rewards, valids, baselines, returns, dist_adjs, channels
+
+    def _segment_advantages(self, seg):
+        """The epoch's advantages of a SegmentBatch: cm_segment_targets' (left on the batch by process_samples), under center_adv
+        normalised ONCE over the whole batch (cm_adv_normalize), then positive_adv."""
+        adv = seg.advantages.clone()
+        if self._center_adv:
+            nb = int(L.lib().cm_adv_normalize_ws_bytes())
+            ws = getattr(self, "_norm_ws", None)
+            if ws is None or ws.device != adv.device:
+                ws = self._norm_ws = torch.empty(nb // 8, dtype=torch.float64, device=adv.device)
+            L.run("cm_adv_normalize", adv.numel(), L.ptr(adv), self._eps, L.ptr(ws), nb, device=adv.device)
+        return self._positive(adv)
 
     # baseline dispatch (:230-233, :654-657): the GNN critic takes the graph, plain baselines only obs
     def _baseline_forward(self, obs, dist_adjs, channels):
@@ -554,6 +632,8 @@ class CentralizedMAPPO:
         """The progress.csv columns of centralized_ma_ppo.py:286-366 (per-path sums -> means over paths).
         With a PathBatch everything is reduced on the device and one small vector comes to the host."""
         N = self.policy._n_agents
+        if isinstance(paths, SegmentBatch):
+            return self._log_segments(itr, paths)
         if isinstance(paths, PathBatch):
             e, dev, lens = paths.engine, self._dev(), paths.length
             P, T, valid, t_idx, b_idx = paths.gather_index()
@@ -600,6 +680,33 @@ class CentralizedMAPPO:
         out.update({k: float(v) for k, v in zip(keys, means)})
         out.update(StdReturn=std, MaxReturn=mx, MinReturn=mn, AveTroughput=trput)
         return out
+
+    def _log_segments(self, itr, seg):
+        """_log_performance's columns for a SegmentBatch, from its episode table (cm_segment_episodes: the episodes that ENDED
+        in the segment; one small host copy): means over those episodes, NaN where there is none (NumTrajs 0).  AveDegree and
+        Diameter are means over the segment's steps."""
+        e, N, n = seg.engine, self.policy._n_agents, seg.n_steps
+        ep = seg.episodes
+        cnt, nA, pp = ep["count"], float(N), e.env.scenario == "pp"
+        nan = float("nan")
+        mean = (lambda x: x / cnt) if cnt > 0 else (lambda x: nan)                        # noqa: E731
+        avg = mean(ep["ret_sum"])
+        if e.dist_adj is not None:
+            deg = float(e.dist_adj[:n].sum(-1).mean(dtype=torch.float64))
+            diam = float(e.diameter[:n].mean(dtype=torch.float64)) if e.diameter is not None else 0.0
+        else:
+            deg = diam = float(N)
+        if cnt > 0:
+            self.episode_reward_mean.append(avg)
+        return dict(Iteration=itr, NumTrajs=int(cnt) * N, AverageReturn=avg, AverageDiscountedReturn=mean(ep["disc_sum"]),
+                    SuccessRate=mean(ep["success"]), AverageCaptureCount=mean(ep["details_0"] if pp else ep["details_0"] / nA),
+                    AverageStepCount=mean(ep["len_sum"]), AverageMovingCount=mean(ep["details_1"] / nA),
+                    AveragePenaltyCount=mean(ep["details_2"] if pp else ep["details_2"] / nA),
+                    AverageVariable=mean(ep["details_4"] / nA), AverageVar2=mean(0.0 if pp else ep["details_3"] / nA),
+                    AveDegree=deg, Diameter=diam,
+                    StdReturn=float(np.sqrt(max(ep["ret_sumsq"] / cnt - avg * avg, 0.0))) if cnt > 0 else nan,
+                    MaxReturn=ep["ret_max"] if cnt > 0 else nan, MinReturn=ep["ret_min"] if cnt > 0 else nan,
+                    AveTroughput=float(e.env.n_empty_cells if not pp else 0))
 
     # ------------------------------------------------------------------------------------------
     # gradient exchange (SURVEY.md §8e)
@@ -743,15 +850,25 @@ class CentralizedMAPPO:
         if runner is not None:
             itr, paths = runner.step_itr, runner.step_path
         t_start = time.time()
-        batch = obs, avail, actions, rewards, valids, baselines, returns, dist_adjs, channels = self.process_samples(itr, paths)
-        T = rewards.shape[1]
         from .dist import is_distributed
         distributed = is_distributed()
+        segments = isinstance(paths, SegmentBatch)
+        if segments:                                         # refused before anything is launched
+            if self._maximum_entropy:
+                raise NotImplementedError(self._SEGMENTS_MAXENT)
+            if distributed:
+                raise NotImplementedError("rollout segments in a distributed update: the batch-wide advantage moments would have "
+                                          "to be reduced over the ranks")
+        batch = obs, avail, actions, rewards, valids, baselines, returns, dist_adjs, channels = self.process_samples(itr, paths)
+        T = rewards.shape[1]
         # entropy_method 'max': no epoch-wide advantages - every loss evaluation derives its own from the current policy's
         # entropy (_max_entropy_advantages), and the full-batch evaluations before / after the update add c * H into `rewards`
         # in place as the reference does (its minibatches are sliced from the tensor loss_before left behind)
         maxent = self._maximum_entropy
-        advantages = None if maxent else self._advantages(rewards, baselines, valids)
+        if segments:
+            advantages = self._segment_advantages(paths)
+        else:
+            advantages = None if maxent else self._advantages(rewards, baselines, valids)
         # The reference evaluates the two policies over the full batch eight times per epoch (old log-likelihood twice, loss
         # before / after, KL + entropy before / after with both nets each).  Only three distinct (weights, batch) pairs are
         # involved - last epoch's pre-update weights, this epoch's (which the old policy becomes at :204) and the post-update

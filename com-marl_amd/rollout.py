@@ -467,6 +467,16 @@ class RolloutEngine:
             args += [L.ptr(src), L.ptr(dst), 0 if src is None else src.numel() * src.element_size()]
         L.run("cm_chunk_tail", L.ptr(self.step_bases[k]), n, *args, device=self.env.device)
 
+    def carry(self, n):
+        """Slot n into slot 0 and the sampler's Philox base += n, every shard on its own stream, joined: a chunk's tail
+        (cm_chunk_tail) as a call of its own.  obtain_segments puts it at the head of every call but the first - behind the
+        chunk it would overwrite the slot 0 of the segment just returned."""
+        self.fork()
+        for k, st in enumerate(self.streams):
+            with torch.cuda.stream(st) if st is not None else _null():
+                self._chunk_tail(k, n)
+        self.join()
+
     def _strides(self):
         e = self.env
         B, N, M, d, Lh, A = e.B, e.N, max(e.M, 1), e.d, e.Lh, self.policy._action_dim

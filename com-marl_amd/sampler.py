@@ -13,6 +13,8 @@ from collections.abc import Sequence
 import numpy as np
 import torch
 
+from . import _lib as L
+from .nets import PolicySet
 from .rollout import RolloutEngine
 
 
@@ -257,6 +259,85 @@ class PathBatch(Sequence):
         raise KeyError(key)
 
 
+class SegmentBatch(Sequence):
+    """One obtain_segments call: every env's next `n_steps` steps, rolled on from where the call before stopped.  The data stay
+    in the engine's time-major buffers (slots 0 .. n_steps-1, valid until the next call; a batch of an earlier call raises):
+    CentralizedMAPPO reads them there.  An env's fragment may hold the end of one episode and the start of the next (`dones`
+    marks the last step of an episode), and the segment's last step is in general no episode end: bootstrap() gives the state
+    behind it for the critic.
+
+    n_samples = n_steps * B * N agent-steps, length [B] (int64, device; all n_steps).
+    episode_table: cm_segment_episodes' row [SEG_COLS] (f64, device) over the episodes that ENDED in this segment, whichever
+    segment they began in; episodes is the same as a {column: float} dict (one small host copy, made on first use and kept).
+    batch[i] / iteration: env i's fragment as a dict of numpy arrays (observations [n, N*d], actions [n, N], rewards [n] f64,
+    dones [n] bool, dist_adjs [n, N*N], channels [n, Lh*N, N]), built on first access."""
+
+    def __init__(self, engine, n_steps, n_agents, episode_table):
+        self.engine, self.n_steps, self.n_agents = engine, int(n_steps), n_agents
+        self.B = engine.env.B
+        self.length = torch.full((self.B,), self.n_steps, dtype=torch.int64, device=engine.obs.device)
+        self.episode_table = episode_table
+        self._episodes, self._bufs, self._rows = None, {}, {}
+        self._generation = engine.generation
+
+    def __len__(self):
+        return self.B
+
+    @property
+    def n_samples(self):
+        return self.n_steps * self.B * self.n_agents
+
+    def _check_fresh(self):
+        if self._generation != self.engine.generation:
+            raise RuntimeError("this SegmentBatch belongs to an earlier rollout: the engine's trajectory buffers were "
+                               "overwritten by a later obtain_segments / obtain_samples / reset")
+
+    @property
+    def episodes(self):
+        if self._episodes is None:
+            self._episodes = dict(zip(L.SEG_COLUMNS, self.episode_table.cpu().tolist()))
+        return self._episodes
+
+    def bootstrap(self):
+        """-> (obs [B, N*d], dist_adj [B,N,N] | None, channels [B,Lh,N,N] | None): views of slot n_steps, the state after the
+        segment's last step (after an episode end: the next episode's first observation - its row's targets never use it)."""
+        self._check_fresh()
+        e, n = self.engine, self.n_steps
+        return (e.obs[n].view(self.B, -1), None if e.dist_adj is None else e.dist_adj[n],
+                None if e.channels is None else e.channels[n])
+
+    def _buf(self, name):
+        if name not in self._bufs:
+            self._check_fresh()
+            t = getattr(self.engine, name)
+            self._bufs[name] = None if t is None else t[:self.n_steps].cpu().numpy()
+        return self._bufs[name]
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        row = self._rows.get(i)
+        if row is None:
+            env, n = self.engine.env, self.n_steps
+            N, Lh = env.N, env.Lh
+            adj, ch = self._buf("dist_adj"), self._buf("channels")
+            row = self._rows[i] = dict(
+                observations=self._buf("obs")[:, i].reshape(n, -1).astype(np.float64),
+                actions=self._buf("actions")[:, i].astype(np.int64), rewards=self._buf("reward64")[:, i].copy(),
+                dones=self._buf("done")[:, i].astype(bool),
+                dist_adjs=adj[:, i].reshape(n, N * N) if adj is not None else np.ones((n, N * N), np.float64),
+                channels=ch[:, i].reshape(n, Lh * N, N) if ch is not None
+                else np.broadcast_to(env.channels[0].cpu().numpy().reshape(Lh * N, N), (n, Lh * N, N)).copy())
+        return row
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
 class CentralizedMAOnPolicyVectorizedSampler:
     """sampler.py:20.  ``env`` is a com_marl_amd.envs wrapper (or anything exposing ``.batch``)."""
 
@@ -274,6 +355,7 @@ class CentralizedMAOnPolicyVectorizedSampler:
         self._env_spec = getattr(env, "spec", None)
         self.engine = None
         self._capacity = 0
+        self._seg = None                         # obtain_segments' state: (engine, its generation, n_steps, episode records)
 
     def start_worker(self):
         """Reference builds the VecEnvExecutor here (:41-56); we size the device trajectory lazily."""
@@ -334,6 +416,9 @@ class CentralizedMAOnPolicyVectorizedSampler:
         (RolloutEngine.run_span; captured on the first rollout of an engine, reused by every later one) - eager
         stepping (``use_graph=False``) gives the same PathBatch, 2.3x slower at the headline
         config.  No check happens before step batch_size / (B N): the completed paths cannot hold the batch earlier."""
+        seg = getattr(self.algo, "_segment_steps", None)
+        if seg is not None:                                        # CentralizedMAPPO(segment_steps=...): fixed-length segments instead
+            return self.obtain_segments(itr, seg, use_graph=use_graph)
         mpl = self.algo.max_path_length
         B, N = self._n_envs, self._n_agents
         if not batch_size:
@@ -403,6 +488,67 @@ class CentralizedMAOnPolicyVectorizedSampler:
         self.last_steps = T
         self.last_steps_run = t
         return paths if whole_paths else truncate_paths(paths, batch_size)
+
+    def obtain_segments(self, itr, n_steps, use_graph=True, restart=False):
+        """The next `n_steps` steps of every env -> SegmentBatch (opt-in, not in the reference; CentralizedMAPPO(segment_steps=...)).
+        The first call - also one with restart=True, or the first after an obtain_samples, which resets the envs - resets every
+        env and fills slot 0.  Every later call first carries slot n_steps into slot 0 and advances the sampler's Philox base by
+        n_steps (cm_chunk_tail); the env state stays in the handle, so the episodes go on where they were: nothing is reset, no
+        step is thrown away, and the shapes are the same in every epoch.  Then slots 0 .. n_steps-1 run on obtain_samples' span
+        route (RolloutEngine.run_span: one persistent launch for teams of 4, a replayed graph otherwise, eager steps with
+        use_graph=False).  The carry sits at the head of the NEXT call, not behind the chunk: the returned batch owns its slot 0.
+        Episodes that end inside the segment are booked by cm_segment_episodes into the batch's episode table (the carried
+        per-env records live here, on the device).  Per-env comm conditions are env state and allowed; a PolicySet engine and
+        the tape RNG mode are refused."""
+        try:
+            n = int(n_steps)
+        except (TypeError, ValueError):
+            n = 0
+        if n < 1 or n != n_steps:
+            raise ValueError(f"obtain_segments: n_steps must be an integer >= 1, got {n_steps!r}")
+        policy = self.algo.policy
+        if isinstance(policy, PolicySet):
+            raise ValueError("obtain_segments: a PolicySet engine is refused (segments train one policy; evaluate sets with play())")
+        if getattr(getattr(self.batch, "cfg", None), "rng_mode", L.RNG_PHILOX) != L.RNG_PHILOX:
+            raise L.CommarlError("obtain_segments: the tape RNG mode is refused (a tape is recorded for one rollout from a reset, "
+                                 "segments go on without one)")
+        B, N = self._n_envs, self._n_agents
+        eng = self._ensure_engine(n)
+        dev = eng.obs.device
+        policy.sync_weights()
+        t_all = time.time()
+        seg = self._seg
+        fresh = restart or seg is None or seg[0] is not eng or seg[1] != eng.generation
+        if fresh:
+            nb = int(L.lib().cm_segment_episodes_ws_bytes(B))
+            rec_f, rec_i = torch.zeros(3, B, dtype=torch.float64, device=dev), torch.zeros(6, B, dtype=torch.int64, device=dev)
+            rec_f[2].fill_(1.0)
+            rec = (rec_f, rec_i, torch.empty(nb // 8, dtype=torch.float64, device=dev), nb)
+            eng.reset()
+            policy.reset([True] * B)
+        else:
+            rec = seg[3]
+            eng.carry(seg[2])                                          # the segment before this one ended in slot seg[2]
+        pol_share = self._kernel_split(eng)
+        eng.generation += 1                                            # an earlier call's batch may not read the slots any more
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        eng.run_span(0, n, use_graph=use_graph)
+        ev1.record()
+        table = torch.empty(L.SEG_COLS, dtype=torch.float64, device=dev)
+        L.run("cm_segment_episodes", n, B, L.ptr(eng.reward64), L.ptr(eng.done), L.ptr(eng.details), L.ptr(eng.success),
+              float(self.algo.discount), L.ptr(rec[0]), L.ptr(rec[1]), L.ptr(table), L.ptr(rec[2]), rec[3], device=dev)
+        self.batch.check_status()
+        self._seg = (eng, eng.generation, n, rec)
+        torch.cuda.synchronize(dev)
+        total = time.time() - t_all
+        gpu = ev0.elapsed_time(ev1) * 1e-3
+        tabular.record('PolicyExecTime', gpu * pol_share)
+        tabular.record('EnvExecTime', gpu * (1.0 - pol_share))
+        tabular.record('ProcessExecTime', max(total - gpu, 0.0))
+        tabular.record('BoundReturn', float(getattr(self._base, "bound_return", 0.0)))
+        self.last_steps = self.last_steps_run = n
+        return SegmentBatch(eng, n, N, table)
 
 
 def truncate_paths(paths, max_samples):

@@ -1145,6 +1145,58 @@ int cm_ppo_update_stats(int32_t P, int32_t T, int32_t N, int32_t A, const float 
                         const float *old_ll, const int32_t *lens, float clip, double kl_stop, double *rows, int32_t max_rows,
                         int32_t *row_cursor, int32_t *gate, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Fixed-length rollout segments (csrc/cm_segments.hip, DESIGN.md "Rollout segments") ----
+ * A batch of P fragments of T steps each, rolled without a reset in between.  None of the entry points below merges floats with
+ * atomics: every sum has one order, fixed by the shape, so the bits repeat from run to run on one GPU type and there is no
+ * deterministic twin.
+ *
+ * cm_segment_targets: advantages and critic targets in one launch.  rewards64 (f64) and dones (u8) are read in place: step t of
+ * row p is element p * row_stride + t * step_stride of both (the engine's time-major [T,B] buffers: row_stride 1, step_stride B;
+ * a [P,T] copy: T and 1).  baselines, adv, returns are [P,T] f32, v_last [P] is the critic's value of the observation after the
+ * row's last step.  Per row, backwards, with cm_gae's and cm_discount_returns' arithmetic (f32 delta with gamma and lam rounded
+ * to f32, f64 accumulator; f64 return recurrence with gamma as given):
+ *   a set dones[t] clears the carried V_{t+1}, the accumulator and the running return before step t is processed (the episode
+ *   ended with step t, whatever ended it - the time limit is a terminal state);
+ *   at t = T-1 without a done, V_{t+1} = v_last[p] and the running return starts from (double)v_last[p].
+ * A null pointer or T <= 0 returns CM_ERR_ARG before any launch. */
+int cm_segment_targets(int32_t P, int32_t T, const double *rewards64, const uint8_t *dones, int64_t row_stride, int64_t step_stride,
+                       const float *baselines, const float *v_last, double gamma, double lam, float *adv, float *returns,
+                       void *stream);
+
+/* Batch-wide advantage normalisation, in place: mean and biased variance over all `count` values in f64, two passes (the second
+ * around the mean of the first), then adv = (adv - (float)mean) * (1 / sqrtf((float)var + eps)) - the expression cm_gae applies
+ * per path.  ws: cm_adv_normalize_ws_bytes() bytes of DEVICE memory, contents ignored. */
+size_t cm_adv_normalize_ws_bytes(void);
+int cm_adv_normalize(int64_t count, float *adv, float eps, void *ws, size_t ws_bytes, void *stream);
+
+/* Episode bookkeeping across segments.  One record per env, DEVICE memory the caller zeroes - with rec_f64's third plane at 1 -
+ * when the envs are reset:
+ *   rec_f64 [3][B]  undiscounted return so far, discounted return so far, gamma^length
+ *   rec_i64 [6][B]  length, the sums of details columns 0..4
+ * A call scans slots 0 .. n_steps-1 of reward_f64 [T,B], done [T,B] (u8), details [T,B,6] and success [T,B] per env, carries the
+ * records on and writes table [CM_SEG_COLS]: the episodes that ended in these slots (done set), summed in a fixed order -
+ *   CM_SEG_COUNT      their number
+ *   CM_SEG_RET_SUM / _SUMSQ / _MIN / _MAX   of their undiscounted returns (no episode: 0, 0, +inf, -inf)
+ *   CM_SEG_DISC_SUM   sum of their discounted returns (sum_k gamma^k r_k from the episode's first step)
+ *   CM_SEG_LEN_SUM    sum of their lengths
+ *   CM_SEG_SUCCESS    sum of success at their last step
+ *   CM_SEG_DETAILS+k  sum of their details column k, k = 0..4 (raw counts)
+ * ws: cm_segment_episodes_ws_bytes(B) bytes of DEVICE memory, contents ignored. */
+#define CM_SEG_COLS 13
+#define CM_SEG_COUNT 0
+#define CM_SEG_RET_SUM 1
+#define CM_SEG_RET_SUMSQ 2
+#define CM_SEG_RET_MIN 3
+#define CM_SEG_RET_MAX 4
+#define CM_SEG_DISC_SUM 5
+#define CM_SEG_LEN_SUM 6
+#define CM_SEG_SUCCESS 7
+#define CM_SEG_DETAILS 8
+size_t cm_segment_episodes_ws_bytes(int32_t B);
+int cm_segment_episodes(int32_t n_steps, int32_t B, const double *reward_f64, const uint8_t *done, const int32_t *details,
+                        const int32_t *success, double gamma, double *rec_f64, int64_t *rec_i64, double *table, void *ws,
+                        size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
